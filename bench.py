@@ -11,6 +11,11 @@ Prints ONE JSON line on rank 0 (DESIGN.md section 6 has the roofline accounting)
 This file is the contract: arguments, the headline workload, roofline / traffic / cpu_baseline, the line.  Everything else it measures
 -- the other BASELINE configurations riding in the same line, --mix (configs[2]), --wideband (configs[3]), the multi-GPU runs -- lives
 in bench_configs.py.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it builds the resident blocks, ramps the clock,
+warms up, times exactly K steps, writes the last step's outputs if --dump-outputs is given and prints the line (metric, value, unit,
+ms_per_step, ...).  Everything else -- kernel-timing events, the HBM read probe, the rocprofv3 trace / counter sub-runs (roofline,
+traffic), frame counts, the CPU baseline, the other configurations, the back-to-back layout and the low-SNR point -- runs with --full.
 """
 from __future__ import annotations
 
@@ -94,8 +99,8 @@ def parse_args():
     ap.add_argument("--wb-overlap", action="store_true", help="--wideband: filter bank and decoder on two internal streams (consecutive submits may overlap)")
     ap.add_argument("--wb-blocks", type=int, default=1, choices=(1, 2, 4, 8), help="--wideband: blocks of 1 280 000 samples (0.128 s) per submit")
     ap.add_argument("--wb-occupied", type=int, default=16, help="--wideband: bins of every stream that carry an RS41 transmitter (16: a sparse band; 256: every other bin, the FEC stage busy)")
-    ap.add_argument("--time-every", type=int, default=None, help="kernel-timing HIP events on every n-th timed step (1: all; default 8, "
-                    "4 for runs of fewer than 16 steps).  A timed step carries two event records of 6.4 us of command-stream bubble each "
+    ap.add_argument("--time-every", type=int, default=None, help="kernel-timing HIP events on every n-th timed step (1: all; with --full default 8, "
+                    "4 for runs of fewer than 16 steps; a plain run records none).  A timed step carries two event records of 6.4 us of command-stream bubble each "
                     "(profiles/r2_notes.md), inside the timed region: every 8th costs 0.6 %% of the step")
     ap.add_argument("--flags", type=int, default=None, help="SondeBatchConfig.flags (1: wide, 2: FEC as its own kernel, 4: never-joined launch units, 32: launch units joined "
                     "one submit late; default 0 = ordinary stream semantics)")
@@ -116,12 +121,38 @@ def parse_args():
                     "process driving every GPU through the native node-level host (sonde_node_*, ncclCommInitAll)")
     ap.add_argument("--node", action="store_true", help="run through the node-level host even with --gpus 1 (a node of one device: test hook)")
     ap.add_argument("--rank-local", action="store_true", help="--gpus > 1: every rank generates its own shard (no scatter): kernel scaling without xGMI time")
+    ap.add_argument("--full", action="store_true", help="besides the headline: kernel-timing events (default --time-every), the HBM read probe, roofline "
+                    "and traffic (rocprofv3 sub-runs), frame counts, the CPU baseline, the other BASELINE configurations, the back-to-back layout "
+                    "and the low-SNR point (--no-cpu / --no-others trim it); without it the line carries the headline figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the frames the last timed step produced "
+                    "(what sonde_batch_frames hands a caller, ordered by channel and bit position) as DIR/frames_<field>.npy, at most 64 MB")
     args = ap.parse_args()
     if args.trace_child:      # the headline workload itself, 60 timed steps, no timing events: nothing printed
         args.steps, args.warmup, args.ramp_ms, args.no_cpu, args.no_others, args.time_every = 60, 20, 150.0, True, True, 0
+        args.full, args.dump_outputs = True, None
     elif args.pmc_child:      # a short headline-shaped run for the counter passes: one block re-submitted, nothing printed
         args.steps, args.warmup, args.ramp_ms, args.blocks, args.no_cpu, args.no_others, args.time_every = 10, 2, 60.0, 1, True, True, 0
+        args.full, args.dump_outputs = True, None
     return args
+
+
+# the fields of a SondeFrame record (sdrpp_radiosonde_amd._lib.FRAME_DTYPE), each dumped as one array
+DUMP_FIELDS = ("channel", "type", "len", "nerr", "flags", "bitpos", "data")
+DUMP_MAX_BYTES = 60_000_000          # (the .npy headers come on top: the whole dump stays under 64 MB)
+
+
+def dump_frames(dirname, frames, prefix=""):
+    """The frames of one submit as DIR/<prefix>frames_<field>.npy: `data` (the frame bytes) in float32, the other fields in float64
+    (integers below 2**53: exact).  At most DUMP_MAX_BYTES in all: a larger submit is cut to a fixed, seeded sample of its frames
+    (the headline's ~4 000 frames per step take ~9 MB and are written whole).  Returns the number of frames written."""
+    per_frame = frames.dtype["data"].shape[0] * 4 + sum(int(np.prod(frames.dtype[f].shape or (1,))) * 8 for f in DUMP_FIELDS if f != "data")
+    keep = DUMP_MAX_BYTES // per_frame
+    if len(frames) > keep:
+        frames = frames[np.sort(np.random.default_rng(12345).choice(len(frames), keep, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(dirname, f"{prefix}frames_{f}.npy"), frames[f].astype(np.float32 if f == "data" else np.float64))
+    return len(frames)
 
 
 def cpu_baseline(iq, C, n, args):
@@ -192,6 +223,8 @@ def main():
     node_mode = (args.gpus > 1 or args.node) and not args.multiproc and not args.wideband and not args.mix and not args.sonde_type \
         and os.environ.get("SONDE_BENCH_BACKEND", "nccl") != "gloo"
     if node_mode and torch.cuda.is_available() and torch.cuda.device_count() >= args.gpus:
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs covers the one-process-per-GPU channel path (not the node host: add --multiproc)")
         world = int(os.environ.get("WORLD_SIZE", "1"))
         rank = int(os.environ.get("RANK", "0"))
         dist = None
@@ -262,6 +295,8 @@ def main():
         dist.all_reduce(c, op=dist.ReduceOp.SUM)
         return float(t.item()), float(c.item())
 
+    if args.dump_outputs and (args.wideband or args.iq16 or args.iq8):
+        sys.exit("bench.py: --dump-outputs covers the channel path (not --wideband, --iq16, --iq8)")
     if args.wideband:
         out = run_wideband(args, rank, local_rank, world, dev, barrier, reduce_max_sum)
     else:
@@ -355,6 +390,48 @@ def traced_kernel_us(args):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def headline_config(args, kind, C, n, world, blocks, m, scatter):
+    return {"workload": (f"RS41/M10/DFM09 by channel % 3 x {C} channels/GPU x {n} samples (48 kS/s)" if kind == "mix" else
+                         f"SONDE type {args.sonde_type} x {C} channels/GPU x {n} samples (48 kS/s)" if args.sonde_type else
+                         f"RS41-SG x {C} channels/GPU x {n} samples per step (4800 Bd GFSK, 48 kS/s, Eb/N0 {args.ebn0} dB)")
+                        + (f"; {len(blocks)} consecutive blocks of a continuous signal resident in HBM, cycled" if len(blocks) > 1 else ""),
+            "channels_per_gpu": C, "samples_per_channel": n, "sharding": f"channels/{world}", "flags": args.flags,
+            "launch_units": m["launch"]["units"], "join": JOIN_NAMES[m["launch"]["join"]] if m["launch"]["units"] > 1 else "one launch on the caller's stream",
+            "channel_stride_samples": int(blocks[0].stride(0) // 2),
+            "layout": ("rows back to back" if int(blocks[0].stride(0) // 2) == n else
+                       f"rows {int(blocks[0].stride(0) // 2) * 8 // 1024} KiB apart (sonde_row_stride; --row-stride contiguous puts them back to back)"),
+            "ingest": "rank-local" if scatter is None else scatter["ingest"]}
+
+
+def headline_line(args, kind, m, blocks, C, n, world, dt, scatter, dumped):
+    """The figures of the K timed steps that every run prints (a plain run prints nothing else; --full adds to it)."""
+    msps = C * n * world * args.steps / dt / 1e6
+    out = {
+        "metric": "IQ Msamples/s through demod+FEC @ 48 kS/s/ch",
+        "value": round(msps, 3),
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ramp_ms": args.ramp_ms,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": headline_config(args, kind, C, n, world, blocks, m, scatter),
+        "realtime_channels": round(msps * 1e6 / 48000.0, 1),
+        "full": bool(args.full),
+    }
+    if scatter is not None:
+        out["scatter"] = scatter
+        out["scatter_ms"] = scatter["ms"]
+    if dumped:
+        out["outputs_dumped"] = dict(dumped, dir=args.dump_outputs)
+    return out
+
+
 def run_channels(args, rank, local_rank, world, dev, dist, barrier, reduce_max_sum):
     from sdrpp_radiosonde_amd import _lib
     import ctypes
@@ -362,7 +439,7 @@ def run_channels(args, rank, local_rank, world, dev, dist, barrier, reduce_max_s
     if args.channels is None:
         args.channels = 4096 if args.mix else 1024
     if args.time_every is None:
-        args.time_every = 8 if args.steps >= 16 else 4
+        args.time_every = (8 if args.steps >= 16 else 4) if args.full else 0      # (a plain run records no timing events)
     if args.flags is None:
         args.flags = 0
     C, n = args.channels, args.tiles * 2048
@@ -373,7 +450,7 @@ def run_channels(args, rank, local_rank, world, dev, dist, barrier, reduce_max_s
         if rank == 0:
             print(json.dumps(rec))
         return None
-    default_run = kind == "rs41" and world == 1 and not args.no_others and not args.pmc_child
+    default_run = args.full and kind == "rs41" and world == 1 and not args.no_others and not args.pmc_child
     scatter = None
     if os.environ.get("SONDE_BENCH_BACKEND", "nccl") == "gloo":
         args.scatter_torch = True                  # test hook (ranks share devices): RCCL needs one device per rank
@@ -383,11 +460,22 @@ def run_channels(args, rank, local_rank, world, dev, dist, barrier, reduce_max_s
         blocks, types = make_blocks(kind, C, args.tiles, args.blocks, args.ebn0, dev, seed=1000 + rank, first_channel=rank * C)
     if not (scatter is not None and scatter.get("rows_delivered_strided")):      # (the native scatter delivers strided rows itself)
         blocks = restride(blocks, args)
-    m = measure(blocks, types, args.flags, args, local_rank, barrier, stream)
+    dumped = {}
+
+    def dump(batch):                                 # the last timed step's frames, before anything else is submitted
+        frames = batch.frames()
+        dumped["frames"] = dump_frames(args.dump_outputs, frames, prefix=f"rank{rank}_" if world > 1 else "")
+        dumped["of"] = int(len(frames))
+
+    m = measure(blocks, types, args.flags, args, local_rank, barrier, stream, counts=args.full, after_timed=dump if args.dump_outputs else None,
+                ramp_decoder=True)
     if args.pmc_child:
         return None
+    dt, nfr_total = reduce_max_sum(m["dt"], m["nfr_step"] or 0)
+    out = headline_line(args, kind, m, blocks, C, n, world, dt, scatter, dumped)
+    if not args.full:
+        return out
     demod_ms, framer_ms = m["demod_ms"], m["framer_ms"]
-    dt, nfr_total = reduce_max_sum(m["dt"], m["nfr_step"])
 
     # read-only streaming kernel over the same IQ buffer: what this GPU's HBM delivers to a pure read
     gbs = ctypes.c_float(0.0)
@@ -395,8 +483,6 @@ def run_channels(args, rank, local_rank, world, dev, dist, barrier, reduce_max_s
         raise RuntimeError(_lib.last_error())
     achievable = float(gbs.value)
 
-    samples_per_step = C * n * world
-    msps = samples_per_step * args.steps / dt / 1e6
     ms_per_step = dt / args.steps * 1e3
     # roofline of the dominant kernel (the demodulator): algorithmic bytes = 8 B per complex64 sample read once
     # + bits written (n/sps/8 bytes per channel) -- DESIGN.md section 6
@@ -448,34 +534,10 @@ def run_channels(args, rank, local_rank, world, dev, dist, barrier, reduce_max_s
         if pipelined:
             kernel_ms["note"] += ("; pipelined class streams: `demod` spans a submit's fork to its completion and overlaps the neighbouring "
                                   "submits, per_class = each class's demod kernel alone")
-    out = {
-        "metric": "IQ Msamples/s through demod+FEC @ 48 kS/s/ch",
-        "value": round(msps, 3),
-        "unit": "Msamples/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ramp_ms": args.ramp_ms,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": (f"RS41/M10/DFM09 by channel % 3 x {C} channels/GPU x {n} samples (48 kS/s)" if kind == "mix" else
-                                f"SONDE type {args.sonde_type} x {C} channels/GPU x {n} samples (48 kS/s)" if args.sonde_type else
-                                f"RS41-SG x {C} channels/GPU x {n} samples per step (4800 Bd GFSK, 48 kS/s, Eb/N0 {args.ebn0} dB)")
-                               + (f"; {len(blocks)} consecutive blocks of a continuous signal resident in HBM, cycled" if len(blocks) > 1 else ""),
-                   "channels_per_gpu": C, "samples_per_channel": n, "sharding": f"channels/{world}", "flags": args.flags,
-                   "launch_units": m["launch"]["units"], "join": JOIN_NAMES[m["launch"]["join"]] if m["launch"]["units"] > 1 else "one launch on the caller's stream",
-                   "channel_stride_samples": int(blocks[0].stride(0) // 2),
-                   "layout": ("rows back to back" if int(blocks[0].stride(0) // 2) == n else
-                              f"rows {int(blocks[0].stride(0) // 2) * 8 // 1024} KiB apart (sonde_row_stride; --row-stride contiguous puts them back to back)"),
-                   "ingest": "rank-local" if scatter is None else scatter["ingest"]},
+    out.update({
         "frames_per_s": round(nfr_total * args.steps / dt, 1),
         "frames_per_step_steady": round(nfr_total, 2),
         "frames_first_submit": m["nfr_first"],
-        "realtime_channels": round(msps * 1e6 / 48000.0, 1),
         "kernel_ms": kernel_ms,
         "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4),
@@ -485,10 +547,7 @@ def run_channels(args, rank, local_rank, world, dev, dist, barrier, reduce_max_s
                      "traffic": traffic, "traffic_source": traffic_source,
                      "achievable_read": round(achievable, 1), "frac_of_achievable": round(achieved / achievable, 4),
                      "algorithmic_bytes": alg_bytes, "kernel": "sd_demod_kernel (dominant kernel of the step; frac = algorithmic bytes / its duration [kernel_time_source], step_frac = the same bytes / the whole step by the wall clock)"},
-    }
-    if scatter is not None:
-        out["scatter"] = scatter
-        out["scatter_ms"] = scatter["ms"]
+    })
     if rank == 0 and world == 1 and not args.no_cpu and kind == "rs41":
         out["cpu_baseline"] = cpu_baseline(blocks[0], C, n, args)
         out["cpu_baseline"]["frames_match_gpu_first_submit"] = bool(out["cpu_baseline"]["frames_per_pass"] == m["nfr_first"]) \

@@ -24,14 +24,16 @@ JOIN_NAMES = ("every submit (default: ordinary stream semantics)", "one submit l
 CLASS_NAMES = ("dec1_nt16", "dec2_nt16", "dec4_nt8 (RS41/DFM/iMS-100/MRZ-N1)", "dec2_nt8 (M10)")
 
 
-def ramp_and_time(submit, sync, args, barrier, reset=None):
+def ramp_and_time(submit, sync, args, barrier, reset=None, ramp=None):
     """Clock ramp (untimed), W warmup steps, then EXACTLY K timed steps bracketed by barrier + synchronize.
-    reset(): called between warmup and the timed region (empties the library's kernel-event ring)."""
+    reset(): called between warmup and the timed region (empties the library's kernel-event ring).
+    ramp: (submit, sync) that load the GPU during the ramp instead (a second decoder: the measured one then sees exactly W + K submits)."""
+    ramp_submit, ramp_sync = ramp or (submit, sync)
     t_r = time.perf_counter()
     while (time.perf_counter() - t_r) * 1e3 < args.ramp_ms:
         for _ in range(32):
-            submit()
-        sync()
+            ramp_submit()
+        ramp_sync()
     for _ in range(args.warmup):
         submit()
     sync()
@@ -91,16 +93,21 @@ def make_blocks(kind, C, tiles, NB, ebn0, dev, seed, first_channel=0):
     return blocks, types
 
 
-def measure(blocks, types, flags, args, local_rank, barrier, stream, input_kind=0):
-    """Time args.steps submits cycling through `blocks` (W warmup, clock ramp first); returns the raw figures of this rank."""
+def measure(blocks, types, flags, args, local_rank, barrier, stream, input_kind=0, counts=True, after_timed=None, ramp_decoder=False):
+    """Time args.steps submits cycling through `blocks` (W warmup, clock ramp first); returns the raw figures of this rank.
+    counts=False: no frame counts (nfr_first / nfr_step None: a plain bench run); after_timed(batch): called right after the timed steps.
+    ramp_decoder: the clock ramp runs on a second decoder of the same configuration, so that the measured decoder's state and
+    its last step (input block, frames, bit positions) depend only on W and K, not on how many submits the ramp took."""
     from sdrpp_radiosonde_amd.batch import SondeBatch
     C, n = blocks[0].shape[0], blocks[0].shape[1]
     # frames of a FIRST submit from a fresh decoder: the quantity the CPU baseline's `frames_per_pass` counts
     ts = int(getattr(args, "time_slices", 0) or 0)
-    fresh = SondeBatch(C, n, device=local_rank, types=types, flags=flags, input_kind=input_kind, time_slices=ts)
-    fresh.submit(blocks[0], stream)
-    nfr_first = int(fresh.sync())
-    fresh.close()
+    nfr_first = None
+    if counts:
+        fresh = SondeBatch(C, n, device=local_rank, types=types, flags=flags, input_kind=input_kind, time_slices=ts)
+        fresh.submit(blocks[0], stream)
+        nfr_first = int(fresh.sync())
+        fresh.close()
     batch = SondeBatch(C, n, device=local_rank, types=types, flags=flags, input_kind=input_kind, time_slices=ts)
     launch = batch.launch_info()                   # launch units per submit and how they are joined (the library's choice at these flags)
     turn = [0]
@@ -110,16 +117,31 @@ def measure(blocks, types, flags, args, local_rank, barrier, stream, input_kind=
         turn[0] += 1
     # kernel times: HIP events recorded by the library around the launches of every --time-every-th timed step
     # (an event record is a few microseconds of bubble in the command stream)
-    dt = ramp_and_time(submit, batch.sync, args, barrier, reset=lambda: batch.set_timing(args.time_every))
+    ramp, ramp_batch = None, None
+    if ramp_decoder:
+        ramp_batch = SondeBatch(C, n, device=local_rank, types=types, flags=flags, input_kind=input_kind, time_slices=ts)
+        ramp_turn = [0]
+
+        def ramp_submit():
+            ramp_batch.submit(blocks[ramp_turn[0] % len(blocks)], stream)
+            ramp_turn[0] += 1
+        ramp = (ramp_submit, ramp_batch.sync)
+    dt = ramp_and_time(submit, batch.sync, args, barrier, reset=lambda: batch.set_timing(args.time_every), ramp=ramp)
+    if ramp_batch is not None:
+        ramp_batch.close()
+    if after_timed is not None:
+        after_timed(batch)
     demod_ms, framer_ms, class_ms = 0.0, 0.0, {}
     if args.time_every:
         demod_ms, framer_ms = batch.kernel_ms()
         class_ms = batch.class_ms()
-    nfr_step = 0                                   # frames of one more pass over the cycle, per step
-    for _ in range(0 if args.pmc_child else len(blocks)):      # (profiled sub-runs end with the timed steps)
-        submit()
-        nfr_step += batch.sync()
-    nfr_step /= len(blocks)
+    nfr_step = None
+    if counts:
+        nfr_step = 0                               # frames of one more pass over the cycle, per step
+        for _ in range(0 if args.pmc_child else len(blocks)):      # (profiled sub-runs end with the timed steps)
+            submit()
+            nfr_step += batch.sync()
+        nfr_step /= len(blocks)
     batch.close()
     return {"dt": dt, "demod_ms": demod_ms, "framer_ms": framer_ms, "class_ms": class_ms, "nfr_first": nfr_first, "nfr_step": nfr_step, "launch": launch}
 

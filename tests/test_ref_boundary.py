@@ -4,8 +4,9 @@
 stand-ins for the absent sondedump headers, decoder.hpp:6-14) and a test-only dsp/block.h skeleton; the seven
 radiosonde::Decoder<...> instantiations of /root/reference/src/main.hpp:36-42 link against libsonde_mi355.so.
 CPU: compile + link + construct.  GPU: one RS41 stream through the REFERENCE's run() loop (decoder.hpp:53-119) gives
-the same callbacks as include/sonde_decoder.hpp.  The binary is built here (where /root/reference exists) into
-tests/cpp/_build/ (git-ignored, travels to the GPU box); everything skips when neither source nor binary is there.
+the same callbacks as include/sonde_decoder.hpp.  The binary is built where the reference's sources are (REF_SRC), by `make -C oracle ref-boundary`
+(build() does it), into oracle/_ref/ (git-ignored, beside the other reference builds; it goes with the tree to a GPU machine);
+everything skips when neither source nor binary is there.
 This is boundary evidence, not an oracle."""
 import os
 import subprocess
@@ -17,26 +18,24 @@ from sdrpp_radiosonde_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_SRC = "/root/reference/src"
-BUILD = os.path.join(ROOT, "tests", "cpp", "_build")
-EXE = os.path.join(BUILD, "ref_boundary_test")
+EXE = os.path.join(ROOT, "oracle", "_ref", "ref_boundary_test")
 
 
 def build_ref_boundary() -> str:
-    """Compile tests/cpp/ref_boundary_test.cpp against the reference's decoder.hpp (in place) and libsonde_mi355.so."""
+    """Compile tests/cpp/ref_boundary_test.cpp against the reference's decoder.hpp (in place) and libsonde_mi355.so
+    (the recipe: oracle/Makefile, target ref-boundary)."""
     _lib.load()
-    os.makedirs(BUILD, exist_ok=True)
-    libdir = os.path.dirname(_lib.LIB_PATH)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "tests", "cpp", "refstub"), "-I", REF_SRC,
-                           "-I", os.path.join(REF_SRC, "decode"), "-I", os.path.join(ROOT, "include", "compat"),
-                           "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "ref_boundary_test.cpp"),
-                           "-o", EXE, "-L", libdir, "-l:libsonde_mi355.so", "-Wl,-rpath,$ORIGIN/../../../sdrpp_radiosonde_amd",
-                           "-Wl,-rpath,/opt/rocm/lib"])
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "ref-boundary", f"LIBDIR={os.path.dirname(_lib.LIB_PATH)}"])
     return EXE
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_SRC, "decode", "decoder.hpp")), reason="/root/reference absent")
+def _have_ref_src() -> bool:
+    return os.path.exists(os.path.join(REF_SRC, "decode", "decoder.hpp"))
+
+
+@pytest.mark.skipif(not _have_ref_src() and not os.path.exists(EXE), reason="neither the reference sources nor a prebuilt oracle/_ref/ref_boundary_test")
 def test_reference_decoder_hpp_compiles_and_links_against_this_abi():
-    exe = build_ref_boundary()
+    exe = build_ref_boundary() if _have_ref_src() else EXE
     out = subprocess.check_output([exe, "link"], text=True)
     assert out.strip() == "LINK OK 7"
     # the seven triples resolve to this library, not to anything else
@@ -49,8 +48,8 @@ def test_reference_decoder_hpp_compiles_and_links_against_this_abi():
 @pytest.mark.gpu
 def test_reference_run_loop_on_gpu_decoder(oracle, tmp_path):
     if not os.path.exists(EXE):
-        if not os.path.exists(os.path.join(REF_SRC, "decode", "decoder.hpp")):
-            pytest.skip("neither /root/reference nor a prebuilt tests/cpp/_build/ref_boundary_test")
+        if not _have_ref_src():
+            pytest.skip("neither the reference sources nor a prebuilt oracle/_ref/ref_boundary_test")
         build_ref_boundary()
     from sdrpp_radiosonde_amd import synth
     n = 2048 * 80

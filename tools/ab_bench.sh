@@ -5,7 +5,7 @@ for rep in $(seq 1 $REPS); do
   for spec in "$@"; do
     lib=${spec%%:*}; extra=""; [[ "$spec" == *:* ]] && extra=${spec#*:}
     echo -n "$spec rep$rep: "
-    SONDE_MI355_LIB=$PWD/$lib python bench.py --steps ${STEPS:-100} --warmup 20 --no-cpu $extra 2>&1 | tail -1 | python -c "
+    SONDE_MI355_LIB=$PWD/$lib python bench.py --full --steps ${STEPS:-100} --warmup 20 --no-cpu $extra 2>&1 | tail -1 | python -c "
 import sys, json
 try:
     j = json.loads(sys.stdin.read())

@@ -4,7 +4,7 @@
   python tools/design_table.py profiles/r6           # prints the markdown
   python tools/design_table.py profiles/r6 --write   # replaces the region between the table markers of DESIGN.md
 
-Reads <prefix>_bench.json (python bench.py), <prefix>_bench_driver_args.json (--steps 20 --warmup 5), <prefix>_rocprof.csv,
+Reads <prefix>_bench.json (python bench.py --full), <prefix>_bench_driver_args.json (--full --steps 20 --warmup 5), <prefix>_rocprof.csv,
 <prefix>_wb_rocprof.csv, <prefix>_counters.csv, <prefix>_wb_counters.csv, <prefix>_pytest_gpu.log.  Nothing is typed in by hand."""
 import json
 import os

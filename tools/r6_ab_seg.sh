@@ -7,7 +7,7 @@ out=gpurun_out/r6_ab_seg.txt
 : > $out
 run() {  # label, args
   for rep in 1 2; do
-    python bench.py $2 --no-cpu --no-others --steps 100 --warmup 20 2>/dev/null | python -c "
+    python bench.py $2 --full --no-cpu --no-others --steps 100 --warmup 20 2>/dev/null | python -c "
 import json,sys; d=json.load(sys.stdin); print('$1 rep$rep', d['ms_per_step'], d['roofline']['step_frac'], d['config'].get('launch_units'), d['config'].get('join'))" | tee -a $out
   done
 }

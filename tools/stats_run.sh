@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 R=$PWD
 cd /tmp && rm -rf /tmp/p_stats
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -o st -- python $R/bench.py --no-cpu > /tmp/st.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -o st -- python $R/bench.py --full --no-cpu > /tmp/st.log 2>&1
 cd $R
 mkdir -p gpurun_out
 find /tmp/p_stats -name '*stats*.csv' | head -5
