@@ -352,6 +352,33 @@ int    sonde_vfo_process_host(SondeVfo *v, const void *iq_host, size_t n_in, siz
                               const float **out48_dev, size_t *out_stride);
 int    sonde_vfo_taps(int rate_in, float *g /* up * 16 */);      /* parity-test introspection */
 
+/* ------------------------------------------------------------------ type detector (DESIGN SPEC 3.8)
+ * What sonde type is on each of many 48 kS/s channels.  It takes the rows sonde_batch_submit takes (the same input kinds, the same
+ * row stride, lengths in multiples of SONDE_TILE) and keeps, per channel and sonde type, the best normalised correlation of the
+ * type's on-air sync with the channel's quantised discriminator stream since create / reset: its sign, its position and, from
+ * all seven, a decision.  The GFSK types (RS41, DFM, iMS-100, M10, MRZ-N1) are matched at 24 kS/s, iMet-4 and SRS-C50 behind their
+ * tone demodulators at 6 kS/s.  Front-end state and the stream history are carried, so a sync across two submits is found.
+ * Recommended flow for channels of unknown type: detect, then create the SondeBatch with the detected types. */
+typedef struct SondeDetector SondeDetector;
+typedef struct {
+	int32_t  type;                    /* SONDE_* decided, -1 = nothing yet */
+	uint32_t inverted;                /* bit k: type k's best match had negative sign (never set for iMS-100: its code is differential) */
+	double   best[SONDE_NTYPES];      /* max |r| per type since create / reset (the exact double of the SPEC) */
+	uint64_t pos[SONDE_NTYPES];       /* absolute input-sample index of that match */
+} SondeDetection;
+/* type_mask: n_channels bitmasks, bit k = SONDE type k may be decided; NULL = all 7.  No CPU path: a device is required. */
+int  sonde_detect_create(uint32_t n_channels, uint32_t max_samples, int input_kind, const uint8_t *type_mask, int device, SondeDetector **out);
+void sonde_detect_destroy(SondeDetector *d);
+/* samples: DEVICE pointer, channel c at element c * channel_stride; one kernel on `stream` (NULL = default stream), ordinary stream
+ * semantics: work queued on `stream` afterwards runs after the submit's last read of `samples` */
+int  sonde_detect_submit(SondeDetector *d, const void *samples, size_t n_samples, size_t channel_stride, void *stream);
+int  sonde_detect_results(SondeDetector *d, SondeDetection *out, size_t cap);   /* synchronises; returns channels written */
+int  sonde_detect_reset(SondeDetector *d);
+int  sonde_detect_thresholds(float out[SONDE_NTYPES]);
+/* test introspection: the last submit's quantised streams of one channel; returns that submit's n_samples */
+int  sonde_detect_read(SondeDetector *d, uint32_t channel, int32_t *D /* n/2 */, int32_t *a_imet /* n/8 */, int32_t *a_c50 /* n/8 */);
+int  sonde_detect_templates(int type, int8_t *s, int cap);    /* returns L; writes min(L, cap) values of +-1 (s may be NULL) */
+
 /* post-FEC derived quantities, as /root/reference/src/decode/decoder.hpp:132-174 computes them */
 float sonde_dewpt(float temp, float rh);
 float sonde_altitude_to_pressure(float alt);

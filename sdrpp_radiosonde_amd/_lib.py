@@ -39,6 +39,14 @@ class SondeData(C.Structure):
                 ("serial", C.c_char * 32), ("shutdown", C.c_int), ("o3_mpa", C.c_float)]
 
 
+class SondeDetection(C.Structure):
+    _fields_ = [("type", C.c_int32), ("inverted", C.c_uint32), ("best", C.c_double * 7), ("pos", C.c_uint64 * 7)]
+
+
+DETECTION_DTYPE = np.dtype([("type", "<i4"), ("inverted", "<u4"), ("best", "<f8", (7,)), ("pos", "<u8", (7,))])
+assert DETECTION_DTYPE.itemsize == C.sizeof(SondeDetection)
+
+
 class SondeBatchConfig(C.Structure):
     _fields_ = [("n_channels", C.c_uint32), ("types", C.POINTER(C.c_uint8)), ("max_samples", C.c_uint32),
                 ("input_kind", C.c_int32), ("device", C.c_int32), ("flags", C.c_uint32), ("launch_units", C.c_uint32),
@@ -71,6 +79,8 @@ ABI_SYMBOLS = [
     "sonde_chan_create", "sonde_chan_create_multi", "sonde_chan_create_dual", "sonde_chan_streams", "sonde_chan_channels", "sonde_chan_set_fused", "sonde_chan_set_input", "sonde_chan_set_overlap", "sonde_chan_destroy", "sonde_chan_samples_per_submit", "sonde_chan_submit", "sonde_chan_batch",
     "sonde_chan_read", "sonde_chan_tables", "sonde_chan_kernel_ms",
     "sonde_vfo_create", "sonde_vfo_destroy", "sonde_vfo_ratio", "sonde_vfo_out_samples", "sonde_vfo_process", "sonde_vfo_process_host", "sonde_vfo_taps",
+    "sonde_detect_create", "sonde_detect_destroy", "sonde_detect_submit", "sonde_detect_results", "sonde_detect_reset", "sonde_detect_thresholds",
+    "sonde_detect_read", "sonde_detect_templates",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -187,6 +197,16 @@ def load() -> C.CDLL:
         L.sonde_vfo_process.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]
         L.sonde_vfo_process_host.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t)]
         L.sonde_vfo_taps.argtypes = [C.c_int, vp]
+    if hasattr(L, "sonde_detect_create"):
+        L.sonde_detect_create.argtypes = [C.c_uint32, C.c_uint32, C.c_int, vp, C.c_int, C.POINTER(vp)]
+        L.sonde_detect_destroy.argtypes = [vp]
+        L.sonde_detect_destroy.restype = None
+        L.sonde_detect_submit.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+        L.sonde_detect_results.argtypes = [vp, vp, C.c_size_t]
+        L.sonde_detect_reset.argtypes = [vp]
+        L.sonde_detect_thresholds.argtypes = [vp]
+        L.sonde_detect_read.argtypes = [vp, C.c_uint32, vp, vp, vp]
+        L.sonde_detect_templates.argtypes = [C.c_int, vp, C.c_int]
     f = C.c_float
     L.sonde_gpx_open.restype = vp
     L.sonde_gpx_open.argtypes = [C.c_char_p]

@@ -99,8 +99,6 @@ void sd_launch_afsk(int type, int kind /* 0 real, 1 complex64, 2 int16 IQ, 3 int
 }
 
 // ---------------------------------------------------------------- iMet framer: one wave per channel
-#define IMET_SYNC     0x405u    // bits 1,0,1,0,0,0,0,0,0,0,1,0 in stream order, first bit = bit 0
-#define IMET_SYNC_INV 0xBFAu
 #define IMET_MAXLEN   64
 
 __device__ __forceinline__ uint32_t bits_at(const uint32_t *ring, uint32_t mask, uint64_t p, int nbits)
@@ -217,8 +215,6 @@ void sd_launch_framer_imet(uint32_t n_list, hipStream_t stream, const SdChanStat
 // C34/C50 decoder notes].  Sync = the 21 bits  1 | 0 00000000 1 | 0 11111111 1  (stop/idle, the characters 00 and FF),
 // exact match in either polarity.  A candidate whose characters have a wrong start/stop bit is dropped (search
 // resumes one bit later); it waits while the packet is incomplete; checksum failures are recorded, not dropped.
-#define C50_SYNC     0x1FF401u
-#define C50_SYNC_INV 0x000BFEu
 #define C50_LEN      9
 
 __global__ __launch_bounds__(64) void sd_c50_kernel(

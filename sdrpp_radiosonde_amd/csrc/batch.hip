@@ -89,7 +89,7 @@ static void make_taps(const ModemDef *md, int type, float *out /* [32][32] */)
 }
 
 // mixer table of the AFSK tone demodulator: (cos, -sin) of 2 pi 17 k / 480 (1700 Hz at 48 kS/s), SPEC 3.6
-static void make_mixer(float *out, int cycles, int per)
+void make_mixer(float *out, int cycles, int per)
 {
 	const double PI = 3.14159265358979323846;
 	for (int k = 0; k < per; k++) {

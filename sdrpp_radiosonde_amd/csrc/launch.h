@@ -85,5 +85,8 @@ void sd_launch_framer_other(int type, uint32_t n_list, hipStream_t stream,
 void sd_launch_rs255_unit(uint8_t *cw_io, uint32_t n_pairs, int n, int32_t *status, const uint8_t *gf_exp, const uint8_t *gf_log,
 	const uint32_t *gf_swar, hipStream_t stream);
 
+// SPEC 3.6's mixer table (batch.hip): out[2k], out[2k + 1] = (cos, -sin)(2 pi cycles k / per) as float32
+void make_mixer(float *out, int cycles, int per);
+
 // sets the text sonde_last_error() returns; returns -1
 int sd_fail(const char *what, hipError_t e = hipSuccess);

@@ -43,6 +43,14 @@ struct SdModem {            // per sonde type, built on the host
 #define SD_AF_DEC 8        // AFSK tone demodulator (SPEC 3.6): 48 kS/s -> 6 kS/s
 #define SD_AF_PER 480      // iMet mixer table period: 17 cycles of 1700 Hz at 48 kS/s
 #define SD_C50_PER 240     // SRS-C50 mixer table period: 19 cycles of 3800 Hz at 48 kS/s
+// sync words of the AFSK framers (afsk.hip; SPEC 3.6), stream order, first bit = bit 0; the type detector (detect.hip) renders its
+// templates from the same words
+#define IMET_SYNC      0x405u      // the 12 bits 1 0 10000000 1 0 (stop/idle, the character 0x01, the next start bit)
+#define IMET_SYNC_INV  0xBFAu
+#define IMET_SYNC_BITS 12
+#define C50_SYNC       0x1FF401u   // the 21 bits 1 0 00000000 1 0 11111111 1 (stop/idle, the characters 00 and FF)
+#define C50_SYNC_INV   0x000BFEu
+#define C50_SYNC_BITS  21
 struct SdAfskState {        // tone-demodulator state, one per channel (64 B)
 	float    iq_last[2];    // previous IQ sample of the first discriminator
 	float    b[4][2];       // the four 8-sample block sums before the next one, oldest first
