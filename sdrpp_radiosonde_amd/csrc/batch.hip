@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 #include "sonde_dev.h"
+#include "sd_input.h"
 #include "../../include/sonde_abi.h"
 
 #include "launch.h"
@@ -249,8 +250,7 @@ extern "C" int sonde_batch_create(const SondeBatchConfig *cfg, SondeBatch **out)
 	if (cfg->time_slices > 16) return fail("sonde_batch_create: time_slices must be 0 (the library's choice) or 1..16");
 	if (cfg->n_channels == 0) return fail("sonde_batch_create: n_channels == 0");
 	if (cfg->max_samples == 0 || cfg->max_samples % SONDE_TILE) return fail("sonde_batch_create: max_samples must be a positive multiple of SONDE_TILE");
-	if (cfg->input_kind != SONDE_INPUT_IQ && cfg->input_kind != SONDE_INPUT_REAL && cfg->input_kind != SONDE_INPUT_IQ16 && cfg->input_kind != SONDE_INPUT_IQ8)
-		return fail("sonde_batch_create: bad input_kind");
+	if (!sd_input_known(cfg->input_kind)) return fail("sonde_batch_create: bad input_kind");
 	int ndev = 0;
 	HIPCHK(hipGetDeviceCount(&ndev));
 	if (cfg->device < 0 || cfg->device >= ndev) return fail("sonde_batch_create: no such HIP device");
@@ -558,7 +558,7 @@ extern "C" int sonde_batch_submit(SondeBatch *b, const void *samples, size_t n_s
 	if (n_samples == 0 || n_samples % b->granule || n_samples > b->max_samples) return fail("sonde_batch_submit: n_samples must be a multiple of SONDE_TILE (16384 with iMet channels) and <= max_samples");
 	if (channel_stride < n_samples) return fail("sonde_batch_submit: channel_stride < n_samples");
 	// the kernels read 16 bytes per lane: every channel row must start on a 16-byte boundary
-	if (((uintptr_t)samples & 15u) || channel_stride % (b->input_kind == SONDE_INPUT_IQ ? 2 : (b->input_kind == SONDE_INPUT_IQ8 ? 8 : 4)))
+	if (((uintptr_t)samples & 15u) || channel_stride % (16 / sd_sample_bytes(b->input_kind)))
 		return fail("sonde_batch_submit: samples must be 16-byte aligned and channel_stride a multiple of 2 (IQ) / 4 (real, 16-bit IQ) / 8 (8-bit IQ) samples");
 	return submit_impl(b, samples, n_samples, channel_stride, stream_, nullptr);
 }
@@ -636,7 +636,6 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 	b->n_submits++;
 	hipEvent_t *ev = b->ev + 3 * (b->ev_used % SondeBatch::kEvSlots);
 	if (timed) HIPCHK(hipEventRecord(ev[0], stream));
-	const int iq = (b->input_kind == SONDE_INPUT_IQ ? SD_IN_IQ : (b->input_kind == SONDE_INPUT_IQ16 ? SD_IN_IQ16 : (b->input_kind == SONDE_INPUT_IQ8 ? SD_IN_IQ8 : SD_IN_REAL)));      // what the rows hold
 	const int slot = (int)(b->tickets & 1);
 	SondeFrame *const d_frames = b->d_frames2[slot];
 	uint32_t *const d_counts = b->d_counts2[slot];
@@ -680,7 +679,7 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 	if (!one_launch) { total_wg = 0; for (const SondeBatch::Unit &u : b->units) total_wg += u.n; }
 	int max_seg = 1;
 	auto slice_of = [&](uint32_t n_wg, int tiles, SdSlice &sl, int decim, int nt) -> const SdSlice * {
-		if (!sd_slices_supported(iq, decim, nt)) return nullptr;
+		if (!sd_slices_supported(b->input_kind, decim, nt)) return nullptr;
 		// the library slices by itself only a submit that is ONE launch: the no-deadlock argument of launch.h (a segment's predecessor
 		// has a lower block index of the same grid) is about one grid; several sliced grids side by side (launch units) run only when
 		// SondeBatchConfig.time_slices asks for them (tests), under the poll's give-up guard
@@ -694,7 +693,7 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 		return &sl;
 	};
 	if (b->mixed_one && !bins_in) {
-		sd_launch_demod_mixed(iq, b->n_cls[2], b->d_cls[2], b->cls_type[2], b->n_cls[3], b->d_cls[3], b->cls_type[3], stream, (const float *)samples, channel_stride,
+		sd_launch_demod_mixed(b->input_kind, b->n_cls[2], b->d_cls[2], b->cls_type[2], b->n_cls[3], b->d_cls[3], b->cls_type[3], stream, (const float *)samples, channel_stride,
 			n_tiles, b->d_states, b->d_hist, b->d_bitring, b->ring_words, b->d_taps, b->d_modems, fo);
 		HIPCHK(hipGetLastError());
 		if (timed) HIPCHK(hipEventRecord(ev[1], stream));
@@ -704,7 +703,7 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 				b->d_states, b->d_hist, b->d_bitring, b->ring_words, b->d_taps, b->h_modems, &b->h_fo2[slot], bins_in->g_comp, b->cls_type[b->only_class]);
 		else {
 			SdSlice sl;
-			sd_launch_demod(iq, k_cls_decim[b->only_class], k_cls_nt[b->only_class], b->n_channels, stream, (const float *)samples, channel_stride, n_tiles,
+			sd_launch_demod(b->input_kind, k_cls_decim[b->only_class], k_cls_nt[b->only_class], b->n_channels, stream, (const float *)samples, channel_stride, n_tiles,
 				b->d_states, b->d_hist, b->d_bitring, b->ring_words, b->d_taps, b->d_modems, nullptr, false, fo, b->cls_type[b->only_class],
 				slice_of(b->n_channels, n_tiles, sl, k_cls_decim[b->only_class], k_cls_nt[b->only_class]));
 		}
@@ -726,13 +725,13 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 				// AFSK channels: tone demodulator into 6 kS/s scratch rows, then kernel A's real-input path over those rows
 				// (one kernel-A tile = 2048 scratch samples = 16384 input samples)
 				float *rows = b->d_afq + u.row0 * (size_t)(b->max_samples / SD_AF_DEC);
-				sd_launch_afsk(u.type, iq == SD_IN_IQ ? 1 : (iq == SD_IN_IQ16 ? 2 : (iq == SD_IN_IQ8 ? 3 : 0)), u.n, u.st, (const float *)samples, channel_stride, n_tiles,
+				sd_launch_afsk(u.type, b->input_kind, u.n, u.st, (const float *)samples, channel_stride, n_tiles,
 					b->d_chlist[u.type], b->d_astates, u.type == SONDE_C50 ? b->d_wtab_c50 : b->d_wtab, rows, nq);
-				sd_launch_demod(SD_IN_REAL, 1, 16, u.n, u.st, rows, nq, (int)(nq / SONDE_TILE),
+				sd_launch_demod(SONDE_INPUT_REAL, 1, 16, u.n, u.st, rows, nq, (int)(nq / SONDE_TILE),
 					b->d_states, b->d_hist, b->d_bitring, b->ring_words, b->d_taps, b->d_modems, b->d_chlist[u.type], true, fo, u.type);
 			} else {
 				SdSlice sl;
-				sd_launch_demod(iq, k_cls_decim[u.cls], k_cls_nt[u.cls], u.n, u.st, (const float *)samples, channel_stride, n_tiles,
+				sd_launch_demod(b->input_kind, k_cls_decim[u.cls], k_cls_nt[u.cls], u.n, u.st, (const float *)samples, channel_stride, n_tiles,
 					b->d_states, b->d_hist, b->d_bitring, b->ring_words, b->d_taps, b->d_modems,
 					u.type < 0 ? b->d_cls[u.cls] : b->d_chlist[u.type] + u.off, false, fo, u.type < 0 ? b->cls_type[u.cls] : u.type,
 					slice_of(u.n, n_tiles, sl, k_cls_decim[u.cls], k_cls_nt[u.cls]));
@@ -814,7 +813,7 @@ extern "C" int sonde_batch_launch_info(const SondeBatch *b, uint32_t *n_units, i
 // than the contiguous layout: how the rows that are in flight together spread over the HBM channels.
 extern "C" size_t sonde_sample_bytes(int input_kind)
 {
-	return input_kind == SONDE_INPUT_IQ ? 2 * sizeof(float) : (input_kind == SONDE_INPUT_IQ16 ? 2 * sizeof(int16_t) : (input_kind == SONDE_INPUT_IQ8 ? 2 * sizeof(int8_t) : sizeof(float)));
+	return sd_sample_bytes(input_kind);
 }
 
 extern "C" size_t sonde_row_stride(size_t n_samples, int input_kind)

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include "sonde_dev.h"
+#include "sd_input.h"
 #include "sd_math.h"
 #include "sd_wave.h"
 #include "sd_rs41.h"
@@ -151,8 +152,8 @@ __global__ __launch_bounds__(64 * BK_WAVES, 4) void sd_bins_kernel(
 			const uint32_t e3 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, p.w) - __builtin_bit_cast(u16x2, x3));
 			if (lane < 42) {
 				float4 *dst = reinterpret_cast<float4 *>(&w.d[8 * lane]);
-				dst[0] = make_float4((float)(int16_t)(e0 & 0xffffu), (float)((int32_t)e0 >> 16), (float)(int16_t)(e1 & 0xffffu), (float)((int32_t)e1 >> 16));
-				dst[1] = make_float4((float)(int16_t)(e2 & 0xffffu), (float)((int32_t)e2 >> 16), (float)(int16_t)(e3 & 0xffffu), (float)((int32_t)e3 >> 16));
+				dst[0] = sd_cs16_f4(make_uint2(e0, e1));
+				dst[1] = sd_cs16_f4(make_uint2(e2, e3));
 			}
 		}
 		WAVE_SYNC();

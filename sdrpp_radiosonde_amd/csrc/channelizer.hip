@@ -18,6 +18,7 @@
 #include <vector>
 #include "sd_math.h"
 #include "sonde_dev.h"
+#include "sd_input.h"
 #include "../../include/sonde_abi.h"
 #include "launch.h"
 
@@ -169,9 +170,9 @@ __device__ __forceinline__ void pfb_fft512n(float2 *fb, const float2 w64 /* tw[6
 	for (int j = 0; j < 4; j++) pfb_bfly(e[j], e[j + 4], t.c3[j]);
 }
 
-// I16: the wideband stream (and the carried history) as 16-bit integer I, Q pairs -- what a 10 MS/s receiver delivers -- converted on
-// the way into LDS (exactly, no scaling: a phase does not see the amplitude); everything behind the window is the float path
-// (IK: 0 complex64, 1 int16 pairs, 2 int8 pairs -- a 10 MS/s 8-bit receiver's format)
+// IK: what the wideband stream (and the carried history) holds: SONDE_INPUT_IQ, or 16- / 8-bit integer I, Q pairs (IQ16, IQ8) -- what a
+// 10 MS/s receiver delivers -- converted on the way into the fold (exactly, no scaling: a phase does not see the amplitude; sd_input.h);
+// everything behind the window is the float path
 template <int IK>
 __global__ __launch_bounds__(P_NT, 6) void sd_pfb_kernel(const void *__restrict__ iq_all_, size_t stream_stride,
                                                            const void *__restrict__ hist_in_all_, void *__restrict__ hist_out_all_,
@@ -209,9 +210,8 @@ __global__ __launch_bounds__(P_NT, 6) void sd_pfb_kernel(const void *__restrict_
 	const bool odd = dual && (sidx & 1u);
 	const uint32_t phys = dual ? sidx >> 1 : sidx;
 	const float *h = odd ? h_odd : h_even;
-	constexpr bool I16 = IK == 1, I8 = IK == 2;
-	using ET = typename std::conditional<I8, uint16_t, typename std::conditional<I16, uint32_t, float2>::type>::type;       // one complex sample
-	using PT = typename std::conditional<I8, uint32_t, typename std::conditional<I16, uint2, float4>::type>::type;          // a pair of them (the history copy)
+	using ET = sd_iq_t<IK>;                   // one complex sample; PT: a pair of them (the history copy)
+	using PT = typename std::conditional<IK == SONDE_INPUT_IQ8, uint32_t, typename std::conditional<IK == SONDE_INPUT_IQ16, uint2, float4>::type>::type;
 	const ET *iq = reinterpret_cast<const ET *>(iq_all_) + (size_t)phys * stream_stride;
 	const ET *hist_in = reinterpret_cast<const ET *>(hist_in_all_) + (size_t)phys * CH_H;
 	ET *hist_out_all = reinterpret_cast<ET *>(hist_out_all_);
@@ -255,11 +255,6 @@ __global__ __launch_bounds__(P_NT, 6) void sd_pfb_kernel(const void *__restrict_
 	__syncthreads();
 	P_STAMP(2);
 	// 2. fold (SPEC 3.5: v[r] = sum_t fmaf(h[r+512t], x[r+512t], acc), t ascending)
-	auto sample = [&](int k) -> float2 {
-		if constexpr (I8) return make_float2((float)(int8_t)(xr[k] & 0xffu), (float)(int8_t)(xr[k] >> 8));
-		else if constexpr (I16) return make_float2((float)(int16_t)(xr[k] & 0xffffu), (float)((int32_t)xr[k] >> 16));
-		else return xr[k];
-	};
 	float2 v[P_S];
 #pragma unroll
 	for (int q = 0; q < P_S; q++) v[q] = make_float2(0.0f, 0.0f);
@@ -291,7 +286,7 @@ __global__ __launch_bounds__(P_NT, 6) void sd_pfb_kernel(const void *__restrict_
 #pragma unroll
 		for (int k = 0; k < P_NS; k++) {
 			taps_of(k, hk, he);                                  // (no software prefetch of the next sample's taps: at six waves per SIMD the
-			const float2 xv = sample(k);                          // other waves cover the LDS latency, and the 9 registers are the difference to spilling)
+			const float2 xv = sd_iq_f2<IK>(xr[k]);                // other waves cover the LDS latency, and the 9 registers are the difference to spilling)
 			if (edge && k + 1 < P_S) {                           // d = -1 comes first in q = k + 1's sum
 				const int q = k + 1;
 				const bool ok = c + (CH_M - CH_D) * q >= CH_M;
@@ -636,13 +631,13 @@ static bool chan_overlap_setup(SondeChannelizer *c)
 	return ok;
 }
 
-// What the wideband block holds: SONDE_INPUT_IQ (complex64, the default) or SONDE_INPUT_IQ16 (int16 I, int16 Q: what a 10 MS/s
-// receiver delivers; half the bytes to move).  Before the first submit only (the carried window is kept in the input's format).
-// Returns the kind in force, or -1.
+// What the wideband block holds: SONDE_INPUT_IQ (complex64, the default), SONDE_INPUT_IQ16 (int16 I, int16 Q: what a 10 MS/s
+// receiver delivers; half the bytes to move) or SONDE_INPUT_IQ8 (int8 pairs).  Before the first submit only (the carried window is
+// kept in the input's format).  Returns the kind in force, or -1.
 extern "C" int sonde_chan_set_input(SondeChannelizer *c, int input_kind)
 {
 	if (!c) return -1;
-	if (c->n_blocks == 0 && (input_kind == SONDE_INPUT_IQ || input_kind == SONDE_INPUT_IQ16 || input_kind == SONDE_INPUT_IQ8)) c->input_kind = input_kind;
+	if (c->n_blocks == 0 && sd_input_known(input_kind) && input_kind != SONDE_INPUT_REAL) c->input_kind = input_kind;
 	return c->input_kind;
 }
 
@@ -651,12 +646,11 @@ static void launch_pfb(SondeChannelizer *c, hipStream_t st, const void *iq_dev, 
 	const dim3 g(c->n_steps / P_S, c->n_streams), blk(P_NT);
 	const void *hin = c->d_hist[c->n_blocks & 1];
 	void *hout = c->d_hist[(c->n_blocks + 1) & 1];
-	if (c->input_kind == SONDE_INPUT_IQ8)
-		hipLaunchKernelGGL(sd_pfb_kernel<2>, g, blk, 0, st, iq_dev, n_samples, hin, hout, c->d_h, c->d_tw, bins, c->n_steps, c->xcd_map, c->dual, c->d_h_odd, c->d_twist);
-	else if (c->input_kind == SONDE_INPUT_IQ16)
-		hipLaunchKernelGGL(sd_pfb_kernel<1>, g, blk, 0, st, iq_dev, n_samples, hin, hout, c->d_h, c->d_tw, bins, c->n_steps, c->xcd_map, c->dual, c->d_h_odd, c->d_twist);
-	else
-		hipLaunchKernelGGL(sd_pfb_kernel<0>, g, blk, 0, st, iq_dev, n_samples, hin, hout, c->d_h, c->d_tw, bins, c->n_steps, c->xcd_map, c->dual, c->d_h_odd, c->d_twist);
+	sd_input_dispatch(c->input_kind, [&](auto k) {
+		if constexpr (decltype(k)::value != SONDE_INPUT_REAL)      // (sonde_chan_set_input refuses REAL)
+			hipLaunchKernelGGL(sd_pfb_kernel<decltype(k)::value>, g, blk, 0, st, iq_dev, n_samples, hin, hout, c->d_h, c->d_tw, bins, c->n_steps, c->xcd_map, c->dual,
+				c->d_h_odd, c->d_twist);
+	});
 }
 
 extern "C" uint32_t sonde_chan_samples_per_submit(const SondeChannelizer *c) { return c ? c->n_steps * CH_D : 0; }

@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "sonde_dev.h"
-
+#include "sd_input.h"
 #include "sd_math.h"
 #include "sd_wave.h"
 #include "sd_rs41.h"
@@ -30,51 +30,11 @@
 typedef float sd_f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned sd_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned sd_u32x4 __attribute__((ext_vector_type(4)));
-typedef short sd_i16x2 __attribute__((ext_vector_type(2)));
-// SD_IN_IQ8: two complex samples of 8-bit integers (I0 Q0 I1 Q1) -> the float4 of the float path (exact, no scaling)
-static __device__ __forceinline__ float4 sd_cs8_f4(uint32_t q)
-{
-	return make_float4((float)(int8_t)(q & 0xffu), (float)(int8_t)((q >> 8) & 0xffu), (float)(int8_t)((q >> 16) & 0xffu), (float)((int32_t)q >> 24));
-}
-// SPEC 3.0d: the two half-sums of a group of four, (samples 0 + 1, samples 2 + 3), each exact in integers: (P0.re, P0.im, P1.re, P1.im)
-static __device__ __forceinline__ float4 sd_cs16_halves(uint4 q)
-{
-	const sd_i16x2 lo = {1, 0}, hi = {0, 1};
-	int a = 0, b = 0, c = 0, d = 0;
-	a = __builtin_amdgcn_sdot2(__builtin_bit_cast(sd_i16x2, q.x), lo, a, false); b = __builtin_amdgcn_sdot2(__builtin_bit_cast(sd_i16x2, q.x), hi, b, false);
-	a = __builtin_amdgcn_sdot2(__builtin_bit_cast(sd_i16x2, q.y), lo, a, false); b = __builtin_amdgcn_sdot2(__builtin_bit_cast(sd_i16x2, q.y), hi, b, false);
-	c = __builtin_amdgcn_sdot2(__builtin_bit_cast(sd_i16x2, q.z), lo, c, false); d = __builtin_amdgcn_sdot2(__builtin_bit_cast(sd_i16x2, q.z), hi, d, false);
-	c = __builtin_amdgcn_sdot2(__builtin_bit_cast(sd_i16x2, q.w), lo, c, false); d = __builtin_amdgcn_sdot2(__builtin_bit_cast(sd_i16x2, q.w), hi, d, false);
-	return make_float4((float)a, (float)b, (float)c, (float)d);
-}
-static __device__ __forceinline__ float4 sd_cs8_halves(uint2 q)
-{
-	int a = 0, b = 0, c = 0, d = 0;
-	a = __builtin_amdgcn_sdot4((int)q.x, 0x00010001, a, false); b = __builtin_amdgcn_sdot4((int)q.x, 0x01000100, b, false);
-	c = __builtin_amdgcn_sdot4((int)q.y, 0x00010001, c, false); d = __builtin_amdgcn_sdot4((int)q.y, 0x01000100, d, false);
-	return make_float4((float)a, (float)b, (float)c, (float)d);
-}
-static __device__ __forceinline__ float4 sd_cs16_halves_uniform(uint4 q)
-{
-	return make_float4((float)((int)(int16_t)(q.x & 0xffffu) + (int)(int16_t)(q.y & 0xffffu)), (float)(((int32_t)q.x >> 16) + ((int32_t)q.y >> 16)),
-	                   (float)((int)(int16_t)(q.z & 0xffffu) + (int)(int16_t)(q.w & 0xffffu)), (float)(((int32_t)q.z >> 16) + ((int32_t)q.w >> 16)));
-}
-static __device__ __forceinline__ float4 sd_cs8_halves_uniform(uint2 q)
-{
-	return make_float4((float)((int)(int8_t)(q.x & 0xffu) + (int)(int8_t)((q.x >> 16) & 0xffu)), (float)((int)(int8_t)((q.x >> 8) & 0xffu) + ((int32_t)q.x >> 24)),
-	                   (float)((int)(int8_t)(q.y & 0xffu) + (int)(int8_t)((q.y >> 16) & 0xffu)), (float)((int)(int8_t)((q.y >> 8) & 0xffu) + ((int32_t)q.y >> 24)));
-}
 // SPEC 3.0d, the carrier-following boxcar: z = P0 + R P1, R = (rr, ri) = (1 - u^2 / 2, -u): the second half of a group turned back by
 // about atan u before it is added (oracle or_demod_feed)
 static __device__ __forceinline__ float2 sd_follow(float p0r, float p0i, float p1r, float p1i, float rr, float ri)
 {
 	return make_float2(p0r + __builtin_fmaf(-p1i, ri, p1r * rr), p0i + __builtin_fmaf(p1r, ri, p1i * rr));
-}
-// SD_IN_IQ16: two complex samples of 16-bit integers (I0 Q0 I1 Q1, little endian) -> the float4 the float path would have loaded
-// (int16 -> float is exact; no scaling: the discriminator's output does not depend on the amplitude)
-static __device__ __forceinline__ float4 sd_cs16_f4(uint2 q)
-{
-	return make_float4((float)(int16_t)(q.x & 0xffffu), (float)((int32_t)q.x >> 16), (float)(int16_t)(q.y & 0xffffu), (float)((int32_t)q.y >> 16));
 }
 
 // ---- carried per-channel data (state, history, bit-ring words, framer state, frame count).  In a time-sliced launch (launch.h SdSlice)
@@ -189,8 +149,8 @@ static __device__ __attribute__((noinline)) void sd_rs41_decode_frame_call(const
 // factor and the taps per filter row of every channel of this launch (the host launches once per class), so that the
 // discriminator and FIR variants do not share one register allocation.  Classes in use: (4, 8) RS41 / DFM / iMS-100 / MRZ-N1,
 // (2, 8) M10, (2, 16) and (1, 16) the same two groups under SONDE_FLAG_WIDE, (1, 16) also the 6 kS/s AFSK streams.
-// IN: what `in` holds per channel: SD_IN_REAL 48 kS/s discriminator samples, SD_IN_IQ 48 kS/s complex samples, SD_IN_IQ16 / SD_IN_IQ8 the
-// same as 16- / 8-bit integer pairs.  (Channelizer bins have their own kernel: bins_kernel.hip, one wave per bin.)
+// IN: what `in` holds per channel, a SONDE_INPUT_* kind (sd_input.h): 48 kS/s discriminator samples, complex samples, or the same as
+// 16- / 8-bit integer pairs.  (Channelizer bins have their own kernel: bins_kernel.hip, one wave per bin.)
 // The kernel's BODY, a device function so that two classes can share one launch (sd_demod_mixed_kernel below): bidx = the workgroup's
 // index in ITS launch (or in its class's share of a mixed launch), grid_wg = the workgroups that share the GPU with it (the in-loop FEC's
 // one-residency test), s = the workgroup's LDS (declared once, by the __global__ wrapper).
@@ -204,8 +164,8 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 	const float *__restrict__ taps_all, const SdModem *__restrict__ modems,
 	const uint32_t *__restrict__ chlist, int compact_in, const SdFramerOut *__restrict__ fo, int utype, const SdSlice sl)
 {
-	// integer IQ rows: IQ16 = int16 pairs (SD_IN_IQ16) OR int8 pairs (SD_IN_IQ8): one code path, IQ8 picks the element size
-	constexpr bool IQ8 = IN == SD_IN_IQ8, IQ16 = IN == SD_IN_IQ16 || IQ8, IS_IQ = IN == SD_IN_IQ || IQ16;
+	// integer IQ rows: IQ16 = int16 pairs OR int8 pairs: one code path, IQ8 picks the element size
+	constexpr bool IQ8 = IN == SONDE_INPUT_IQ8, IQ16 = IN == SONDE_INPUT_IQ16 || IQ8, IS_IQ = IN == SONDE_INPUT_IQ || IQ16;
 	constexpr bool IQ16D4 = IQ16 && DEC == 4;                                 // one load of four samples = one decimated sample each (16 bytes; int8: 8)
 	// what one lane holds per load: two input samples (IQ; four in the integer 4:1 classes), four (real)
 	using LoadT = typename std::conditional<IQ8, typename std::conditional<IQ16D4, uint2, uint32_t>::type,
@@ -227,10 +187,10 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 	const uint32_t row = (LIST && compact_in) ? wgi : ch;              // row of `in`
 
 	// ---- discriminator waves: the first two tiles' loads go out before anything else (see the prologue note below)
-	constexpr int NLD = (IS_IQ && !IQ16D4) ? 4 : 2;     // loads per thread per tile (float4; SD_IN_IQ16: 8 bytes, the same two samples, or 16 bytes, four)
+	constexpr int NLD = (IS_IQ && !IQ16D4) ? 4 : 2;     // loads per thread per tile (float4; 16-bit IQ: 8 bytes, the same two samples, or 16 bytes, four)
 	constexpr int TILE_F4 = ((IS_IQ && !IQ16D4) ? 2 : 1) * SD_TILE / 4;      // load units (LoadT) per tile
-	// (ch_stride counts samples: 8 bytes each for complex64, 4 for real input and for 16-bit IQ)
-	const LoadT *src = reinterpret_cast<const LoadT *>(reinterpret_cast<const char *>(in) + (size_t)row * ch_stride * (IQ8 ? 2 : ((IS_IQ && !IQ16) ? 8 : 4)))
+	// (ch_stride counts samples)
+	const LoadT *src = reinterpret_cast<const LoadT *>(reinterpret_cast<const char *>(in) + (size_t)row * ch_stride * sd_sample_bytes(IN))
 	                   + (sliced ? (size_t)seg * (size_t)sl.seg_tiles * TILE_F4 : 0);
 	LoadT va[NLD], vb[NLD];                // two register sets: tiles are prefetched two phases ahead
 	// Work split: wave kw of the four owns 256 consecutive float4s of the tile, load r covers 64 of them, so
@@ -289,7 +249,7 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 	if (utype >= 0) stype = utype;
 	else stype = __builtin_amdgcn_readfirstlane(st.type);
 	const SdModem md = modems[stype];
-	constexpr bool AF = IN == SD_IN_REAL && DEC == 1;                  // the instantiation the 6 kS/s AFSK streams run through
+	constexpr bool AF = IN == SONDE_INPUT_REAL && DEC == 1;            // the instantiation the 6 kS/s AFSK streams run through
 	const bool afsk = AF && (stype == SONDE_IMET4 || stype == SONDE_C50);
 	const int rounds = md.rounds;          // sub-phases (= barriers) per tile: 1, or 2 for the SRS-C50 6 kS/s stream
 	constexpr int IT = SD_TILE / DEC;      // internal samples per input tile (= md.itile)
@@ -457,19 +417,10 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 			return;
 		}
 		float4 v[NLD], pv, pw;
-		if constexpr (IQ16D4) {
-		} else if constexpr (IQ8) {
+		if constexpr (!IQ16D4) {
 #pragma unroll
-			for (int r = 0; r < NLD; r++) v[r] = sd_cs8_f4(vraw[r]);
-			pv = sd_cs8_f4(pvraw); pw = sd_cs8_f4(pwraw);
-		} else if constexpr (IQ16) {
-#pragma unroll
-			for (int r = 0; r < NLD; r++) v[r] = sd_cs16_f4(vraw[r]);
-			pv = sd_cs16_f4(pvraw); pw = sd_cs16_f4(pwraw);
-		} else {
-#pragma unroll
-			for (int r = 0; r < NLD; r++) v[r] = vraw[r];
-			pv = pvraw; pw = pwraw;
+			for (int r = 0; r < NLD; r++) v[r] = sd_iq_f4<IN>(vraw[r]);
+			pv = sd_iq_f4<IN>(pvraw); pw = sd_iq_f4<IN>(pwraw);
 		}
 		// lane 0's predecessor (decimated) sample; after each load: lane 63's last sample
 		float cx = pv.z, cy = pv.w;
@@ -971,18 +922,15 @@ void sd_launch_demod_mixed(int in_kind, uint32_t n_a, const uint32_t *list_a, in
 	const float *in, size_t ch_stride, int n_tiles, SdChanState *states, float *hist, uint32_t *bitring, uint32_t ring_words,
 	const float *taps_all, const SdModem *modems, const SdFramerOut *fo)
 {
-	const dim3 g(n_a + n_b), blk(SD_WGT);
-#define SD_MIXED_ARGS in, ch_stride, n_tiles, states, hist, bitring, ring_words, taps_all, modems, list_a, n_a, utype_a, list_b, n_b, utype_b, fo
-	if (in_kind == SD_IN_IQ8) hipLaunchKernelGGL((sd_demod_mixed_kernel<SD_IN_IQ8>), g, blk, 0, stream, SD_MIXED_ARGS);
-	else if (in_kind == SD_IN_IQ16) hipLaunchKernelGGL((sd_demod_mixed_kernel<SD_IN_IQ16>), g, blk, 0, stream, SD_MIXED_ARGS);
-	else if (in_kind == SD_IN_IQ) hipLaunchKernelGGL((sd_demod_mixed_kernel<SD_IN_IQ>), g, blk, 0, stream, SD_MIXED_ARGS);
-	else hipLaunchKernelGGL((sd_demod_mixed_kernel<SD_IN_REAL>), g, blk, 0, stream, SD_MIXED_ARGS);
-#undef SD_MIXED_ARGS
+	sd_input_dispatch(in_kind, [&](auto kind) {
+		hipLaunchKernelGGL((sd_demod_mixed_kernel<decltype(kind)::value>), dim3(n_a + n_b), dim3(SD_WGT), 0, stream,
+			in, ch_stride, n_tiles, states, hist, bitring, ring_words, taps_all, modems, list_a, n_a, utype_a, list_b, n_b, utype_b, fo);
+	});
 }
 
 bool sd_slices_supported(int in_kind, int decim, int nt)
 {
-	return (in_kind == SD_IN_IQ || in_kind == SD_IN_IQ16 || in_kind == SD_IN_IQ8) && nt == 8 && (decim == 4 || decim == 2);
+	return (in_kind == SONDE_INPUT_IQ || in_kind == SONDE_INPUT_IQ16 || in_kind == SONDE_INPUT_IQ8) && nt == 8 && (decim == 4 || decim == 2);
 }
 
 void sd_launch_demod(int in_kind, int decim, int nt, uint32_t n_channels, hipStream_t stream,
@@ -990,38 +938,32 @@ void sd_launch_demod(int in_kind, int decim, int nt, uint32_t n_channels, hipStr
 	uint32_t *bitring, uint32_t ring_words, const float *taps_all, const SdModem *modems,
 	const uint32_t *chlist, bool compact_in, const SdFramerOut *fo /* device memory */, int utype, const SdSlice *slice)
 {
-	SdSlice sl = { 1, n_tiles, n_channels, 0u, nullptr, 0u };
+	// the time-sliced instantiations: the two default classes, IQ input of every kind (the classes BASELINE's configurations run)
+	const bool sliced = slice && slice->n_seg > 1 && sd_slices_supported(in_kind, decim, nt);
+	const SdSlice sl = sliced ? *slice : SdSlice{ 1, n_tiles, n_channels, 0u, nullptr, 0u };
 	const int ci = compact_in ? 1 : 0;
-#define SD_DEMOD_ARGS in, ch_stride, n_tiles, states, hist, bitring, ring_words, taps_all, modems, chlist, ci, fo, utype, sl
-	if (slice && slice->n_seg > 1 && sd_slices_supported(in_kind, decim, nt)) {
-		// the time-sliced instantiations: the two default classes, IQ input of every kind (the classes BASELINE's configurations run)
-		sl = *slice;
-		const dim3 gs(n_channels * (uint32_t)sl.n_seg), blks(SD_WGT);
-#define SD_SLICED_LAUNCH(KIND) do { \
-		if (decim == 4 && chlist) hipLaunchKernelGGL((sd_demod_kernel<KIND, true, 4, 8, true>), gs, blks, 0, stream, SD_DEMOD_ARGS); \
-		else if (decim == 4) hipLaunchKernelGGL((sd_demod_kernel<KIND, false, 4, 8, true>), gs, blks, 0, stream, SD_DEMOD_ARGS); \
-		else if (chlist) hipLaunchKernelGGL((sd_demod_kernel<KIND, true, 2, 8, true>), gs, blks, 0, stream, SD_DEMOD_ARGS); \
-		else hipLaunchKernelGGL((sd_demod_kernel<KIND, false, 2, 8, true>), gs, blks, 0, stream, SD_DEMOD_ARGS); } while (0)
-		if (in_kind == SD_IN_IQ8) SD_SLICED_LAUNCH(SD_IN_IQ8);
-		else if (in_kind == SD_IN_IQ16) SD_SLICED_LAUNCH(SD_IN_IQ16);
-		else SD_SLICED_LAUNCH(SD_IN_IQ);
-#undef SD_SLICED_LAUNCH
-		return;
-	}
-	const dim3 g(n_channels), blk(SD_WGT);
-#define SD_DEMOD_LAUNCH(KIND, LS) do { \
-		if (decim == 4) hipLaunchKernelGGL((sd_demod_kernel<KIND, LS, 4, 8>), g, blk, 0, stream, SD_DEMOD_ARGS); \
-		else if (decim == 2 && nt == 8) hipLaunchKernelGGL((sd_demod_kernel<KIND, LS, 2, 8>), g, blk, 0, stream, SD_DEMOD_ARGS); \
-		else if (decim == 2) hipLaunchKernelGGL((sd_demod_kernel<KIND, LS, 2, 16>), g, blk, 0, stream, SD_DEMOD_ARGS); \
-		else hipLaunchKernelGGL((sd_demod_kernel<KIND, LS, 1, 16>), g, blk, 0, stream, SD_DEMOD_ARGS); } while (0)
-	if (in_kind == SD_IN_IQ8 && !chlist) SD_DEMOD_LAUNCH(SD_IN_IQ8, false);
-	else if (in_kind == SD_IN_IQ8) SD_DEMOD_LAUNCH(SD_IN_IQ8, true);
-	else if (in_kind == SD_IN_IQ16 && !chlist) SD_DEMOD_LAUNCH(SD_IN_IQ16, false);
-	else if (in_kind == SD_IN_IQ16) SD_DEMOD_LAUNCH(SD_IN_IQ16, true);
-	else if (in_kind == SD_IN_IQ && !chlist) SD_DEMOD_LAUNCH(SD_IN_IQ, false);
-	else if (in_kind == SD_IN_IQ) SD_DEMOD_LAUNCH(SD_IN_IQ, true);
-	else if (!chlist) SD_DEMOD_LAUNCH(SD_IN_REAL, false);
-	else SD_DEMOD_LAUNCH(SD_IN_REAL, true);
+	const dim3 g(n_channels * (uint32_t)sl.n_seg), blk(SD_WGT);
+#define SD_DEMOD_LAUNCH(...) hipLaunchKernelGGL((sd_demod_kernel<__VA_ARGS__>), g, blk, 0, stream, \
+		in, ch_stride, n_tiles, states, hist, bitring, ring_words, taps_all, modems, chlist, ci, fo, utype, sl)
+#define SD_CLASS_LAUNCH(IN, LS) do { \
+		if (decim == 4) SD_DEMOD_LAUNCH(IN, LS, 4, 8); \
+		else if (decim == 2 && nt == 8) SD_DEMOD_LAUNCH(IN, LS, 2, 8); \
+		else if (decim == 2) SD_DEMOD_LAUNCH(IN, LS, 2, 16); \
+		else SD_DEMOD_LAUNCH(IN, LS, 1, 16); } while (0)
+	sd_input_dispatch(in_kind, [&](auto kind) {
+		constexpr int IN = decltype(kind)::value;
+		if constexpr (IN != SONDE_INPUT_REAL) {
+			if (sliced) {
+				if (decim == 4 && chlist) SD_DEMOD_LAUNCH(IN, true, 4, 8, true);
+				else if (decim == 4) SD_DEMOD_LAUNCH(IN, false, 4, 8, true);
+				else if (chlist) SD_DEMOD_LAUNCH(IN, true, 2, 8, true);
+				else SD_DEMOD_LAUNCH(IN, false, 2, 8, true);
+				return;
+			}
+		}
+		if (chlist) SD_CLASS_LAUNCH(IN, true);
+		else SD_CLASS_LAUNCH(IN, false);
+	});
+#undef SD_CLASS_LAUNCH
 #undef SD_DEMOD_LAUNCH
-#undef SD_DEMOD_ARGS
 }

@@ -16,6 +16,7 @@
 #include <string.h>
 #include <vector>
 #include "sonde_dev.h"
+#include "sd_input.h"
 #include "sd_math.h"
 #include "sd_rs41.h"
 #include "sd_fixed.h"
@@ -111,13 +112,8 @@ __device__ __forceinline__ int32_t dt_qz(float v)
 	return (int32_t)__builtin_rintf(v * DT_QSCALE);
 }
 
-template <int KIND>      // 1 complex64, 2 int16 pairs, 3 int8 pairs: converted exactly, no scaling (SPEC 3.0c)
-__device__ __forceinline__ float2 dt_iq(const void *row, int64_t i)
-{
-	if (KIND == 2) { const uint32_t q = reinterpret_cast<const uint32_t *>(row)[i]; return make_float2((float)(int16_t)(q & 0xffffu), (float)((int32_t)q >> 16)); }
-	if (KIND == 3) { const uint16_t q = reinterpret_cast<const uint16_t *>(row)[i]; return make_float2((float)(int8_t)(q & 0xffu), (float)(int8_t)(q >> 8)); }
-	return reinterpret_cast<const float2 *>(row)[i];
-}
+template <int KIND>      // sample i of a row of an IQ kind (sd_input.h)
+__device__ __forceinline__ float2 dt_iq(const void *row, int64_t i) { return sd_iq_f2<KIND>(reinterpret_cast<const sd_iq_t<KIND> *>(row)[i]); }
 
 struct DtLds {
 	uint32_t P[DT_E + 1];
@@ -230,7 +226,7 @@ __device__ __forceinline__ void dt_scan(DtLds &s, const int32_t *row, int H, uin
 	__syncthreads();
 }
 
-template <int KIND>      // 0 real, 1 complex64, 2 int16 pairs, 3 int8 pairs
+template <int KIND>      // what the rows hold (SONDE_INPUT_*)
 __global__ __launch_bounds__(DT_WG) void sd_detect_kernel(
 	const void *__restrict__ in, size_t row_bytes, uint32_t n, SdDetState *__restrict__ states,
 	int32_t *__restrict__ dD, size_t rowD, int32_t *__restrict__ dA, size_t rowA,
@@ -250,7 +246,7 @@ __global__ __launch_bounds__(DT_WG) void sd_detect_kernel(
 	const float2 y_prev = st->y_prev;
 	for (uint32_t m = tid; m < n2; m += DT_WG) {
 		float d;
-		if (KIND == 0) {
+		if (KIND == SONDE_INPUT_REAL) {
 			const float *r = reinterpret_cast<const float *>(row);
 			d = r[2 * m] + r[2 * m + 1];
 		} else {
@@ -271,7 +267,7 @@ __global__ __launch_bounds__(DT_WG) void sd_detect_kernel(
 	for (uint32_t tile = 0; tile < n / SD_TILE; tile++) {
 		const uint32_t s0 = tile * SD_TILE + 8u * (uint32_t)tid;
 		float d[8];
-		if (KIND == 0) {
+		if (KIND == SONDE_INPUT_REAL) {
 #pragma unroll
 			for (int i = 0; i < 8; i++) d[i] = reinterpret_cast<const float *>(row)[s0 + i];
 		} else {
@@ -370,7 +366,7 @@ __global__ __launch_bounds__(DT_WG) void sd_detect_kernel(
 	if (tid < 2) st->bc[tid] = s.bc[tid];
 	if (tid == 0) {
 		st->n = n_abs + n;
-		if (KIND != 0) {
+		if (KIND != SONDE_INPUT_REAL) {
 			const float2 a = dt_iq<KIND>(row, (int64_t)n - 2), b = dt_iq<KIND>(row, (int64_t)n - 1);
 			st->y_prev = make_float2(a.x + b.x, a.y + b.y);
 			st->x_prev = b;
@@ -448,8 +444,7 @@ extern "C" int sonde_detect_create(uint32_t n_channels, uint32_t max_samples, in
 	if (!out) return sd_fail("sonde_detect_create: null argument");
 	*out = nullptr;
 	if (!n_channels || !max_samples || max_samples % SD_TILE) return sd_fail("sonde_detect_create: n_channels must be > 0 and max_samples a positive multiple of SONDE_TILE");
-	if (input_kind != SONDE_INPUT_IQ && input_kind != SONDE_INPUT_REAL && input_kind != SONDE_INPUT_IQ16 && input_kind != SONDE_INPUT_IQ8)
-		return sd_fail("sonde_detect_create: bad input kind");
+	if (!sd_input_known(input_kind)) return sd_fail("sonde_detect_create: bad input kind");
 	int ndev = 0;
 	hipError_t e = hipGetDeviceCount(&ndev);
 	if (e != hipSuccess || device < 0 || device >= ndev) return sd_fail("sonde_detect_create: no such HIP device (this library has no CPU path)", e);
@@ -480,21 +475,15 @@ extern "C" int sonde_detect_submit(SondeDetector *d, const void *samples, size_t
 	if (!d || !samples) return sd_fail("sonde_detect_submit: null argument");
 	if (n_samples == 0 || n_samples % SD_TILE || n_samples > d->max_samples) return sd_fail("sonde_detect_submit: n_samples must be a positive multiple of SONDE_TILE and <= max_samples");
 	if (channel_stride < n_samples) return sd_fail("sonde_detect_submit: channel_stride < n_samples");
-	const size_t eb = sonde_sample_bytes(d->input_kind);
-	if ((uintptr_t)samples % (eb == 8 ? 8 : eb)) return sd_fail("sonde_detect_submit: samples not aligned to the sample size");
+	const size_t eb = sd_sample_bytes(d->input_kind);
+	if ((uintptr_t)samples % eb) return sd_fail("sonde_detect_submit: samples not aligned to the sample size");
 	hipError_t e = hipSetDevice(d->device);
 	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
 	hipStream_t s = (hipStream_t)stream;
-	const dim3 grid(d->n_channels), block(DT_WG);
-#define DT_GO(K) hipLaunchKernelGGL(sd_detect_kernel<K>, grid, block, 0, s, samples, channel_stride * eb, (uint32_t)n_samples, d->d_state, \
-		d->d_D, d->rowD, d->d_A, d->rowA, d->d_wi, d->d_wc)
-	switch (d->input_kind) {
-	case SONDE_INPUT_REAL: DT_GO(0); break;
-	case SONDE_INPUT_IQ: DT_GO(1); break;
-	case SONDE_INPUT_IQ16: DT_GO(2); break;
-	default: DT_GO(3); break;
-	}
-#undef DT_GO
+	sd_input_dispatch(d->input_kind, [&](auto k) {
+		hipLaunchKernelGGL(sd_detect_kernel<decltype(k)::value>, dim3(d->n_channels), dim3(DT_WG), 0, s, samples, channel_stride * eb, (uint32_t)n_samples,
+			d->d_state, d->d_D, d->rowD, d->d_A, d->rowA, d->d_wi, d->d_wc);
+	});
 	if ((e = hipGetLastError()) != hipSuccess) return sd_fail("sd_detect_kernel launch", e);
 	d->last_stream = s;
 	d->last_n = (uint32_t)n_samples;

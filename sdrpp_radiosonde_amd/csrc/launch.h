@@ -41,7 +41,7 @@ struct SdSlice {
 };
 // which launches have a time-sliced instantiation (the two default classes, IQ input of every kind); the host asks before it slices
 bool sd_slices_supported(int in_kind, int decim, int nt);
-// in_kind: what the 48 kS/s rows hold (SD_IN_REAL / SD_IN_IQ / SD_IN_IQ16 / SD_IN_IQ8)
+// in_kind: what the 48 kS/s rows hold (SONDE_INPUT_*, sd_input.h)
 void sd_launch_demod(int in_kind, int decim, int nt, uint32_t n_channels, hipStream_t stream,
 	const float *in, size_t ch_stride, int n_tiles, SdChanState *states, float *hist,
 	uint32_t *bitring, uint32_t ring_words, const float *taps_all, const SdModem *modems,
@@ -64,7 +64,7 @@ void sd_launch_bins(uint32_t n_channels, hipStream_t stream, const int16_t *phas
 int sd_batch_submit_bins(SondeBatch *b, const SdBinsArgs *ba, size_t n_steps, void *stream);
 int sd_batch_bins_capable(const SondeBatch *b);      // 1: every channel's class has a bins instantiation (no AFSK sonde, no class without one)
 
-void sd_launch_afsk(int type /* SONDE_IMET4 or SONDE_C50 */, int kind /* 0 real, 1 complex64, 2 int16 IQ pairs */, uint32_t n_list, hipStream_t stream, const float *in, size_t ch_stride, int n_tiles,
+void sd_launch_afsk(int type /* SONDE_IMET4 or SONDE_C50 */, int kind /* SONDE_INPUT_* */, uint32_t n_list, hipStream_t stream, const float *in, size_t ch_stride, int n_tiles,
 	const uint32_t *chlist, SdAfskState *astates, const float *wtab, float *out, size_t out_stride);
 void sd_launch_framer_imet(uint32_t n_list, hipStream_t stream, const SdChanState *states, SdFramerState *fstates,
 	const uint32_t *bitring, uint32_t ring_words, SondeFrame *frames, uint32_t *counts, uint32_t max_frames, const uint32_t *chlist);
