@@ -379,6 +379,31 @@ int  sonde_detect_thresholds(float out[SONDE_NTYPES]);
 int  sonde_detect_read(SondeDetector *d, uint32_t channel, int32_t *D /* n/2 */, int32_t *a_imet /* n/8 */, int32_t *a_c50 /* n/8 */);
 int  sonde_detect_templates(int type, int8_t *s, int cap);    /* returns L; writes min(L, cap) values of +-1 (s may be NULL) */
 
+/* ------------------------------------------------------------------ wideband tuner (DESIGN SPEC 3.9)
+ * A bank of VFOs over one wideband complex stream at rate_in (1..20 MHz, integer Hz): VFO k is mixed down from its integer offset
+ * offset_hz (exact 64-bit phase, phi = offset * n mod rate_in for the absolute input index n since create), low-pass filtered to
+ * bandwidth_hz (the Blackman-windowed sinc of SPEC 3.7 with 32 ceil(rate_in / bandwidth) taps per phase) and resampled by
+ * up / down = rate_out / rate_in in lowest terms (rate_out <= 100 kHz, <= rate_in / 8, up <= 64).  Its rows are the complex64 rows
+ * sonde_batch_submit (SONDE_INPUT_IQ at 48 kHz), sonde_vfo_process (at the type's VFO rate) and sonde_detect_submit take: the SDR++
+ * VFO of the reference's chain (/root/reference/src/main.cpp:55-68) for any number of sondes at any offset, M10 / M20 included.
+ * Input kinds: SONDE_INPUT_IQ, SONDE_INPUT_IQ16, SONDE_INPUT_IQ8 (converted exactly; REAL is refused).  Rows are bit-identical however
+ * the stream is cut into submits.  Ordinary stream semantics (as sonde_detect_submit); the offsets travel with each launch, so a
+ * retune reaches the next submit only. */
+typedef struct { int32_t offset_hz; uint32_t bandwidth_hz; /* 0 = rate_out */ } SondeTunerVfo;
+typedef struct SondeTuner SondeTuner;
+int    sonde_tuner_ratio(uint32_t rate_in, uint32_t rate_out, int *up, int *down);
+/* the float32 taps g[p][t] of one bandwidth (SPEC 3.9), up * T of them; writes min(up * T, cap) (g may be NULL); returns up * T */
+int    sonde_tuner_taps(uint32_t rate_in, uint32_t rate_out, uint32_t bandwidth_hz, float *g, size_t cap);
+int    sonde_tuner_create(uint32_t rate_in, uint32_t rate_out, uint32_t n_vfos, const SondeTunerVfo *vfos,
+                          size_t max_in, int input_kind, int device, SondeTuner **out);
+void   sonde_tuner_destroy(SondeTuner *t);
+size_t sonde_tuner_out_samples(const SondeTuner *t, size_t n_in);         /* n_in * up / down */
+int    sonde_tuner_retune(SondeTuner *t, uint32_t vfo, int32_t offset_hz);   /* from the next submit on */
+/* wide_dev: DEVICE pointer to n_in samples (a multiple of down, <= max_in); out_dev: VFO k's n_out complex64 samples at
+ * element k * out_stride (complex samples; sonde_row_stride(n_out, SONDE_INPUT_IQ) writes straight into a SondeBatch input buffer) */
+int    sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n_in,
+                           void *out_dev /* complex64 rows */, size_t out_stride /* complex samples */, void *stream);
+
 /* post-FEC derived quantities, as /root/reference/src/decode/decoder.hpp:132-174 computes them */
 float sonde_dewpt(float temp, float rh);
 float sonde_altitude_to_pressure(float alt);

@@ -47,6 +47,10 @@ DETECTION_DTYPE = np.dtype([("type", "<i4"), ("inverted", "<u4"), ("best", "<f8"
 assert DETECTION_DTYPE.itemsize == C.sizeof(SondeDetection)
 
 
+class SondeTunerVfo(C.Structure):
+    _fields_ = [("offset_hz", C.c_int32), ("bandwidth_hz", C.c_uint32)]
+
+
 class SondeBatchConfig(C.Structure):
     _fields_ = [("n_channels", C.c_uint32), ("types", C.POINTER(C.c_uint8)), ("max_samples", C.c_uint32),
                 ("input_kind", C.c_int32), ("device", C.c_int32), ("flags", C.c_uint32), ("launch_units", C.c_uint32),
@@ -81,6 +85,8 @@ ABI_SYMBOLS = [
     "sonde_vfo_create", "sonde_vfo_destroy", "sonde_vfo_ratio", "sonde_vfo_out_samples", "sonde_vfo_process", "sonde_vfo_process_host", "sonde_vfo_taps",
     "sonde_detect_create", "sonde_detect_destroy", "sonde_detect_submit", "sonde_detect_results", "sonde_detect_reset", "sonde_detect_thresholds",
     "sonde_detect_read", "sonde_detect_templates",
+    "sonde_tuner_ratio", "sonde_tuner_taps", "sonde_tuner_create", "sonde_tuner_destroy", "sonde_tuner_out_samples", "sonde_tuner_retune",
+    "sonde_tuner_process",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -207,6 +213,16 @@ def load() -> C.CDLL:
         L.sonde_detect_thresholds.argtypes = [vp]
         L.sonde_detect_read.argtypes = [vp, C.c_uint32, vp, vp, vp]
         L.sonde_detect_templates.argtypes = [C.c_int, vp, C.c_int]
+    if hasattr(L, "sonde_tuner_create"):
+        L.sonde_tuner_ratio.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.sonde_tuner_taps.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t]
+        L.sonde_tuner_create.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SondeTunerVfo), C.c_size_t, C.c_int, C.c_int, C.POINTER(vp)]
+        L.sonde_tuner_destroy.argtypes = [vp]
+        L.sonde_tuner_destroy.restype = None
+        L.sonde_tuner_out_samples.argtypes = [vp, C.c_size_t]
+        L.sonde_tuner_out_samples.restype = C.c_size_t
+        L.sonde_tuner_retune.argtypes = [vp, C.c_uint32, C.c_int32]
+        L.sonde_tuner_process.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
     f = C.c_float
     L.sonde_gpx_open.restype = vp
     L.sonde_gpx_open.argtypes = [C.c_char_p]

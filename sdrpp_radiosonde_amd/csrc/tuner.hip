@@ -1,0 +1,328 @@
+// tuner.hip -- wideband tuner (DESIGN SPEC 3.9): a bank of VFOs over one wideband complex stream at Fs, each at its own integer-Hz
+// offset f_k and bandwidth B_k, each mixed to DC, low-pass filtered and resampled by up/down = R/Fs to complex rows at R.  It stands
+// where the SDR++ VFO stands in the reference's chain (/root/reference/src/main.cpp:55-68): its rows are the IQ rows SondeBatch,
+// SondeVfo and SondeDetector take.
+//
+// One workgroup per (VFO, tile of TN_JT outputs).  The tile's input window (T_k - 1 samples in front of its first output's i0 up to
+// its last output's i0) is streamed through LDS in segments of TN_SEG samples, newest first; each segment is read from the raw
+// block (or the carried history), converted exactly (sd_input.h), mixed with the VFO's phasor and stored once.  A wave owns every
+// fourth output of the tile; lane l takes the taps t = l (mod 64) of each output, ascending, in one fmaf chain per component that
+// runs on from segment to segment, and a fixed xor butterfly adds the 64 chains.  The order of output j's sum therefore depends on
+// j alone: rows are bit-identical however the stream is cut into submits.  The history (the last H = max_k T_k - 1 raw samples, as
+// float2) is double-buffered and refreshed by a second kernel behind the first.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdlib.h>
+#include <map>
+#include <string>
+#include <vector>
+#include "launch.h"
+#include "sd_input.h"
+#include "../../include/sonde_abi.h"
+
+#define TN_WG    256
+#define TN_JT    64                     // outputs per workgroup (16 per wave)
+#define TN_SEG   4096                   // samples per LDS segment (32 KB of float2)
+#define TN_VMAX  64                     // VFOs per launch: their mixer steps travel with the launch, by value (256 B of arguments)
+#define TN_LOB   12                     // mixer: phi = hi * 2^12 + lo, two tables
+#define TN_MAXUP 64
+
+struct SdTunerOffs { uint32_t F[TN_VMAX]; };      // f_k mod Fs of the launch's VFOs
+
+// e = H[hi] (1 + D[lo]), D = exp(-2 pi i lo / Fs) - 1 (|D| <= 0.026): about 2^-24 per component (SPEC 3.9 allows 2^-22)
+static __device__ __forceinline__ float2 tn_phasor(uint32_t phi, const float2 *__restrict__ th, const float2 *__restrict__ tl)
+{
+	const float2 h = th[phi >> TN_LOB], d = tl[phi & ((1u << TN_LOB) - 1u)];
+	return make_float2(h.x + __builtin_fmaf(h.x, d.x, -(h.y * d.y)), h.y + __builtin_fmaf(h.x, d.y, h.y * d.x));
+}
+
+template <int K>
+__global__ __launch_bounds__(TN_WG) void sd_tuner_kernel(const void *__restrict__ xin, const float2 *__restrict__ hist, uint32_t H,
+	uint32_t n_out, int64_t n_base, uint32_t up, uint32_t down, uint32_t fs,
+	const float *__restrict__ taps, const uint64_t *__restrict__ tapoff, const uint32_t *__restrict__ vT,
+	const float2 *__restrict__ th, const float2 *__restrict__ tl, SdTunerOffs offs, uint32_t vbase,
+	float2 *__restrict__ out, size_t out_stride)
+{
+	__shared__ float2 s_v[TN_SEG];
+	const sd_iq_t<K> *x = (const sd_iq_t<K> *)xin;        // (a void pointer in the signature: sd_iq_t names an anonymous enum, mangled apart on host and device)
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const uint32_t k = vbase + blockIdx.y, F = offs.F[blockIdx.y];
+	const int32_t T = (int32_t)vT[k];
+	const float *g = taps + tapoff[k];
+	const uint32_t jt0 = blockIdx.x * TN_JT;
+	const uint32_t nj = min((uint32_t)TN_JT, n_out - jt0);
+	// window index w: absolute sample n_base - H + w (w < H: the history, H <= w < H + n_in: the block)
+	int32_t w0[TN_JT / 4];
+	uint32_t ph[TN_JT / 4];
+	float ar[TN_JT / 4], ai[TN_JT / 4];
+#pragma unroll
+	for (int r = 0; r < TN_JT / 4; r++) {
+		const uint64_t q = (uint64_t)(jt0 + min((uint32_t)(wave + 4 * r), nj - 1)) * down;      // j down - n_base up (n_base up = j_base down)
+		w0[r] = (int32_t)(H + q / up);
+		ph[r] = (uint32_t)(q % up);
+		ar[r] = 0.0f; ai[r] = 0.0f;
+	}
+	const int32_t w_min = (int32_t)(H + (uint64_t)jt0 * down / up) - (T - 1);                     // >= 0: H >= T - 1
+	const int32_t w_max = (int32_t)(H + (uint64_t)(jt0 + nj - 1) * down / up);
+	// the mixer phase of the first sample this thread stores, then steps of 256 samples (all 32-bit: phi, D < Fs <= 2e7)
+	const uint32_t d256 = (uint32_t)((256ull * F) % fs);
+	for (int32_t seg_hi = w_max + 1; seg_hi > w_min;) {
+		const int32_t seg_lo = max(w_min, seg_hi - TN_SEG), len = seg_hi - seg_lo;
+		const int64_t s0 = n_base - (int64_t)H + seg_lo + tid;
+		uint32_t phi = (uint32_t)(((uint64_t)F * (uint64_t)(((s0 % (int64_t)fs) + (int64_t)fs) % (int64_t)fs)) % fs);
+		for (int32_t i = tid; i < len; i += TN_WG) {
+			const int32_t w = seg_lo + i;
+			const float2 xv = w < (int32_t)H ? hist[w] : sd_iq_f2<K>(x[w - (int32_t)H]);
+			const float2 e = tn_phasor(phi, th, tl);
+			s_v[i] = make_float2(__builtin_fmaf(xv.x, e.x, -(xv.y * e.y)), __builtin_fmaf(xv.x, e.y, xv.y * e.x));
+			phi += d256;
+			phi -= phi >= fs ? fs : 0u;
+		}
+		__syncthreads();
+#pragma unroll
+		for (int r = 0; r < TN_JT / 4; r++) {
+			if ((uint32_t)(wave + 4 * r) >= nj) continue;
+			// output r reads samples w0 - t for t in [t_a, t_b]: the part of its window in this segment
+			const int32_t t_a = max(0, w0[r] - seg_hi + 1), t_b = min(T - 1, w0[r] - seg_lo);
+			const float *gp = g + (size_t)ph[r] * (uint32_t)T;
+			const float2 *vp = s_v + (w0[r] - seg_lo);
+			for (int32_t t = (t_a & ~63) + lane; t <= t_b; t += 64) {
+				if (t < t_a) continue;
+				const float gv = gp[t];
+				const float2 v = vp[-t];
+				ar[r] = __builtin_fmaf(gv, v.x, ar[r]);
+				ai[r] = __builtin_fmaf(gv, v.y, ai[r]);
+			}
+		}
+		__syncthreads();
+		seg_hi = seg_lo;
+	}
+#pragma unroll
+	for (int r = 0; r < TN_JT / 4; r++) {
+#pragma unroll
+		for (int o = 32; o >= 1; o >>= 1) { ar[r] += __shfl_xor(ar[r], o, 64); ai[r] += __shfl_xor(ai[r], o, 64); }
+		const uint32_t q = wave + 4 * r;
+		if (lane == 0 && q < nj) out[(size_t)k * out_stride + jt0 + q] = make_float2(ar[r], ai[r]);
+	}
+}
+
+// the history of the next submit: the last H samples of (history ++ block), as float2
+template <int K>
+__global__ __launch_bounds__(TN_WG) void sd_tuner_hist_kernel(const void *__restrict__ xin, const float2 *__restrict__ h_in,
+	float2 *__restrict__ h_out, uint32_t H, uint32_t n_in)
+{
+	const sd_iq_t<K> *x = (const sd_iq_t<K> *)xin;
+	const uint32_t i = blockIdx.x * TN_WG + threadIdx.x;
+	if (i >= H) return;
+	const uint64_t w = (uint64_t)n_in + i;
+	h_out[i] = w < H ? h_in[w] : sd_iq_f2<K>(x[w - H]);
+}
+
+// ---------------------------------------------------------------- host
+struct SondeTuner {
+	int device = 0, input_kind = SONDE_INPUT_IQ;
+	uint32_t fs = 0, rate_out = 0, up = 0, down = 0, n_vfos = 0, H = 0;
+	size_t max_in = 0;
+	std::vector<int32_t> offset;        // Hz, per VFO
+	std::vector<uint32_t> bw;           // Hz, per VFO
+	int64_t n_base = 0;                 // absolute input index of the next submit's first sample
+	unsigned parity = 0;
+	float *d_taps = nullptr;
+	uint64_t *d_tapoff = nullptr;
+	uint32_t *d_T = nullptr;
+	float2 *d_th = nullptr, *d_tl = nullptr, *d_hist[2] = {};
+};
+
+static uint64_t tn_gcd(uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; }
+
+static int tn_ratio(uint32_t fs, uint32_t r, uint32_t *up, uint32_t *down, const char *fn)
+{
+	if (fs < 1000000u || fs > 20000000u) return sd_fail((std::string(fn) + ": rate_in must be 1 000 000 .. 20 000 000 Hz").c_str());
+	if (r == 0 || r > 100000u || 8ull * r > fs) return sd_fail((std::string(fn) + ": rate_out must be 1 .. 100 000 Hz and at most rate_in / 8").c_str());
+	const uint64_t g = tn_gcd(fs, r);
+	if (r / g > TN_MAXUP) return sd_fail((std::string(fn) + ": rate_out / rate_in in lowest terms has a numerator above 64").c_str());
+	*up = (uint32_t)(r / g);
+	*down = (uint32_t)(fs / g);
+	return 0;
+}
+
+static uint32_t tn_T(uint32_t fs, uint32_t b) { return 32u * ((fs + b - 1) / b); }
+
+// SPEC 3.9: the prototype of SPEC 3.7 (vfo.hip vfo_taps: Blackman-windowed sinc) with N = up T taps, cutoff B / 2 at Fs up; each
+// phase normalised to unit DC gain in double, g[p][t] = (float)(h[t up + p] / sum_t h[t up + p])
+static void tn_taps(uint32_t up, uint32_t T, double fs_up, double cutoff_hz, float *g)
+{
+	const double PI = 3.14159265358979323846;
+	const size_t N = (size_t)up * T;
+	const double fc = cutoff_hz / fs_up;
+	std::vector<double> tmp(N);
+	for (size_t i = 0; i < N; i++) {
+		const double t = (double)i - 0.5 * (double)(N - 1);
+		const double x = (double)i / (double)(N - 1);
+		const double w = 0.42 - 0.5 * cos(2.0 * PI * x) + 0.08 * cos(4.0 * PI * x);
+		const double s = (t == 0.0) ? 2.0 * fc : sin(2.0 * PI * fc * t) / (PI * t);
+		tmp[i] = s * w;
+	}
+	for (uint32_t p = 0; p < up; p++) {
+		double sum = 0.0;
+		for (uint32_t t = 0; t < T; t++) sum += tmp[(size_t)t * up + p];
+		for (uint32_t t = 0; t < T; t++) g[(size_t)p * T + t] = (float)(tmp[(size_t)t * up + p] / sum);
+	}
+}
+
+extern "C" int sonde_tuner_ratio(uint32_t rate_in, uint32_t rate_out, int *up, int *down)
+{
+	uint32_t u, d;
+	if (tn_ratio(rate_in, rate_out, &u, &d, "sonde_tuner_ratio")) return -1;
+	if (up) *up = (int)u;
+	if (down) *down = (int)d;
+	return 0;
+}
+
+extern "C" int sonde_tuner_taps(uint32_t rate_in, uint32_t rate_out, uint32_t bandwidth_hz, float *g, size_t cap)
+{
+	uint32_t up, down;
+	if (tn_ratio(rate_in, rate_out, &up, &down, "sonde_tuner_taps")) return -1;
+	const uint32_t b = bandwidth_hz ? bandwidth_hz : rate_out;
+	if (b < 5000u || b > rate_out) return sd_fail("sonde_tuner_taps: bandwidth_hz must be 5000 .. rate_out (0 = rate_out)");
+	const uint32_t T = tn_T(rate_in, b);
+	const size_t N = (size_t)up * T;
+	if (g && cap) {
+		std::vector<float> v(N);
+		tn_taps(up, T, (double)rate_in * up, 0.5 * b, v.data());
+		for (size_t i = 0; i < N && i < cap; i++) g[i] = v[i];
+	}
+	return (int)N;
+}
+
+extern "C" void sonde_tuner_destroy(SondeTuner *t)
+{
+	if (!t) return;
+	(void)hipSetDevice(t->device);
+	(void)hipFree(t->d_taps); (void)hipFree(t->d_tapoff); (void)hipFree(t->d_T); (void)hipFree(t->d_th); (void)hipFree(t->d_tl);
+	(void)hipFree(t->d_hist[0]); (void)hipFree(t->d_hist[1]);
+	delete t;
+}
+
+static int tn_check_offset(uint32_t fs, uint32_t b, int32_t f, const char *fn)
+{
+	if (2 * llabs((long long)f) + (long long)b > (long long)fs)
+		return sd_fail((std::string(fn) + ": a VFO must lie inside the band (|offset_hz| + bandwidth_hz / 2 <= rate_in / 2)").c_str());
+	return 0;
+}
+
+extern "C" int sonde_tuner_create(uint32_t rate_in, uint32_t rate_out, uint32_t n_vfos, const SondeTunerVfo *vfos, size_t max_in, int input_kind,
+	int device, SondeTuner **out)
+{
+	if (!out || !vfos || !n_vfos) return sd_fail("sonde_tuner_create: bad argument");
+	uint32_t up, down;
+	if (tn_ratio(rate_in, rate_out, &up, &down, "sonde_tuner_create")) return -1;
+	if (input_kind != SONDE_INPUT_IQ && input_kind != SONDE_INPUT_IQ16 && input_kind != SONDE_INPUT_IQ8)
+		return sd_fail("sonde_tuner_create: input_kind must be SONDE_INPUT_IQ, SONDE_INPUT_IQ16 or SONDE_INPUT_IQ8 (the tuner mixes complex samples)");
+	if (max_in < down) return sd_fail("sonde_tuner_create: max_in must be at least the ratio's denominator");
+	std::map<uint32_t, uint32_t> sets;      // bandwidth -> T
+	uint32_t Tmax = 0;
+	for (uint32_t k = 0; k < n_vfos; k++) {
+		const uint32_t b = vfos[k].bandwidth_hz ? vfos[k].bandwidth_hz : rate_out;
+		if (b < 5000u || b > rate_out) return sd_fail("sonde_tuner_create: bandwidth_hz must be 5000 .. rate_out (0 = rate_out)");
+		if (tn_check_offset(rate_in, b, vfos[k].offset_hz, "sonde_tuner_create")) return -1;
+		sets[b] = tn_T(rate_in, b);
+		Tmax = sets[b] > Tmax ? sets[b] : Tmax;
+	}
+	if (max_in + Tmax >= (1u << 30) || (max_in / down) * up >= (1u << 30))
+		return sd_fail("sonde_tuner_create: max_in too large (window indices are 32-bit)");
+	int ndev = 0;
+	hipError_t e = hipGetDeviceCount(&ndev);
+	if (e != hipSuccess || device < 0 || device >= ndev) return sd_fail("sonde_tuner_create: no such HIP device (this library has no CPU path)", e);
+	if ((e = hipSetDevice(device)) != hipSuccess) return sd_fail("hipSetDevice", e);
+	SondeTuner *t = new SondeTuner;
+	t->device = device; t->input_kind = input_kind; t->fs = rate_in; t->rate_out = rate_out; t->up = up; t->down = down;
+	t->n_vfos = n_vfos; t->max_in = max_in; t->H = Tmax - 1;
+	// the tap sets, one per distinct bandwidth, back to back
+	std::map<uint32_t, uint64_t> off;
+	size_t total = 0;
+	for (auto &s : sets) { off[s.first] = total; total += (size_t)up * s.second; }
+	std::vector<float> g(total);
+	for (auto &s : sets) tn_taps(up, s.second, (double)rate_in * up, 0.5 * s.first, g.data() + off[s.first]);
+	std::vector<uint64_t> tapoff(n_vfos);
+	std::vector<uint32_t> T(n_vfos);
+	for (uint32_t k = 0; k < n_vfos; k++) {
+		const uint32_t b = vfos[k].bandwidth_hz ? vfos[k].bandwidth_hz : rate_out;
+		t->offset.push_back(vfos[k].offset_hz);
+		t->bw.push_back(b);
+		tapoff[k] = off[b];
+		T[k] = sets[b];
+	}
+	// the mixer tables (double on the host, stored as float): H[h] = exp(-2 pi i h 2^12 / Fs), D[l] = exp(-2 pi i l / Fs) - 1
+	const double PI = 3.14159265358979323846;
+	const uint32_t nh = (rate_in + (1u << TN_LOB) - 1) >> TN_LOB, nl = 1u << TN_LOB;
+	std::vector<float2> th(nh), tl(nl);
+	for (uint32_t h = 0; h < nh; h++) {
+		const double a = -2.0 * PI * (double)(((uint64_t)h << TN_LOB) % rate_in) / (double)rate_in;
+		th[h] = make_float2((float)cos(a), (float)sin(a));
+	}
+	for (uint32_t l = 0; l < nl; l++) {
+		const double a = -2.0 * PI * (double)l / (double)rate_in, s = sin(0.5 * a);
+		tl[l] = make_float2((float)(-2.0 * s * s), (float)sin(a));
+	}
+	const size_t hb = (size_t)t->H * sizeof(float2);
+	bool ok = hipMalloc((void **)&t->d_taps, total * sizeof(float)) == hipSuccess &&
+	          hipMalloc((void **)&t->d_tapoff, n_vfos * sizeof(uint64_t)) == hipSuccess &&
+	          hipMalloc((void **)&t->d_T, n_vfos * sizeof(uint32_t)) == hipSuccess &&
+	          hipMalloc((void **)&t->d_th, nh * sizeof(float2)) == hipSuccess && hipMalloc((void **)&t->d_tl, nl * sizeof(float2)) == hipSuccess &&
+	          hipMalloc((void **)&t->d_hist[0], hb) == hipSuccess && hipMalloc((void **)&t->d_hist[1], hb) == hipSuccess;
+	ok = ok && hipMemcpy(t->d_taps, g.data(), total * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+	     hipMemcpy(t->d_tapoff, tapoff.data(), n_vfos * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess &&
+	     hipMemcpy(t->d_T, T.data(), n_vfos * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
+	     hipMemcpy(t->d_th, th.data(), nh * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess &&
+	     hipMemcpy(t->d_tl, tl.data(), nl * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess &&
+	     hipMemset(t->d_hist[0], 0, hb) == hipSuccess && hipMemset(t->d_hist[1], 0, hb) == hipSuccess;
+	if (!ok) { sonde_tuner_destroy(t); return sd_fail("sonde_tuner_create: device allocation failed"); }
+	*out = t;
+	return 0;
+}
+
+extern "C" size_t sonde_tuner_out_samples(const SondeTuner *t, size_t n_in) { return t ? n_in / t->down * t->up : 0; }
+
+extern "C" int sonde_tuner_retune(SondeTuner *t, uint32_t vfo, int32_t offset_hz)
+{
+	if (!t) return sd_fail("sonde_tuner_retune: null argument");
+	if (vfo >= t->n_vfos) return sd_fail("sonde_tuner_retune: no such VFO");
+	if (tn_check_offset(t->fs, t->bw[vfo], offset_hz, "sonde_tuner_retune")) return -1;
+	t->offset[vfo] = offset_hz;
+	return 0;
+}
+
+extern "C" int sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n_in, void *out_dev, size_t out_stride, void *stream)
+{
+	if (!t || !wide_dev || !out_dev) return sd_fail("sonde_tuner_process: null argument");
+	if (!n_in || n_in > t->max_in || n_in % t->down) return sd_fail("sonde_tuner_process: n_in must be a multiple of the ratio's denominator and <= max_in");
+	const size_t n_out = sonde_tuner_out_samples(t, n_in);
+	if (out_stride < n_out) return sd_fail("sonde_tuner_process: out_stride shorter than the row");
+	if ((uintptr_t)wide_dev % sd_sample_bytes(t->input_kind)) return sd_fail("sonde_tuner_process: the block is not aligned to the sample size");
+	if ((uintptr_t)out_dev & 7u) return sd_fail("sonde_tuner_process: out must be 8-byte aligned");
+	hipError_t e = hipSetDevice(t->device);
+	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	hipStream_t s = (hipStream_t)stream;
+	const float2 *h_in = t->d_hist[t->parity & 1];
+	float2 *h_out = t->d_hist[(t->parity + 1) & 1];
+	sd_input_dispatch(t->input_kind, [&](auto kk) {
+		constexpr int K = decltype(kk)::value;
+		if constexpr (K != SONDE_INPUT_REAL) {
+			const void *x = wide_dev;
+			for (uint32_t vb = 0; vb < t->n_vfos; vb += TN_VMAX) {
+				const uint32_t nv = t->n_vfos - vb < TN_VMAX ? t->n_vfos - vb : TN_VMAX;
+				SdTunerOffs o = {};
+				for (uint32_t i = 0; i < nv; i++) o.F[i] = (uint32_t)((((int64_t)t->offset[vb + i] % (int64_t)t->fs) + (int64_t)t->fs) % (int64_t)t->fs);
+				const dim3 grid((unsigned)((n_out + TN_JT - 1) / TN_JT), nv);
+				hipLaunchKernelGGL(sd_tuner_kernel<K>, grid, dim3(TN_WG), 0, s, x, h_in, t->H, (uint32_t)n_out, t->n_base, t->up, t->down, t->fs,
+					t->d_taps, t->d_tapoff, t->d_T, t->d_th, t->d_tl, o, vb, (float2 *)out_dev, out_stride);
+			}
+			hipLaunchKernelGGL(sd_tuner_hist_kernel<K>, dim3((t->H + TN_WG - 1) / TN_WG), dim3(TN_WG), 0, s, x, h_in, h_out, t->H, (uint32_t)n_in);
+		}
+	});
+	if ((e = hipGetLastError()) != hipSuccess) return sd_fail("sd_tuner_kernel launch", e);
+	t->parity++;
+	t->n_base += (int64_t)n_in;
+	return 0;
+}

@@ -1151,3 +1151,42 @@ def make_c50_batch(n_channels: int, n_samples: int, *, seed: int = 1, snr_db: fl
     iq, cfo, tau, amp = afsk_modulate(bits, n_samples, seed=seed + first_channel, snr_db=snr_db, device=device, baud=C50_BAUD,
                                       mark_hz=C50_MARK_HZ, space_hz=C50_SPACE_HZ, fm_dev_hz=4000.0, **mod_kw)
     return SynthBatch(iq=iq, frames=frames, bits=bits, cfo_hz=cfo, tau=tau, amp=amp)
+
+
+# ================================================================ wideband scene of any sonde types (the tuner's input)
+SCENE_BAUD = {0: 4800.0, 1: 5000.0, 2: 4800.0, 3: 9600.0, 4: IMET_BAUD, 5: C50_BAUD, 6: 4800.0}     # on-air symbols (bits / chips) per second
+
+
+def make_wideband_scene(sondes, n_samples: int, *, fs: float = WB_FS, ebn0_db: float = 20.0, seed: int = 1, noise_sigma: float = 0.02,
+                        device: str | torch.device = "cpu", cfo_max_hz: float = 300.0):
+    """Transmitters of any sonde type at the given offsets, summed into one complex stream at fs [n_samples, 2] with ONE white noise
+    floor (sigma per component): sondes = [(offset_hz, sonde type, m20), ...] (m20 optional: M20 frames for type 3).  Each carrier's
+    amplitude sets its own Eb/N0 against that floor (GFSK), or its C/N in 48 kHz (iMet-4, SRS-C50) to ebn0_db; ebn0_db may be a
+    list (one per sonde).  Returns (iq, frames, symbols): per sonde the list of (symbol offset, frame bytes) and the number of
+    on-air symbols the stream holds."""
+    ebn0 = list(ebn0_db) if np.ndim(ebn0_db) else [float(ebn0_db)] * len(sondes)
+    total = torch.zeros((n_samples, 2), dtype=torch.float32, device=device)
+    n = torch.arange(n_samples, device=device, dtype=torch.float64)
+    frames, symbols = [], []
+    for i, s in enumerate(sondes):
+        f, t = float(s[0]), int(s[1])
+        m20 = bool(s[2]) if len(s) > 2 else False
+        kw = dict(fs=fs, cfo_max_hz=cfo_max_hz, device=device)
+        if t in (4, 5):
+            a = noise_sigma * math.sqrt(2.0 * 10.0 ** (ebn0[i] / 10.0) * 48000.0 / fs)
+            mk = make_imet_batch if t == 4 else make_c50_batch
+            sb = mk(1, n_samples, seed=seed + 17 * i, snr_db=200.0, amp_range=(a, a), first_channel=i, **kw)
+        else:
+            a = noise_sigma * math.sqrt(2.0 * 10.0 ** (ebn0[i] / 10.0) * SCENE_BAUD[t] / fs)
+            sb = make_batch(t, 1, n_samples, seed=seed + 17 * i, ebn0_db=200.0, amp_range=(a, a), first_channel=i, m20=m20, **kw)
+        ph = (2.0 * math.pi * f / fs) * n
+        c, s_ = torch.cos(ph).to(torch.float32), torch.sin(ph).to(torch.float32)
+        total[:, 0] += sb.iq[0, :, 0] * c - sb.iq[0, :, 1] * s_
+        total[:, 1] += sb.iq[0, :, 0] * s_ + sb.iq[0, :, 1] * c
+        frames.append(sb.frames[0])
+        symbols.append(int(n_samples * SCENE_BAUD[t] / fs))
+        del sb
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed * 7 + 1)
+    total += noise_sigma * torch.randn((n_samples, 2), generator=gen, device=device, dtype=torch.float32)
+    return total, frames, symbols

@@ -1,0 +1,256 @@
+"""Python face of the wideband tuner (include/sonde_abi.h, DESIGN SPEC 3.9): thin, no compute -- every call goes through the C ABI of
+libsonde_mi355.so.
+
+    SondeTuner          a bank of VFOs at any integer-Hz offset over one wideband stream -> complex rows at rate_out
+    WidebandReceiver    wideband stream -> tuner -> decoders, for a list of (offset, sonde type): the chain of the reference
+                        (VFO -> FM -> resampler -> decoder, /root/reference/src/main.cpp:55-68) or the tuner straight to 48 kHz IQ
+
+Use the tuner when the frequencies are known (any sonde type, M10 / M20 included; the cost grows with the number of VFOs), the
+channelizer (batch.SondeChannelizer) to decode every 19.53 kHz bin of the band at once (fixed cost, no M10 / M20)."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _lib
+from ._lib import INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE
+from .batch import VFO_RATE, SondeBatch, SondeError, SondeVfo
+
+IMET4, C50 = _lib.IMET4, _lib.C50
+AFSK_TILE = 16384          # a batch with an AFSK sonde (iMet-4, SRS-C50) takes rows in multiples of this
+IQ48_MAX_BW = 40000        # the iq48 chain's VFO bandwidth cap (M10 / M20: 50 kHz does not fit a 48 kHz row)
+
+
+def _chk(rc):
+    if rc < 0:
+        raise SondeError(_lib.last_error())
+    return rc
+
+
+def ratio(rate_in: int, rate_out: int) -> tuple[int, int]:
+    """(up, down) = rate_out / rate_in in lowest terms (sonde_tuner_ratio; raises for rates the tuner refuses)"""
+    up, down = C.c_int(), C.c_int()
+    _chk(_lib.load().sonde_tuner_ratio(int(rate_in), int(rate_out), C.byref(up), C.byref(down)))
+    return up.value, down.value
+
+
+def tuner_taps(rate_in: int, rate_out: int, bandwidth_hz: int = 0) -> np.ndarray:
+    """the float32 taps g[p][t] of one bandwidth (SPEC 3.9): [up, T]"""
+    L = _lib.load()
+    n = _chk(L.sonde_tuner_taps(int(rate_in), int(rate_out), int(bandwidth_hz), None, 0))
+    g = np.zeros(n, np.float32)
+    _chk(L.sonde_tuner_taps(int(rate_in), int(rate_out), int(bandwidth_hz), g.ctypes.data_as(C.c_void_p), n))
+    up, _ = ratio(rate_in, rate_out)
+    return g.reshape(up, n // up)
+
+
+class SondeTuner:
+    """A bank of VFOs over one wideband complex stream.  vfos: [(offset_hz, bandwidth_hz), ...] or [offset_hz, ...]
+    (bandwidth 0 = rate_out).  process() takes a device block [n_in, 2] (float32; int16 for INPUT_IQ16, int8 for INPUT_IQ8),
+    n_in a multiple of `down`, and returns [V, n_out, 2] float32 rows or writes them into `out` (a [V, >= n_out, 2] float32 view
+    whose rows may lie any stride apart)."""
+
+    def __init__(self, rate_in: int, rate_out: int, vfos, max_in: int, *, input_kind: int = INPUT_IQ, device: int = 0):
+        self.L = _lib.load()
+        spec = [(v, 0) if np.isscalar(v) else (v[0], v[1]) for v in vfos]
+        self.n_vfos = len(spec)
+        arr = (_lib.SondeTunerVfo * max(1, self.n_vfos))()
+        for i, (f, b) in enumerate(spec):
+            arr[i].offset_hz, arr[i].bandwidth_hz = int(f), int(b)
+        h = C.c_void_p()
+        _chk(self.L.sonde_tuner_create(int(rate_in), int(rate_out), self.n_vfos, arr, int(max_in), int(input_kind), int(device), C.byref(h)))
+        self.h = h
+        self.rate_in, self.rate_out, self.max_in = int(rate_in), int(rate_out), int(max_in)
+        self.input_kind, self.device = int(input_kind), int(device)
+        self.offsets = [int(f) for f, _ in spec]
+        self.bandwidths = [int(b) or int(rate_out) for _, b in spec]
+        self.up, self.down = ratio(rate_in, rate_out)
+
+    def out_samples(self, n_in: int) -> int:
+        return int(self.L.sonde_tuner_out_samples(self.h, int(n_in)))
+
+    def retune(self, k: int, hz: int):
+        """VFO k to offset hz from the next process() on"""
+        _chk(self.L.sonde_tuner_retune(self.h, int(k), int(hz)))
+        self.offsets[k] = int(hz)
+
+    def process(self, block, out=None, stream: int | None = None):
+        import torch
+        want = {INPUT_IQ16: torch.int16, INPUT_IQ8: torch.int8}.get(self.input_kind, torch.float32)
+        if block.dtype != want:
+            raise SondeError(f"the wideband block must be {want}, got {block.dtype}")
+        if not block.is_cuda or block.dim() != 2 or block.shape[1] != 2 or not block.is_contiguous():
+            raise SondeError("the wideband block must be a contiguous device tensor [n_in, 2]")
+        if block.device.index is not None and block.device.index != self.device:
+            raise SondeError(f"the block lives on device {block.device.index}, the tuner on device {self.device}")
+        n_in = block.shape[0]
+        n_out = self.out_samples(n_in)
+        if out is None:
+            out = torch.empty((self.n_vfos, n_out, 2), dtype=torch.float32, device=block.device)
+        elif (out.dtype != torch.float32 or out.dim() != 3 or out.shape[0] != self.n_vfos or out.shape[1] < n_out or out.shape[2] != 2
+              or out.stride(1) != 2 or out.stride(2) != 1 or out.device != block.device):
+            raise SondeError("out must be a float32 device view [n_vfos, >= n_out, 2], contiguous inside a row")
+        if stream is None:
+            stream = torch.cuda.current_stream(block.device).cuda_stream
+        self._keep = block
+        _chk(self.L.sonde_tuner_process(self.h, C.c_void_p(block.data_ptr()), n_in, C.c_void_p(out.data_ptr()), out.stride(0) // 2,
+                                        C.c_void_p(stream)))
+        return out[:, :n_out]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.sonde_tuner_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _multiple_for(a: int, b: int, c: int) -> int:
+    """the smallest n > 0 with n * a / b a multiple of c (a / b in lowest terms or not)"""
+    g = math.gcd(a, b)
+    a, b = a // g, b // g
+    return c * b // math.gcd(a, c * b)
+
+
+def _lcm(*v: int) -> int:
+    out = 1
+    for x in v:
+        out = out * x // math.gcd(out, x)
+    return out
+
+
+class WidebandReceiver:
+    """Decode sondes at known offsets from one wideband stream.  sondes: [(offset_hz, sonde type), ...]; the `channel` of a frame
+    (and of a poll() fragment) is the index into `sondes`.
+
+      chain="iq48"       one tuner at 48 kHz, VFO k at B = VFO_RATE[type] (M10 / M20: 40 kHz), into one SondeBatch(INPUT_IQ)
+      chain="reference"  the reference's chain: one tuner per distinct VFO_RATE at R = B, SondeVfo(B), the 48 kHz FM rows of every
+                         sonde in one SondeBatch(INPUT_REAL) buffer
+
+    submit() takes a device block [n, 2] (float32 / int16 / int8 by input_kind), n a multiple of `granule` and <= max_in
+    (default: one granule): the smallest block that leaves whole decoder tiles at 48 kHz."""
+
+    def __init__(self, rate_in: int, sondes, *, chain: str = "iq48", input_kind: int = INPUT_IQ, device: int = 0, max_in: int | None = None):
+        import torch
+        if chain not in ("iq48", "reference"):
+            raise SondeError('chain must be "iq48" or "reference"')
+        self.rate_in, self.chain, self.device, self.input_kind = int(rate_in), chain, int(device), int(input_kind)
+        self.sondes = [(int(f), int(t)) for f, t in sondes]
+        if not self.sondes:
+            raise SondeError("no sondes")
+        types = [t for _, t in self.sondes]
+        tile = AFSK_TILE if any(t in (IMET4, C50) for t in types) else TILE
+        fs = self.rate_in
+        if chain == "iq48":
+            bws = [min(VFO_RATE[t], IQ48_MAX_BW) for t in types]
+            down = ratio(fs, 48000)[1]
+            self.granule = _lcm(down, _multiple_for(48000, fs, tile))
+            groups = {48000: list(range(len(types)))}
+        else:
+            groups = {}
+            for i, t in enumerate(types):
+                groups.setdefault(VFO_RATE[t], []).append(i)
+            parts = [_multiple_for(48000, fs, tile)]
+            for b in groups:
+                parts += [ratio(fs, b)[1], _multiple_for(b, fs, _vfo_down(b))]
+            self.granule = _lcm(*parts)
+        self.max_in = int(max_in or self.granule)
+        if self.max_in % self.granule:
+            raise SondeError(f"max_in must be a multiple of the granule ({self.granule})")
+        n48 = self.max_in * 48000 // fs
+        # batch channel c = order[c]: the sondes grouped by tuner, so that every group's rows are evenly spaced
+        self.order = np.array([i for g in groups.values() for i in g], dtype=np.int64)
+        self.stages = []          # (tuner, SondeVfo or None, first batch channel, sonde indices)
+        c0 = 0
+        for rate, idx in groups.items():
+            if chain == "iq48":
+                tu = SondeTuner(fs, 48000, [(self.sondes[i][0], bws[i]) for i in idx], self.max_in, input_kind=input_kind, device=device)
+                self.stages.append((tu, None, c0, idx))
+            else:
+                tu = SondeTuner(fs, rate, [(self.sondes[i][0], rate) for i in idx], self.max_in, input_kind=input_kind, device=device)
+                vo = SondeVfo(len(idx), rate, tu.out_samples(self.max_in), device=device)
+                self.stages.append((tu, vo, c0, idx))
+            c0 += len(idx)
+        bt = np.array([types[i] for i in self.order], dtype=np.uint8)
+        kind = INPUT_IQ if chain == "iq48" else INPUT_REAL
+        self.batch = SondeBatch(len(types), n48, types=bt, input_kind=kind, device=device)
+        stride = int(_lib.load().sonde_row_stride(n48, kind))
+        shape = (len(types), stride, 2) if kind == INPUT_IQ else (len(types), stride)
+        self._rows = torch.empty(shape, dtype=torch.float32, device=f"cuda:{device}")
+        self._tmp = {}
+        self._n48 = 0
+        self._inv = np.empty(len(types), dtype=np.int64)
+        self._inv[:] = self.order          # batch channel -> sonde index
+
+    def _where(self, i: int):
+        for tu, _, _, idx in self.stages:
+            if i in idx:
+                return tu, idx.index(i)
+        raise SondeError("no such sonde")
+
+    def retune(self, i: int, hz: int):
+        """sonde i's VFO to offset hz from the next submit on"""
+        tu, k = self._where(int(i))
+        tu.retune(k, hz)
+        self.sondes[i] = (int(hz), self.sondes[i][1])
+
+    def rows(self):
+        """the 48 kHz rows of the last submit, in batch-channel order (IQ [C, n, 2] for iq48, FM [C, n] for reference)"""
+        return self._rows[:, :self._n48]
+
+    def submit(self, block, stream: int | None = None):
+        import torch
+        n = int(block.shape[0])
+        if n == 0 or n % self.granule or n > self.max_in:
+            raise SondeError(f"the block must hold a positive multiple of the granule ({self.granule}) samples, at most max_in ({self.max_in})")
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        n48 = n * 48000 // self.rate_in
+        for tu, vo, c0, idx in self.stages:
+            nv = len(idx)
+            if vo is None:
+                tu.process(block, out=self._rows[c0:c0 + nv], stream=stream)
+            else:
+                m = tu.out_samples(n)
+                buf = self._tmp.get(id(tu))
+                if buf is None or buf.shape[1] < m:
+                    buf = self._tmp[id(tu)] = torch.empty((nv, tu.out_samples(self.max_in), 2), dtype=torch.float32, device=block.device)
+                tu.process(block, out=buf, stream=stream)
+                _vfo_process(vo, buf[:, :m], self._rows[c0:c0 + nv], stream)
+        self._n48 = n48
+        self.batch.submit(self._rows[:, :n48], stream)
+
+    def frames(self) -> np.ndarray:
+        f = self.batch.frames()
+        f["channel"] = self._inv[f["channel"]]
+        return f
+
+    def poll(self):
+        """[(sonde index, SondeData), ...] of the last submit (SondeBatch.poll)"""
+        return [(int(self._inv[c]), d) for c, d in self.batch.poll()]
+
+    def close(self):
+        for tu, vo, _, _ in self.stages:
+            tu.close()
+            if vo is not None:
+                vo.close()
+        self.stages = []
+        self.batch.close()
+
+
+def _vfo_down(rate: int) -> int:
+    down = C.c_int()
+    _chk(_lib.load().sonde_vfo_ratio(int(rate), None, C.byref(down)))
+    return down.value
+
+
+def _vfo_process(vo: SondeVfo, iq, out, stream):
+    """SondeVfo.process into a strided row view (its rows: the batch buffer's)"""
+    _chk(vo.L.sonde_vfo_process(vo.h, C.c_void_p(iq.data_ptr()), iq.shape[1], iq.stride(0) // 2, C.c_void_p(out.data_ptr()), out.stride(0),
+                                C.c_void_p(stream)))

@@ -1,0 +1,281 @@
+"""The wideband tuner on the GPU (DESIGN SPEC 3.9) against tests/tuner_reference.py: rows within a formula bound at several rates,
+bandwidths, offsets and input kinds; bit-identical rows however the stream is cut; strided rows; retune; tone rejection; refusals;
+then whole scenes: every sonde type decoded from one 10 MS/s stream through both chains of WidebandReceiver, adjacent channels,
+and detect-then-decode."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import tuner_reference as R
+from sdrpp_radiosonde_amd import _lib, synth
+from sdrpp_radiosonde_amd.batch import SondeChannelizer, SondeError
+from sdrpp_radiosonde_amd.detect import SondeDetector
+from sdrpp_radiosonde_amd.tuner import SondeTuner, WidebandReceiver, tuner_taps
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+IQ, IQ16, IQ8 = _lib.INPUT_IQ, _lib.INPUT_IQ16, _lib.INPUT_IQ8
+DT = {IQ: torch.float32, IQ16: torch.int16, IQ8: torch.int8}
+
+# (Fs, R, B (0 = R), offsets: negative, off the 1 kHz raster, at the band edge, input kind, submits in units of `down`)
+CFG = [
+    (10_000_000, 10_000, 0, [-1_234_567, 4_995_000, 3_000_000], IQ, [7, 25, 40]),
+    (10_000_000, 48_000, 40_000, [-4_980_000, 123_457], IQ16, [13, 40, 11]),
+    (10_000_000, 48_000, 10_000, [2_000_001], IQ, [64, 3]),
+    (2_400_000, 50_000, 0, [-1_175_000, 7_777], IQ8, [100, 37, 200]),
+    (2_048_000, 15_000, 0, [-333_333, 1_016_500], IQ, [3, 5, 2]),
+    (2_400_000, 20_000, 0, [-600_001, 1_189_999], IQ16, [50, 101]),
+]
+
+
+def _stream(fs, n, kind, seed, tones=((0.3, 31_234), (0.2, -1_234_000))):
+    """integer-valued complex samples (exact in every kind): noise plus tones"""
+    rng = np.random.default_rng(seed)
+    a = {IQ: 3000.0, IQ16: 3000.0, IQ8: 40.0}[kind]
+    t = np.arange(n)
+    x = a * 0.3 * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+    for amp, f in tones:
+        x = x + a * amp * np.exp(2j * np.pi * (f * t / fs + rng.uniform()))
+    x = np.round(x)
+    return x, torch.from_numpy(np.stack([x.real, x.imag], axis=1)).to(DT[kind]).to(DEV)
+
+
+def _run(tu, dev, subs, down, out=None):
+    got, a = [], 0
+    for k in subs:
+        y = tu.process(dev[a:a + k * down].contiguous(), out=out)
+        got.append(y.cpu().numpy().copy())
+        a += k * down
+    return np.concatenate(got, axis=1)
+
+
+@pytest.mark.parametrize("cfg", CFG, ids=[f"{c[0]}-{c[1]}-{c[2]}-k{c[4]}" for c in CFG])
+def test_rows_within_the_bound(cfg):
+    fs, r, b, offs, kind, subs = cfg
+    up, down = R.ratio(fs, r)
+    n = sum(subs) * down
+    x, dev = _stream(fs, n, kind, seed=fs % 997 + r)
+    tu = SondeTuner(fs, r, [(f, b) for f in offs], max(subs) * down, input_kind=kind)
+    assert (tu.up, tu.down) == (up, down)
+    got = _run(tu, dev, subs, down)
+    g = tuner_taps(fs, r, b).astype(np.float64)
+    for k, f in enumerate(offs):
+        y, A = R.tuner_ref(x, fs, r, g, [f] * len(subs), [s * down for s in subs])
+        bnd = R.bound(A, g.shape[1])
+        gk = got[k, :, 0] + 1j * got[k, :, 1]
+        assert len(gk) == len(y) == n * up // down
+        dev_re, dev_im = np.abs(gk.real - y.real), np.abs(gk.imag - y.imag)
+        assert np.all(dev_re <= bnd) and np.all(dev_im <= bnd), (k, float(np.max(np.maximum(dev_re, dev_im) / bnd)))
+        assert np.max(np.abs(y)) > 100.0 * np.max(bnd)          # the rows carry signal: the bound is not vacuous
+    tu.close()
+
+
+def test_ragged_submits_strided_rows_and_integer_kinds_bit_identical():
+    fs, r, b = 10_000_000, 48_000, 10_000
+    up, down = R.ratio(fs, r)
+    offs = [(-2_345_678, b), (17_001, 0), (4_970_000, 20_000)]
+    subs = [1, 13, 200, 7, 64, 2]
+    n = sum(subs) * down
+    x, d16 = _stream(fs, n, IQ16, seed=3)
+    dflt = d16.to(torch.float32)
+    one = SondeTuner(fs, r, offs, n, input_kind=IQ).process(dflt).cpu().numpy()
+    tu = SondeTuner(fs, r, offs, max(subs) * down, input_kind=IQ)
+    buf = torch.full((3, 1000, 2), float("nan"), device=DEV)               # rows 1000 samples apart, longer than any submit's
+    got = _run(tu, dflt, subs, down, out=buf)
+    assert got.view(np.uint32).shape == one.view(np.uint32).shape and np.array_equal(got.view(np.uint32), one.view(np.uint32))
+    for kind, dev in ((IQ16, d16), (IQ8, None)):
+        if dev is None:
+            x8, dev = _stream(fs, n, IQ8, seed=4)
+            one = SondeTuner(fs, r, offs, n, input_kind=IQ).process(dev.to(torch.float32)).cpu().numpy()
+        tk = SondeTuner(fs, r, offs, max(subs) * down, input_kind=kind)
+        got = _run(tk, dev, subs, down)
+        assert np.array_equal(got.view(np.uint32), one.view(np.uint32)), kind
+
+
+def test_retune_between_submits():
+    fs, r = 2_400_000, 20_000
+    up, down = R.ratio(fs, r)
+    subs = [40, 40, 40]
+    plan = [[-500_000, -500_000, 31_234], [100_003, 700_000, 700_000]]
+    x, dev = _stream(fs, sum(subs) * down, IQ, seed=9, tones=((0.4, 31_234), (0.4, 700_000)))
+    tu = SondeTuner(fs, r, [p[0] for p in plan], max(subs) * down)
+    got, a = [], 0
+    for s, k in enumerate(subs):
+        for v in range(2):
+            if s and plan[v][s] != plan[v][s - 1]:
+                tu.retune(v, plan[v][s])
+        got.append(tu.process(dev[a:a + k * down].contiguous()).cpu().numpy())
+        a += k * down
+    got = np.concatenate(got, axis=1)
+    g = tuner_taps(fs, r).astype(np.float64)
+    for v in range(2):
+        y, A = R.tuner_ref(x, fs, r, g, plan[v], [k * down for k in subs])
+        gk = got[v, :, 0] + 1j * got[v, :, 1]
+        bnd = R.bound(A, g.shape[1])
+        assert np.all(np.abs(gk.real - y.real) <= bnd) and np.all(np.abs(gk.imag - y.imag) <= bnd)
+    with pytest.raises(SondeError, match="inside the band"):
+        tu.retune(0, 1_195_000)
+    with pytest.raises(SondeError, match="no such VFO"):
+        tu.retune(2, 0)
+
+
+def test_tone_rejection():
+    """A tone at f_k + 0.7 B leaves VFO k at least 70 dB below an in-band tone of the same amplitude."""
+    fs, r, b, f = 10_000_000, 48_000, 10_000, -1_500_321
+    up, down = R.ratio(fs, r)
+    n = 80 * down
+    t = torch.arange(n, dtype=torch.float64, device=DEV)
+    pw = []
+    for d in (0.1 * b, 0.7 * b, -0.7 * b):
+        ph = 2 * np.pi * (f + d) / fs * t
+        blk = torch.stack([torch.cos(ph), torch.sin(ph)], 1).to(torch.float32).contiguous()
+        y = SondeTuner(fs, r, [(f, b)], n).process(blk)[0].double()
+        T = R.taps_per_phase(fs, b)
+        settled = y[-(-T * up // down) + 1:]
+        pw.append(float((settled ** 2).sum(1).mean()))
+    assert 10 * np.log10(pw[1] / pw[0]) <= -70.0 and 10 * np.log10(pw[2] / pw[0]) <= -70.0, pw
+
+
+def test_refusals():
+    with pytest.raises(SondeError, match="input_kind"):
+        SondeTuner(10_000_000, 48_000, [0], 12500, input_kind=_lib.INPUT_REAL)
+    with pytest.raises(SondeError, match="numerator above 64"):
+        SondeTuner(10_000_000, 48_001, [0], 1_000_000)
+    with pytest.raises(SondeError, match="rate_out"):
+        SondeTuner(1_000_000, 200_000, [0], 1000)
+    with pytest.raises(SondeError, match="rate_in"):
+        SondeTuner(30_000_000, 48_000, [0], 1000)
+    with pytest.raises(SondeError, match="bandwidth"):
+        SondeTuner(10_000_000, 48_000, [(0, 4000)], 12500)
+    with pytest.raises(SondeError, match="bandwidth"):
+        SondeTuner(10_000_000, 10_000, [(0, 20_000)], 12500)
+    with pytest.raises(SondeError, match="inside the band"):
+        SondeTuner(10_000_000, 48_000, [(4_980_001, 40_000)], 12500)
+    tu = SondeTuner(10_000_000, 48_000, [0], 6250)
+    blk = torch.zeros((6250, 2), device=DEV)
+    with pytest.raises(SondeError, match="multiple"):
+        tu.process(blk[:1000])
+    with pytest.raises(SondeError, match="max_in"):
+        tu.process(torch.zeros((12500, 2), device=DEV))
+    with pytest.raises(SondeError, match="float32"):
+        tu.process(blk.to(torch.int16))
+    out = torch.zeros((1, 16, 2), device=DEV)
+    L = _lib.load()
+    assert L.sonde_tuner_process(tu.h, C.c_void_p(blk.data_ptr()), 6250, C.c_void_p(out.data_ptr()), 16, None) != 0
+    assert b"out_stride" in L.sonde_last_error()
+
+
+# ---------------------------------------------------------------- whole scenes
+FS = 10_000_000
+N_SCENE = 30_720_000                       # 3.07 s: three granules of the iq48 chain with an AFSK sonde
+# (offset, type, m20): off the channelizer's 19 531.25 Hz grid
+SCENE = [(-3_512_345, 0, False), (-2_100_777, 1, False), (1_234_567, 2, False), (2_500_003, 3, False), (3_700_111, 3, True),
+         (-700_321, 4, False), (150_013, 5, False), (4_200_999, 6, False)]
+EMPTY = -4_400_000
+
+
+def _match(t, m20, f, txs):
+    if t == 0:
+        return [i for i, (_, tx) in enumerate(txs) if np.array_equal(tx[8:], f["data"][8:f["len"]])]
+    if t == 3 and m20:
+        return [i for i, (_, tx) in enumerate(txs) if np.array_equal(tx[:70], f["data"][:70])]
+    if t == 5:
+        return [i for i, (_, tx) in enumerate(txs) if np.array_equal(tx, f["data"][:len(tx)])]
+    return [i for i, (_, tx) in enumerate(txs) if np.array_equal(tx, f["data"][:f["len"]])]
+
+
+def _check_frames(got, sondes, frames, symbols, allow_lost=1):
+    for i, (_, t, m20) in enumerate(sondes):
+        fr = got[got["channel"] == i]
+        hit = set()
+        for f in fr:
+            m = _match(t, m20, f, frames[i])
+            assert m, f"sonde {i} (type {t}): a decoded frame matches no transmitted one"
+            hit.update(m)
+        starts = np.array([p for p, _ in frames[i]])
+        period = int(np.median(np.diff(starts))) if len(starts) > 1 else symbols[i]
+        complete = [k for k, p in enumerate(starts) if p + period <= symbols[i]]
+        lost = len(set(complete) - hit)
+        assert len(complete) >= 1 and lost <= allow_lost, (i, t, len(complete), sorted(hit))
+
+
+@pytest.fixture(scope="module")
+def scene20():
+    iq, frames, symbols = synth.make_wideband_scene(SCENE, N_SCENE, fs=FS, ebn0_db=20.0, seed=21, device=DEV)
+    return iq.contiguous(), frames, symbols
+
+
+@pytest.mark.parametrize("chain", ["iq48", "reference"])
+def test_every_type_decoded_from_one_wideband_stream(scene20, chain):
+    iq, frames, symbols = scene20
+    sondes = [(f, t) for f, t, _ in SCENE] + [(EMPTY, 0)]
+    rx = WidebandReceiver(FS, sondes, chain=chain, max_in=N_SCENE // 3 if chain == "iq48" else None)
+    assert N_SCENE % rx.granule == 0
+    if chain == "iq48":
+        assert rx.granule == 10_240_000
+    got = []
+    for a in range(0, N_SCENE, rx.max_in):
+        rx.submit(iq[a:a + rx.max_in])
+        got.append(rx.frames())
+    got = np.concatenate(got)
+    assert not np.any(got["channel"] == len(SCENE)), "a VFO on an empty frequency decoded something"
+    _check_frames(got, SCENE, frames, symbols)
+    rx.close()
+
+
+def test_m10_decoded_where_the_channelizer_refuses_it(scene20):
+    iq, frames, symbols = scene20
+    types = np.zeros(512, np.uint8)
+    types[int(round(SCENE[3][0] / (FS / 512))) % 512] = 3
+    with pytest.raises(SondeError):
+        SondeChannelizer(types)
+    rx = WidebandReceiver(FS, [(SCENE[3][0], 3)], chain="iq48")
+    assert rx.granule == 1_280_000
+    got = []
+    for a in range(0, N_SCENE // 2, rx.max_in):
+        rx.submit(iq[a:a + rx.max_in])
+        got.append(rx.frames())
+    got = np.concatenate(got)
+    assert len(got) >= 1
+    for f in got:
+        assert _match(3, False, f, frames[3])
+
+
+def test_adjacent_channel_30_db_stronger():
+    sondes = [(1_000_003, 0), (1_020_003, 0)]
+    n = 24 * 1_280_000
+    iq, frames, symbols = synth.make_wideband_scene(sondes, n, fs=FS, ebn0_db=[20.0, 50.0], seed=33, device=DEV)
+    rx = WidebandReceiver(FS, sondes, chain="iq48", max_in=8 * 1_280_000)
+    got = []
+    for a in range(0, n, rx.max_in):
+        rx.submit(iq[a:a + rx.max_in].contiguous())
+        got.append(rx.frames())
+    got = np.concatenate(got)
+    _check_frames(got, [(f, t, False) for f, t in sondes], frames, symbols)
+
+
+def test_detect_then_decode():
+    iq, frames, symbols = synth.make_wideband_scene(SCENE, N_SCENE, fs=FS, ebn0_db=30.0, seed=45, device=DEV)
+    truth = np.array([t for _, t, _ in SCENE])
+    bws = [min(synth_rate(t), 40_000) for t in truth]
+    tu = SondeTuner(FS, 48_000, [(f, b) for (f, _, _), b in zip(SCENE, bws)], N_SCENE)
+    rows = tu.process(iq)
+    det = SondeDetector(len(SCENE), rows.shape[1])
+    det.submit(rows)
+    kind = det.results()["type"]
+    assert np.array_equal(kind, truth), (kind, truth)
+    rx = WidebandReceiver(FS, [(f, int(k)) for (f, _, _), k in zip(SCENE, kind)], chain="iq48", max_in=N_SCENE // 3)
+    got = []
+    for a in range(0, N_SCENE, rx.max_in):
+        rx.submit(iq[a:a + rx.max_in])
+        got.append(rx.frames())
+    _check_frames(np.concatenate(got), SCENE, frames, symbols)
+
+
+def synth_rate(t):
+    from sdrpp_radiosonde_amd.batch import VFO_RATE
+    return VFO_RATE[int(t)]
