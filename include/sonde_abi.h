@@ -404,6 +404,47 @@ int    sonde_tuner_retune(SondeTuner *t, uint32_t vfo, int32_t offset_hz);   /* 
 int    sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n_in,
                            void *out_dev /* complex64 rows */, size_t out_stride /* complex samples */, void *stream);
 
+/* ------------------------------------------------------------------ band scanner (DESIGN SPEC 3.10)
+ * Where in a wideband complex stream at rate_in (1..20 MHz, integer Hz) the sondes are: the step a person does by eye on the SDR++
+ * waterfall before dragging a VFO onto a carrier (/root/reference/src/main.cpp:55-68).  The GPU keeps Welch's averaged power spectrum
+ * of the stream (segments of fft_size samples, a power of two 1024 .. 16384, 50 % overlap, periodic Hann window; one double per bin,
+ * added in ascending segment order, so the spectrum is bit-identical however the stream is cut into submits); the host searches
+ * it in double (sonde_scan_search, no GPU: exactly reproducible) for candidates: offset, occupied bandwidth, C/N0.  The candidates'
+ * offsets are what sonde_tuner_create takes; the detector then tells their types.  Input kinds: SONDE_INPUT_IQ, SONDE_INPUT_IQ16,
+ * SONDE_INPUT_IQ8 (converted exactly; REAL is refused).  Ordinary stream semantics (as sonde_detect_submit), one stream per scanner;
+ * nothing synchronises before the spectrum is read. */
+typedef struct SondeScanner SondeScanner;
+typedef struct {
+	uint32_t struct_size;             /* sizeof(SondeScanParams) */
+	uint32_t smooth_hz;               /* width of the moving sum the peaks are taken from; 0 = 8000 */
+	uint32_t min_sep_hz;              /* a candidate is the maximum within +- this; 0 = 10000 */
+	uint32_t centroid_hz;             /* width of the centroid that gives the offset; 0 = 16000 */
+	float    threshold;               /* moving sum / its median over the band, a linear power ratio; 0 = 4.0 (6.02 dB) */
+} SondeScanParams;
+typedef struct {
+	int32_t  offset_hz;               /* centroid of the power above the noise floor, from the band's centre */
+	uint32_t bandwidth_hz;            /* between the 5 % and the 95 % point of the power above the floor within +- min_sep_hz */
+	float    cn0_dbhz;                /* that power over the noise density */
+	float    excess_db;               /* the moving sum at the peak over its median */
+	uint32_t bin;                     /* the peak's bin, 0 .. fft_size - 1 in ascending frequency: bin i <-> (i - fft_size / 2) rate_in / fft_size */
+} SondeScanCandidate;
+int  sonde_scan_create(uint32_t rate_in, uint32_t fft_size /* 0 = sonde_scan_auto_fft_size */, size_t max_in, int input_kind, int device, SondeScanner **out);
+void sonde_scan_destroy(SondeScanner *s);
+int  sonde_scan_fft_size(const SondeScanner *s);
+/* wide_dev: DEVICE pointer to n_in samples, 1 <= n_in <= max_in (no multiple is required: the unfinished segment is carried) */
+int  sonde_scan_submit(SondeScanner *s, const void *wide_dev, size_t n_in, void *stream);
+int  sonde_scan_reset(SondeScanner *s);                  /* accumulator, segment count and origin; queued work finishes first */
+long long sonde_scan_segments(SondeScanner *s);          /* whole segments since create / reset; synchronises */
+/* P[i], i = 0 .. fft_size - 1 in ascending frequency: the mean |FFT|^2 of the segments so far; synchronises; returns fft_size; an
+ * error before the first whole segment */
+int  sonde_scan_spectrum(SondeScanner *s, float *P, size_t cap);
+/* sonde_scan_spectrum + sonde_scan_search; returns the count found, writes min(count, cap) in ascending bin order; p NULL = defaults */
+int  sonde_scan_candidates(SondeScanner *s, const SondeScanParams *p, SondeScanCandidate *out, size_t cap);
+/* pure host, no GPU: the search of SPEC 3.10 over any spectrum of n bins in ascending frequency */
+int  sonde_scan_search(const float *P, uint32_t n, uint32_t rate_in, const SondeScanParams *p, SondeScanCandidate *out, size_t cap);
+int  sonde_scan_window(uint32_t n, float *w, size_t cap);       /* pure host: the float32 window; returns n (w may be NULL) */
+int  sonde_scan_auto_fft_size(uint32_t rate_in);         /* pure host: the smallest allowed power of two with rate_in / N <= 1000 Hz, at most 16384 */
+
 /* post-FEC derived quantities, as /root/reference/src/decode/decoder.hpp:132-174 computes them */
 float sonde_dewpt(float temp, float rh);
 float sonde_altitude_to_pressure(float alt);

@@ -4,6 +4,7 @@
     batch     SondeBatch (many 48 kS/s channels), SondeChannelizer (10 MS/s -> 512 bins), SondeVfo (VFO-rate front-end)
     detect    SondeDetector: the sonde type of each channel (sync-template correlation on the GPU); detect, then build the batch
     tuner     SondeTuner (VFOs at any offset over one wideband stream), WidebandReceiver (wideband stream -> tuner -> decoders)
+    scan      SondeScanner (where in a wideband stream the carriers are: averaged power spectrum on the GPU, candidate search), survey
     node      SondeNode: the one-process node-level host (libsonde_rccl.so, include/sonde_node.h): one batch per GPU, RCCL scatter of IQ rows
     shard     channel sharding for a rank-per-GPU host on plain torch.distributed (range arithmetic, scatter, frame gather)
     synth     synthetic signal generator for all seven sonde types (tests and bench; independent of the decoders' code)

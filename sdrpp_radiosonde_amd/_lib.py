@@ -51,6 +51,20 @@ class SondeTunerVfo(C.Structure):
     _fields_ = [("offset_hz", C.c_int32), ("bandwidth_hz", C.c_uint32)]
 
 
+class SondeScanParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("smooth_hz", C.c_uint32), ("min_sep_hz", C.c_uint32), ("centroid_hz", C.c_uint32),
+                ("threshold", C.c_float)]
+
+
+class SondeScanCandidate(C.Structure):
+    _fields_ = [("offset_hz", C.c_int32), ("bandwidth_hz", C.c_uint32), ("cn0_dbhz", C.c_float), ("excess_db", C.c_float),
+                ("bin", C.c_uint32)]
+
+
+CANDIDATE_DTYPE = np.dtype([("offset_hz", "<i4"), ("bandwidth_hz", "<u4"), ("cn0_dbhz", "<f4"), ("excess_db", "<f4"), ("bin", "<u4")])
+assert CANDIDATE_DTYPE.itemsize == C.sizeof(SondeScanCandidate)
+
+
 class SondeBatchConfig(C.Structure):
     _fields_ = [("n_channels", C.c_uint32), ("types", C.POINTER(C.c_uint8)), ("max_samples", C.c_uint32),
                 ("input_kind", C.c_int32), ("device", C.c_int32), ("flags", C.c_uint32), ("launch_units", C.c_uint32),
@@ -87,6 +101,8 @@ ABI_SYMBOLS = [
     "sonde_detect_read", "sonde_detect_templates",
     "sonde_tuner_ratio", "sonde_tuner_taps", "sonde_tuner_create", "sonde_tuner_destroy", "sonde_tuner_out_samples", "sonde_tuner_retune",
     "sonde_tuner_process",
+    "sonde_scan_create", "sonde_scan_destroy", "sonde_scan_fft_size", "sonde_scan_submit", "sonde_scan_reset", "sonde_scan_segments",
+    "sonde_scan_spectrum", "sonde_scan_candidates", "sonde_scan_search", "sonde_scan_window", "sonde_scan_auto_fft_size",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -223,6 +239,20 @@ def load() -> C.CDLL:
         L.sonde_tuner_out_samples.restype = C.c_size_t
         L.sonde_tuner_retune.argtypes = [vp, C.c_uint32, C.c_int32]
         L.sonde_tuner_process.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp]
+    if hasattr(L, "sonde_scan_create"):
+        L.sonde_scan_create.argtypes = [C.c_uint32, C.c_uint32, C.c_size_t, C.c_int, C.c_int, C.POINTER(vp)]
+        L.sonde_scan_destroy.argtypes = [vp]
+        L.sonde_scan_destroy.restype = None
+        L.sonde_scan_fft_size.argtypes = [vp]
+        L.sonde_scan_submit.argtypes = [vp, vp, C.c_size_t, vp]
+        L.sonde_scan_reset.argtypes = [vp]
+        L.sonde_scan_segments.argtypes = [vp]
+        L.sonde_scan_segments.restype = C.c_longlong
+        L.sonde_scan_spectrum.argtypes = [vp, vp, C.c_size_t]
+        L.sonde_scan_candidates.argtypes = [vp, C.POINTER(SondeScanParams), vp, C.c_size_t]
+        L.sonde_scan_search.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(SondeScanParams), vp, C.c_size_t]
+        L.sonde_scan_window.argtypes = [C.c_uint32, vp, C.c_size_t]
+        L.sonde_scan_auto_fft_size.argtypes = [C.c_uint32]
     f = C.c_float
     L.sonde_gpx_open.restype = vp
     L.sonde_gpx_open.argtypes = [C.c_char_p]
