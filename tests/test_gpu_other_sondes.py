@@ -69,7 +69,7 @@ def test_mixed_types_per_channel_dispatch(oracle):
 
 
 def test_m20_frames_bit_exact(oracle):
-    """M20 (label "M10/M20", /root/reference/src/main.hpp:48): 70-byte frames through the same framer; the length byte
+    """M20 (the reference lists the type as "M10/M20" in its table of sonde types, main.hpp): 70-byte frames through the same framer; the length byte
     selects where the checksum sits.  GPU records == oracle records, and equal to what was transmitted."""
     C, n = 8, TILE * 40
     sb = synth.make_batch(3, C, n, seed=47, ebn0_db=28.0, m20=True)
