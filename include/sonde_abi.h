@@ -388,7 +388,10 @@ int  sonde_detect_templates(int type, int8_t *s, int cap);    /* returns L; writ
  * VFO of the reference's chain (/root/reference/src/main.cpp:55-68) for any number of sondes at any offset, M10 / M20 included.
  * Input kinds: SONDE_INPUT_IQ, SONDE_INPUT_IQ16, SONDE_INPUT_IQ8 (converted exactly; REAL is refused).  Rows are bit-identical however
  * the stream is cut into submits.  Ordinary stream semantics (as sonde_detect_submit); the offsets travel with each launch, so a
- * retune reaches the next submit only. */
+ * retune reaches the next submit only.  A plain retune restarts the mixer's phase "as if tuned there since create" (one phase jump
+ * in the row at the boundary); a continuous retune picks theta in phi = (offset * n + theta) mod rate_in so that the row's phase runs
+ * on across the boundary (the mixer's phase is kept at the sample the filter's group delay puts under the submit's first output),
+ * which is what a loop that follows a drifting carrier wants. */
 typedef struct { int32_t offset_hz; uint32_t bandwidth_hz; /* 0 = rate_out */ } SondeTunerVfo;
 typedef struct SondeTuner SondeTuner;
 int    sonde_tuner_ratio(uint32_t rate_in, uint32_t rate_out, int *up, int *down);
@@ -398,7 +401,9 @@ int    sonde_tuner_create(uint32_t rate_in, uint32_t rate_out, uint32_t n_vfos, 
                           size_t max_in, int input_kind, int device, SondeTuner **out);
 void   sonde_tuner_destroy(SondeTuner *t);
 size_t sonde_tuner_out_samples(const SondeTuner *t, size_t n_in);         /* n_in * up / down */
-int    sonde_tuner_retune(SondeTuner *t, uint32_t vfo, int32_t offset_hz);   /* from the next submit on */
+int    sonde_tuner_retune(SondeTuner *t, uint32_t vfo, int32_t offset_hz);   /* from the next submit on; theta = 0 */
+/* from the next submit on, the row's phase continuous at that submit's first output */
+int    sonde_tuner_retune_continuous(SondeTuner *t, uint32_t vfo, int32_t offset_hz);
 /* wide_dev: DEVICE pointer to n_in samples (a multiple of down, <= max_in); out_dev: VFO k's n_out complex64 samples at
  * element k * out_stride (complex samples; sonde_row_stride(n_out, SONDE_INPUT_IQ) writes straight into a SondeBatch input buffer) */
 int    sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n_in,
@@ -444,6 +449,55 @@ int  sonde_scan_candidates(SondeScanner *s, const SondeScanParams *p, SondeScanC
 int  sonde_scan_search(const float *P, uint32_t n, uint32_t rate_in, const SondeScanParams *p, SondeScanCandidate *out, size_t cap);
 int  sonde_scan_window(uint32_t n, float *w, size_t cap);       /* pure host: the float32 window; returns n (w may be NULL) */
 int  sonde_scan_auto_fft_size(uint32_t rate_in);         /* pure host: the smallest allowed power of two with rate_in / N <= 1000 Hz, at most 16384 */
+
+/* ------------------------------------------------------------------ carrier meter and tracking step (DESIGN SPEC 3.11)
+ * How far each VFO's carrier is from the VFO's centre, and how strong it is, several times a second: what a loop needs to follow a
+ * sonde whose transmitter drifts by kilohertz during the ascent.  The meter takes n_rows complex64 rows at `rate` (what
+ * sonde_tuner_process writes) and keeps, per row and per look of look_samples samples counted from the row's last restart,
+ * A = sum x[m] conj(x[m - lag]) and P = sum |x[m]|^2: float32 products, each aligned 256-sample block summed in a fixed order, the
+ * block sums added into doubles in ascending order, so the looks are bit-identical however the stream is cut into submits.  One
+ * launch per submit (per 512 rows) on the caller's stream, ordinary stream semantics (as sonde_detect_submit), one stream per meter;
+ * nothing synchronises before the looks are read.  sonde_track_step is the loop's rule: pure host, exactly reproducible.  The
+ * caller applies its result with sonde_tuner_retune_continuous and sonde_track_restart. */
+#define SONDE_TRACK_DEADBAND_HZ 400
+#define SONDE_TRACK_MAX_STEP_HZ 4000
+typedef struct SondeTracker SondeTracker;
+typedef struct {
+	uint32_t row, reserved;
+	uint64_t look;                    /* index of the look, counted from the row's last restart (or create) */
+	double   a_re, a_im;              /* A */
+	double   p;                       /* P */
+} SondeTrackLook;
+typedef struct {
+	uint32_t struct_size;             /* sizeof(SondeTrackParams) */
+	uint32_t deadband_hz;             /* hold while |err_hz| is below this; 0 = SONDE_TRACK_DEADBAND_HZ */
+	uint32_t max_step_hz;             /* largest step of one look; 0 = SONDE_TRACK_MAX_STEP_HZ */
+} SondeTrackParams;
+/* pure host: the defaults of look_samples (256 ceil(rate / 2560), about 0.1 s) and lag (max(1, rate div 24000)) */
+int  sonde_track_defaults(uint32_t rate, uint32_t *look_samples, uint32_t *lag);
+/* look_samples: a multiple of 256 (0 = default); lag: 1 .. 64 (0 = default); input_kind: SONDE_INPUT_IQ (anything else is refused:
+ * REAL rows carry no carrier).  No CPU path: a device is required. */
+int  sonde_track_create(uint32_t n_rows, uint32_t rate, uint32_t max_samples, uint32_t look_samples, uint32_t lag, int input_kind,
+                        int device, SondeTracker **out);
+void sonde_track_destroy(SondeTracker *t);
+int  sonde_track_look_samples(const SondeTracker *t);
+int  sonde_track_lag(const SondeTracker *t);
+int  sonde_track_ring(const SondeTracker *t);      /* looks kept per row between two reads: at least 16 */
+/* rows_dev: DEVICE pointer, row r at element r * row_stride (complex samples); n_samples: a positive multiple of 256, <= max_samples */
+int  sonde_track_submit(SondeTracker *t, const void *rows_dev, size_t n_samples, size_t row_stride, void *stream);
+/* synchronises; writes the looks finished since the last call, row by row, oldest first (at most sonde_track_ring() per row: older
+ * ones are dropped, dropped[r] counts them; dropped may be NULL); cap >= n_rows * sonde_track_ring() always suffices; returns the count */
+int  sonde_track_results(SondeTracker *t, SondeTrackLook *out, size_t cap, uint64_t *dropped /* n_rows */);
+/* drops the row's unfinished look and lag history: its next look starts at the next submit's first sample, with index 0 */
+int  sonde_track_restart(SondeTracker *t, uint32_t row);
+/* pure host, in double: err_hz = rate / (2 pi lag) * atan2(a_im, a_re); level_db = 10 log10(p / look_samples); q = |A| / P (0 if P = 0) */
+double sonde_track_err_hz(uint32_t rate, uint32_t lag, double a_re, double a_im);
+double sonde_track_level_db(double p, uint32_t look_samples);
+double sonde_track_quality(double a_re, double a_im, double p);
+/* pure host, no GPU: if |err_hz| >= deadband_hz the new offset is offset_hz + rnd(err_hz), the step clamped to +- max_step_hz, the
+ * result clamped so that |offset| + bandwidth_hz / 2 <= rate_in / 2; else offset_hz.  Returns 1 if it moved, 0 if not; p NULL = defaults */
+int  sonde_track_step(int32_t offset_hz, uint32_t bandwidth_hz, uint32_t rate_in, uint32_t rate, uint32_t lag, const SondeTrackLook *look,
+                      const SondeTrackParams *p, int32_t *new_offset);
 
 /* post-FEC derived quantities, as /root/reference/src/decode/decoder.hpp:132-174 computes them */
 float sonde_dewpt(float temp, float rh);

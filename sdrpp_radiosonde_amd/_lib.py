@@ -61,6 +61,20 @@ class SondeScanCandidate(C.Structure):
                 ("bin", C.c_uint32)]
 
 
+class SondeTrackLook(C.Structure):
+    _fields_ = [("row", C.c_uint32), ("reserved", C.c_uint32), ("look", C.c_uint64), ("a_re", C.c_double), ("a_im", C.c_double),
+                ("p", C.c_double)]
+
+
+class SondeTrackParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("deadband_hz", C.c_uint32), ("max_step_hz", C.c_uint32)]
+
+
+LOOK_DTYPE = np.dtype([("row", "<u4"), ("reserved", "<u4"), ("look", "<u8"), ("a_re", "<f8"), ("a_im", "<f8"), ("p", "<f8")])
+assert LOOK_DTYPE.itemsize == C.sizeof(SondeTrackLook)
+TRACK_DEADBAND_HZ, TRACK_MAX_STEP_HZ = 400, 4000          # SONDE_TRACK_DEADBAND_HZ, SONDE_TRACK_MAX_STEP_HZ
+
+
 CANDIDATE_DTYPE = np.dtype([("offset_hz", "<i4"), ("bandwidth_hz", "<u4"), ("cn0_dbhz", "<f4"), ("excess_db", "<f4"), ("bin", "<u4")])
 assert CANDIDATE_DTYPE.itemsize == C.sizeof(SondeScanCandidate)
 
@@ -100,7 +114,10 @@ ABI_SYMBOLS = [
     "sonde_detect_create", "sonde_detect_destroy", "sonde_detect_submit", "sonde_detect_results", "sonde_detect_reset", "sonde_detect_thresholds",
     "sonde_detect_read", "sonde_detect_templates",
     "sonde_tuner_ratio", "sonde_tuner_taps", "sonde_tuner_create", "sonde_tuner_destroy", "sonde_tuner_out_samples", "sonde_tuner_retune",
-    "sonde_tuner_process",
+    "sonde_tuner_process", "sonde_tuner_retune_continuous",
+    "sonde_track_defaults", "sonde_track_create", "sonde_track_destroy", "sonde_track_look_samples", "sonde_track_lag", "sonde_track_ring",
+    "sonde_track_submit", "sonde_track_results", "sonde_track_restart", "sonde_track_err_hz", "sonde_track_level_db", "sonde_track_quality",
+    "sonde_track_step",
     "sonde_scan_create", "sonde_scan_destroy", "sonde_scan_fft_size", "sonde_scan_submit", "sonde_scan_reset", "sonde_scan_segments",
     "sonde_scan_spectrum", "sonde_scan_candidates", "sonde_scan_search", "sonde_scan_window", "sonde_scan_auto_fft_size",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
@@ -253,6 +270,26 @@ def load() -> C.CDLL:
         L.sonde_scan_search.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(SondeScanParams), vp, C.c_size_t]
         L.sonde_scan_window.argtypes = [C.c_uint32, vp, C.c_size_t]
         L.sonde_scan_auto_fft_size.argtypes = [C.c_uint32]
+    if hasattr(L, "sonde_track_create"):
+        u32 = C.c_uint32
+        L.sonde_tuner_retune_continuous.argtypes = [vp, u32, C.c_int32]
+        L.sonde_track_defaults.argtypes = [u32, C.POINTER(u32), C.POINTER(u32)]
+        L.sonde_track_create.argtypes = [u32, u32, u32, u32, u32, C.c_int, C.c_int, C.POINTER(vp)]
+        L.sonde_track_destroy.argtypes = [vp]
+        L.sonde_track_destroy.restype = None
+        L.sonde_track_look_samples.argtypes = [vp]
+        L.sonde_track_lag.argtypes = [vp]
+        L.sonde_track_ring.argtypes = [vp]
+        L.sonde_track_submit.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+        L.sonde_track_results.argtypes = [vp, vp, C.c_size_t, vp]
+        L.sonde_track_restart.argtypes = [vp, u32]
+        L.sonde_track_err_hz.argtypes = [u32, u32, C.c_double, C.c_double]
+        L.sonde_track_err_hz.restype = C.c_double
+        L.sonde_track_level_db.argtypes = [C.c_double, u32]
+        L.sonde_track_level_db.restype = C.c_double
+        L.sonde_track_quality.argtypes = [C.c_double, C.c_double, C.c_double]
+        L.sonde_track_quality.restype = C.c_double
+        L.sonde_track_step.argtypes = [C.c_int32, u32, u32, u32, u32, C.POINTER(SondeTrackLook), C.POINTER(SondeTrackParams), C.POINTER(C.c_int32)]
     f = C.c_float
     L.sonde_gpx_open.restype = vp
     L.sonde_gpx_open.argtypes = [C.c_char_p]

@@ -1,0 +1,265 @@
+// track.hip -- carrier meter (DESIGN SPEC 3.11): per row of complex samples at rate R (the rows sonde_tuner_process writes) and per
+// look of L samples, the lag-d autocorrelation A = sum x[m] conj(x[m - d]) and the power P = sum |x[m]|^2, from which the host reads
+// how far the carrier is from the VFO's centre (arg A), how strong it is (P) and how much of it is carrier (|A| / P); and the
+// pure-host step rule that turns one look into the VFO's next offset (sonde_track_step).  It stands where a person watches the
+// SDR++ waterfall and drags the VFO after a drifting sonde (/root/reference/src/main.cpp:55-68).
+//
+// One workgroup per (row, look-piece): the part of one look that lies in this submit.  Wave w takes the piece's 256-sample blocks
+// w, w + 4, ...; lane l the samples l, l + 64, l + 128, l + 192 of the block, products in float32 with explicit fmaf, the four added
+// in ascending order, then a fixed xor butterfly over the 64 lanes.  The block sums go through LDS, 32 blocks at a time; three lanes
+// (one per quantity) add them to a double each in ascending block order.  A look's sums therefore depend on the row's samples and
+// its restart points alone, never on how the stream was cut into submits.  A finished look goes to the row's ring, an unfinished
+// one to the carry; the carry and the lag history (the row's last d samples) are double-buffered, because the workgroup that
+// writes them is not the one that reads them.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdlib.h>
+#include <deque>
+#include <string>
+#include <vector>
+#include "launch.h"
+#include "../../include/sonde_abi.h"
+
+#define TK_WG     256
+#define TK_BLK    256                   // samples per block
+#define TK_CHUNK  32                    // blocks per trip through LDS (8 per wave)
+#define TK_VMAX   512                   // rows per launch: their look phases and ring slots travel with the launch, by value (2 KB)
+#define TK_DMAX   64                    // largest lag
+#define TK_MAXLB  16384                 // largest look, in blocks (the phase travels in 15 bits)
+#define TK_FRESH  0x8000u               // the row starts here: no lag history, no carry
+
+struct SdTrackRows { uint16_t ph[TK_VMAX]; uint16_t slot[TK_VMAX]; };     // blocks into the row's current look (| TK_FRESH); ring slot of its next look
+
+__global__ __launch_bounds__(TK_WG) void sd_track_kernel(const float2 *__restrict__ rows, size_t stride, uint32_t nb, uint32_t LB, uint32_t d,
+	SdTrackRows rs, uint32_t vbase, const float2 *__restrict__ hist_in, float2 *__restrict__ hist_out,
+	const double *__restrict__ carry_in, double *__restrict__ carry_out, double *__restrict__ ring, uint32_t ring_len)
+{
+	__shared__ float s_bs[3][TK_CHUNK];
+	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	const uint32_t row = vbase + blockIdx.y;
+	const uint32_t ph = rs.ph[blockIdx.y] & (TK_FRESH - 1u);
+	const bool fresh = (rs.ph[blockIdx.y] & TK_FRESH) != 0;
+	// piece p of the row: blocks [b0, b1) of the submit
+	const uint32_t first = LB - ph;                                       // blocks of piece 0 if the submit is long enough
+	const uint32_t p = blockIdx.x;
+	const uint32_t b0 = p == 0 ? 0u : first + (p - 1u) * LB;
+	if (b0 >= nb) return;
+	const uint32_t b1 = min(nb, p == 0 ? first : b0 + LB);
+	const float2 *x = rows + (size_t)row * stride;
+	const float2 *hi = hist_in + (size_t)row * TK_DMAX;
+	double acc = 0.0;
+	if (p == 0 && ph > 0 && tid < 3) acc = carry_in[(size_t)row * 3 + tid];
+	for (uint32_t c0 = b0; c0 < b1; c0 += TK_CHUNK) {
+		const uint32_t cn = min((uint32_t)TK_CHUNK, b1 - c0);
+		for (uint32_t q = wave; q < cn; q += 4) {
+			const int64_t m0 = (int64_t)(c0 + q) * TK_BLK + lane;
+			float2 xv[4], yv[4];
+#pragma unroll
+			for (int r = 0; r < 4; r++) {
+				const int64_t m = m0 + 64 * r, ml = m - (int64_t)d;
+				xv[r] = x[m];
+				yv[r] = ml >= 0 ? x[ml] : (fresh ? make_float2(0.0f, 0.0f) : hi[ml + (int64_t)d]);
+			}
+			float ar = 0.0f, ai = 0.0f, pw = 0.0f;
+#pragma unroll
+			for (int r = 0; r < 4; r++) {
+				const float cr = __builtin_fmaf(xv[r].x, yv[r].x, xv[r].y * yv[r].y);
+				const float ci = __builtin_fmaf(xv[r].y, yv[r].x, -(xv[r].x * yv[r].y));
+				const float pp = __builtin_fmaf(xv[r].x, xv[r].x, xv[r].y * xv[r].y);
+				ar = r ? ar + cr : cr; ai = r ? ai + ci : ci; pw = r ? pw + pp : pp;
+			}
+#pragma unroll
+			for (int o = 32; o >= 1; o >>= 1) { ar += __shfl_xor(ar, o, 64); ai += __shfl_xor(ai, o, 64); pw += __shfl_xor(pw, o, 64); }
+			if (lane == 0) { s_bs[0][q] = ar; s_bs[1][q] = ai; s_bs[2][q] = pw; }
+		}
+		__syncthreads();
+		if (tid < 3)
+			for (uint32_t q = 0; q < cn; q++) acc += (double)s_bs[tid][q];
+		__syncthreads();
+	}
+	const bool done = (p == 0 ? ph : 0u) + (b1 - b0) == LB;                // the look ends in this submit
+	if (tid < 3) {
+		if (done) ring[((size_t)row * ring_len + (rs.slot[blockIdx.y] + p) % ring_len) * 3 + tid] = acc;
+		else carry_out[(size_t)row * 3 + tid] = acc;
+	}
+	if (b1 == nb && tid < d) hist_out[(size_t)row * TK_DMAX + tid] = x[(size_t)nb * TK_BLK - d + tid];
+}
+
+// ---------------------------------------------------------------- host
+struct SdTrackPending { uint64_t seq, look; };
+struct SondeTracker {
+	int device = 0;
+	uint32_t n_rows = 0, rate = 0, max_samples = 0, L = 0, LB = 0, d = 0, ring_len = 0;
+	unsigned parity = 0;
+	hipStream_t last = nullptr;
+	std::vector<uint32_t> ph;           // blocks into the current look, per row
+	std::vector<uint8_t> fresh;         // the row starts at the next submit
+	std::vector<uint64_t> look, seq;    // index of the look in progress (from the last restart); looks finished since create
+	std::vector<std::deque<SdTrackPending>> pending;
+	std::vector<uint64_t> dropped;
+	float2 *d_hist[2] = {};
+	double *d_carry[2] = {}, *d_ring = nullptr;
+};
+
+static const double TK_PI = 3.14159265358979323846;
+
+extern "C" void sonde_track_destroy(SondeTracker *t)
+{
+	if (!t) return;
+	(void)hipSetDevice(t->device);
+	(void)hipFree(t->d_hist[0]); (void)hipFree(t->d_hist[1]); (void)hipFree(t->d_carry[0]); (void)hipFree(t->d_carry[1]); (void)hipFree(t->d_ring);
+	delete t;
+}
+
+extern "C" int sonde_track_defaults(uint32_t rate, uint32_t *look_samples, uint32_t *lag)
+{
+	if (rate < 5000u || rate > 100000u) return sd_fail("sonde_track_defaults: rate must be 5000 .. 100 000 Hz");
+	if (look_samples) *look_samples = TK_BLK * ((rate + 2559u) / 2560u);
+	if (lag) *lag = rate / 24000u > 1u ? rate / 24000u : 1u;
+	return 0;
+}
+
+extern "C" int sonde_track_create(uint32_t n_rows, uint32_t rate, uint32_t max_samples, uint32_t look_samples, uint32_t lag, int input_kind,
+	int device, SondeTracker **out)
+{
+	if (!out || !n_rows) return sd_fail("sonde_track_create: bad argument");
+	if (input_kind != SONDE_INPUT_IQ)
+		return sd_fail("sonde_track_create: input_kind must be SONDE_INPUT_IQ (the meter takes the tuner's complex64 rows; REAL rows carry no carrier)");
+	uint32_t L0, d0;
+	if (sonde_track_defaults(rate, &L0, &d0)) return sd_fail("sonde_track_create: rate must be 5000 .. 100 000 Hz");
+	const uint32_t L = look_samples ? look_samples : L0, d = lag ? lag : d0;
+	if (L % TK_BLK || L / TK_BLK > TK_MAXLB) return sd_fail("sonde_track_create: look_samples must be a multiple of 256, at most 4 194 304 (0 = about 0.1 s)");
+	if (d > TK_DMAX) return sd_fail("sonde_track_create: lag must be 1 .. 64 (0 = by rate)");
+	if (!max_samples || max_samples % TK_BLK || max_samples >= (1u << 30)) return sd_fail("sonde_track_create: max_samples must be a positive multiple of 256 below 2^30");
+	if ((max_samples / TK_BLK) / (L / TK_BLK) + 2 > 65535u) return sd_fail("sonde_track_create: max_samples holds more than 65 533 looks");
+	int ndev = 0;
+	hipError_t e = hipGetDeviceCount(&ndev);
+	if (e != hipSuccess || device < 0 || device >= ndev) return sd_fail("sonde_track_create: no such HIP device (this library has no CPU path)", e);
+	if ((e = hipSetDevice(device)) != hipSuccess) return sd_fail("hipSetDevice", e);
+	SondeTracker *t = new SondeTracker;
+	t->device = device; t->n_rows = n_rows; t->rate = rate; t->max_samples = max_samples; t->L = L; t->LB = L / TK_BLK; t->d = d;
+	const uint32_t per_submit = (max_samples / TK_BLK) / t->LB + 2;       // looks one submit can finish, and one more
+	t->ring_len = per_submit > 16u ? per_submit : 16u;
+	t->ph.assign(n_rows, 0); t->fresh.assign(n_rows, 1); t->look.assign(n_rows, 0); t->seq.assign(n_rows, 0);
+	t->pending.resize(n_rows); t->dropped.assign(n_rows, 0);
+	const size_t hb = (size_t)n_rows * TK_DMAX * sizeof(float2), cb = (size_t)n_rows * 3 * sizeof(double), rb = cb * t->ring_len;
+	bool ok = hipMalloc((void **)&t->d_hist[0], hb) == hipSuccess && hipMalloc((void **)&t->d_hist[1], hb) == hipSuccess &&
+	          hipMalloc((void **)&t->d_carry[0], cb) == hipSuccess && hipMalloc((void **)&t->d_carry[1], cb) == hipSuccess &&
+	          hipMalloc((void **)&t->d_ring, rb) == hipSuccess;
+	ok = ok && hipMemset(t->d_hist[0], 0, hb) == hipSuccess && hipMemset(t->d_hist[1], 0, hb) == hipSuccess &&
+	     hipMemset(t->d_carry[0], 0, cb) == hipSuccess && hipMemset(t->d_carry[1], 0, cb) == hipSuccess && hipMemset(t->d_ring, 0, rb) == hipSuccess;
+	if (!ok) { sonde_track_destroy(t); return sd_fail("sonde_track_create: device allocation failed"); }
+	*out = t;
+	return 0;
+}
+
+extern "C" int sonde_track_look_samples(const SondeTracker *t) { return t ? (int)t->L : sd_fail("sonde_track_look_samples: null argument"); }
+extern "C" int sonde_track_lag(const SondeTracker *t) { return t ? (int)t->d : sd_fail("sonde_track_lag: null argument"); }
+extern "C" int sonde_track_ring(const SondeTracker *t) { return t ? (int)t->ring_len : sd_fail("sonde_track_ring: null argument"); }
+
+extern "C" int sonde_track_submit(SondeTracker *t, const void *rows_dev, size_t n_samples, size_t row_stride, void *stream)
+{
+	if (!t || !rows_dev) return sd_fail("sonde_track_submit: null argument");
+	if (!n_samples || n_samples % TK_BLK || n_samples > t->max_samples)
+		return sd_fail("sonde_track_submit: n_samples must be a positive multiple of 256 and <= max_samples");
+	if (row_stride < n_samples) return sd_fail("sonde_track_submit: row_stride shorter than the row");
+	if ((uintptr_t)rows_dev & 7u) return sd_fail("sonde_track_submit: rows must be 8-byte aligned");
+	hipError_t e = hipSetDevice(t->device);
+	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	hipStream_t s = (hipStream_t)stream;
+	const uint32_t nb = (uint32_t)(n_samples / TK_BLK), LB = t->LB;
+	const float2 *h_in = t->d_hist[t->parity & 1];
+	float2 *h_out = t->d_hist[(t->parity + 1) & 1];
+	const double *c_in = t->d_carry[t->parity & 1];
+	double *c_out = t->d_carry[(t->parity + 1) & 1];
+	const dim3 wg(TK_WG);
+	for (uint32_t vb = 0; vb < t->n_rows; vb += TK_VMAX) {
+		const uint32_t nv = t->n_rows - vb < TK_VMAX ? t->n_rows - vb : TK_VMAX;
+		SdTrackRows rs = {};
+		for (uint32_t i = 0; i < nv; i++) {
+			rs.ph[i] = (uint16_t)(t->ph[vb + i] | (t->fresh[vb + i] ? TK_FRESH : 0u));
+			rs.slot[i] = (uint16_t)(t->seq[vb + i] % t->ring_len);
+		}
+		const dim3 grid((nb + LB - 1) / LB + 1, nv);
+		hipLaunchKernelGGL(sd_track_kernel, grid, wg, 0, s, (const float2 *)rows_dev, row_stride, nb, LB, t->d, rs, vb, h_in, h_out, c_in, c_out,
+			t->d_ring, t->ring_len);
+	}
+	if ((e = hipGetLastError()) != hipSuccess) return sd_fail("sd_track_kernel launch", e);
+	for (uint32_t r = 0; r < t->n_rows; r++) {
+		const uint32_t tot = t->ph[r] + nb, fin = tot / LB;
+		for (uint32_t i = 0; i < fin; i++) {
+			t->pending[r].push_back({t->seq[r]++, t->look[r]++});
+			if (t->pending[r].size() > t->ring_len) { t->pending[r].pop_front(); t->dropped[r]++; }
+		}
+		t->ph[r] = tot % LB;
+		t->fresh[r] = 0;
+	}
+	t->parity++;
+	t->last = s;
+	return 0;
+}
+
+extern "C" int sonde_track_restart(SondeTracker *t, uint32_t row)
+{
+	if (!t) return sd_fail("sonde_track_restart: null argument");
+	if (row >= t->n_rows) return sd_fail("sonde_track_restart: no such row");
+	t->ph[row] = 0; t->fresh[row] = 1; t->look[row] = 0;
+	return 0;
+}
+
+extern "C" int sonde_track_results(SondeTracker *t, SondeTrackLook *out, size_t cap, uint64_t *dropped)
+{
+	if (!t || (!out && cap)) return sd_fail("sonde_track_results: null argument");
+	size_t count = 0;
+	for (uint32_t r = 0; r < t->n_rows; r++) count += t->pending[r].size();
+	if (cap < count) return sd_fail("sonde_track_results: the buffer is shorter than n_rows * sonde_track_ring()");
+	hipError_t e = hipSetDevice(t->device);
+	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	if ((e = hipStreamSynchronize(t->last)) != hipSuccess) return sd_fail("sonde_track_results: hipStreamSynchronize", e);
+	std::vector<double> ring((size_t)t->n_rows * t->ring_len * 3);
+	if (count && (e = hipMemcpy(ring.data(), t->d_ring, ring.size() * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess)
+		return sd_fail("sonde_track_results: hipMemcpy", e);
+	size_t k = 0;
+	for (uint32_t r = 0; r < t->n_rows; r++) {
+		for (const SdTrackPending &p : t->pending[r]) {
+			const double *v = ring.data() + ((size_t)r * t->ring_len + p.seq % t->ring_len) * 3;
+			out[k].row = r; out[k].reserved = 0; out[k].look = p.look; out[k].a_re = v[0]; out[k].a_im = v[1]; out[k].p = v[2];
+			k++;
+		}
+		t->pending[r].clear();
+		if (dropped) dropped[r] = t->dropped[r];
+		t->dropped[r] = 0;
+	}
+	return (int)count;
+}
+
+// ---------------------------------------------------------------- the host conversions and the step rule (SPEC 3.11: pure host, double)
+extern "C" double sonde_track_err_hz(uint32_t rate, uint32_t lag, double a_re, double a_im)
+{
+	return (double)rate / (2.0 * TK_PI * (double)lag) * atan2(a_im, a_re);
+}
+
+extern "C" double sonde_track_level_db(double p, uint32_t look_samples) { return 10.0 * log10(p / (double)look_samples); }
+
+extern "C" double sonde_track_quality(double a_re, double a_im, double p) { return p > 0.0 ? sqrt(a_re * a_re + a_im * a_im) / p : 0.0; }
+
+extern "C" int sonde_track_step(int32_t offset_hz, uint32_t bandwidth_hz, uint32_t rate_in, uint32_t rate, uint32_t lag, const SondeTrackLook *look,
+	const SondeTrackParams *p, int32_t *new_offset)
+{
+	if (!look || !new_offset) return sd_fail("sonde_track_step: null argument");
+	if (p && p->struct_size != sizeof(SondeTrackParams)) return sd_fail("sonde_track_step: SondeTrackParams.struct_size is not sizeof(SondeTrackParams)");
+	if (!rate || !lag || !rate_in || bandwidth_hz > rate_in) return sd_fail("sonde_track_step: rate, lag and rate_in must be positive, bandwidth_hz at most rate_in");
+	const double deadband = p && p->deadband_hz ? p->deadband_hz : (double)SONDE_TRACK_DEADBAND_HZ;
+	const double max_step = p && p->max_step_hz ? p->max_step_hz : (double)SONDE_TRACK_MAX_STEP_HZ;
+	const double err = sonde_track_err_hz(rate, lag, look->a_re, look->a_im);
+	int64_t f = offset_hz;
+	if (fabs(err) >= deadband) {
+		double step = floor(err + 0.5);
+		step = step > max_step ? max_step : step < -max_step ? -max_step : step;
+		f += (int64_t)step;
+		const int64_t lim = ((int64_t)rate_in - (int64_t)bandwidth_hz) / 2;      // |offset| + bandwidth / 2 <= rate_in / 2
+		f = f > lim ? lim : f < -lim ? -lim : f;
+	}
+	*new_offset = (int32_t)f;
+	return f != offset_hz;
+}

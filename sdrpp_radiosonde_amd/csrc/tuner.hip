@@ -23,11 +23,11 @@
 #define TN_WG    256
 #define TN_JT    64                     // outputs per workgroup (16 per wave)
 #define TN_SEG   4096                   // samples per LDS segment (32 KB of float2)
-#define TN_VMAX  64                     // VFOs per launch: their mixer steps travel with the launch, by value (256 B of arguments)
+#define TN_VMAX  64                     // VFOs per launch: their mixer steps and phase offsets travel with the launch, by value (512 B of arguments)
 #define TN_LOB   12                     // mixer: phi = hi * 2^12 + lo, two tables
 #define TN_MAXUP 64
 
-struct SdTunerOffs { uint32_t F[TN_VMAX]; };      // f_k mod Fs of the launch's VFOs
+struct SdTunerOffs { uint32_t F[TN_VMAX], TH[TN_VMAX]; };      // f_k mod Fs and the phase offset theta_k of the launch's VFOs
 
 // e = H[hi] (1 + D[lo]), D = exp(-2 pi i lo / Fs) - 1 (|D| <= 0.026): about 2^-24 per component (SPEC 3.9 allows 2^-22)
 static __device__ __forceinline__ float2 tn_phasor(uint32_t phi, const float2 *__restrict__ th, const float2 *__restrict__ tl)
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(TN_WG) void sd_tuner_kernel(const void *__restrict_
 	__shared__ float2 s_v[TN_SEG];
 	const sd_iq_t<K> *x = (const sd_iq_t<K> *)xin;        // (a void pointer in the signature: sd_iq_t names an anonymous enum, mangled apart on host and device)
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const uint32_t k = vbase + blockIdx.y, F = offs.F[blockIdx.y];
+	const uint32_t k = vbase + blockIdx.y, F = offs.F[blockIdx.y], TH = offs.TH[blockIdx.y];
 	const int32_t T = (int32_t)vT[k];
 	const float *g = taps + tapoff[k];
 	const uint32_t jt0 = blockIdx.x * TN_JT;
@@ -69,7 +69,8 @@ __global__ __launch_bounds__(TN_WG) void sd_tuner_kernel(const void *__restrict_
 	for (int32_t seg_hi = w_max + 1; seg_hi > w_min;) {
 		const int32_t seg_lo = max(w_min, seg_hi - TN_SEG), len = seg_hi - seg_lo;
 		const int64_t s0 = n_base - (int64_t)H + seg_lo + tid;
-		uint32_t phi = (uint32_t)(((uint64_t)F * (uint64_t)(((s0 % (int64_t)fs) + (int64_t)fs) % (int64_t)fs)) % fs);
+		uint32_t phi = (uint32_t)(((uint64_t)F * (uint64_t)(((s0 % (int64_t)fs) + (int64_t)fs) % (int64_t)fs)) % fs) + TH;      // both < Fs <= 2e7
+		phi -= phi >= fs ? fs : 0u;
 		for (int32_t i = tid; i < len; i += TN_WG) {
 			const int32_t w = seg_lo + i;
 			const float2 xv = w < (int32_t)H ? hist[w] : sd_iq_f2<K>(x[w - (int32_t)H]);
@@ -124,6 +125,7 @@ struct SondeTuner {
 	uint32_t fs = 0, rate_out = 0, up = 0, down = 0, n_vfos = 0, H = 0;
 	size_t max_in = 0;
 	std::vector<int32_t> offset;        // Hz, per VFO
+	std::vector<uint32_t> theta;        // the mixer's phase offset, 0 .. Fs - 1, per VFO (0 unless retuned continuously)
 	std::vector<uint32_t> bw;           // Hz, per VFO
 	int64_t n_base = 0;                 // absolute input index of the next submit's first sample
 	unsigned parity = 0;
@@ -249,6 +251,7 @@ extern "C" int sonde_tuner_create(uint32_t rate_in, uint32_t rate_out, uint32_t 
 	for (uint32_t k = 0; k < n_vfos; k++) {
 		const uint32_t b = vfos[k].bandwidth_hz ? vfos[k].bandwidth_hz : rate_out;
 		t->offset.push_back(vfos[k].offset_hz);
+		t->theta.push_back(0);
 		t->bw.push_back(b);
 		tapoff[k] = off[b];
 		T[k] = sets[b];
@@ -290,6 +293,24 @@ extern "C" int sonde_tuner_retune(SondeTuner *t, uint32_t vfo, int32_t offset_hz
 	if (vfo >= t->n_vfos) return sd_fail("sonde_tuner_retune: no such VFO");
 	if (tn_check_offset(t->fs, t->bw[vfo], offset_hz, "sonde_tuner_retune")) return -1;
 	t->offset[vfo] = offset_hz;
+	t->theta[vfo] = 0;
+	return 0;
+}
+
+static uint32_t tn_mod(int64_t f, uint32_t fs) { return (uint32_t)(((f % (int64_t)fs) + (int64_t)fs) % (int64_t)fs); }
+
+// SPEC 3.9 "Continuous retune": theta' = (theta + (f_old - f_new) (n0 - T_k / 2)) mod Fs for the next submit's first index n0: the mixer's
+// phase is what the old offset would have given at the sample the filter's group delay (T_k / 2 - 1 / (2 up) samples) puts under the
+// submit's first output, so that the ROW's phase runs on across the boundary
+extern "C" int sonde_tuner_retune_continuous(SondeTuner *t, uint32_t vfo, int32_t offset_hz)
+{
+	if (!t) return sd_fail("sonde_tuner_retune_continuous: null argument");
+	if (vfo >= t->n_vfos) return sd_fail("sonde_tuner_retune_continuous: no such VFO");
+	if (tn_check_offset(t->fs, t->bw[vfo], offset_hz, "sonde_tuner_retune_continuous")) return -1;
+	const uint64_t df = tn_mod((int64_t)t->offset[vfo] - (int64_t)offset_hz, t->fs);
+	const uint64_t n0 = tn_mod(t->n_base - (int64_t)(tn_T(t->fs, t->bw[vfo]) / 2), t->fs);
+	t->theta[vfo] = (uint32_t)((t->theta[vfo] + df * n0 % t->fs) % t->fs);
+	t->offset[vfo] = offset_hz;
 	return 0;
 }
 
@@ -313,7 +334,10 @@ extern "C" int sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n
 			for (uint32_t vb = 0; vb < t->n_vfos; vb += TN_VMAX) {
 				const uint32_t nv = t->n_vfos - vb < TN_VMAX ? t->n_vfos - vb : TN_VMAX;
 				SdTunerOffs o = {};
-				for (uint32_t i = 0; i < nv; i++) o.F[i] = (uint32_t)((((int64_t)t->offset[vb + i] % (int64_t)t->fs) + (int64_t)t->fs) % (int64_t)t->fs);
+				for (uint32_t i = 0; i < nv; i++) {
+					o.F[i] = (uint32_t)((((int64_t)t->offset[vb + i] % (int64_t)t->fs) + (int64_t)t->fs) % (int64_t)t->fs);
+					o.TH[i] = t->theta[vb + i];
+				}
 				const dim3 grid((unsigned)((n_out + TN_JT - 1) / TN_JT), nv);
 				hipLaunchKernelGGL(sd_tuner_kernel<K>, grid, dim3(TN_WG), 0, s, x, h_in, t->H, (uint32_t)n_out, t->n_base, t->up, t->down, t->fs,
 					t->d_taps, t->d_tapoff, t->d_T, t->d_th, t->d_tl, o, vb, (float2 *)out_dev, out_stride);

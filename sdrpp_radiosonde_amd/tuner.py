@@ -71,9 +71,10 @@ class SondeTuner:
     def out_samples(self, n_in: int) -> int:
         return int(self.L.sonde_tuner_out_samples(self.h, int(n_in)))
 
-    def retune(self, k: int, hz: int):
-        """VFO k to offset hz from the next process() on"""
-        _chk(self.L.sonde_tuner_retune(self.h, int(k), int(hz)))
+    def retune(self, k: int, hz: int, continuous: bool = False):
+        """VFO k to offset hz from the next process() on.  continuous=False restarts the mixer's phase "as if tuned there since
+        create" (a phase jump in the row at the boundary); continuous=True keeps the mixer's phase at the boundary (SPEC 3.9)"""
+        _chk((self.L.sonde_tuner_retune_continuous if continuous else self.L.sonde_tuner_retune)(self.h, int(k), int(hz)))
         self.offsets[k] = int(hz)
 
     def process(self, block, out=None, stream: int | None = None):
@@ -134,9 +135,16 @@ class WidebandReceiver:
                          sonde in one SondeBatch(INPUT_REAL) buffer
 
     submit() takes a device block [n, 2] (float32 / int16 / int8 by input_kind), n a multiple of `granule` and <= max_in
-    (default: one granule): the smallest block that leaves whole decoder tiles at 48 kHz."""
+    (default: one granule): the smallest block that leaves whole decoder tiles at 48 kHz.
 
-    def __init__(self, rate_in: int, sondes, *, chain: str = "iq48", input_kind: int = INPUT_IQ, device: int = 0, max_in: int | None = None):
+    track=True follows drifting carriers (SPEC 3.11): a SondeTracker meters the tuner's rows of every submit; at the start of the
+    next submit the newest look of each VFO goes through track.step(), and the VFOs that moved are retuned continuously and their
+    meter rows restarted.  track_params: {"deadband_hz", "max_step_hz", "look_samples"} (absent / 0 = default).  `sondes[i]` follows
+    the retunes; `track_log[i]` lists (first input sample of the submit the offset applies from, offset_hz, err_hz, level_db) per
+    look acted on.  With track=True the granule of the "reference" chain also leaves whole 256-sample blocks at every VFO rate."""
+
+    def __init__(self, rate_in: int, sondes, *, chain: str = "iq48", input_kind: int = INPUT_IQ, device: int = 0, max_in: int | None = None,
+                 track: bool = False, track_params: dict | None = None):
         import torch
         if chain not in ("iq48", "reference"):
             raise SondeError('chain must be "iq48" or "reference"')
@@ -159,6 +167,8 @@ class WidebandReceiver:
             parts = [_multiple_for(48000, fs, tile)]
             for b in groups:
                 parts += [ratio(fs, b)[1], _multiple_for(b, fs, _vfo_down(b))]
+                if track:
+                    parts.append(_multiple_for(b, fs, 256))
             self.granule = _lcm(*parts)
         self.max_in = int(max_in or self.granule)
         if self.max_in % self.granule:
@@ -167,6 +177,11 @@ class WidebandReceiver:
         # batch channel c = order[c]: the sondes grouped by tuner, so that every group's rows are evenly spaced
         self.order = np.array([i for g in groups.values() for i in g], dtype=np.int64)
         self.stages = []          # (tuner, SondeVfo or None, first batch channel, sonde indices)
+        self.track = bool(track)
+        self.track_params = dict(track_params or {})
+        self.track_log = [[] for _ in self.sondes]
+        self.trackers = {}        # id(tuner) -> SondeTracker (track=True only)
+        self._n_in = 0            # input samples submitted so far
         c0 = 0
         for rate, idx in groups.items():
             if chain == "iq48":
@@ -176,6 +191,10 @@ class WidebandReceiver:
                 tu = SondeTuner(fs, rate, [(self.sondes[i][0], rate) for i in idx], self.max_in, input_kind=input_kind, device=device)
                 vo = SondeVfo(len(idx), rate, tu.out_samples(self.max_in), device=device)
                 self.stages.append((tu, vo, c0, idx))
+            if self.track:
+                from .track import SondeTracker
+                self.trackers[id(tu)] = SondeTracker(len(idx), tu.rate_out, tu.out_samples(self.max_in), device=device,
+                                                     look_samples=int(self.track_params.get("look_samples", 0)))
             c0 += len(idx)
         bt = np.array([types[i] for i in self.order], dtype=np.uint8)
         kind = INPUT_IQ if chain == "iq48" else INPUT_REAL
@@ -194,11 +213,30 @@ class WidebandReceiver:
                 return tu, idx.index(i)
         raise SondeError("no such sonde")
 
-    def retune(self, i: int, hz: int):
-        """sonde i's VFO to offset hz from the next submit on"""
+    def retune(self, i: int, hz: int, continuous: bool = False):
+        """sonde i's VFO to offset hz from the next submit on (SondeTuner.retune)"""
         tu, k = self._where(int(i))
-        tu.retune(k, hz)
+        tu.retune(k, hz, continuous)
+        if self.track:
+            self.trackers[id(tu)].restart(k)          # no look straddles two offsets
         self.sondes[i] = (int(hz), self.sondes[i][1])
+
+    def _track_update(self):
+        """the loop (SPEC 3.11): the newest look of every VFO -> step -> continuous retune + restart for those that moved"""
+        from . import track as tk
+        for tu, _, _, idx in self.stages:
+            tr = self.trackers[id(tu)]
+            looks, _ = tr.results()
+            newest = {}
+            for lk in looks:
+                newest[int(lk["row"])] = lk           # rows come oldest look first
+            for k, lk in newest.items():
+                i = idx[k]
+                new = tk.step(tu.offsets[k], tu.bandwidths[k], self.rate_in, tr.rate, tr.lag, lk["a_re"], lk["a_im"], self.track_params)
+                if new != tu.offsets[k]:
+                    self.retune(i, new, continuous=True)
+                self.track_log[i].append((self._n_in, new, tk.err_hz(tr.rate, tr.lag, lk["a_re"], lk["a_im"]),
+                                          tk.level_db(lk["p"], tr.look_samples)))
 
     def rows(self):
         """the 48 kHz rows of the last submit, in batch-channel order (IQ [C, n, 2] for iq48, FM [C, n] for reference)"""
@@ -212,18 +250,25 @@ class WidebandReceiver:
         if stream is None:
             stream = torch.cuda.current_stream(self.device).cuda_stream
         n48 = n * 48000 // self.rate_in
+        if self.track and self._n_in:
+            self._track_update()
         for tu, vo, c0, idx in self.stages:
             nv = len(idx)
             if vo is None:
                 tu.process(block, out=self._rows[c0:c0 + nv], stream=stream)
+                if self.track:
+                    self.trackers[id(tu)].submit(self._rows[c0:c0 + nv, :n48], stream)
             else:
                 m = tu.out_samples(n)
                 buf = self._tmp.get(id(tu))
                 if buf is None or buf.shape[1] < m:
                     buf = self._tmp[id(tu)] = torch.empty((nv, tu.out_samples(self.max_in), 2), dtype=torch.float32, device=block.device)
                 tu.process(block, out=buf, stream=stream)
+                if self.track:
+                    self.trackers[id(tu)].submit(buf[:, :m], stream)
                 _vfo_process(vo, buf[:, :m], self._rows[c0:c0 + nv], stream)
         self._n48 = n48
+        self._n_in += n
         self.batch.submit(self._rows[:, :n48], stream)
 
     def frames(self) -> np.ndarray:
@@ -238,6 +283,8 @@ class WidebandReceiver:
     def close(self):
         for tu, vo, _, _ in self.stages:
             tu.close()
+            if id(tu) in self.trackers:
+                self.trackers.pop(id(tu)).close()
             if vo is not None:
                 vo.close()
         self.stages = []
