@@ -200,6 +200,15 @@ int  sonde_batch_submit_host(SondeBatch *b, const void *samples, size_t n_sample
  * nothing (stream order already says so); it is what a SONDE_FLAG_LATE_JOIN / SONDE_FLAG_PIPELINE host calls before it refills a
  * single buffer, and what any host calls to release the buffer on ANOTHER stream (a copy engine's).  0 = ok. */
 int  sonde_batch_wait_input(SondeBatch *b, void *stream);
+/* From the next submit on each listed channel decodes as a stream that begins there (DESIGN SPEC 3.12): demodulator, AFC, discriminator
+ * history, bit ring and bit count (bitpos counts from the restart), framer, tone demodulator, time-slice progress and the poll parser
+ * are what sonde_batch_create set for the channel's type, which stays.  One launch for any number of channels, ordered behind the
+ * last submit's kernels and before the next submit's in every completion mode; no host synchronisation.  Frames and fragments of
+ * earlier submits stay readable (and are parsed by the old parser).  Refused for the batch behind a channelizer.  The reset is
+ * ordered against submits, not against the host: sonde_batch_nbits / _read_bits / _read_state called between the restart and the
+ * next submit may still see the old state (with SONDE_FLAG_LATE_JOIN / _PIPELINE the completion they wait for was recorded
+ * before the reset); after the next submit they see the restarted channel. */
+int  sonde_batch_restart_channels(SondeBatch *b, const uint32_t *channels, size_t n);
 /* Wait for the last submit; returns number of frames it produced (or negative error). */
 long sonde_batch_sync(SondeBatch *b);
 /* Copy the last submit's frames to host memory, ordered by (channel, bitpos).  Returns count copied. */
@@ -374,6 +383,9 @@ void sonde_detect_destroy(SondeDetector *d);
 int  sonde_detect_submit(SondeDetector *d, const void *samples, size_t n_samples, size_t channel_stride, void *stream);
 int  sonde_detect_results(SondeDetector *d, SondeDetection *out, size_t cap);   /* synchronises; returns channels written */
 int  sonde_detect_reset(SondeDetector *d);
+/* the listed channels back to their state after create (best, signs, positions, decision, front-end state, carried streams; positions
+ * count from the restart); one launch on the last submit's stream, no host synchronisation; the other channels are untouched */
+int  sonde_detect_restart_channels(SondeDetector *d, const uint32_t *channels, size_t n);
 int  sonde_detect_thresholds(float out[SONDE_NTYPES]);
 /* test introspection: the last submit's quantised streams of one channel; returns that submit's n_samples */
 int  sonde_detect_read(SondeDetector *d, uint32_t channel, int32_t *D /* n/2 */, int32_t *a_imet /* n/8 */, int32_t *a_c50 /* n/8 */);
@@ -404,6 +416,17 @@ size_t sonde_tuner_out_samples(const SondeTuner *t, size_t n_in);         /* n_i
 int    sonde_tuner_retune(SondeTuner *t, uint32_t vfo, int32_t offset_hz);   /* from the next submit on; theta = 0 */
 /* from the next submit on, the row's phase continuous at that submit's first output */
 int    sonde_tuner_retune_continuous(SondeTuner *t, uint32_t vfo, int32_t offset_hz);
+/* Slots (DESIGN SPEC 3.12): a tuner of n_slots VFOs that are active or idle, all idle at first, with one tap set per listed bandwidth
+ * (0 = rate_out) and the history of the longest of them.  sonde_tuner_slot_set tunes a slot from the next process on (theta = 0: "as if
+ * tuned there since create"; bandwidth_hz must be a listed one; the band-edge check of sonde_tuner_create), sonde_tuner_slot_clear idles
+ * it.  A VFO has no device state of its own, so from that process on a slot's row is, bit for bit, the row of a tuner that had the VFO
+ * since create.  sonde_tuner_process mixes the active slots only and writes zeros to the rows of the idle ones: every process writes
+ * every row.  sonde_tuner_create is "every slot active" over the tap sets of its VFOs; the retunes refuse an idle slot. */
+int    sonde_tuner_create_slots(uint32_t rate_in, uint32_t rate_out, uint32_t n_slots, const uint32_t *bandwidths, uint32_t n_bandwidths,
+                                size_t max_in, int input_kind, int device, SondeTuner **out);
+int    sonde_tuner_slot_set(SondeTuner *t, uint32_t slot, int32_t offset_hz, uint32_t bandwidth_hz);
+int    sonde_tuner_slot_clear(SondeTuner *t, uint32_t slot);
+int    sonde_tuner_slot_active(const SondeTuner *t, uint32_t slot);      /* 1 active, 0 idle */
 /* wide_dev: DEVICE pointer to n_in samples (a multiple of down, <= max_in); out_dev: VFO k's n_out complex64 samples at
  * element k * out_stride (complex samples; sonde_row_stride(n_out, SONDE_INPUT_IQ) writes straight into a SondeBatch input buffer) */
 int    sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n_in,
@@ -498,6 +521,13 @@ double sonde_track_quality(double a_re, double a_im, double p);
  * result clamped so that |offset| + bandwidth_hz / 2 <= rate_in / 2; else offset_hz.  Returns 1 if it moved, 0 if not; p NULL = defaults */
 int  sonde_track_step(int32_t offset_hz, uint32_t bandwidth_hz, uint32_t rate_in, uint32_t rate, uint32_t lag, const SondeTrackLook *look,
                       const SondeTrackParams *p, int32_t *new_offset);
+
+/* ------------------------------------------------------------------ live receiver: the matching rule (DESIGN SPEC 3.12)
+ * Pure host, integers, exactly reproducible: which scan candidate belongs to which live VFO.  Each candidate goes to the nearest VFO no
+ * further than match_hz away (0 = the scanner's min_sep_hz default, 10000; a tie: the lower VFO index); a VFO keeps only the nearest of
+ * those candidates (a tie: the lower candidate index).  cand_of_vfo[v] / vfo_of_cand[c]: the partner's index, -1 = unmatched. */
+int  sonde_live_match(const int32_t *vfo_offsets, uint32_t n_vfos, const int32_t *cand_offsets, uint32_t n_cand, uint32_t match_hz,
+                      int32_t *cand_of_vfo, int32_t *vfo_of_cand);
 
 /* post-FEC derived quantities, as /root/reference/src/decode/decoder.hpp:132-174 computes them */
 float sonde_dewpt(float temp, float rh);

@@ -120,6 +120,8 @@ ABI_SYMBOLS = [
     "sonde_track_step",
     "sonde_scan_create", "sonde_scan_destroy", "sonde_scan_fft_size", "sonde_scan_submit", "sonde_scan_reset", "sonde_scan_segments",
     "sonde_scan_spectrum", "sonde_scan_candidates", "sonde_scan_search", "sonde_scan_window", "sonde_scan_auto_fft_size",
+    "sonde_tuner_create_slots", "sonde_tuner_slot_set", "sonde_tuner_slot_clear", "sonde_tuner_slot_active",
+    "sonde_batch_restart_channels", "sonde_detect_restart_channels", "sonde_live_match",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -290,6 +292,15 @@ def load() -> C.CDLL:
         L.sonde_track_quality.argtypes = [C.c_double, C.c_double, C.c_double]
         L.sonde_track_quality.restype = C.c_double
         L.sonde_track_step.argtypes = [C.c_int32, u32, u32, u32, u32, C.POINTER(SondeTrackLook), C.POINTER(SondeTrackParams), C.POINTER(C.c_int32)]
+    if hasattr(L, "sonde_live_match"):
+        u32 = C.c_uint32
+        L.sonde_tuner_create_slots.argtypes = [u32, u32, u32, vp, u32, C.c_size_t, C.c_int, C.c_int, C.POINTER(vp)]
+        L.sonde_tuner_slot_set.argtypes = [vp, u32, C.c_int32, u32]
+        L.sonde_tuner_slot_clear.argtypes = [vp, u32]
+        L.sonde_tuner_slot_active.argtypes = [vp, u32]
+        L.sonde_batch_restart_channels.argtypes = [vp, vp, C.c_size_t]
+        L.sonde_detect_restart_channels.argtypes = [vp, vp, C.c_size_t]
+        L.sonde_live_match.argtypes = [vp, u32, vp, u32, u32, vp, vp]
     f = C.c_float
     L.sonde_gpx_open.restype = vp
     L.sonde_gpx_open.argtypes = [C.c_char_p]

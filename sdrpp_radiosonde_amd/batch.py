@@ -97,6 +97,12 @@ class SondeBatch:
         """Device-side: work queued on `stream` after this call may overwrite the last submit's sample buffer (sonde_batch_wait_input)."""
         self._chk(self.L.sonde_batch_wait_input(self.h, C.c_void_p(stream or 0)))
 
+    def restart_channels(self, channels):
+        """From the next submit on the listed channels decode as streams that begin there (sonde_batch_restart_channels): one launch
+        behind the last submit, no host synchronisation; earlier frames stay readable."""
+        ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
+        self._chk(self.L.sonde_batch_restart_channels(self.h, ch.ctypes.data_as(C.c_void_p), len(ch)))
+
     def sync(self) -> int:
         return self._chk(self.L.sonde_batch_sync(self.h))
 

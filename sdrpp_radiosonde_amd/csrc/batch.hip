@@ -18,6 +18,7 @@
 
 #include "launch.h"
 #include "parse.h"
+#include "sd_chanlist.h"
 #include <deque>
 #include <memory>
 
@@ -39,6 +40,7 @@ static int fail(const char *what, hipError_t e = hipSuccess)
 
 extern "C" const char *sonde_last_error(void) { return g_err.c_str(); }
 int sd_fail(const char *what, hipError_t e) { return fail(what, e); }     // for the other host objects of the library (vfo.hip)
+int sd_fail_msg(const char *what) { return fail(what); }                  // the same for pure-host sources (sd_host.h)
 extern "C" const char *sonde_version(void) { return "sonde_mi355 0.1 (gfx950)"; }
 
 // ---------------------------------------------------------------- modem table (SPEC)
@@ -213,6 +215,12 @@ struct SondeBatch {
 	std::vector<std::unique_ptr<SondeParser>> parsers;
 	std::deque<std::pair<uint32_t, SondeData>> frags;
 	uint64_t polled_ticket = 0;            // submits up to this one have been parsed by sonde_batch_poll
+	// sonde_batch_restart_channels (SPEC 3.12): the channel lists on their way to the reset kernel, the event that orders the next
+	// submit's launch units behind it, and (submits so far, channel): the channel's parser is replaced before a later submit is parsed
+	SdChanLists restart_lists;
+	hipEvent_t ev_restart = nullptr;
+	std::deque<std::pair<uint64_t, uint32_t>> parser_restarts;
+	bool behind_channelizer = false;
 };
 
 static uint32_t pow2ceil(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
@@ -225,6 +233,8 @@ extern "C" void sonde_batch_destroy(SondeBatch *b)
 	(void)hipFree(b->d_states); (void)hipFree(b->d_fstates); (void)hipFree(b->d_hist); (void)hipFree(b->d_bitring);
 	for (int k = 0; k < 2; k++) { (void)hipFree(b->d_frames2[k]); (void)hipFree(b->d_counts2[k]); (void)hipFree(b->d_fo2[k]); if (b->ev_done[k]) (void)hipEventDestroy(b->ev_done[k]); }
 	if (b->ev_xs) (void)hipEventDestroy(b->ev_xs);
+	if (b->ev_restart) (void)hipEventDestroy(b->ev_restart);
+	b->restart_lists.destroy();
 	(void)hipFree(b->d_taps); (void)hipFree(b->d_modems); (void)hipFree(b->d_prog);
 	(void)hipFree(b->d_astates); (void)hipFree(b->d_wtab); (void)hipFree(b->d_wtab_c50); (void)hipFree(b->d_afq);
 	for (auto &u : b->units) { if (u.st) (void)hipStreamDestroy(u.st); for (int k = 0; k < 2; k++) if (u.ev_join[k]) (void)hipEventDestroy(u.ev_join[k]); }
@@ -459,6 +469,7 @@ extern "C" int sonde_batch_create(const SondeBatchConfig *cfg, SondeBatch **out)
 			CHK(hipEventCreateWithFlags(&b->ev_done[k], hipEventDisableTiming));
 		}
 		CHK(hipEventCreateWithFlags(&b->ev_xs, SD_EV_ORDER));
+		CHK(hipEventCreateWithFlags(&b->ev_restart, SD_EV_ORDER));
 	}
 	// initial channel state
 	std::vector<SdChanState> st(C);
@@ -777,6 +788,66 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 	return 0;
 }
 
+// ---------------------------------------------------------------- restart of single channels (SPEC 3.12)
+// One workgroup per listed channel puts back what sonde_batch_create set: SdChanState for the channel's type (which stays), zeros in
+// the discriminator history, the bit ring, SdFramerState, SdAfskState and the time-slice progress word.  Stores only.
+__global__ __launch_bounds__(256) void sd_batch_restart_kernel(const uint32_t *__restrict__ list, SdChanState *__restrict__ states,
+	SdFramerState *__restrict__ fstates, float *__restrict__ hist, uint32_t *__restrict__ bitring, uint32_t ring_words,
+	SdAfskState *__restrict__ astates, uint32_t *__restrict__ prog, const SdModem *__restrict__ modems)
+{
+	const uint32_t c = list[blockIdx.x], tid = threadIdx.x;
+	uint32_t *ring = bitring + (size_t)c * ring_words;
+	for (uint32_t i = tid; i < ring_words; i += 256) ring[i] = 0u;
+	for (uint32_t i = tid; i < SD_HIST; i += 256) hist[(size_t)c * SD_HIST + i] = 0.0f;
+	if (tid < sizeof(SdFramerState) / 4) ((uint32_t *)(fstates + c))[tid] = 0u;
+	if (astates && tid < sizeof(SdAfskState) / 4) ((uint32_t *)(astates + c))[tid] = 0u;
+	if (tid == 0) {
+		const int32_t type = states[c].type, p0 = modems[type].period0;
+		SdChanState st = {};
+		st.type = type;
+		st.period = p0;
+		st.t_next = ((int64_t)SD_NTAPS << 16) + p0;
+		st.amp = 0.25f;
+		states[c] = st;
+		prog[c] = 0u;
+	}
+}
+
+void sd_batch_mark_channelizer(SondeBatch *b) { if (b) b->behind_channelizer = true; }
+
+extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *channels, size_t n)
+{
+	if (!b || (!channels && n)) return fail("sonde_batch_restart_channels: null argument");
+	if (b->behind_channelizer) return fail("sonde_batch_restart_channels: the batch sits behind a channelizer (its bins carry state the batch does not own)");
+	for (size_t i = 0; i < n; i++)
+		if (channels[i] >= b->n_channels) return fail("sonde_batch_restart_channels: no such channel");
+	if (n == 0) return 0;
+	// the poll parsers: an entry two submits old no longer separates anything a poll can still parse, so it is dropped (its parser
+	// replaced, if there is one) -- the list stays short for a host that never polls
+	while (!b->parser_restarts.empty() && b->parser_restarts.front().first + 2 <= b->tickets) {
+		if (!b->parsers.empty()) b->parsers[b->parser_restarts.front().second].reset();
+		b->parser_restarts.pop_front();
+	}
+	for (size_t i = 0; i < n; i++) b->parser_restarts.emplace_back(b->tickets, channels[i]);
+	if (b->tickets == 0) return 0;             // nothing has run: the device state is what create set
+	HIPCHK(hipSetDevice(b->device));
+	SdChanLists::Buf *lb = b->restart_lists.put(channels, n);
+	if (!lb) return fail("sonde_batch_restart_channels: no pinned memory for the channel list");
+	// last_stream is where the last submit completes: the caller's stream (the launch units joined into it), or the completion
+	// stream of the late-joined modes, which waits for every unit's last kernel.  The next submit follows it there (or through
+	// ev_xs from another stream); launch units that are not joined keep their own streams from submit to submit, so each waits.
+	hipStream_t s = b->last_stream;
+	hipLaunchKernelGGL(sd_batch_restart_kernel, dim3((unsigned)n), dim3(256), 0, s, lb->dev, b->d_states, b->d_fstates, b->d_hist, b->d_bitring,
+		b->ring_words, b->d_astates, b->d_prog, b->d_modems);
+	HIPCHK(hipGetLastError());
+	HIPCHK(b->restart_lists.done(lb, s));
+	if (b->pipeline) {
+		HIPCHK(hipEventRecord(b->ev_restart, s));
+		for (const SondeBatch::Unit &u : b->units) HIPCHK(hipStreamWaitEvent(u.st, b->ev_restart, 0));
+	}
+	return 0;
+}
+
 // Device-side release of the last submit's sample buffer on `stream_` (include/sonde_abi.h).  Unit batches: the units' join events of
 // the last submit (recorded behind each unit's last kernel: a superset of its readers); a plain launch: stream order on the submit's
 // own stream, an event recorded there now for any other stream.
@@ -970,6 +1041,11 @@ extern "C" long sonde_batch_poll(SondeBatch *b, SondeData *out, uint32_t *channe
 		const long got = n ? sonde_batch_frames_of(b, t, fr.data(), (size_t)n) : 0;
 		if (got < 0) return got;
 		if (b->parsers.empty()) b->parsers.resize(b->n_channels);
+		// channels restarted before submit t was queued: their frames from here on belong to a new stream, a new parser
+		while (!b->parser_restarts.empty() && b->parser_restarts.front().first < t) {
+			b->parsers[b->parser_restarts.front().second].reset();
+			b->parser_restarts.pop_front();
+		}
 		std::vector<SondeData> v;
 		for (long i = 0; i < got; i++) {
 			const uint32_t c = fr[(size_t)i].channel;

@@ -548,6 +548,7 @@ static int chan_create(const uint8_t *types, uint32_t blocks_per_submit, uint32_
 	cfg.device = device;
 	cfg.flags = 0;                                           // default completion: the bins decoder is one launch behind the filter bank, in the caller's stream
 	if (sonde_batch_create(&cfg, &c->batch) != 0) { delete c; return -1; }
+	sd_batch_mark_channelizer(c->batch);
 	std::vector<float> h, tw, g;
 	make_tables(h, tw, g);
 	const size_t hist_bytes = (size_t)n_phys * CH_H * sizeof(float2);

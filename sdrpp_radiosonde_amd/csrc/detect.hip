@@ -21,6 +21,7 @@
 #include "sd_rs41.h"
 #include "sd_fixed.h"
 #include "launch.h"
+#include "sd_chanlist.h"
 #include "../../include/sonde_abi.h"
 
 #define DT_WG   256
@@ -388,6 +389,7 @@ struct SondeDetector {
 	float2 *d_wi = nullptr, *d_wc = nullptr;
 	hipStream_t last_stream = nullptr;
 	bool submitted = false;
+	SdChanLists restart_lists;              // sonde_detect_restart_channels
 };
 
 static DtTmpl dt_tmpl(int type)
@@ -423,6 +425,7 @@ extern "C" void sonde_detect_destroy(SondeDetector *d)
 	if (!d) return;
 	(void)hipSetDevice(d->device);
 	if (d->submitted) (void)hipStreamSynchronize(d->last_stream);
+	d->restart_lists.destroy();
 	(void)hipFree(d->d_state); (void)hipFree(d->d_D); (void)hipFree(d->d_A); (void)hipFree(d->d_wi); (void)hipFree(d->d_wc);
 	delete d;
 }
@@ -531,6 +534,33 @@ extern "C" int sonde_detect_reset(SondeDetector *d)
 	if (!d) return sd_fail("sonde_detect_reset: null argument");
 	if (dt_sync(d)) return -1;
 	return dt_clear(d);
+}
+
+// the listed channels back to their state after create (SPEC 3.12): records, front-end state and the carried streams, zeros all
+__global__ __launch_bounds__(DT_WG) void sd_detect_restart_kernel(const uint32_t *__restrict__ list, SdDetState *__restrict__ state,
+	int32_t *__restrict__ D, size_t rowD, int32_t *__restrict__ A, size_t rowA)
+{
+	const uint32_t c = list[blockIdx.x], tid = threadIdx.x;
+	if (tid < sizeof(SdDetState) / 4) ((uint32_t *)(state + c))[tid] = 0u;
+	for (size_t i = tid; i < rowD; i += DT_WG) D[c * rowD + i] = 0;
+	for (size_t i = tid; i < 2 * rowA; i += DT_WG) A[2 * c * rowA + i] = 0;
+}
+
+extern "C" int sonde_detect_restart_channels(SondeDetector *d, const uint32_t *channels, size_t n)
+{
+	if (!d || (!channels && n)) return sd_fail("sonde_detect_restart_channels: null argument");
+	for (size_t i = 0; i < n; i++)
+		if (channels[i] >= d->n_channels) return sd_fail("sonde_detect_restart_channels: no such channel");
+	if (n == 0 || !d->submitted) return 0;      // nothing has run: the state is what create set
+	hipError_t e = hipSetDevice(d->device);
+	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	SdChanLists::Buf *lb = d->restart_lists.put(channels, n);
+	if (!lb) return sd_fail("sonde_detect_restart_channels: no pinned memory for the channel list");
+	// on the stream of the last submit: behind its kernel; a submit on another stream is the caller's to order, as between submits
+	hipLaunchKernelGGL(sd_detect_restart_kernel, dim3((unsigned)n), dim3(DT_WG), 0, d->last_stream, lb->dev, d->d_state, d->d_D, d->rowD, d->d_A, d->rowA);
+	if ((e = hipGetLastError()) != hipSuccess || (e = d->restart_lists.done(lb, d->last_stream)) != hipSuccess)
+		return sd_fail("sd_detect_restart_kernel launch", e);
+	return 0;
 }
 
 extern "C" int sonde_detect_read(SondeDetector *d, uint32_t channel, int32_t *D, int32_t *a_imet, int32_t *a_c50)

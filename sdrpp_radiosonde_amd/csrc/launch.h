@@ -62,6 +62,7 @@ void sd_launch_bins(uint32_t n_channels, hipStream_t stream, const int16_t *phas
 	const float *g_comp, int utype /* >= 0: every bin is of this sonde type; -1: per bin */);
 // the batch object behind a channelizer takes its input as phase rows (channelizer.hip): 3 tiles per 2560 phase samples
 int sd_batch_submit_bins(SondeBatch *b, const SdBinsArgs *ba, size_t n_steps, void *stream);
+void sd_batch_mark_channelizer(SondeBatch *b);      // sonde_batch_restart_channels refuses such a batch (the bins' carried phases are the channelizer's)
 int sd_batch_bins_capable(const SondeBatch *b);      // 1: every channel's class has a bins instantiation (no AFSK sonde, no class without one)
 
 void sd_launch_afsk(int type /* SONDE_IMET4 or SONDE_C50 */, int kind /* SONDE_INPUT_* */, uint32_t n_list, hipStream_t stream, const float *in, size_t ch_stride, int n_tiles,

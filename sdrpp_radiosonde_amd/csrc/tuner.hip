@@ -10,6 +10,10 @@
 // runs on from segment to segment, and a fixed xor butterfly adds the 64 chains.  The order of output j's sum therefore depends on
 // j alone: rows are bit-identical however the stream is cut into submits.  The history (the last H = max_k T_k - 1 raw samples, as
 // float2) is double-buffered and refreshed by a second kernel behind the first.
+//
+// SLOTS (SPEC 3.12): the VFOs are slots that are active or idle.  The tap sets are per listed bandwidth, the history is shared and the
+// mixer's phase is a function of the absolute sample index, so a VFO has no device state of its own: the mixing kernel is launched
+// over the active slots only (slot, tap set, f and theta travel with the launch), a fill kernel writes zeros to the idle slots' rows.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -27,7 +31,9 @@
 #define TN_LOB   12                     // mixer: phi = hi * 2^12 + lo, two tables
 #define TN_MAXUP 64
 
-struct SdTunerOffs { uint32_t F[TN_VMAX], TH[TN_VMAX]; };      // f_k mod Fs and the phase offset theta_k of the launch's VFOs
+// f_k mod Fs, the phase offset theta_k, the slot (= output row) and the tap set of the launch's VFOs
+struct SdTunerOffs { uint32_t F[TN_VMAX], TH[TN_VMAX], SLOT[TN_VMAX]; uint8_t SET[TN_VMAX]; };
+struct SdTunerIdle { uint32_t SLOT[TN_VMAX]; };
 
 // e = H[hi] (1 + D[lo]), D = exp(-2 pi i lo / Fs) - 1 (|D| <= 0.026): about 2^-24 per component (SPEC 3.9 allows 2^-22)
 static __device__ __forceinline__ float2 tn_phasor(uint32_t phi, const float2 *__restrict__ th, const float2 *__restrict__ tl)
@@ -40,15 +46,15 @@ template <int K>
 __global__ __launch_bounds__(TN_WG) void sd_tuner_kernel(const void *__restrict__ xin, const float2 *__restrict__ hist, uint32_t H,
 	uint32_t n_out, int64_t n_base, uint32_t up, uint32_t down, uint32_t fs,
 	const float *__restrict__ taps, const uint64_t *__restrict__ tapoff, const uint32_t *__restrict__ vT,
-	const float2 *__restrict__ th, const float2 *__restrict__ tl, SdTunerOffs offs, uint32_t vbase,
+	const float2 *__restrict__ th, const float2 *__restrict__ tl, SdTunerOffs offs,
 	float2 *__restrict__ out, size_t out_stride)
 {
 	__shared__ float2 s_v[TN_SEG];
 	const sd_iq_t<K> *x = (const sd_iq_t<K> *)xin;        // (a void pointer in the signature: sd_iq_t names an anonymous enum, mangled apart on host and device)
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const uint32_t k = vbase + blockIdx.y, F = offs.F[blockIdx.y], TH = offs.TH[blockIdx.y];
-	const int32_t T = (int32_t)vT[k];
-	const float *g = taps + tapoff[k];
+	const uint32_t k = offs.SLOT[blockIdx.y], F = offs.F[blockIdx.y], TH = offs.TH[blockIdx.y], set = offs.SET[blockIdx.y];
+	const int32_t T = (int32_t)vT[set];
+	const float *g = taps + tapoff[set];
 	const uint32_t jt0 = blockIdx.x * TN_JT;
 	const uint32_t nj = min((uint32_t)TN_JT, n_out - jt0);
 	// window index w: absolute sample n_base - H + w (w < H: the history, H <= w < H + n_in: the block)
@@ -107,6 +113,13 @@ __global__ __launch_bounds__(TN_WG) void sd_tuner_kernel(const void *__restrict_
 	}
 }
 
+// the rows of idle slots: zeros (bytes only, no arithmetic), so that whatever reads all rows of a submit reads defined ones
+__global__ __launch_bounds__(TN_WG) void sd_tuner_fill_kernel(SdTunerIdle idle, uint32_t n_out, float2 *__restrict__ out, size_t out_stride)
+{
+	const uint32_t j = blockIdx.x * TN_WG + threadIdx.x;
+	if (j < n_out) out[(size_t)idle.SLOT[blockIdx.y] * out_stride + j] = make_float2(0.0f, 0.0f);
+}
+
 // the history of the next submit: the last H samples of (history ++ block), as float2
 template <int K>
 __global__ __launch_bounds__(TN_WG) void sd_tuner_hist_kernel(const void *__restrict__ xin, const float2 *__restrict__ h_in,
@@ -127,6 +140,8 @@ struct SondeTuner {
 	std::vector<int32_t> offset;        // Hz, per VFO
 	std::vector<uint32_t> theta;        // the mixer's phase offset, 0 .. Fs - 1, per VFO (0 unless retuned continuously)
 	std::vector<uint32_t> bw;           // Hz, per VFO
+	std::vector<uint8_t> set, active;   // per VFO (slot): its tap set, and whether it is tuned at all
+	std::map<uint32_t, uint32_t> set_of;        // listed bandwidth -> tap set (ascending bandwidth)
 	int64_t n_base = 0;                 // absolute input index of the next submit's first sample
 	unsigned parity = 0;
 	float *d_taps = nullptr;
@@ -213,49 +228,36 @@ static int tn_check_offset(uint32_t fs, uint32_t b, int32_t f, const char *fn)
 	return 0;
 }
 
-extern "C" int sonde_tuner_create(uint32_t rate_in, uint32_t rate_out, uint32_t n_vfos, const SondeTunerVfo *vfos, size_t max_in, int input_kind,
-	int device, SondeTuner **out)
+// the object over n_slots idle slots and one tap set per listed bandwidth (ascending); H from the longest tap set (the narrowest bandwidth)
+static int tn_build(uint32_t rate_in, uint32_t rate_out, uint32_t up, uint32_t down, uint32_t n_slots, const std::map<uint32_t, uint32_t> &sets /* bandwidth -> T */,
+	size_t max_in, int input_kind, int device, const char *fn, SondeTuner **out)
 {
-	if (!out || !vfos || !n_vfos) return sd_fail("sonde_tuner_create: bad argument");
-	uint32_t up, down;
-	if (tn_ratio(rate_in, rate_out, &up, &down, "sonde_tuner_create")) return -1;
-	if (input_kind != SONDE_INPUT_IQ && input_kind != SONDE_INPUT_IQ16 && input_kind != SONDE_INPUT_IQ8)
-		return sd_fail("sonde_tuner_create: input_kind must be SONDE_INPUT_IQ, SONDE_INPUT_IQ16 or SONDE_INPUT_IQ8 (the tuner mixes complex samples)");
-	if (max_in < down) return sd_fail("sonde_tuner_create: max_in must be at least the ratio's denominator");
-	std::map<uint32_t, uint32_t> sets;      // bandwidth -> T
 	uint32_t Tmax = 0;
-	for (uint32_t k = 0; k < n_vfos; k++) {
-		const uint32_t b = vfos[k].bandwidth_hz ? vfos[k].bandwidth_hz : rate_out;
-		if (b < 5000u || b > rate_out) return sd_fail("sonde_tuner_create: bandwidth_hz must be 5000 .. rate_out (0 = rate_out)");
-		if (tn_check_offset(rate_in, b, vfos[k].offset_hz, "sonde_tuner_create")) return -1;
-		sets[b] = tn_T(rate_in, b);
-		Tmax = sets[b] > Tmax ? sets[b] : Tmax;
-	}
+	for (auto &s : sets) Tmax = s.second > Tmax ? s.second : Tmax;
+	if (sets.size() > 255) return sd_fail((std::string(fn) + ": more than 255 distinct bandwidths").c_str());
 	if (max_in + Tmax >= (1u << 30) || (max_in / down) * up >= (1u << 30))
-		return sd_fail("sonde_tuner_create: max_in too large (window indices are 32-bit)");
+		return sd_fail((std::string(fn) + ": max_in too large (window indices are 32-bit)").c_str());
 	int ndev = 0;
 	hipError_t e = hipGetDeviceCount(&ndev);
-	if (e != hipSuccess || device < 0 || device >= ndev) return sd_fail("sonde_tuner_create: no such HIP device (this library has no CPU path)", e);
+	if (e != hipSuccess || device < 0 || device >= ndev) return sd_fail((std::string(fn) + ": no such HIP device (this library has no CPU path)").c_str(), e);
 	if ((e = hipSetDevice(device)) != hipSuccess) return sd_fail("hipSetDevice", e);
 	SondeTuner *t = new SondeTuner;
 	t->device = device; t->input_kind = input_kind; t->fs = rate_in; t->rate_out = rate_out; t->up = up; t->down = down;
-	t->n_vfos = n_vfos; t->max_in = max_in; t->H = Tmax - 1;
+	t->n_vfos = n_slots; t->max_in = max_in; t->H = Tmax - 1;
 	// the tap sets, one per distinct bandwidth, back to back
-	std::map<uint32_t, uint64_t> off;
+	const uint32_t n_sets = (uint32_t)sets.size();
+	std::vector<uint64_t> tapoff(n_sets);
+	std::vector<uint32_t> T(n_sets);
 	size_t total = 0;
-	for (auto &s : sets) { off[s.first] = total; total += (size_t)up * s.second; }
+	uint32_t si = 0;
+	for (auto &s : sets) { t->set_of[s.first] = si; tapoff[si] = total; T[si] = s.second; total += (size_t)up * s.second; si++; }
 	std::vector<float> g(total);
-	for (auto &s : sets) tn_taps(up, s.second, (double)rate_in * up, 0.5 * s.first, g.data() + off[s.first]);
-	std::vector<uint64_t> tapoff(n_vfos);
-	std::vector<uint32_t> T(n_vfos);
-	for (uint32_t k = 0; k < n_vfos; k++) {
-		const uint32_t b = vfos[k].bandwidth_hz ? vfos[k].bandwidth_hz : rate_out;
-		t->offset.push_back(vfos[k].offset_hz);
-		t->theta.push_back(0);
-		t->bw.push_back(b);
-		tapoff[k] = off[b];
-		T[k] = sets[b];
-	}
+	for (auto &s : sets) tn_taps(up, s.second, (double)rate_in * up, 0.5 * s.first, g.data() + tapoff[t->set_of[s.first]]);
+	t->offset.assign(n_slots, 0);
+	t->theta.assign(n_slots, 0);
+	t->bw.assign(n_slots, 0);
+	t->set.assign(n_slots, 0);
+	t->active.assign(n_slots, 0);
 	// the mixer tables (double on the host, stored as float): H[h] = exp(-2 pi i h 2^12 / Fs), D[l] = exp(-2 pi i l / Fs) - 1
 	const double PI = 3.14159265358979323846;
 	const uint32_t nh = (rate_in + (1u << TN_LOB) - 1) >> TN_LOB, nl = 1u << TN_LOB;
@@ -270,19 +272,97 @@ extern "C" int sonde_tuner_create(uint32_t rate_in, uint32_t rate_out, uint32_t 
 	}
 	const size_t hb = (size_t)t->H * sizeof(float2);
 	bool ok = hipMalloc((void **)&t->d_taps, total * sizeof(float)) == hipSuccess &&
-	          hipMalloc((void **)&t->d_tapoff, n_vfos * sizeof(uint64_t)) == hipSuccess &&
-	          hipMalloc((void **)&t->d_T, n_vfos * sizeof(uint32_t)) == hipSuccess &&
+	          hipMalloc((void **)&t->d_tapoff, n_sets * sizeof(uint64_t)) == hipSuccess &&
+	          hipMalloc((void **)&t->d_T, n_sets * sizeof(uint32_t)) == hipSuccess &&
 	          hipMalloc((void **)&t->d_th, nh * sizeof(float2)) == hipSuccess && hipMalloc((void **)&t->d_tl, nl * sizeof(float2)) == hipSuccess &&
 	          hipMalloc((void **)&t->d_hist[0], hb) == hipSuccess && hipMalloc((void **)&t->d_hist[1], hb) == hipSuccess;
 	ok = ok && hipMemcpy(t->d_taps, g.data(), total * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(t->d_tapoff, tapoff.data(), n_vfos * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(t->d_T, T.data(), n_vfos * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
+	     hipMemcpy(t->d_tapoff, tapoff.data(), n_sets * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess &&
+	     hipMemcpy(t->d_T, T.data(), n_sets * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
 	     hipMemcpy(t->d_th, th.data(), nh * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess &&
 	     hipMemcpy(t->d_tl, tl.data(), nl * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess &&
 	     hipMemset(t->d_hist[0], 0, hb) == hipSuccess && hipMemset(t->d_hist[1], 0, hb) == hipSuccess;
-	if (!ok) { sonde_tuner_destroy(t); return sd_fail("sonde_tuner_create: device allocation failed"); }
+	if (!ok) { sonde_tuner_destroy(t); return sd_fail((std::string(fn) + ": device allocation failed").c_str()); }
 	*out = t;
 	return 0;
+}
+
+static int tn_check_create(uint32_t rate_in, uint32_t rate_out, size_t max_in, int input_kind, uint32_t *up, uint32_t *down, const char *fn)
+{
+	if (tn_ratio(rate_in, rate_out, up, down, fn)) return -1;
+	if (input_kind != SONDE_INPUT_IQ && input_kind != SONDE_INPUT_IQ16 && input_kind != SONDE_INPUT_IQ8)
+		return sd_fail((std::string(fn) + ": input_kind must be SONDE_INPUT_IQ, SONDE_INPUT_IQ16 or SONDE_INPUT_IQ8 (the tuner mixes complex samples)").c_str());
+	if (max_in < *down) return sd_fail((std::string(fn) + ": max_in must be at least the ratio's denominator").c_str());
+	return 0;
+}
+
+static void tn_set(SondeTuner *t, uint32_t slot, int32_t offset_hz, uint32_t b)
+{
+	t->offset[slot] = offset_hz;
+	t->theta[slot] = 0;
+	t->bw[slot] = b;
+	t->set[slot] = (uint8_t)t->set_of[b];
+	t->active[slot] = 1;
+}
+
+// "all slots active" over the slot structure: the tap sets of the VFOs' bandwidths, every slot set at create
+extern "C" int sonde_tuner_create(uint32_t rate_in, uint32_t rate_out, uint32_t n_vfos, const SondeTunerVfo *vfos, size_t max_in, int input_kind,
+	int device, SondeTuner **out)
+{
+	if (!out || !vfos || !n_vfos) return sd_fail("sonde_tuner_create: bad argument");
+	uint32_t up, down;
+	if (tn_check_create(rate_in, rate_out, max_in, input_kind, &up, &down, "sonde_tuner_create")) return -1;
+	std::map<uint32_t, uint32_t> sets;      // bandwidth -> T
+	for (uint32_t k = 0; k < n_vfos; k++) {
+		const uint32_t b = vfos[k].bandwidth_hz ? vfos[k].bandwidth_hz : rate_out;
+		if (b < 5000u || b > rate_out) return sd_fail("sonde_tuner_create: bandwidth_hz must be 5000 .. rate_out (0 = rate_out)");
+		if (tn_check_offset(rate_in, b, vfos[k].offset_hz, "sonde_tuner_create")) return -1;
+		sets[b] = tn_T(rate_in, b);
+	}
+	if (tn_build(rate_in, rate_out, up, down, n_vfos, sets, max_in, input_kind, device, "sonde_tuner_create", out)) return -1;
+	for (uint32_t k = 0; k < n_vfos; k++) tn_set(*out, k, vfos[k].offset_hz, vfos[k].bandwidth_hz ? vfos[k].bandwidth_hz : rate_out);
+	return 0;
+}
+
+extern "C" int sonde_tuner_create_slots(uint32_t rate_in, uint32_t rate_out, uint32_t n_slots, const uint32_t *bandwidths, uint32_t n_bandwidths,
+	size_t max_in, int input_kind, int device, SondeTuner **out)
+{
+	if (!out || !n_slots || !bandwidths || !n_bandwidths) return sd_fail("sonde_tuner_create_slots: bad argument");
+	uint32_t up, down;
+	if (tn_check_create(rate_in, rate_out, max_in, input_kind, &up, &down, "sonde_tuner_create_slots")) return -1;
+	std::map<uint32_t, uint32_t> sets;
+	for (uint32_t i = 0; i < n_bandwidths; i++) {
+		const uint32_t b = bandwidths[i] ? bandwidths[i] : rate_out;
+		if (b < 5000u || b > rate_out) return sd_fail("sonde_tuner_create_slots: a bandwidth must be 5000 .. rate_out (0 = rate_out)");
+		sets[b] = tn_T(rate_in, b);
+	}
+	return tn_build(rate_in, rate_out, up, down, n_slots, sets, max_in, input_kind, device, "sonde_tuner_create_slots", out);
+}
+
+extern "C" int sonde_tuner_slot_set(SondeTuner *t, uint32_t slot, int32_t offset_hz, uint32_t bandwidth_hz)
+{
+	if (!t) return sd_fail("sonde_tuner_slot_set: null argument");
+	if (slot >= t->n_vfos) return sd_fail("sonde_tuner_slot_set: no such slot");
+	const uint32_t b = bandwidth_hz ? bandwidth_hz : t->rate_out;
+	if (!t->set_of.count(b)) return sd_fail("sonde_tuner_slot_set: bandwidth_hz is not one of the bandwidths listed at create");
+	if (tn_check_offset(t->fs, b, offset_hz, "sonde_tuner_slot_set")) return -1;
+	tn_set(t, slot, offset_hz, b);
+	return 0;
+}
+
+extern "C" int sonde_tuner_slot_clear(SondeTuner *t, uint32_t slot)
+{
+	if (!t) return sd_fail("sonde_tuner_slot_clear: null argument");
+	if (slot >= t->n_vfos) return sd_fail("sonde_tuner_slot_clear: no such slot");
+	t->active[slot] = 0;
+	return 0;
+}
+
+extern "C" int sonde_tuner_slot_active(const SondeTuner *t, uint32_t slot)
+{
+	if (!t) return sd_fail("sonde_tuner_slot_active: null argument");
+	if (slot >= t->n_vfos) return sd_fail("sonde_tuner_slot_active: no such slot");
+	return t->active[slot];
 }
 
 extern "C" size_t sonde_tuner_out_samples(const SondeTuner *t, size_t n_in) { return t ? n_in / t->down * t->up : 0; }
@@ -291,6 +371,7 @@ extern "C" int sonde_tuner_retune(SondeTuner *t, uint32_t vfo, int32_t offset_hz
 {
 	if (!t) return sd_fail("sonde_tuner_retune: null argument");
 	if (vfo >= t->n_vfos) return sd_fail("sonde_tuner_retune: no such VFO");
+	if (!t->active[vfo]) return sd_fail("sonde_tuner_retune: the slot is idle (sonde_tuner_slot_set tunes it)");
 	if (tn_check_offset(t->fs, t->bw[vfo], offset_hz, "sonde_tuner_retune")) return -1;
 	t->offset[vfo] = offset_hz;
 	t->theta[vfo] = 0;
@@ -306,6 +387,7 @@ extern "C" int sonde_tuner_retune_continuous(SondeTuner *t, uint32_t vfo, int32_
 {
 	if (!t) return sd_fail("sonde_tuner_retune_continuous: null argument");
 	if (vfo >= t->n_vfos) return sd_fail("sonde_tuner_retune_continuous: no such VFO");
+	if (!t->active[vfo]) return sd_fail("sonde_tuner_retune_continuous: the slot is idle (sonde_tuner_slot_set tunes it)");
 	if (tn_check_offset(t->fs, t->bw[vfo], offset_hz, "sonde_tuner_retune_continuous")) return -1;
 	const uint64_t df = tn_mod((int64_t)t->offset[vfo] - (int64_t)offset_hz, t->fs);
 	const uint64_t n0 = tn_mod(t->n_base - (int64_t)(tn_T(t->fs, t->bw[vfo]) / 2), t->fs);
@@ -331,16 +413,34 @@ extern "C" int sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n
 		constexpr int K = decltype(kk)::value;
 		if constexpr (K != SONDE_INPUT_REAL) {
 			const void *x = wide_dev;
-			for (uint32_t vb = 0; vb < t->n_vfos; vb += TN_VMAX) {
-				const uint32_t nv = t->n_vfos - vb < TN_VMAX ? t->n_vfos - vb : TN_VMAX;
-				SdTunerOffs o = {};
-				for (uint32_t i = 0; i < nv; i++) {
-					o.F[i] = (uint32_t)((((int64_t)t->offset[vb + i] % (int64_t)t->fs) + (int64_t)t->fs) % (int64_t)t->fs);
-					o.TH[i] = t->theta[vb + i];
+			// the active slots, TN_VMAX per launch, in ascending slot order
+			SdTunerOffs o = {};
+			uint32_t nv = 0;
+			for (uint32_t k = 0; k <= t->n_vfos; k++) {
+				if (k < t->n_vfos && t->active[k]) {
+					o.F[nv] = tn_mod((int64_t)t->offset[k], t->fs);
+					o.TH[nv] = t->theta[k];
+					o.SLOT[nv] = k;
+					o.SET[nv] = t->set[k];
+					nv++;
 				}
-				const dim3 grid((unsigned)((n_out + TN_JT - 1) / TN_JT), nv);
-				hipLaunchKernelGGL(sd_tuner_kernel<K>, grid, dim3(TN_WG), 0, s, x, h_in, t->H, (uint32_t)n_out, t->n_base, t->up, t->down, t->fs,
-					t->d_taps, t->d_tapoff, t->d_T, t->d_th, t->d_tl, o, vb, (float2 *)out_dev, out_stride);
+				if (nv == TN_VMAX || (k == t->n_vfos && nv)) {
+					const dim3 grid((unsigned)((n_out + TN_JT - 1) / TN_JT), nv);
+					hipLaunchKernelGGL(sd_tuner_kernel<K>, grid, dim3(TN_WG), 0, s, x, h_in, t->H, (uint32_t)n_out, t->n_base, t->up, t->down, t->fs,
+						t->d_taps, t->d_tapoff, t->d_T, t->d_th, t->d_tl, o, (float2 *)out_dev, out_stride);
+					nv = 0;
+				}
+			}
+			// the idle slots' rows: zeros
+			SdTunerIdle z = {};
+			uint32_t nz = 0;
+			for (uint32_t k = 0; k <= t->n_vfos; k++) {
+				if (k < t->n_vfos && !t->active[k]) z.SLOT[nz++] = k;
+				if (nz == TN_VMAX || (k == t->n_vfos && nz)) {
+					const dim3 grid((unsigned)((n_out + TN_WG - 1) / TN_WG), nz);
+					hipLaunchKernelGGL(sd_tuner_fill_kernel, grid, dim3(TN_WG), 0, s, z, (uint32_t)n_out, (float2 *)out_dev, out_stride);
+					nz = 0;
+				}
 			}
 			hipLaunchKernelGGL(sd_tuner_hist_kernel<K>, dim3((t->H + TN_WG - 1) / TN_WG), dim3(TN_WG), 0, s, x, h_in, h_out, t->H, (uint32_t)n_in);
 		}

@@ -107,6 +107,12 @@ class SondeDetector:
     def reset(self):
         _chk(self.L.sonde_detect_reset(self.h))
 
+    def restart_channels(self, channels):
+        """the listed channels back to their state after create, ordered on the last submit's stream, no synchronisation
+        (sonde_detect_restart_channels)"""
+        ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
+        _chk(self.L.sonde_detect_restart_channels(self.h, ch.ctypes.data_as(C.c_void_p), len(ch)))
+
     def read(self, channel: int):
         """the last submit's quantised streams of one channel: D [n/2], A_imet [n/8], A_c50 [n/8] (int32)"""
         D = np.zeros(self.max_samples // 2, np.int32)

@@ -1158,12 +1158,14 @@ SCENE_BAUD = {0: 4800.0, 1: 5000.0, 2: 4800.0, 3: 9600.0, 4: IMET_BAUD, 5: C50_B
 
 
 def make_wideband_scene(sondes, n_samples: int, *, fs: float = WB_FS, ebn0_db: float = 20.0, seed: int = 1, noise_sigma: float = 0.02,
-                        device: str | torch.device = "cpu", cfo_max_hz: float = 300.0, drift_hz_per_s=0.0):
+                        device: str | torch.device = "cpu", cfo_max_hz: float = 300.0, drift_hz_per_s=0.0, active=None):
     """Transmitters of any sonde type at the given offsets, summed into one complex stream at fs [n_samples, 2] with ONE white noise
     floor (sigma per component): sondes = [(offset_hz, sonde type, m20), ...] (m20 optional: M20 frames for type 3).  Each carrier's
     amplitude sets its own Eb/N0 against that floor (GFSK), or its C/N in 48 kHz (iMet-4, SRS-C50) to ebn0_db; ebn0_db may be a
     list (one per sonde).  drift_hz_per_s (a scalar or one value per sonde) lets a carrier drift linearly: the term pi r (n / fs)^2 is
-    added to its phase, so that its offset at sample n is f + r n / fs.  Returns (iq, frames, symbols): per sonde the list of (symbol offset, frame bytes) and the number of
+    added to its phase, so that its offset at sample n is f + r n / fs.  active (None, or per sonde None or (first_sample, end_sample))
+    puts a carrier on the air for that span only: it is gated before the noise is added, its frames and symbols stay those of the
+    whole stream.  Returns (iq, frames, symbols): per sonde the list of (symbol offset, frame bytes) and the number of
     on-air symbols the stream holds."""
     ebn0 = list(ebn0_db) if np.ndim(ebn0_db) else [float(ebn0_db)] * len(sondes)
     drift = [float(r) for r in drift_hz_per_s] if np.ndim(drift_hz_per_s) else [float(drift_hz_per_s)] * len(sondes)
@@ -1185,8 +1187,13 @@ def make_wideband_scene(sondes, n_samples: int, *, fs: float = WB_FS, ebn0_db: f
         if drift[i] != 0.0:
             ph = ph + (math.pi * drift[i] / (fs * fs)) * (n * n)
         c, s_ = torch.cos(ph).to(torch.float32), torch.sin(ph).to(torch.float32)
-        total[:, 0] += sb.iq[0, :, 0] * c - sb.iq[0, :, 1] * s_
-        total[:, 1] += sb.iq[0, :, 0] * s_ + sb.iq[0, :, 1] * c
+        if active is not None and active[i] is not None:
+            a0, a1 = max(0, int(active[i][0])), min(n_samples, int(active[i][1]))
+            total[a0:a1, 0] += sb.iq[0, a0:a1, 0] * c[a0:a1] - sb.iq[0, a0:a1, 1] * s_[a0:a1]
+            total[a0:a1, 1] += sb.iq[0, a0:a1, 0] * s_[a0:a1] + sb.iq[0, a0:a1, 1] * c[a0:a1]
+        else:
+            total[:, 0] += sb.iq[0, :, 0] * c - sb.iq[0, :, 1] * s_
+            total[:, 1] += sb.iq[0, :, 0] * s_ + sb.iq[0, :, 1] * c
         frames.append(sb.frames[0])
         symbols.append(int(n_samples * SCENE_BAUD[t] / fs))
         del sb

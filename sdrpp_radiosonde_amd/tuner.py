@@ -50,7 +50,10 @@ class SondeTuner:
     """A bank of VFOs over one wideband complex stream.  vfos: [(offset_hz, bandwidth_hz), ...] or [offset_hz, ...]
     (bandwidth 0 = rate_out).  process() takes a device block [n_in, 2] (float32; int16 for INPUT_IQ16, int8 for INPUT_IQ8),
     n_in a multiple of `down`, and returns [V, n_out, 2] float32 rows or writes them into `out` (a [V, >= n_out, 2] float32 view
-    whose rows may lie any stride apart)."""
+    whose rows may lie any stride apart).
+
+    SondeTuner.slots(...) makes a tuner of idle slots instead (SPEC 3.12): slot_set() / slot_clear() tune and idle them between
+    two process() calls; an idle slot costs no mixing and its row is zeros.  `offsets[k]` / `bandwidths[k]` are None while idle."""
 
     def __init__(self, rate_in: int, rate_out: int, vfos, max_in: int, *, input_kind: int = INPUT_IQ, device: int = 0):
         self.L = _lib.load()
@@ -67,6 +70,37 @@ class SondeTuner:
         self.offsets = [int(f) for f, _ in spec]
         self.bandwidths = [int(b) or int(rate_out) for _, b in spec]
         self.up, self.down = ratio(rate_in, rate_out)
+
+    @classmethod
+    def slots(cls, rate_in: int, rate_out: int, n_slots: int, bandwidths, max_in: int, *, input_kind: int = INPUT_IQ, device: int = 0):
+        """n_slots idle slots with one tap set per listed bandwidth (sonde_tuner_create_slots)"""
+        self = cls.__new__(cls)
+        self.L = _lib.load()
+        self.n_vfos = int(n_slots)
+        bws = np.ascontiguousarray([int(b) for b in bandwidths], dtype=np.uint32)
+        h = C.c_void_p()
+        _chk(self.L.sonde_tuner_create_slots(int(rate_in), int(rate_out), self.n_vfos, bws.ctypes.data_as(C.c_void_p), len(bws), int(max_in),
+                                             int(input_kind), int(device), C.byref(h)))
+        self.h = h
+        self.rate_in, self.rate_out, self.max_in = int(rate_in), int(rate_out), int(max_in)
+        self.input_kind, self.device = int(input_kind), int(device)
+        self.offsets = [None] * self.n_vfos
+        self.bandwidths = [None] * self.n_vfos
+        self.up, self.down = ratio(rate_in, rate_out)
+        return self
+
+    def slot_set(self, k: int, hz: int, bandwidth_hz: int = 0):
+        """slot k to offset hz at a listed bandwidth from the next process() on, as if tuned there since create (theta = 0)"""
+        _chk(self.L.sonde_tuner_slot_set(self.h, int(k), int(hz), int(bandwidth_hz)))
+        self.offsets[k], self.bandwidths[k] = int(hz), int(bandwidth_hz) or self.rate_out
+
+    def slot_clear(self, k: int):
+        """slot k idle from the next process() on: its row is zeros"""
+        _chk(self.L.sonde_tuner_slot_clear(self.h, int(k)))
+        self.offsets[k] = self.bandwidths[k] = None
+
+    def slot_active(self, k: int) -> bool:
+        return bool(_chk(self.L.sonde_tuner_slot_active(self.h, int(k))))
 
     def out_samples(self, n_in: int) -> int:
         return int(self.L.sonde_tuner_out_samples(self.h, int(n_in)))
