@@ -102,6 +102,7 @@ enum { SONDE_INPUT_IQ = 0,      /* complex64 interleaved I,Q at 48 kS/s (vfo->ou
                                  * frames are those of SONDE_INPUT_IQ fed with the same integers as floats, for half the bytes over PCIe,
                                  * xGMI and HBM.  Batch / node API, all seven sonde types. */
 
+#define SONDE_FRAME_RESCUED 2u   /* SondeFrame.flags: an RS41 frame the second pass of SONDE_FLAG_RS41_RESCUE filled in */
 #define SONDE_TILE       2048   /* samples; submit lengths are multiples of this */
 #define SONDE_FRAME_MAX  528
 
@@ -110,7 +111,7 @@ typedef struct {
 	uint32_t type;
 	int32_t  len;            /* bytes valid in data[] */
 	int32_t  nerr[2];        /* RS41: bytes corrected per RS codeword, -1 = uncorrectable */
-	uint32_t flags;          /* bit0: signal polarity was inverted */
+	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED */
 	uint64_t bitpos;         /* absolute index (since create) of the first sync bit */
 	uint8_t  data[SONDE_FRAME_MAX];   /* de-whitened, error-corrected frame */
 } SondeFrame;
@@ -172,6 +173,17 @@ typedef struct {
 #define SONDE_FLAG_WIDE_AUTO 8u
 #define SONDE_FLAG_JOIN      16u     /* the default since round 6 (accepted and ignored; round 5: the opt-out of its lagging default) */
 #define SONDE_FLAG_LATE_JOIN 32u     /* see SONDE_FLAG_PIPELINE above */
+/* RS41 channels: a second pass over the frames whose Reed-Solomon stage failed (a codeword at nerr = -1), DESIGN SPEC 3.3c.  After the
+ * frame-type byte an RS41 frame is a chain of blocks type, len, body[len], crc16.  Per channel the library learns the chain's layout
+ * from the frames the first pass found clean or corrected; in a failed frame it writes the learned type / len bytes back, takes the
+ * body and CRC bytes of the blocks whose CRC fails as ERASURES and decodes again: RS(255,231) fills up to 24 erased bytes per
+ * codeword (2 errors + erasures <= 24) where it corrects 12 unknown ones -- the fade of a spinning payload, a burst of wrong bytes in
+ * an otherwise clean frame.  A result is taken only if every block's CRC passes on it (a false accept: about 2^-16 per bad block).
+ * Rescued frames carry SONDE_FRAME_RESCUED and nerr[c] = the bytes of codeword c that changed; every other record is, byte for byte,
+ * what it is without the flag.  One small launch more per launch unit with RS41 channels, behind the kernel that wrote the records;
+ * no host synchronisation.  Limits: nothing before the channel's first good frame; nothing beyond 24 erased bytes per codeword (the
+ * 93-byte GPS-raw block and the XDATA block are out of reach); not for the batch behind a channelizer. */
+#define SONDE_FLAG_RS41_RESCUE 64u
 
 typedef struct SondeBatch SondeBatch;
 
@@ -253,6 +265,17 @@ int      sonde_batch_read_bits(SondeBatch *b, uint32_t channel, uint64_t from, s
 /* parity-test introspection: the RS(255,231) corrector alone on n_pairs codeword pairs of [2][256] bytes (positions >= n zero),
  * corrected in place; status[2 i + c] = 0 clean, > 0 corrected byte errors, -1 uncorrectable (word left as received) */
 int      sonde_batch_test_rs255(SondeBatch *b, uint8_t *cw_pairs, size_t n_pairs, int n, int32_t *status);
+/* the twin of sonde_batch_test_rs255 for the errors-and-erasures corrector of SONDE_FLAG_RS41_RESCUE: erased[i][c][k] != 0 marks
+ * position k of codeword c of pair i as erased (positions >= n are ignored); a word decodes iff a codeword differs from it in erased
+ * positions and in v others with 2 v + e <= 24; status = the bytes changed (0: it was a codeword), -1 = no such codeword or more than
+ * 24 erasures (word left as received).  Works on any batch (the flag is not needed). */
+int      sonde_batch_test_rs255_erasures(SondeBatch *b, uint8_t *cw_pairs, size_t n_pairs, int n, const uint8_t *erased /* [n_pairs][2][256], 0/1 */,
+                                         int32_t *status);
+/* SONDE_FLAG_RS41_RESCUE introspection: the block layouts an RS41 channel has learned, out[0] for 320-byte frames, out[1] for 518-byte
+ * ones (n_blocks = 0: none yet; unused entries zero), the frames with a failed codeword it had a layout to try for, and those it
+ * rescued, since create / the channel's restart.  Synchronises.  An error without the flag or for a channel that is not RS41. */
+typedef struct { uint32_t n_blocks; uint16_t offset[16]; uint8_t type[16]; uint8_t len[16]; } SondeRs41Layout;
+int      sonde_batch_rescue_info(SondeBatch *b, uint32_t channel, SondeRs41Layout out[2], uint32_t *tried, uint32_t *rescued);
 uint64_t sonde_batch_nbits(SondeBatch *b, uint32_t channel);
 int      sonde_batch_read_state(SondeBatch *b, uint32_t channel, int64_t *t_next, int32_t *period, float *bias, float *amp,
                                 float *afc_u /* the newest AFC state u of SPEC 3.0b (the carrier offset the channel is following: 2 atan u per

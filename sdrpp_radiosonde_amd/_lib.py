@@ -47,6 +47,10 @@ DETECTION_DTYPE = np.dtype([("type", "<i4"), ("inverted", "<u4"), ("best", "<f8"
 assert DETECTION_DTYPE.itemsize == C.sizeof(SondeDetection)
 
 
+class SondeRs41Layout(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint32), ("offset", C.c_uint16 * 16), ("type", C.c_uint8 * 16), ("len", C.c_uint8 * 16)]
+
+
 class SondeTunerVfo(C.Structure):
     _fields_ = [("offset_hz", C.c_int32), ("bandwidth_hz", C.c_uint32)]
 
@@ -96,6 +100,8 @@ FLAG_PIPELINE = 4        # launch units never joined into the caller's stream (S
 FLAG_JOIN = 16           # accepted and ignored: joining at every submit is the default since round 6 (SONDE_FLAG_JOIN)
 FLAG_LATE_JOIN = 32      # launch units joined into the caller's stream ONE SUBMIT LATE (SONDE_FLAG_LATE_JOIN; opt-in: round 5's default)
 FLAG_WIDE_AUTO = 8       # SONDE_FLAG_WIDE for the types whose reference channel is >= 20 kHz only (iMS-100, MRZ-N1, M10)
+FLAG_RS41_RESCUE = 64    # RS41: second pass over frames whose RS stage failed, block CRCs as erasure hints (SONDE_FLAG_RS41_RESCUE; opt-in)
+FRAME_RESCUED = 2        # SondeFrame.flags bit of a frame that pass filled in (SONDE_FRAME_RESCUED)
 
 
 # every symbol include/sonde_abi.h declares; tests check the .so exports all of them
@@ -122,6 +128,7 @@ ABI_SYMBOLS = [
     "sonde_scan_spectrum", "sonde_scan_candidates", "sonde_scan_search", "sonde_scan_window", "sonde_scan_auto_fft_size",
     "sonde_tuner_create_slots", "sonde_tuner_slot_set", "sonde_tuner_slot_clear", "sonde_tuner_slot_active",
     "sonde_batch_restart_channels", "sonde_detect_restart_channels", "sonde_live_match",
+    "sonde_batch_test_rs255_erasures", "sonde_batch_rescue_info",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -176,6 +183,9 @@ def load() -> C.CDLL:
                                          C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     if hasattr(L, "sonde_batch_test_rs255"):
         L.sonde_batch_test_rs255.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]
+    if hasattr(L, "sonde_batch_rescue_info"):             # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        L.sonde_batch_test_rs255_erasures.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp]
+        L.sonde_batch_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(SondeRs41Layout), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.sonde_get_taps.argtypes = [C.c_int, vp]
     L.sonde_parse_frame.argtypes = [vp, C.POINTER(SondeData), C.c_int]
     L.sonde_batch_poll.argtypes = [vp, C.POINTER(SondeData), C.POINTER(C.c_uint32), C.c_size_t]

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE
+from ._lib import FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
 
 
 class SondeError(RuntimeError):
@@ -36,6 +36,7 @@ class SondeBatch:
             cfg.types = self._types.ctypes.data_as(C.POINTER(C.c_uint8))
         cfg.max_samples = self.max_samples
         cfg.flags = flags
+        self.flags = int(flags)
         cfg.time_slices = time_slices          # 0: the library's choice (SondeBatchConfig.time_slices)
         cfg.input_kind = input_kind
         cfg.device = device
@@ -166,6 +167,26 @@ class SondeBatch:
     def set_timing(self, every_n: int):
         """Record kernel-timing events on every n-th submit only (0: never); the next submit is timed."""
         self._chk(self.L.sonde_batch_set_timing(self.h, int(every_n)))
+
+    def rescue_info(self, channel: int) -> dict:
+        """FLAG_RS41_RESCUE: what an RS41 channel has learned and done (sonde_batch_rescue_info): {'layouts': {320: [(offset, type,
+        len), ...], 518: [...]}, 'tried': frames with a failed codeword it had a layout for, 'rescued': frames it filled in}."""
+        lay = (_lib.SondeRs41Layout * 2)()
+        tried, rescued = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.sonde_batch_rescue_info(self.h, channel, lay, C.byref(tried), C.byref(rescued)))
+        layouts = {flen: [(int(l.offset[i]), int(l.type[i]), int(l.len[i])) for i in range(l.n_blocks)] for flen, l in ((320, lay[0]), (518, lay[1]))}
+        return {"layouts": layouts, "tried": int(tried.value), "rescued": int(rescued.value)}
+
+    def test_rs255_erasures(self, cw_pairs: np.ndarray, erased: np.ndarray, n: int):
+        """The errors-and-erasures RS(255,231) corrector alone (sonde_batch_test_rs255_erasures): cw_pairs, erased [P, 2, 256] uint8
+        (erased != 0: the position is an erasure).  Returns (corrected pairs, status [P, 2]): status = bytes changed, -1 = undecodable."""
+        cw = np.ascontiguousarray(cw_pairs, dtype=np.uint8).copy()
+        er = np.ascontiguousarray(erased, dtype=np.uint8)
+        assert cw.ndim == 3 and cw.shape[1:] == (2, 256) and er.shape == cw.shape
+        status = np.zeros((len(cw), 2), dtype=np.int32)
+        self._chk(self.L.sonde_batch_test_rs255_erasures(self.h, cw.ctypes.data_as(C.c_void_p), len(cw), int(n), er.ctypes.data_as(C.c_void_p),
+                                                         status.ctypes.data_as(C.c_void_p)))
+        return cw, status
 
     def nbits(self, channel: int) -> int:
         return int(self.L.sonde_batch_nbits(self.h, channel))

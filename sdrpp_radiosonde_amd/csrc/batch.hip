@@ -221,6 +221,9 @@ struct SondeBatch {
 	hipEvent_t ev_restart = nullptr;
 	std::deque<std::pair<uint64_t, uint32_t>> parser_restarts;
 	bool behind_channelizer = false;
+	// SONDE_FLAG_RS41_RESCUE (SPEC 3.3c): per-channel layouts and counters of the second pass (rescue_kernel.hip); null: the flag is
+	// off or the batch has no RS41 channel, and nothing of it is allocated or launched
+	SdRescueState *d_rescue = nullptr;
 };
 
 static uint32_t pow2ceil(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
@@ -235,7 +238,7 @@ extern "C" void sonde_batch_destroy(SondeBatch *b)
 	if (b->ev_xs) (void)hipEventDestroy(b->ev_xs);
 	if (b->ev_restart) (void)hipEventDestroy(b->ev_restart);
 	b->restart_lists.destroy();
-	(void)hipFree(b->d_taps); (void)hipFree(b->d_modems); (void)hipFree(b->d_prog);
+	(void)hipFree(b->d_taps); (void)hipFree(b->d_modems); (void)hipFree(b->d_prog); (void)hipFree(b->d_rescue);
 	(void)hipFree(b->d_astates); (void)hipFree(b->d_wtab); (void)hipFree(b->d_wtab_c50); (void)hipFree(b->d_afq);
 	for (auto &u : b->units) { if (u.st) (void)hipStreamDestroy(u.st); for (int k = 0; k < 2; k++) if (u.ev_join[k]) (void)hipEventDestroy(u.ev_join[k]); }
 	for (int k = 0; k < 4; k++) (void)hipFree(b->d_cls[k]);
@@ -374,6 +377,7 @@ extern "C" int sonde_batch_create(const SondeBatchConfig *cfg, SondeBatch **out)
 		ALLOC(b->d_wtab_c50, SD_C50_PER * 2 * sizeof(float));
 		ALLOC(b->d_afq, n_afsk * (size_t)(cfg->max_samples / SD_AF_DEC) * sizeof(float));
 	}
+	if ((cfg->flags & SONDE_FLAG_RS41_RESCUE) && !b->chlist[SONDE_RS41].empty()) ALLOC(b->d_rescue, C * sizeof(SdRescueState));
 #undef ALLOC
 #define CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { sonde_batch_destroy(b); return fail(#x, e_); } } while (0)
 	// modem tables
@@ -484,6 +488,7 @@ extern "C" int sonde_batch_create(const SondeBatchConfig *cfg, SondeBatch **out)
 	CHK(hipMemcpy(b->d_states, st.data(), C * sizeof(SdChanState), hipMemcpyHostToDevice));
 	CHK(hipMemset(b->d_fstates, 0, C * sizeof(SdFramerState)));
 	CHK(hipMemset(b->d_prog, 0, (C + 1) * sizeof(uint32_t)));
+	if (b->d_rescue) CHK(hipMemset(b->d_rescue, 0, C * sizeof(SdRescueState)));       // no layout, counters zero
 	{
 		hipDeviceProp_t pr;
 		if (hipGetDeviceProperties(&pr, cfg->device) == hipSuccess && pr.multiProcessorCount > 0) b->residency = 4u * (uint32_t)pr.multiProcessorCount;
@@ -596,6 +601,7 @@ int sd_batch_submit_bins(SondeBatch *b, const SdBinsArgs *ba, size_t n_steps, vo
 	if (!b || !ba || !ba->phases || !ba->carry_rows || !ba->g_comp || !sd_batch_bins_capable(b)) return fail("sd_batch_submit_bins: bad argument");
 	//  the launch-unit path knows nothing of phase rows: it would read them as float rows without an error
 	if (!b->units.empty()) return fail("sd_batch_submit_bins: the decoder batch behind a channelizer must be one plain launch (no launch units)");
+	if (b->d_rescue) return fail("sd_batch_submit_bins: SONDE_FLAG_RS41_RESCUE is not available for the decoder batch behind a channelizer");
 	const size_t n_out = n_steps / 5 * 12;
 	if (n_steps == 0 || n_steps % 2560 || n_out > b->max_samples || ba->row_stride < n_steps + 16)
 		return fail("sd_batch_submit_bins: n_steps must be a multiple of 2560 within max_samples");
@@ -684,6 +690,18 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 		framer_launched = true;
 		return 0;
 	};
+	// SONDE_FLAG_RS41_RESCUE: the second pass over the RS41 records of this submit (SPEC 3.3c), on the stream of the kernel that wrote
+	// them and directly behind it (the demod kernel's epilogue, or sd_rsdec_rs41_kernel), before anything joins that stream or records
+	// the submit's completion; list = null: every channel of the batch is RS41
+	auto launch_rescue = [&](hipStream_t sk, const uint32_t *list, uint32_t nch) -> int {
+		if (!b->d_rescue || !nch) return 0;
+		sd_launch_rescue_rs41(nch, sk, b->d_gfexp, b->d_gflog, b->d_gfswar, d_frames, d_counts, b->max_frames, list, b->d_rescue);
+		HIPCHK(hipGetLastError());
+		framer_launched = true;
+		return 0;
+	};
+	const uint32_t n_rs41 = (uint32_t)b->chlist[SONDE_RS41].size();
+	const bool all_rs41 = n_rs41 == b->n_channels;
 	const bool one_launch = b->units.empty();
 	// time slices: every sliced launch of this submit shares seg_base (each channel belongs to exactly one launch)
 	uint32_t total_wg = b->n_channels;
@@ -708,6 +726,7 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 			n_tiles, b->d_states, b->d_hist, b->d_bitring, b->ring_words, b->d_taps, b->d_modems, fo);
 		HIPCHK(hipGetLastError());
 		if (timed) HIPCHK(hipEventRecord(ev[1], stream));
+		if (launch_rescue(stream, b->d_chlist[SONDE_RS41], n_rs41)) return -1;
 	} else if (one_launch) {
 		if (bins_in)      // channelizer bins: one wave per bin (bins_kernel.hip); n_tiles = 3 per block of 2560 phases
 			sd_launch_bins(b->n_channels, stream, bins_in->phases, bins_in->row_stride, n_tiles / 3, bins_in->carry_rows, bins_in->carry_stride,
@@ -720,7 +739,10 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 		}
 		HIPCHK(hipGetLastError());
 		if (timed) HIPCHK(hipEventRecord(ev[1], stream));
-		for (int t = 0; t < SONDE_NTYPES; t++) if (launch_framers(t, stream)) return -1;
+		for (int t = 0; t < SONDE_NTYPES; t++) {
+			if (launch_framers(t, stream)) return -1;
+			if (t == SONDE_RS41 && launch_rescue(stream, all_rs41 ? nullptr : b->d_chlist[SONDE_RS41], n_rs41)) return -1;
+		}
 	} else {
 		// fork: the launch units are independent (disjoint channels), let them share the GPU; a unit's frame decoder follows
 		// its demod kernel on the unit's stream, so that it overlaps the other units' demodulators
@@ -751,9 +773,13 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 			if (timed) HIPCHK(hipEventRecord(ec[1], u.st));
 			if (u.type >= 0) {
 				if (launch_framers(u.type, u.st, u.off, u.n)) return -1;
+				if (u.type == SONDE_RS41 && launch_rescue(u.st, b->d_chlist[SONDE_RS41] + u.off, u.n)) return -1;
 			} else {
-				for (int t = 0; t < SONDE_NTYPES; t++)
-					if (t != SONDE_IMET4 && t != SONDE_C50 && modem_class(b->md, t) == u.cls && launch_framers(t, u.st)) return -1;
+				for (int t = 0; t < SONDE_NTYPES; t++) {
+					if (t == SONDE_IMET4 || t == SONDE_C50 || modem_class(b->md, t) != u.cls) continue;
+					if (launch_framers(t, u.st)) return -1;
+					if (t == SONDE_RS41 && launch_rescue(u.st, b->d_chlist[SONDE_RS41], n_rs41)) return -1;
+				}
 			}
 			// join: into the caller's stream (work queued there afterwards sees the submit finished), or -- pipelined -- into the
 			// library's completion stream only, so that the next submit's units start behind their OWN predecessors and the
@@ -840,6 +866,10 @@ extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *chann
 	hipLaunchKernelGGL(sd_batch_restart_kernel, dim3((unsigned)n), dim3(256), 0, s, lb->dev, b->d_states, b->d_fstates, b->d_hist, b->d_bitring,
 		b->ring_words, b->d_astates, b->d_prog, b->d_modems);
 	HIPCHK(hipGetLastError());
+	if (b->d_rescue) {                         // SPEC 3.3c: a restarted channel has no layout
+		sd_launch_rescue_clear((uint32_t)n, s, lb->dev, b->d_rescue);
+		HIPCHK(hipGetLastError());
+	}
 	HIPCHK(b->restart_lists.done(lb, s));
 	if (b->pipeline) {
 		HIPCHK(hipEventRecord(b->ev_restart, s));
@@ -1148,6 +1178,43 @@ extern "C" int sonde_batch_test_rs255(SondeBatch *b, uint8_t *cw_pairs, size_t n
 	if (e == hipSuccess) e = hipMemcpy(status, d_st, n_pairs * 2 * sizeof(int32_t), hipMemcpyDeviceToHost);
 	(void)hipFree(d_cw); (void)hipFree(d_st);
 	return e == hipSuccess ? 0 : fail("sonde_batch_test_rs255", e);
+}
+
+// The errors-and-erasures corrector of SONDE_FLAG_RS41_RESCUE alone (sd_rsee.h): as above, with erased[i][c][k] != 0 marking position k.
+extern "C" int sonde_batch_test_rs255_erasures(SondeBatch *b, uint8_t *cw_pairs, size_t n_pairs, int n, const uint8_t *erased, int32_t *status)
+{
+	if (!b || !cw_pairs || !erased || !status || !n_pairs || n < 25 || n > 255) return fail("sonde_batch_test_rs255_erasures: bad argument");
+	HIPCHK(hipSetDevice(b->device));
+	uint8_t *d_cw = nullptr, *d_er = nullptr;
+	int32_t *d_st = nullptr;
+	hipError_t e = hipMalloc((void **)&d_cw, n_pairs * 512);
+	if (e == hipSuccess) e = hipMalloc((void **)&d_er, n_pairs * 512);
+	if (e == hipSuccess) e = hipMalloc((void **)&d_st, n_pairs * 2 * sizeof(int32_t));
+	if (e == hipSuccess) e = hipMemcpy(d_cw, cw_pairs, n_pairs * 512, hipMemcpyHostToDevice);
+	if (e == hipSuccess) e = hipMemcpy(d_er, erased, n_pairs * 512, hipMemcpyHostToDevice);
+	if (e == hipSuccess) {
+		sd_launch_rsee_unit(d_cw, d_er, (uint32_t)n_pairs, n, d_st, b->d_gfexp, (const uint8_t *)b->d_gflog, b->d_gfswar, nullptr);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpy(cw_pairs, d_cw, n_pairs * 512, hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(status, d_st, n_pairs * 2 * sizeof(int32_t), hipMemcpyDeviceToHost);
+	(void)hipFree(d_cw); (void)hipFree(d_er); (void)hipFree(d_st);
+	return e == hipSuccess ? 0 : fail("sonde_batch_test_rs255_erasures", e);
+}
+
+extern "C" int sonde_batch_rescue_info(SondeBatch *b, uint32_t channel, SondeRs41Layout out[2], uint32_t *tried, uint32_t *rescued)
+{
+	if (!b || channel >= b->n_channels) return fail("sonde_batch_rescue_info: bad argument");
+	if (b->behind_channelizer) return fail("sonde_batch_rescue_info: SONDE_FLAG_RS41_RESCUE is not available for the batch behind a channelizer");
+	if (!b->d_rescue) return fail("sonde_batch_rescue_info: the batch was created without SONDE_FLAG_RS41_RESCUE (or has no RS41 channel)");
+	if (b->types[channel] != SONDE_RS41) return fail("sonde_batch_rescue_info: not an RS41 channel");
+	if (sonde_batch_sync(b) < 0) return -1;
+	SdRescueState st;
+	HIPCHK(hipMemcpy(&st, b->d_rescue + channel, sizeof(st), hipMemcpyDeviceToHost));
+	if (out) { out[0] = st.lay[0]; out[1] = st.lay[1]; }
+	if (tried) *tried = st.tried;
+	if (rescued) *rescued = st.rescued;
+	return 0;
 }
 
 extern "C" uint64_t sonde_batch_nbits(SondeBatch *b, uint32_t channel)

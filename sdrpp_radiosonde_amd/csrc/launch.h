@@ -86,6 +86,15 @@ void sd_launch_framer_other(int type, uint32_t n_list, hipStream_t stream,
 void sd_launch_rs255_unit(uint8_t *cw_io, uint32_t n_pairs, int n, int32_t *status, const uint8_t *gf_exp, const uint8_t *gf_log,
 	const uint32_t *gf_swar, hipStream_t stream);
 
+// SONDE_FLAG_RS41_RESCUE (rescue_kernel.hip, DESIGN SPEC 3.3c): per RS41 channel the learned block layouts of the two frame lengths
+// (320, 518) and two counters (frames with a failed codeword that had a layout to try; frames rescued), carried from submit to submit
+struct SdRescueState { SondeRs41Layout lay[2]; uint32_t tried, rescued; };
+void sd_launch_rescue_rs41(uint32_t n_list, hipStream_t stream, const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar,
+	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist, SdRescueState *states);
+void sd_launch_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdRescueState *states);
+void sd_launch_rsee_unit(uint8_t *cw_io, const uint8_t *erased, uint32_t n_pairs, int n, int32_t *status, const uint8_t *gf_exp, const uint8_t *gf_log,
+	const uint32_t *gf_swar, hipStream_t stream);
+
 // SPEC 3.6's mixer table (batch.hip): out[2k], out[2k + 1] = (cos, -sin)(2 pi cycles k / per) as float32
 void make_mixer(float *out, int cycles, int per);
 
