@@ -277,18 +277,27 @@ def _clamp_q(v, e, lim, scale):
 
 @dataclass
 class Check:
-    """worst error of one scene as a fraction of each bound, and the ambiguous bits"""
+    """worst error of one scene as a fraction of each bound, and the ambiguous bits; with hidden states (replay's states[j] = None):
+    the spans between observed states, those left unresolved (the candidate set outgrew its limit: counted, not asserted), and, where the
+    caller gave the true hidden states, how many of them lay outside the carried set"""
     worst: dict
     amb: int = 0
     nbits: int = 0
     ntiles: int = 0
+    spans: int = 0
+    unresolved: int = 0
+    hidden: int = 0
+    outside: int = 0
+    cands: int = 0
 
     def put(self, key, frac):
         self.worst[key] = max(self.worst.get(key, 0.0), float(frac))
 
     def line(self, name: str) -> str:
         w = " ".join(f"{k}={v:.3g}" for k, v in sorted(self.worst.items()))
-        return f"DEMOD-REF {name}: tiles={self.ntiles} bits={self.nbits} ambiguous={self.amb} ({self.amb / max(self.nbits, 1):.2e}) {w}"
+        blk = f" spans={self.spans} unresolved={self.unresolved} candidates<={self.cands}" if self.spans != self.ntiles else ""
+        return (f"DEMOD-REF {name}: tiles={self.ntiles}{blk} bits={self.nbits} ambiguous={self.amb} "
+                f"({self.amb / max(self.nbits, 1):.2e}) {w}")
 
     def failures(self):
         return {k: v for k, v in self.worst.items() if not v <= 1.0}
@@ -299,35 +308,77 @@ def initial_state(m: Modem) -> dict:
     return dict(t_next=(32 << 16) + m.period0, period=m.period0, bias=0.0, amp=0.25, afc_u=0.0)
 
 
+CAND_LIMIT = 256                 # candidate states carried through hidden tiles at most; a span that needs more is unresolved
+
+
+@dataclass
+class _Cand:
+    """a state the product may be in: the integers exactly, the two floats as centre and error; the position in the span's bits and
+    what the chain that led here has accumulated"""
+    t: int
+    period: int
+    bias: float
+    eb: float
+    amp: float
+    ea: float
+    nstat: int
+    off: int = 0
+    amb: int = 0
+    nbits: int = 0
+    fr: dict | None = None
+
+
 def replay(d: np.ndarray, bd: np.ndarray, m: Modem, states: list, bits: list, *, afc: bool, chk: Check | None = None,
            cutoff: float = CUTOFF, normalise: bool = True, mid_sign: int = -1, gardner_k0: bool = False,
            gardner_k256: bool = False, e_over_k: bool = False, slack: int = SLACK, pclamp: int = 8, acq_tiles: int = 3,
            afc_lag: int = 3, afc_gain: float = AFC_GAIN, afc_leak: float = AFC_LEAK, shift_sign: int = -1,
-           jump_ratio: int = 17, **mut) -> Check:
+           jump_ratio: int = 17, cand_limit: int = CAND_LIMIT, truth: list | None = None, **mut) -> Check:
     """Check every tile of one channel against one step of the SPEC's recurrence.
     d, bd: the discriminator stream (disc_*) and its bound; states[j], bits[j]: the product's state and new bits after tile j;
     afc: the stream is IQ (the AFC, 3.0d and 3.0e act).  Returns a Check whose worst fractions must all be <= 1.
-    Keys: count (exact), bit, dphase, dper, bias, amp, jump, afc."""
+    Keys: count (exact), bit, dphase, dper, bias, amp, jump, afc.
+
+    states[j] may be None: tile j's end state is not observable (a channelizer bin's smallest submit is a block of 3 tiles).  bits then
+    has one entry per OBSERVED state: the bits of the span of tiles that ends there, concatenated.  A span is accepted if and only if
+    there is a chain of per-tile steps of the recurrence from the observed state before it to the observed state after it whose every
+    step lies within the bounds, whose counts add up to the span's count exactly, and which reproduces every bit that is not ambiguous.
+    Mechanism: a set of candidate states after each hidden tile.  t_next and period are integers and every value their rint intervals
+    allow is enumerated (candidates that agree in both are merged: the hull of their intervals); bias and amp are carried as a centre
+    and the error this replay already computes, which widens the ambiguity
+    test (gap <= by + e_bias), the Gardner term's bound and, twice, the relative error of err (amp squared).  A candidate's (t, period)
+    fix its tile's bit count; one whose counts overrun the span's bits, or which an unambiguous bit contradicts, is dropped.  At the
+    span's end the observed state is tested against every surviving candidate with the tests of the observed case and the candidate
+    with the smallest worst fraction is reported.  More than cand_limit candidates: the span is unresolved (Check.unresolved).  Only
+    the non-AFC path without the tone front-end supports hidden states.  With every state observed each span is one tile and the one
+    candidate has zero error: the computation is the one-step check, term for term.
+    truth (optional): the states the product really had after every tile; Check.outside counts the hidden ones that are not in the
+    carried set (t_next and period among the candidates, bias and amp inside a matching candidate's intervals)."""
     chk = chk or Check({})
     H = taps(m, cutoff=cutoff, normalise=normalise)
-    u_after = np.array([s["afc_u"] for s in states], np.float64)
+    hidden_mode = any(s is None for s in states)
+    assert not hidden_mode or (not afc and m.pre == 1 and m.rounds == 1), "hidden states: the non-AFC, pre == 1 path only"
+    assert states[-1] is not None and len(bits) == sum(s is not None for s in states)
+    u_after = np.array([s["afc_u"] for s in states], np.float64) if afc else None
     prev = initial_state(m)
     nstat = 0
     kp = m.period0 * (0.5 / math.pi)
     e_kp = 2.0 * U * kp
     pmin, pmax = m.period0 - (m.period0 >> pclamp), m.period0 + (m.period0 >> pclamp)
+    cl = lambda q: min(max(q, pmin), pmax)
 
-    for j, (st, b) in enumerate(zip(states, bits)):
-        chk.ntiles += 1
+    def k_total(j, c):
+        limit = (((m.itile * (j + 1)) - 1 - m.T // 2 - slack) << 16) | 0xFFFF
+        return (limit - c.t) // c.period + 1 if c.t <= limit else 0
+
+    def tile(j, c, b, st):
+        """one tile from candidate c with the bits b (len(b) == k_total): st observed -> the fractions of every test (dict), or
+        "skip" (SRS-C50's first round); st None -> the list of candidates after the tile ([] if a bit contradicts c)"""
+        fr = {}
         n0 = m.itile * (j + 1)
-        t, period, bias, amp = prev["t_next"], prev["period"], prev["bias"], prev["amp"]
-        limit = ((n0 - 1 - m.T // 2 - slack) << 16) | 0xFFFF
-        K_total = (limit - t) // period + 1 if t <= limit else 0
-        b = np.asarray(b, np.int64)
-        chk.put("count", 0.0 if b.shape[0] == K_total else math.inf)
-        if b.shape[0] != K_total:
-            return chk
+        t, period, bias, amp, eb, ea = c.t, c.period, c.bias, c.amp, c.eb, c.ea
+        K_total = b.shape[0]
         K = min(K_total, m.rmax)
+        namb = 0
         if K:
             k = np.arange(K)
             pos = t + k * period
@@ -335,15 +386,18 @@ def replay(d: np.ndarray, bd: np.ndarray, m: Modem, states: list, bits: list, *,
             bb = b[:K]
             # (b) each bit
             gap = np.abs(y - bias)
-            amb = gap <= by
+            amb = gap <= by + eb
             wrong = (bb != (y > bias)) & ~amb
-            chk.amb += int(amb.sum())
-            chk.nbits += K
-            chk.put("bit", (gap[wrong] / np.maximum(by[wrong], 1e-300)).max() if wrong.any() else 0.0)
+            namb = int(amb.sum())
+            fr["bit"] = (gap[wrong] / np.maximum(by[wrong] + eb, 1e-300)).max() if wrong.any() else 0.0
+            if st is None and wrong.any():
+                c.fr = fr
+                return []
         if m.rounds > 1 and K_total > m.rmax:
             # SRS-C50: only the end of the second round is observable; the first round's bits are checked above
-            prev = st
-            continue
+            c.fr, c.amb, c.nbits = fr, c.amb + namb, c.nbits + K
+            return "skip"
+        ns = c.nstat
         if K:
             kg = k[(k % 64 != 0) | gardner_k0]
             kg = kg[(kg < ROUND) | gardner_k256]
@@ -358,11 +412,11 @@ def replay(d: np.ndarray, bd: np.ndarray, m: Modem, states: list, bits: list, *,
             C1 = int(one.sum())
             C0 = K - C1
             a = y[kg - 1] - y[kg]
-            ea = by[kg - 1] + by[kg] + U * np.abs(a)
+            ea_ = by[kg - 1] + by[kg] + U * np.abs(a)
             bmv = mm[kg] - bias
-            ebm = bm[kg] + U * np.abs(bmv)
+            ebm = bm[kg] + U * np.abs(bmv) + eb
             e = a * bmv
-            ee = ea * np.abs(bmv) + np.abs(a) * ebm + ea * ebm + U * (np.abs(a) + ea) * (np.abs(bmv) + ebm)
+            ee = ea_ * np.abs(bmv) + np.abs(a) * ebm + ea_ * ebm + U * (np.abs(a) + ea_) * (np.abs(bmv) + ebm)
             Ec, Es = _clamp_q(e, ee, 1e6 / 1024.0, 1024.0)
             E, eE = Ec.sum(), Es.sum()
             if m.pre == 8:
@@ -373,57 +427,76 @@ def replay(d: np.ndarray, bd: np.ndarray, m: Modem, states: list, bits: list, *,
             if C1 > 0 and C0 > 0:
                 hi, ehi = S1 / C1 / 4096.0, eS1 / C1 / 4096.0 + abs(S1 / C1 / 4096.0) * (RECIP_ERR + U)
                 lo, elo = S0 / C0 / 4096.0, eS0 / C0 / 4096.0 + abs(S0 / C0 / 4096.0) * (RECIP_ERR + U)
-                c, ec = 0.5 * (hi + lo), 0.5 * (ehi + elo) + U * abs(0.5 * (hi + lo))
+                cc, ec = 0.5 * (hi + lo), 0.5 * (ehi + elo) + U * abs(0.5 * (hi + lo))
                 av, ev = 0.5 * (hi - lo), 0.5 * (ehi + elo) + U * abs(0.5 * (hi - lo))
-                if nstat == 0:
-                    nb, enb, na, ena = c, ec, av, ev
+                if ns == 0:
+                    nb, enb, na, ena = cc, ec, av, ev
                 else:
-                    nb = bias + 0.5 * (c - bias)
-                    enb = 0.5 * ec + 0.5 * U * abs(c - bias) + U * abs(nb)
+                    # (the carried errors: half of each goes through the average, a rounding's share of it on top)
+                    nb = bias + 0.5 * (cc - bias)
+                    enb = 0.5 * ec + 0.5 * U * abs(cc - bias) + U * abs(nb) + (0.5 + 2 * U) * eb
                     na = amp + 0.5 * (av - amp)
-                    ena = 0.5 * ev + 0.5 * U * abs(av - amp) + U * abs(na)
+                    ena = 0.5 * ev + 0.5 * U * abs(av - amp) + U * abs(na) + (0.5 + 2 * U) * ea
                 if na < 1e-3:
                     na, ena = float(np.float32(1e-3)), ena + 1e-10
-                nstat = 1
+                ns = 1
             else:
                 nb = (S1 + S0) / K / 4096.0
                 enb = (eS1 + eS0) / K / 4096.0 + abs(nb) * (RECIP_ERR + U)
-                na, ena = amp, 0.0
+                na, ena = amp, 0.0 + ea
             if m.pre == 1 and n0 <= acq_tiles * m.itile:
                 nb = (S1 + S0) / K / 4096.0
                 enb = (eS1 + eS0) / K / 4096.0 + abs(nb) * (RECIP_ERR + U)
-            chk.put("amp", abs(st["amp"] - na) / max(ena, 1e-300) if st["amp"] != na else 0.0)
-            # loop filter, from the product's amplitude (observable after the tile: only the round changes it)
+            if st is not None:
+                fr["amp"] = abs(st["amp"] - na) / max(ena, 1e-300) if st["amp"] != na else 0.0
+            # loop filter, from the product's amplitude (observable after the tile: only the round changes it); hidden: from the
+            # carried one, whose relative error r enters 1 / amp^2 as at most 1 / (1 - r)^2 - 1
             N = K if e_over_k else min(K, ROUND)
-            ampp = np.float64(np.float32(st["amp"]))
+            if st is not None:
+                ampp, rel = np.float64(np.float32(st["amp"])), 0.0
+            else:
+                r_ = ena / na
+                ampp, rel = np.float64(na), (1.0 / (1.0 - r_) ** 2 - 1.0 if r_ < 0.5 else math.inf)
             a2 = ampp * ampp
             err = E / N / 1024.0 / a2
             eerr = (eE + U * abs(E)) / N / 1024.0 / a2 + abs(err) * (2 * RECIP_ERR + 4 * U)
+            if rel:
+                eerr = eerr * (1.0 + rel) + abs(err) * rel
             errc = min(max(err, -1.0), 1.0)
             v = errc * kp
             ev = eerr * kp + abs(errc) * e_kp + U * abs(v)
+            if st is None:
+                if not math.isfinite(ev):
+                    return None
+                out = []
+                pers = sorted({cl(period + q) for q in range(int(np.rint((v - ev) / 4096.0)), int(np.rint((v + ev) / 4096.0)) + 1)})
+                for q in range(int(np.rint(v - ev)), int(np.rint(v + ev)) + 1):
+                    for p2 in pers:
+                        out.append(_Cand(t + K * period + q, p2, nb, enb, na, ena, ns, c.off + K_total, c.amb + namb, c.nbits + K))
+                return out
             dph_c, dph_s = _rint_iv(v, ev)
             dpr_c, dpr_s = _rint_iv(v / 4096.0, ev / 4096.0)
             dphase = st["t_next"] - t - K * period
             jumps = [0]
-            if m.pre == 8 and nstat:
+            if m.pre == 8 and ns:
                 # 16 SM > 17 SY with SM, SY within their slack: the jump is certain, excluded or either
                 lo_ = 16 * (SM - eSM) - jump_ratio * (SY + eSY)
                 hi_ = 16 * (SM + eSM) - jump_ratio * (SY - eSY)
                 jumps = [period >> 1] if lo_ > 0 else ([0] if hi_ <= 0 else [0, period >> 1])
             ok = [abs(dphase - jj - dph_c) <= dph_s for jj in jumps]
-            chk.put("dphase", min(abs(dphase - jj - v) / (ev + 0.5) for jj in jumps) if any(ok) else math.inf)
+            fr["dphase"] = min(abs(dphase - jj - v) / (ev + 0.5) for jj in jumps) if any(ok) else math.inf
             if m.pre == 8:
-                chk.put("jump", 0.0 if any(ok) else math.inf)
+                fr["jump"] = 0.0 if any(ok) else math.inf
             # period += rint(err ki), clamped to period0 (1 +- 1/256): the clamp is monotone, so the interval maps through it
-            cl = lambda q: min(max(q, pmin), pmax)
             if cl(period + dpr_c - dpr_s) <= st["period"] <= cl(period + dpr_c + dpr_s):
-                chk.put("dper", abs(st["period"] - cl(period + v / 4096.0)) / (ev / 4096.0 + 0.5))
+                fr["dper"] = abs(st["period"] - cl(period + v / 4096.0)) / (ev / 4096.0 + 0.5)
             else:
-                chk.put("dper", math.inf)
+                fr["dper"] = math.inf
         else:
-            nb, enb = bias, 0.0
-            chk.put("dphase", 0.0 if st["t_next"] == t and st["period"] == period else math.inf)
+            nb, enb = bias, 0.0 + eb
+            if st is None:
+                return [_Cand(t, period, bias, eb, amp, ea, ns, c.off, c.amb, c.nbits)]
+            fr["dphase"] = 0.0 if st["t_next"] == t and st["period"] == period else math.inf
         # 3.0e and 3.0b
         if afc:
             uf = lambda i: u_after[i] if i >= 0 else 0.0
@@ -434,9 +507,103 @@ def replay(d: np.ndarray, bd: np.ndarray, m: Modem, states: list, bits: list, *,
             uprev = uf(j - 1)
             un = min(max(afc_gain * nb + (1.0 - afc_leak) * uprev, -AFC_MAX), AFC_MAX)
             eu = AFC_GAIN * enb + 1e-8 * abs(nb) + 2 * U * (abs(uprev) + abs(un))
-            chk.put("afc", abs(st["afc_u"] - un) / max(eu, 1e-300) if st["afc_u"] != un else 0.0)
+            fr["afc"] = abs(st["afc_u"] - un) / max(eu, 1e-300) if st["afc_u"] != un else 0.0
         else:
             bias_after, eba = nb, enb
-        chk.put("bias", abs(st["bias"] - bias_after) / max(eba, 1e-300) if st["bias"] != bias_after else 0.0)
+        fr["bias"] = abs(st["bias"] - bias_after) / max(eba, 1e-300) if st["bias"] != bias_after else 0.0
+        c.fr, c.amb, c.nbits, c.nstat = fr, c.amb + namb, c.nbits + K, ns
+        return fr
+
+    def merge(cands):
+        """candidates that agree in the integers (and in the position in the span's bits) are one: the hull of their intervals.  Chains
+        that differ by a count in one tile meet again in the next, so the set grows with the sum of the slacks, not their product."""
+        out = {}
+        for c in cands:
+            o = out.setdefault((c.t, c.period, c.off, c.nstat), c)
+            if o is not c:
+                for v, e in (("bias", "eb"), ("amp", "ea")):
+                    lo = min(getattr(o, v) - getattr(o, e), getattr(c, v) - getattr(c, e))
+                    hi = max(getattr(o, v) + getattr(o, e), getattr(c, v) + getattr(c, e))
+                    setattr(o, v, 0.5 * (lo + hi))
+                    setattr(o, e, 0.5 * (hi - lo) * (1.0 + 4 * U) + 4 * U * abs(0.5 * (lo + hi)))
+                o.amb, o.nbits = max(o.amb, c.amb), max(o.nbits, c.nbits)
+        return list(out.values())
+
+    def inside(cands, tr):
+        return any(c.t == tr["t_next"] and c.period == tr["period"] and abs(tr["bias"] - c.bias) <= c.eb
+                   and abs(tr["amp"] - c.amp) <= c.ea for c in cands)
+
+    j, si = 0, 0
+    ntiles = len(states)
+    while j < ntiles:
+        j1 = j
+        while states[j1] is None:
+            j1 += 1
+        st = states[j1]
+        sb = np.asarray(bits[si], np.int64)
+        si += 1
+        chk.ntiles += j1 - j + 1
+        chk.spans += 1
+        cands = [_Cand(prev["t_next"], prev["period"], prev["bias"], 0.0, prev["amp"], 0.0, nstat)]
+        resolved = True
+        last_fr = {}
+        for jj in range(j, j1):                                  # the hidden tiles
+            nxt = []
+            for c in cands:
+                kt = k_total(jj, c)
+                if c.off + kt > sb.shape[0]:
+                    last_fr = {"count": math.inf}
+                    continue
+                out = tile(jj, c, sb[c.off:c.off + kt], None)
+                if out is None:
+                    resolved = False
+                    break
+                if not out:
+                    last_fr = c.fr
+                nxt += out
+            nxt = merge(nxt)
+            if not resolved or len(nxt) > cand_limit:
+                resolved = False
+                break
+            cands = nxt
+            chk.cands = max(chk.cands, len(cands))
+            if truth is not None and cands:
+                chk.hidden += 1
+                chk.outside += 0 if inside(cands, truth[jj]) else 1
+            if not cands:
+                break
+        if not resolved:
+            chk.unresolved += 1
+        elif not cands:
+            # no chain reaches this span's end: what dropped the last candidate says why
+            for k_, v_ in last_fr.items():
+                if not v_ <= 1.0:
+                    chk.put(k_, v_)
+            chk.put("chain", math.inf)
+        else:
+            best = None
+            for c in cands:
+                kt = k_total(j1, c)
+                if c.off + kt != sb.shape[0]:
+                    continue
+                fr = tile(j1, c, sb[c.off:], st)
+                w = 0.0 if fr == "skip" else max(fr.values(), default=0.0)
+                if best is None or w < best[0]:
+                    best = (w, c, fr)
+            chk.put("count", 0.0 if best is not None else math.inf)
+            if best is None:
+                return chk
+            _, c, fr = best
+            chk.amb += c.amb
+            chk.nbits += c.nbits
+            if fr == "skip":
+                chk.put("bit", c.fr.get("bit", 0.0))
+            else:
+                for k_, v_ in fr.items():
+                    chk.put(k_, v_)
+                nstat = c.nstat
         prev = st
+        if not resolved or not cands:
+            nstat = 1 if hidden_mode else nstat
+        j = j1 + 1
     return chk

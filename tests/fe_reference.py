@@ -1,4 +1,4 @@
-"""Float64 reference of the two front-ends, written from DESIGN.md section 3 (SPEC 3.1, 3.5, 3.5c, 3.7) and nothing else: it
+"""Float64 reference of the two front-ends, written from DESIGN.md section 3 (SPEC 3.1, 3.5, 3.5b, 3.5c, 3.7) and nothing else: it
 imports neither the oracle nor the product and loads no table from either; every tap and twiddle is computed here from its
 definition.  The product's and the oracle's float32 arithmetic is compared with it under error bounds that are formulas (the
 float32 rounding of the stages the SPEC prescribes), not constants fitted to data, so a comparison keeps its meaning when a
@@ -315,6 +315,92 @@ def vfo_rows_ref(iq: np.ndarray, rate: int, *, loose: bool = False, g: np.ndarra
         return o, row_bound(S1, S2, ATAN2Q_EVAL_ERR + ATAN2Q_MAX_ERR), Sx == 0.0
     o, S1, S2, Sx = resample(d, g, up, down, extra=amb, **mut)
     return o, row_bound(S1, S2, ATAN2Q_EVAL_ERR, Sx), np.ones(o.shape, bool)
+
+
+# ---------------------------------------------------------------- SPEC 3.5b: the composite resampler + decimator
+DEC_PER_BLOCK = STEPS * 12 // 5 // 4     # 1536 decimated samples (3 tiles of 512) per block of 2560 steps
+
+# every mutation keyword of composite_rows and a value that is a bug (the tests assert that each is rejected)
+COMPOSITE_MUTATIONS = {
+    "b_plus_1": dict(b_off=1),
+    "b_minus_1": dict(b_off=-1),
+    "row_rotated": dict(row_rot=1),
+    "difference_in_32_bits": dict(wrap=False),
+    "carried_phases_zero": dict(carry_zero=True),
+    "quarter_missing": dict(quarter=False),
+    "group_one_late": dict(group_off=1),
+}
+
+
+def _newest_input(n):
+    """b(n) = floor(5 (4 n + 3) / 12): the newest discriminator sample decimated sample n reads (used to place the mutations only)"""
+    return (5 * (4 * np.asarray(n, np.int64) + 3)) // 12
+
+
+def _resample_then_average(d: np.ndarray, g: np.ndarray, group_off: int = 0):
+    """z[n] = 1/4 sum_{i<4} o[4n + i + group_off] and A[n] = 1/4 sum_i sum_t |g_t| |d_t| of the same outputs; d: [n] with n % 5 == 0"""
+    n = d.shape[-1]
+    dd = np.concatenate([d, np.zeros(5)])                         # room for one more output group
+    o, _, S2, _ = resample(dd, g, 12, 5)
+    nz = n * 12 // 5 // 4
+    o, S2 = o[group_off:group_off + 4 * nz], S2[group_off:group_off + 4 * nz]
+    return o.reshape(nz, 4).sum(1) * 0.25, S2.reshape(nz, 4).sum(1) * 0.25
+
+
+def composite_rows(q: np.ndarray, *, loose: bool = False, b_off: int = 0, row_rot: int = 0, wrap: bool = True, carry_zero: bool = False,
+                   quarter: bool = True, group_off: int = 0):
+    """SPEC 3.5b in float64 as "resample, then average": q: the 16-bit phases of ONE bin's whole stream (int64, q[-1] = 0 before
+    the stream, a multiple of 5 steps).  d[m] = wrap16(q[m] - q[m-1]) / 16384 (exact: chan_disc), the 12/5 resampler
+    o[j] = sum_{t<16} g*[5j mod 12][t] d[floor(5j / 12) - t] with the closed-form double taps g* = resamp_taps(20000), and
+    z[n] = 1/4 sum_{i<4} o[4n + i].  Neither b(n) nor the rows G of DESIGN.md's formula are used: if that formula or its
+    implementation is wrong, the two differ.  Returns (z, bound), 12 decimated samples per 20 steps.
+
+    Bound of the float32 row z32[n] = sum_{k<17} fmaf(G[n mod 3][k], d[b(n) - k], acc) against z[n].  In exact arithmetic
+    z[n] = sum_k G*_k d[b(n) - k] with G*_k = 1/4 sum_i g*_i (the taps of the four outputs that meet input b(n) - k).
+      d is exact (a multiple of 2^-14 in [-2, 2)).
+      The taps: the product uses G = fl32(1/4 sum_i fl32(g*_i)), summed in double: |fl32(g*_i) - g*_i| <= u |g*_i|, the final
+      rounding u |G*| (1 + u), so per term |G_k - G*_k| <= u |G*_k| + 1/4 sum_i u |g*_i| <= 2 u a_k, a_k = 1/4 sum_i |g*_i|.
+      The 17-term fmaf chain: at most 17 u sum_k |G_k d_k| <= 17 u (1 + 2 u) sum_k a_k |d_k|.
+    With A[n] = sum_k a_k |d_k| = 1/4 sum_{i<4} sum_t |g*[p_i][t]| |d[i0_i - t]| (resample()'s S2 averaged over the group):
+      bound[n] = 19 u (1 + 2^-20) A[n]           (2 u A for the taps, 17 u (1 + 2 u) A for the chain, second order terms rounded up)
+    -- a formula of the inputs alone.  loose = True has nothing to add (there is no approximant in this stage); it is accepted so that
+    the callers can pass their layer through.
+    Mutations: b_off (b(n) +- 1: every read one sample later / earlier), row_rot (row (n + 1) mod 3 at b(n)), wrap = False (the
+    difference taken in 32 bits), carry_zero (the 16 carried phases at the head of every block of 2560 steps replaced by zeros),
+    quarter = False (the 1/4 missing), group_off = 1 (the averaging group starts one resampler output late)."""
+    q = np.asarray(q, np.int64)
+    assert q.ndim == 1 and q.shape[0] % 5 == 0
+    g = resamp_taps(20000)
+    prev = np.concatenate([[0], q[:-1]])
+    d = (wrap16(q - prev) if wrap else (q - prev)) / 16384.0
+    if b_off > 0:
+        d = np.concatenate([d[b_off:], np.zeros(b_off)])
+    elif b_off < 0:
+        d = np.concatenate([np.zeros(-b_off), d[:b_off]])
+    z, A = _resample_then_average(d, g, group_off=group_off)
+    n = np.arange(z.shape[0])
+    if row_rot:
+        # row (n + 1) mod 3 applied at b(n): sample n + 1 of the stream delayed by b(n + 1) - b(n) (1 or 2) steps
+        delta = _newest_input(n + 1) - _newest_input(n)
+        z0, A0 = z, A
+        z, A = z0.copy(), A0.copy()
+        for dl in (1, 2):
+            zs, As = _resample_then_average(np.concatenate([np.zeros(dl), d, np.zeros(5 - dl)]), g)
+            sel = delta == dl
+            z[sel], A[sel] = zs[n[sel] + 1], As[n[sel] + 1]
+    if carry_zero:
+        # what a block sees of the stream before it is zeros: its first difference is q[first] - 0, the 16 before it vanish
+        edge = np.arange(STEPS, q.shape[0], STEPS)
+        dz = d.copy()
+        for e in edge:
+            dz[e - 16:e] = 0.0
+            dz[e] = (wrap16(q[e]) if wrap else q[e]) / 16384.0
+        zz, Az = _resample_then_average(dz, g)
+        head = (_newest_input(n % DEC_PER_BLOCK) <= 16) & (n >= DEC_PER_BLOCK)
+        z, A = np.where(head, zz, z), np.where(head, Az, A)
+    if not quarter:
+        z, A = 4.0 * z, 4.0 * A
+    return z, 19.0 * U * (1.0 + 2.0 ** -20) * A
 
 
 # ---------------------------------------------------------------- test signals (complex128 streams at 10 MS/s)

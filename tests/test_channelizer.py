@@ -1,6 +1,8 @@
 """Wideband front-end (BASELINE config 4): 10 MS/s -> 512-bin polyphase channelizer (20 kS/s per bin, one PHASE sample per
 step) -> per-bin discriminator (wrapped phase difference) -> 12/5 resampler -> decoder.  CPU: the oracle's building blocks and an end-to-end decode.  GPU: the HIP
-front-end against the oracle, bit-exact at both intermediate products and in the decoded frames."""
+front-end against the oracle, bit-exact at both intermediate products and in the decoded frames.
+This is the parity suite.  SPEC 3.5b (the composite resampler + decimator) has an independent float64 reference of its own,
+fe_reference.composite_rows: test_bins_reference.py holds the oracle to it and test_gpu_bins_reference.py the bins kernel."""
 import ctypes as C
 
 import numpy as np

@@ -41,6 +41,7 @@ class Scene:
     noise_tiles: int = 0        # leading tiles of noise only (the burst starts after them)
     ntiles: int = NT
     ramp_ppm: float = 0.0       # a symbol clock that drifts linearly from 0 to this offset (own NRZ FSK modulator)
+    dc: float = 0.0             # dec rows only: a constant added in quadrants (a carrier 5 kHz x dc off a channelizer bin's centre)
 
 
 def _tile_in(s: Scene) -> int:
@@ -53,7 +54,8 @@ def make_input(s: Scene):
     kw = dict(fs=D.FS / (1.0 + 1e-6 * s.ppm))
     if s.ramp_ppm:
         z = ramp_clock(n, synth.SONDE_BAUD[s.stype], s.ramp_ppm, s.ebn0, s.seed)
-        return (np.stack([z.real, z.imag], axis=1) * s.level).astype(np.float32)
+        x = (np.stack([z.real, z.imag], axis=1) * s.level).astype(np.float32)
+        return x if s.kind == "iq" else _audio_of(s, x)
     if s.stype in (4, 5):
         sb = synth.make_batch(s.stype, 1, n, seed=s.seed, ebn0_db=s.ebn0, cfo_max_hz=0.0, **kw)
     else:
@@ -74,13 +76,17 @@ def make_input(s: Scene):
     x = (np.stack([z.real, z.imag], axis=1) * s.level).astype(np.float32)
     if s.kind == "iq":
         return x
-    # real input: the discriminator audio of the IQ (any float32 stream will do; this one carries the signal)
+    return _audio_of(s, x)
+
+
+def _audio_of(s: Scene, x):
+    """real input: the discriminator audio of the IQ (any float32 stream will do; this one carries the signal)"""
     zz = x[:, 0].astype(np.float64) + 1j * x[:, 1]
     audio = (np.angle(zz * np.conj(np.concatenate([[0], zz[:-1]]))) * (2 / np.pi)).astype(np.float32)
     if s.kind == "real":
         return audio
     dec = D.modem(s.stype, s.wide).decim
-    return audio.reshape(-1, dec).mean(1).astype(np.float32)
+    return (audio.reshape(-1, dec).mean(1) + s.dc).astype(np.float32)
 
 
 def ramp_clock(n: int, baud: float, ppm_end: float, ebn0: float, seed: int) -> np.ndarray:
@@ -151,6 +157,23 @@ def run_oracle(oracle, s: Scene, x):
     return states, bits
 
 
+# the pre-decimated path (what a channelizer bin feeds the loop, SPEC 3.5b) for every bin type at 10 and 20 dB, with the DC term an
+# off-centre carrier leaves (+-0.9 quadrant = 4.5 kHz), clocks +-100 ppm, a noise-only lead-in, a squelched stretch, the period at its
+# clamp, and M10's 2:1 class (more than 256 symbols per tile).  18 tiles: whole spans of 3 and of 6 (test_bins_reference.py hides states)
+DEC_SCENES = [Scene("rs41-10dB-dec+0.9dc+100ppm", 0, kind="dec", ebn0=10.0, dc=0.9, ppm=100.0, seed=201, ntiles=18),
+              Scene("rs41-20dB-dec-0.9dc-100ppm", 0, kind="dec", ebn0=20.0, dc=-0.9, ppm=-100.0, seed=202, ntiles=18),
+              Scene("dfm-10dB-dec-0.9dc+100ppm", 1, kind="dec", ebn0=10.0, dc=-0.9, ppm=100.0, seed=203, ntiles=18),
+              Scene("dfm-20dB-dec+0.4dc-100ppm", 1, kind="dec", ebn0=20.0, dc=0.4, ppm=-100.0, seed=204, ntiles=18),
+              Scene("ims-10dB-dec+0.4dc-100ppm", 2, kind="dec", ebn0=10.0, dc=0.4, ppm=-100.0, seed=205, ntiles=18),
+              Scene("ims-20dB-dec+0.9dc+100ppm", 2, kind="dec", ebn0=20.0, dc=0.9, ppm=100.0, seed=206, ntiles=18),
+              Scene("mrz-10dB-dec-0.4dc+100ppm", 6, kind="dec", ebn0=10.0, dc=-0.4, ppm=100.0, seed=207, ntiles=18),
+              Scene("mrz-20dB-dec-0.9dc-100ppm", 6, kind="dec", ebn0=20.0, dc=-0.9, ppm=-100.0, seed=208, ntiles=18),
+              Scene("dfm-12dB-dec-noise-then-burst", 1, kind="dec", ebn0=12.0, dc=0.9, noise_tiles=4, seed=209, ntiles=18),
+              Scene("rs41-20dB-dec-squelch", 0, kind="dec", ebn0=20.0, dc=-0.4, squelch=(5, 6, 7), seed=210, ntiles=18),
+              Scene("rs41-20dB-dec-clock-ramp-to-clamp", 0, kind="dec", ebn0=20.0, ramp_ppm=-6000.0, seed=211, ntiles=420),
+              Scene("m10-15dB-dec", 3, kind="dec", ebn0=15.0, dc=0.4, ppm=100.0, seed=212, ntiles=18)]
+
+
 def _scenes():
     S = []
     seed = 10
@@ -176,6 +199,7 @@ def _scenes():
           Scene("rs41-20dB-level1e-6", 0, ebn0=20.0, cfo=500.0, level=1e-6, seed=104),
           Scene("m10-20dB-level1e6", 3, ebn0=20.0, cfo=-500.0, level=1e6, seed=105),
           Scene("rs41-wide-iq16", 0, wide=True, kind="iq16", ebn0=15.0, cfo=-1500.0, level=3000.0, seed=106),
+          *DEC_SCENES,
           Scene("imet-20dB", 4, ebn0=20.0, seed=107, ntiles=6),
           Scene("imet-12dB-real", 4, kind="real", ebn0=12.0, seed=108, ntiles=6),
           Scene("imet-20dB-iq8", 4, kind="iq8", ebn0=20.0, level=60.0, seed=109, ntiles=6),
