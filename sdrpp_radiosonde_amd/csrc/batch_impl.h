@@ -1,0 +1,155 @@
+// batch_impl.h -- private to the batch files (batch.hip: create / submit / restart; batch_results.cpp: frames, poll, timing queries;
+// batch_probe.hip: test introspection): the SondeBatch object behind the B0 batch API of include/sonde_abi.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <deque>
+#include <memory>
+#include <vector>
+#include "sonde_dev.h"
+#include "../../include/sonde_abi.h"
+#include "launch.h"
+#include "parse.h"
+#include "sd_chanlist.h"
+#include "sd_host.h"
+#include "sd_tables.h"
+
+// Events that only order streams of this device, or time kernels on it, need no system-scope release (a cache write-back
+// towards the host): hipEventDisableSystemFence.  Slot::ev_done is what the host waits on before it reads frames: it keeps the fence.
+#ifndef SD_EV_FLAGS
+#define SD_EV_FLAGS hipEventDisableSystemFence
+#endif
+#define SD_EV_TIMING (SD_EV_FLAGS)
+#define SD_EV_ORDER  (hipEventDisableTiming | SD_EV_FLAGS)
+
+#pragma GCC visibility push(hidden)       // private types: their inline members are not among the library's exported symbols
+// The FEC tables of the frame decoders (sd_tables.h), each its own allocation
+struct SdFecTables {
+	uint8_t *gfexp = nullptr;              // zero-absorbing antilog table of the RS decoder (GF_EXP2 in framer_kernel.hip)
+	uint8_t *gflog = nullptr;              // 256 x u16 logarithms, log 0 = 768
+	uint32_t *gfswar = nullptr;            // byte-slice tables of the 24 syndrome multipliers alpha^(4j), framer_kernel.hip
+	uint8_t *g64 = nullptr;                // GF(2^6): iMS-100's BCH(63,51)
+	uint16_t *m10tab = nullptr;            // Meteomodem checksum as a GF(2) matrix product: rows A^k B, sd_fixed.h
+};
+
+// Timing events.  An event record is a bubble of a few microseconds in the command stream (three of them cost a 0.29 ms step 3 %), so
+// only every `every`-th submit is timed (0: none), into the next of kSlots slots; all events are created with the batch.
+struct SdTiming {
+	static const int kSlots = 128;         // submits timed between two sonde_batch_kernel_ms() calls
+	struct Submit { hipEvent_t ev[3] = {}; bool has_framer = false; };      // start, behind the demodulators, behind the frame decoders (if any ran behind)
+	std::vector<Submit> submit;            // [kSlots]
+	int used = 0;
+	// batches of launch units: the same for each unit's demod kernel alone, on the unit's stream (sonde_batch_class_ms)
+	std::vector<hipEvent_t> unit;          // [kSlots][units][2]
+	int unit_used = 0;
+	int every = 8;
+	unsigned long n_submits = 0;           // since sonde_batch_set_timing
+
+	Submit &slot() { return submit[(size_t)(used % kSlots)]; }
+	hipEvent_t *unit_pair(size_t n_units, int slot, size_t ui) { return &unit[2 * (n_units * (size_t)slot + ui)]; }
+};
+#pragma GCC visibility pop
+
+struct SondeBatch {
+	uint32_t n_channels = 0, max_samples = 0;
+	int input_kind = 0, device = 0;
+	uint32_t ring_words = 0, max_frames = 0;
+	uint32_t type_frames[SONDE_NTYPES] = {};   // upper bound of complete frames per submit, per sonde type (B2 grid)
+	std::vector<uint8_t> types;
+	std::vector<uint32_t> chlist[SONDE_NTYPES];
+	ModemDef md[SONDE_NTYPES];             // this batch's modem table (k_modems, with the configuration flags applied)
+
+	SdChanState *d_states = nullptr;
+	SdFramerState *d_fstates = nullptr;
+	float *d_hist = nullptr;
+	uint32_t *d_bitring = nullptr;
+	// frame slots, per-channel frame counts and the demod kernel's framer descriptor exist TWICE: submit number t (1-based) uses
+	// slot[(t - 1) & 1], so the frames of submit t stay readable while submit t + 1 is queued or running (sonde_batch_frames_of)
+	struct Slot {
+		SondeFrame *d_frames = nullptr;
+		uint32_t *d_counts = nullptr;
+		SdFramerOut *d_fo = nullptr;       // where the demod kernel's in-kernel sync search keeps its state and lists frames (device copy)
+		SdFramerOut h_fo = {};             // host copy: the bins decoder takes the descriptor by value (bins_kernel.hip)
+		hipEvent_t ev_done = nullptr;      // recorded behind the last kernel of the submit once the host works with tickets
+		bool ev_valid = false;             // (an event record is a bubble in the command stream: not paid by hosts that sync every submit)
+		bool have_counts = false;          // h_counts, n_frames, n_overflow hold this submit's
+		std::vector<uint32_t> h_counts;
+		long n_frames = 0, n_overflow = 0;
+	} slot[2];
+	bool ticketing = false;
+	hipEvent_t ev_xs = nullptr;            // orders a submit behind the previous one when the host changes streams
+	uint64_t tickets = 0;                  // submits so far
+	float *d_taps = nullptr;
+	SdModem *d_modems = nullptr;
+	SdModem h_modems[SONDE_NTYPES] = {};   // host copy: the bins decoder takes the table by value
+	SdFecTables fec;
+	uint32_t fuse_fec = 1;                 // RS41 FEC in the demod kernel's epilogue (default) or as its own kernel (SONDE_FLAG_SPLIT_FEC)
+	uint32_t fixed_epi = 1;                // the fixed-length framers' frames decoded in the demod kernel's epilogue too (round 6; not behind a channelizer: bins_kernel.hip)
+	void *d_descs = nullptr;
+	uint32_t *d_chlist[SONDE_NTYPES] = {};
+	void *d_stage = nullptr;               // sonde_batch_submit_host's device rows
+	size_t stage_bytes = 0;
+	// AFSK sondes (iMet): tone-demodulator state, mixer table, 6 kS/s scratch rows; the other channels' list for kernel A
+	SdAfskState *d_astates = nullptr;
+	float *d_wtab = nullptr, *d_wtab_c50 = nullptr, *d_afq = nullptr;
+	// kernel A is instantiated per (decimation, taps) class (k_cls_*).  One class in the batch = one plain launch over all
+	// channels.  Several (or AFSK channels) = LAUNCH UNITS: every sonde type's channel list is cut into n_chunks pieces, a unit is
+	// (type, piece): its demod launch (the type's class) and its frame decoder behind it on the unit's OWN stream, so that the
+	// units overlap on the GPU and a unit's submits stay ordered from submit to submit.  Units are launched piece by piece,
+	// inside a piece the type with the longest-running workgroups first (M10: twice the symbols per tile; then RS41, whose
+	// workgroups end with the FEC epilogue): with n_chunks > 1 every compute unit holds a mix of heavy (M10: VALU / LDS bound)
+	// and light (HBM bound) workgroups at any time instead of a generation of M10 followed by generations of the others.
+	uint32_t n_cls[4] = {};
+	int cls_type[4] = { -1, -1, -1, -1 };  // the sonde type of a class whose channels are all of one type, else -1 (sd_launch_demod's utype)
+	int n_classes = 0, only_class = 0;
+	// Joined batches (the default: every submit ends in the caller's stream) launch per CLASS instead (type = -1: the types
+	// of a class share one launch over the class's channel list, their frame decoders follow): measured 0.319 ms per step
+	// against 0.336 per type for 4096 RS41 / M10 / DFM channels x 24 tiles; pipelined (SONDE_FLAG_PIPELINE) it is the other way
+	// round, 0.321 per class against 0.289 per type, and more pieces than one only add launches (profiles/r3_notes.md).
+	struct Unit {
+		int type, cls; uint32_t off, n; size_t row0;
+		uint32_t types;                    // bit t: the frame decoders of sonde type t follow this unit's demod launch
+		hipStream_t st; hipEvent_t ev_join[2];      // ev_join[submit parity]
+	};
+	std::vector<Unit> units;
+	uint32_t *d_cls[4] = {};               // joined batches: the channel list of each class
+	int n_chunks = 1;
+	hipEvent_t ev_fork = nullptr;
+	// How a submit of several launch units completes (include/sonde_abi.h): 0 (default): the unit streams are joined into the
+	// caller's stream before sonde_batch_submit returns; 1 SONDE_FLAG_LATE_JOIN: one submit late -- submit t joins the units of submit
+	// t - 1 into the caller's stream, so that a unit's submit t + 1 may start beside the other units' submit t; 2 SONDE_FLAG_PIPELINE:
+	// never.  In modes 1 and 2 done_stream collects the unit streams for completion (sonde_batch_sync, tickets).
+	int join_mode = 0;
+	hipStream_t done_stream = nullptr;
+	uint32_t granule = SONDE_TILE;         // submit sizes must be a multiple of this
+	// one residency of the GPU: the demod workgroups it holds at once, 4 (39.7 KB of LDS, 8 waves each) per CU.  The launch-unit
+	// rule, the in-loop FEC bound (SdFramerOut.loop_fec_max_wg) and the time-slice policy all work with it.
+	uint32_t residency = 0;
+	// time slices (launch.h SdSlice): per-channel segment counters, the value they hold before the next sliced launch and the knob
+	// (SondeBatchConfig.time_slices; 0: the library's choice)
+	uint32_t *d_prog = nullptr;
+	uint32_t seg_base = 0;
+	int seg_force = 0;
+	bool sliced_once = false;
+	// round 6: a batch of exactly the two default classes -- (4, 8): RS41 / DFM / iMS-100 / MRZ-N1 and (2, 8): M10; BASELINE config 3 --
+	// at the default completion mode is ONE launch on the caller's stream (sd_demod_mixed_kernel: the classes interleaved block by
+	// block), frame decoders in its epilogue: no fork, no join, no launch units
+	bool mixed_one = false;
+
+	SdTiming timing;
+	hipStream_t last_stream = nullptr;     // where the last submit completes
+	bool pending = false;
+	std::vector<SondeFrame> h_slots;
+	// sonde_batch_poll: per-channel parsers (created on first use), fragments waiting to be fetched
+	std::vector<std::unique_ptr<SondeParser>> parsers;
+	std::deque<std::pair<uint32_t, SondeData>> frags;
+	uint64_t polled_ticket = 0;            // submits up to this one have been parsed by sonde_batch_poll
+	// sonde_batch_restart_channels (SPEC 3.12): the channel lists on their way to the reset kernel, the event that orders the next
+	// submit's launch units behind it, and (submits so far, channel): the channel's parser is replaced before a later submit is parsed
+	SdChanLists restart_lists;
+	hipEvent_t ev_restart = nullptr;
+	std::deque<std::pair<uint64_t, uint32_t>> parser_restarts;
+	bool behind_channelizer = false;
+	// SONDE_FLAG_RS41_RESCUE (SPEC 3.3c): per-channel layouts and counters of the second pass (rescue_kernel.hip); null: the flag is
+	// off or the batch has no RS41 channel, and nothing of it is allocated or launched
+	SdRescueState *d_rescue = nullptr;
+};

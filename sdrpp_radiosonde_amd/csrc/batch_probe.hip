@@ -1,0 +1,157 @@
+// batch_probe.hip -- introspection for the staged parity tests and the bench: the RS correctors alone, a channel's state and bits,
+// what the rescue pass has learned, and the HBM read probe.  Not on the product path.
+#include <hip/hip_runtime.h>
+#include <vector>
+#include "batch_impl.h"
+
+// The RS(255,231) corrector alone: n_pairs codeword pairs of [2][256] bytes (positions >= n zero), corrected in place;
+// status[2 * i + c]: 0 clean, > 0 corrected byte errors, -1 uncorrectable (word left as received).
+// erased = null: errors only (sd_rsdec.h); else the errors-and-erasures corrector of SONDE_FLAG_RS41_RESCUE (sd_rsee.h), with
+// erased[i][c][k] != 0 marking position k.
+static int test_rs255(const char *who, SondeBatch *b, uint8_t *cw_pairs, size_t n_pairs, int n, const uint8_t *erased, int32_t *status)
+{
+	HIPCHK(hipSetDevice(b->device));
+	uint8_t *d_cw = nullptr, *d_er = nullptr;
+	int32_t *d_st = nullptr;
+	hipError_t e = hipMalloc((void **)&d_cw, n_pairs * 512);
+	if (e == hipSuccess && erased) e = hipMalloc((void **)&d_er, n_pairs * 512);
+	if (e == hipSuccess) e = hipMalloc((void **)&d_st, n_pairs * 2 * sizeof(int32_t));
+	if (e == hipSuccess) e = hipMemcpy(d_cw, cw_pairs, n_pairs * 512, hipMemcpyHostToDevice);
+	if (e == hipSuccess && erased) e = hipMemcpy(d_er, erased, n_pairs * 512, hipMemcpyHostToDevice);
+	if (e == hipSuccess) {
+		if (erased) sd_launch_rsee_unit(d_cw, d_er, (uint32_t)n_pairs, n, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
+		else sd_launch_rs255_unit(d_cw, (uint32_t)n_pairs, n, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpy(cw_pairs, d_cw, n_pairs * 512, hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(status, d_st, n_pairs * 2 * sizeof(int32_t), hipMemcpyDeviceToHost);
+	(void)hipFree(d_cw); (void)hipFree(d_er); (void)hipFree(d_st);
+	return e == hipSuccess ? 0 : sd_fail(who, e);
+}
+
+extern "C" int sonde_batch_test_rs255(SondeBatch *b, uint8_t *cw_pairs, size_t n_pairs, int n, int32_t *status)
+{
+	if (!b || !cw_pairs || !status || !n_pairs || n < 25 || n > 255) return sd_fail("sonde_batch_test_rs255: bad argument");
+	return test_rs255("sonde_batch_test_rs255", b, cw_pairs, n_pairs, n, nullptr, status);
+}
+
+extern "C" int sonde_batch_test_rs255_erasures(SondeBatch *b, uint8_t *cw_pairs, size_t n_pairs, int n, const uint8_t *erased, int32_t *status)
+{
+	if (!b || !cw_pairs || !erased || !status || !n_pairs || n < 25 || n > 255) return sd_fail("sonde_batch_test_rs255_erasures: bad argument");
+	return test_rs255("sonde_batch_test_rs255_erasures", b, cw_pairs, n_pairs, n, erased, status);
+}
+
+extern "C" int sonde_batch_rescue_info(SondeBatch *b, uint32_t channel, SondeRs41Layout out[2], uint32_t *tried, uint32_t *rescued)
+{
+	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_rescue_info: bad argument");
+	if (b->behind_channelizer) return sd_fail("sonde_batch_rescue_info: SONDE_FLAG_RS41_RESCUE is not available for the batch behind a channelizer");
+	if (!b->d_rescue) return sd_fail("sonde_batch_rescue_info: the batch was created without SONDE_FLAG_RS41_RESCUE (or has no RS41 channel)");
+	if (b->types[channel] != SONDE_RS41) return sd_fail("sonde_batch_rescue_info: not an RS41 channel");
+	if (sonde_batch_sync(b) < 0) return -1;
+	SdRescueState st;
+	HIPCHK(hipMemcpy(&st, b->d_rescue + channel, sizeof(st), hipMemcpyDeviceToHost));
+	if (out) { out[0] = st.lay[0]; out[1] = st.lay[1]; }
+	if (tried) *tried = st.tried;
+	if (rescued) *rescued = st.rescued;
+	return 0;
+}
+
+// wait for the last submit and fetch the channel's demodulator state
+static int fetch_state(SondeBatch *b, uint32_t channel, SdChanState *st)
+{
+	if (sonde_batch_sync(b) < 0) return -1;
+	HIPCHK(hipMemcpy(st, b->d_states + channel, sizeof(*st), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" uint64_t sonde_batch_nbits(SondeBatch *b, uint32_t channel)
+{
+	if (!b || channel >= b->n_channels) { sd_fail("sonde_batch_nbits: bad argument"); return 0; }
+	SdChanState st;
+	return fetch_state(b, channel, &st) ? 0 : st.wpos;
+}
+
+extern "C" int sonde_batch_read_bits(SondeBatch *b, uint32_t channel, uint64_t from, size_t count, uint8_t *out)
+{
+	if (!b || channel >= b->n_channels || !out) return sd_fail("sonde_batch_read_bits: bad argument");
+	SdChanState st;
+	if (fetch_state(b, channel, &st)) return -1;
+	const uint64_t ring_bits = (uint64_t)b->ring_words * 32;
+	if (from + count > st.wpos || st.wpos - from > ring_bits) return sd_fail("sonde_batch_read_bits: range not in the ring");
+	std::vector<uint32_t> ring(b->ring_words);
+	HIPCHK(hipMemcpy(ring.data(), b->d_bitring + (size_t)channel * b->ring_words, (size_t)b->ring_words * 4, hipMemcpyDeviceToHost));
+	for (size_t i = 0; i < count; i++) {
+		const uint64_t p = from + i;
+		out[i] = (ring[(p >> 5) & (b->ring_words - 1)] >> (p & 31)) & 1u;
+	}
+	return 0;
+}
+
+extern "C" int sonde_batch_read_state(SondeBatch *b, uint32_t channel, int64_t *t_next, int32_t *period, float *bias, float *amp, float *afc_u)
+{
+	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_read_state: bad argument");
+	SdChanState st;
+	if (fetch_state(b, channel, &st)) return -1;
+	if (t_next) *t_next = st.t_next;
+	if (period) *period = st.period;
+	if (bias) *bias = st.bias;
+	if (amp) *amp = st.amp;
+	if (afc_u) *afc_u = st.afc[2];          // the newest AFC state u (SPEC 3.0b); 0 for real input
+	return 0;
+}
+
+// ---- read-only streaming probe: the HBM read bandwidth this GPU actually delivers, measured in the same
+// process as the bench so that kernel A's GB/s can be quoted against *achievable* as well as against the
+// 8 TB/s spec peak (SURVEY.md section 8d asks for both).
+// 8 independent 16-byte loads in flight per lane, grid-stride; the xor keeps the loads alive and the store
+// never happens for real data.
+typedef uint32_t sd_u32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void sd_read_probe_kernel(const sd_u32x4 *__restrict__ src, size_t n16, uint32_t *sink)
+{
+	const size_t stride = (size_t)gridDim.x * 256;
+	size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+	uint32_t acc = 0;
+	for (; i + 7 * stride < n16; i += 8 * stride) {
+		sd_u32x4 v[8];
+#pragma unroll
+		for (int k = 0; k < 8; k++) v[k] = __builtin_nontemporal_load(src + i + k * stride);
+#pragma unroll
+		for (int k = 0; k < 8; k++) acc ^= v[k].x ^ v[k].y ^ v[k].z ^ v[k].w;
+	}
+	for (; i < n16; i += stride) {
+		const sd_u32x4 v = src[i];
+		acc ^= v.x ^ v.y ^ v.z ^ v.w;
+	}
+	if (acc == 0x5EEDBEEFu) sink[0] = acc;
+}
+
+extern "C" int sonde_hbm_read_probe(const void *d_buf, size_t bytes, int reps, float *gbs_out)
+{
+	if (!d_buf || bytes < 16 || reps < 1 || !gbs_out) return sd_fail("sonde_hbm_read_probe: bad argument");
+	uint32_t *sink = nullptr;
+	HIPCHK(hipMalloc(&sink, 4));
+	hipEvent_t e0, e1;
+	HIPCHK(hipEventCreate(&e0));
+	HIPCHK(hipEventCreate(&e1));
+	const size_t n16 = bytes / 16;
+	float best = 1e30f;
+	for (int grid = 256 * 4; grid <= 256 * 32; grid *= 2) {      // best over a few occupancies
+		sd_read_probe_kernel<<<grid, 256>>>((const sd_u32x4 *)d_buf, n16, sink);   // warm-up
+		for (int r = 0; r < reps; r++) {
+			(void)hipEventRecord(e0, 0);
+			sd_read_probe_kernel<<<grid, 256>>>((const sd_u32x4 *)d_buf, n16, sink);
+			(void)hipEventRecord(e1, 0);
+			(void)hipEventSynchronize(e1);
+			float ms = 0.f;
+			(void)hipEventElapsedTime(&ms, e0, e1);
+			if (ms < best) best = ms;
+		}
+	}
+	const hipError_t err = hipGetLastError();
+	(void)hipEventDestroy(e0);
+	(void)hipEventDestroy(e1);
+	(void)hipFree(sink);
+	if (err != hipSuccess) return sd_fail("sonde_hbm_read_probe", err);
+	*gbs_out = (float)((double)(n16 * 16) / ((double)best * 1e-3) / 1e9);
+	return 0;
+}

@@ -310,7 +310,7 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 	}
 	// K4: the sync search of the framed sondes runs in here, on round wave 3, over an LDS mirror of the newest ring words
 	// (RS41 always; DFM / iMS-100 / M10 unless the batch asked for the stand-alone framer kernels)
-	// Which sonde types an instantiation can meet follows from its class (batch.hip k_modems): (4, 8) and, wide, (2, 16) ->
+	// Which sonde types an instantiation can meet follows from its class (sd_tables.cpp k_modems): (4, 8) and, wide, (2, 16) ->
 	// RS41, DFM, iMS-100, MRZ-N1; (2, 8) and, wide, (1, 16) -> M10 (and the AFSK 6 kS/s streams, which are framed elsewhere).
 	// Testing the class first lets the compiler drop the other types' code from each instantiation.
 	constexpr bool cls_slow = DEC == 4 || (DEC == 2 && NT == 16);     // the ~5000 chips/s sondes

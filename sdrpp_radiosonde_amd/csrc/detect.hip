@@ -21,6 +21,7 @@
 #include "sd_rs41.h"
 #include "sd_fixed.h"
 #include "launch.h"
+#include "sd_tables.h"
 #include "sd_chanlist.h"
 #include "../../include/sonde_abi.h"
 

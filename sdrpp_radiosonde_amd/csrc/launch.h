@@ -95,8 +95,5 @@ void sd_launch_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list
 void sd_launch_rsee_unit(uint8_t *cw_io, const uint8_t *erased, uint32_t n_pairs, int n, int32_t *status, const uint8_t *gf_exp, const uint8_t *gf_log,
 	const uint32_t *gf_swar, hipStream_t stream);
 
-// SPEC 3.6's mixer table (batch.hip): out[2k], out[2k + 1] = (cos, -sin)(2 pi cycles k / per) as float32
-void make_mixer(float *out, int cycles, int per);
-
-// sets the text sonde_last_error() returns; returns -1
+// sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);

@@ -176,7 +176,7 @@ def test_split_fec_kernels(state):
         verify(sc, rows, bits, recs, f"split-fec step {step}")
 
 
-# Which launches csrc/batch.hip really slices (submit_impl: slice_of / choose_segments; there is no public indicator of it):
+# Which launches csrc/batch.hip really slices (launch_plain / launch_unit_demod: slice_of / choose_segments; there is no public indicator of it):
 #  * a batch of ONE demodulator class with default flags is one launch (`units` empty) and takes SondeBatchConfig.time_slices as told,
 #    if the count is <= the submit's tiles: "class2" (DFM + iMS-100 + MRZ-N1: the 4:1 class) and "m10" (M10 / M20: the 2:1 class);
 #  * a batch with launch units slices every GFSK unit when time_slices is forced: "all-rows" (default flags; the AFSK rows keep the
