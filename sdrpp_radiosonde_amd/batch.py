@@ -248,7 +248,7 @@ class SondeChannelizer:
         h = C.c_void_p()
         create = self.L.sonde_chan_create_dual if dual else self.L.sonde_chan_create_multi
         if create(tp, blocks_per_submit, self.n_streams, device, C.byref(h)) != 0:
-            raise SondeError(_lib.last_error() or "sonde_chan_create failed")
+            raise SondeError(_lib.last_error())
         self.h = h
         # fused (default where possible): discriminator + resampler inside the decoder kernel; fused=False keeps the 48 kS/s rows
         # (read()); fused=None leaves the library's choice alone
@@ -275,7 +275,7 @@ class SondeChannelizer:
             raise SondeError(f"wideband block must be {want}, got {iq.dtype}")
         self._keep = iq
         if self.L.sonde_chan_submit(self.h, C.c_void_p(iq.data_ptr()), self.samples_per_submit, C.c_void_p(stream or 0)) != 0:
-            raise SondeError(_lib.last_error() or "sonde_chan_submit failed")
+            raise SondeError(_lib.last_error())
 
     def frames(self) -> np.ndarray:
         return SondeBatch.frames(self.batch)
@@ -284,7 +284,7 @@ class SondeChannelizer:
         """(filter bank, discriminator + resampler, demodulator, framers) average ms over the timed submits."""
         v = [C.c_float() for _ in range(4)]
         if self.L.sonde_chan_kernel_ms(self.h, *[C.byref(x) for x in v]) != 0:
-            raise SondeError(_lib.last_error() or "sonde_chan_kernel_ms failed")
+            raise SondeError(_lib.last_error())
         return tuple(x.value for x in v)
 
     def read(self):
@@ -292,7 +292,7 @@ class SondeChannelizer:
         bins = np.zeros((self.n_channels, self.n_steps), dtype=np.float32)
         out48 = None if self.fused else np.zeros((self.n_channels, self.n_steps * 12 // 5), dtype=np.float32)
         if self.L.sonde_chan_read(self.h, bins.ctypes.data_as(C.c_void_p), out48.ctypes.data_as(C.c_void_p) if out48 is not None else None) != 0:
-            raise SondeError("sonde_chan_read failed")
+            raise SondeError(_lib.last_error())
         return bins, out48
 
     def close(self):
@@ -323,7 +323,7 @@ class SondeVfo:
         self.L = _lib.load()
         h = C.c_void_p()
         if self.L.sonde_vfo_create(n_channels, rate_in, max_in, device, C.byref(h)) != 0:
-            raise SondeError(_lib.last_error() or "sonde_vfo_create failed")
+            raise SondeError(_lib.last_error())
         self.h = h
         self.n_channels, self.rate_in, self.max_in = n_channels, rate_in, max_in
         up, down = C.c_int(), C.c_int()
@@ -345,13 +345,13 @@ class SondeVfo:
             stream = torch.cuda.current_stream(iq.device).cuda_stream
         if self.L.sonde_vfo_process(self.h, C.c_void_p(iq.data_ptr()), n_in, iq.stride(0) // 2, C.c_void_p(out.data_ptr()), out.stride(0),
                                     C.c_void_p(stream)) != 0:
-            raise SondeError(_lib.last_error() or "sonde_vfo_process failed")
+            raise SondeError(_lib.last_error())
         return out
 
     def taps(self) -> np.ndarray:
         g = np.zeros((self.up, 16), dtype=np.float32)
         if self.L.sonde_vfo_taps(self.rate_in, g.ctypes.data_as(C.c_void_p)) != 0:
-            raise SondeError(_lib.last_error() or "sonde_vfo_taps failed")
+            raise SondeError(_lib.last_error())
         return g
 
     def close(self):

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <vector>
 #include "batch_impl.h"
+#include "sd_devmem.h"
 #include "sd_input.h"
 
 static uint32_t pow2ceil(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
@@ -52,18 +53,6 @@ extern "C" void sonde_batch_destroy(SondeBatch *b)
 }
 
 // ---------------------------------------------------------------- create
-template <typename T> static hipError_t dev_alloc(T *&p, size_t bytes) { return hipMalloc((void **)&p, bytes); }
-template <typename T> static hipError_t dev_upload(T *&p, const void *src, size_t bytes)
-{
-	const hipError_t e = dev_alloc(p, bytes);
-	return e != hipSuccess ? e : hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-}
-template <typename T> static hipError_t dev_zeros(T *&p, size_t bytes)
-{
-	const hipError_t e = dev_alloc(p, bytes);
-	return e != hipSuccess ? e : hipMemset(p, 0, bytes);
-}
-
 static int upload_fec_tables(SdFecTables &f)
 {
 	uint8_t exp2[SD_GFEXP_BYTES];
@@ -279,10 +268,7 @@ extern "C" int sonde_batch_create(const SondeBatchConfig *cfg, SondeBatch **out)
 	if (cfg->n_channels == 0) return sd_fail("sonde_batch_create: n_channels == 0");
 	if (cfg->max_samples == 0 || cfg->max_samples % SONDE_TILE) return sd_fail("sonde_batch_create: max_samples must be a positive multiple of SONDE_TILE");
 	if (!sd_input_known(cfg->input_kind)) return sd_fail("sonde_batch_create: bad input_kind");
-	int ndev = 0;
-	HIPCHK(hipGetDeviceCount(&ndev));
-	if (cfg->device < 0 || cfg->device >= ndev) return sd_fail("sonde_batch_create: no such HIP device");
-	HIPCHK(hipSetDevice(cfg->device));
+	if (sd_select_device(cfg->device, "sonde_batch_create")) return -1;
 
 	SondeBatch *b = new SondeBatch;
 	b->device = cfg->device;

@@ -14,13 +14,15 @@
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
-#include <string>
 #include <vector>
 #include "sd_math.h"
 #include "sonde_dev.h"
 #include "sd_input.h"
 #include "../../include/sonde_abi.h"
 #include "launch.h"
+#include "sd_host.h"
+#include "sd_devmem.h"
+#include "sd_design.h"
 
 #define CH_M 512
 #define CH_D 500
@@ -66,7 +68,7 @@ static_assert(3 * ((CH_L / 2 + 128) * sizeof(float) + P_S * PFB_FB * sizeof(floa
 
 #ifdef P_TS       // experiment: cycle stamps of one wave's phases (make EXTRA=-DP_TS; tools/pfb_ts.py reads them)
 __device__ unsigned long long g_pfb_ts[128];
-extern "C" int sonde_debug_pfb_ts(unsigned long long *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pfb_ts), sizeof(g_pfb_ts)) == hipSuccess ? 0 : -1; }
+extern "C" int sonde_debug_pfb_ts(unsigned long long *out) { HIPCHK_IN("sonde_debug_pfb_ts", hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pfb_ts), sizeof(g_pfb_ts))); return 0; }
 #define P_STAMP(i) do { if (blockIdx.x == P_TS_WG && blockIdx.y == 0 && (threadIdx.x & 63) == 0) g_pfb_ts[8 * (i) + (threadIdx.x >> 6)] = __builtin_readcyclecounter(); } while (0)
 #ifndef P_TS_WG
 #define P_TS_WG 100
@@ -396,15 +398,12 @@ __global__ __launch_bounds__(256) void sd_phase_resamp_kernel(const int16_t *__r
 }
 
 // ---------------------------------------------------------------- host object
-static thread_local std::string g_cerr;
-extern "C" const char *sonde_last_error(void);
-
-struct SondeChannelizer {
+struct __attribute__((visibility("hidden"))) SondeChannelizer {
 	int device = 0;
 	uint32_t n_steps = 0, n_streams = 1;     // n_streams: LOGICAL streams (grid.y, 512 decoder channels each)
 	int input_kind = SONDE_INPUT_IQ;       // what sonde_chan_submit's block holds: complex64 or (sonde_chan_set_input) 16-bit integer IQ
 	uint32_t n_phys = 1, dual = 0;            // physical input streams; dual: every physical stream feeds an even and an odd-stacked bank (SPEC 3.5c)
-	float *d_h_odd = nullptr; float2 *d_twist = nullptr;
+	DevBuf<float> d_h_odd; DevBuf<float2> d_twist;
 	bool fused = false;                    // the decoder kernel takes the bins themselves (discriminator + resampler in its load path): two launches per submit
 	hipStream_t last_stream = nullptr;     // a submit on another stream waits for the previous one (the state is carried)
 	hipEvent_t ev_xs = nullptr;
@@ -417,13 +416,14 @@ struct SondeChannelizer {
 	bool overlap = false;
 	hipStream_t s_pfb = nullptr, s_dec = nullptr;
 	hipEvent_t ev_in = nullptr, ev_pfb[2] = {}, ev_dec[2] = {};
-	int16_t *d_bins_b = nullptr;           // the second phase buffer (allocated at the first overlapped submit)
-	int16_t *d_bins_last = nullptr;        // the phases of the last submit (sonde_chan_read)
+	DevBuf<int16_t> d_bins_b;              // the second phase buffer (allocated at the first overlapped submit)
+	const int16_t *bins_last = nullptr;    // the phases of the last submit (sonde_chan_read): d_bins or d_bins_b
 	SondeBatch *batch = nullptr;
-	float2 *d_hist[2] = {}, *d_tw = nullptr;
-	int16_t *d_bins = nullptr;             // per bin: [16 phases carried from the previous block | n_steps phases], 16-bit fractions of a turn
-	int32_t *d_philast = nullptr;          // unfused mode: per bin, the last phase of the previous block
-	float *d_h = nullptr, *d_g = nullptr, *d_gc = nullptr, *d_dhist = nullptr, *d_out48 = nullptr;
+	DevPair<float2> d_hist;                // the window history, in the input's format
+	DevBuf<float2> d_tw;
+	DevBuf<int16_t> d_bins;                // per bin: [16 phases carried from the previous block | n_steps phases], 16-bit fractions of a turn
+	DevBuf<int32_t> d_philast;             // unfused mode: per bin, the last phase of the previous block
+	DevBuf<float> d_h, d_g, d_gc, d_dhist, d_out48;
 	// kernel timing (HIP events on the submit stream), sampled: every 8th submit
 	hipEvent_t ev[3] = {};
 	unsigned long n_submits = 0, n_blocks = 0;
@@ -452,44 +452,20 @@ static void composite_rows(const std::vector<float> &g, int dec, float *G /* 3 *
 
 static void make_tables(std::vector<float> &h, std::vector<float> &tw, std::vector<float> &g)
 {
-	const double PI = 3.14159265358979323846;
 	h.resize(CH_L); tw.resize(CH_M); g.resize(RS_UP * RS_TAPS);
-	{
-		const double fc = 8000.0 / 10000000.0;
-		std::vector<double> tmp(CH_L);
+	{      // the window: the prototype at 8 kHz of 10 MS/s, the whole of it normalised to unit DC gain
+		const std::vector<double> tmp = sd_design_prototype(CH_L, 8000.0 / 10000000.0);
 		double sum = 0.0;
-		for (int i = 0; i < CH_L; i++) {
-			const double t = (double)i - 0.5 * (double)(CH_L - 1);
-			const double x = (double)i / (double)(CH_L - 1);
-			const double w = 0.42 - 0.5 * cos(2.0 * PI * x) + 0.08 * cos(4.0 * PI * x);
-			const double s = (t == 0.0) ? 2.0 * fc : sin(2.0 * PI * fc * t) / (PI * t);
-			tmp[i] = s * w;
-			sum += tmp[i];
-		}
+		for (int i = 0; i < CH_L; i++) sum += tmp[i];
 		for (int i = 0; i < CH_L; i++) h[i] = (float)(tmp[i] / sum);
 	}
 	for (int k = 0; k < CH_M / 2; k++) {
-		tw[2 * k] = (float)cos(2.0 * PI * (double)k / (double)CH_M);
-		tw[2 * k + 1] = (float)(-sin(2.0 * PI * (double)k / (double)CH_M));
+		tw[2 * k] = (float)cos(2.0 * SD_PI * (double)k / (double)CH_M);
+		tw[2 * k + 1] = (float)(-sin(2.0 * SD_PI * (double)k / (double)CH_M));
 	}
 	tw[2 * 128] = 0.0f;          // SPEC 3.5 (round 6): exp(-j pi / 2) = (0, -1) exactly (oracle or_chan_twiddles: the same line)
-	{
-		const int N = RS_UP * RS_TAPS;
-		const double fc = 9000.0 / 240000.0;         // 0.45 x the 20 kS/s input rate: the VFO front-end's 20 kS/s taps (vfo.hip)
-		std::vector<double> tmp(N);
-		for (int i = 0; i < N; i++) {
-			const double t = (double)i - 0.5 * (double)(N - 1);
-			const double x = (double)i / (double)(N - 1);
-			const double w = 0.42 - 0.5 * cos(2.0 * PI * x) + 0.08 * cos(4.0 * PI * x);
-			const double s = (t == 0.0) ? 2.0 * fc : sin(2.0 * PI * fc * t) / (PI * t);
-			tmp[i] = s * w;
-		}
-		for (int p = 0; p < RS_UP; p++) {
-			double sum = 0.0;
-			for (int t = 0; t < RS_TAPS; t++) sum += tmp[t * RS_UP + p];
-			for (int t = 0; t < RS_TAPS; t++) g[p * RS_TAPS + t] = (float)(tmp[t * RS_UP + p] / sum);
-		}
-	}
+	// the 12/5 resampler: 0.45 x the 20 kS/s input rate, the VFO front-end's 20 kS/s taps (vfo.hip)
+	sd_design_rows(sd_design_prototype(RS_UP * RS_TAPS, 9000.0 / 240000.0), RS_UP, RS_TAPS, g.data());
 }
 
 extern "C" void sonde_chan_destroy(SondeChannelizer *c)
@@ -503,9 +479,6 @@ extern "C" void sonde_chan_destroy(SondeChannelizer *c)
 	for (int i = 0; i < 2; i++) { if (c->ev_pfb[i]) (void)hipEventDestroy(c->ev_pfb[i]); if (c->ev_dec[i]) (void)hipEventDestroy(c->ev_dec[i]); }
 	if (c->s_pfb) (void)hipStreamDestroy(c->s_pfb);
 	if (c->s_dec) (void)hipStreamDestroy(c->s_dec);
-	(void)hipFree(c->d_bins_b);
-	(void)hipFree(c->d_hist[0]); (void)hipFree(c->d_hist[1]); (void)hipFree(c->d_bins); (void)hipFree(c->d_tw); (void)hipFree(c->d_philast);
-	(void)hipFree(c->d_h); (void)hipFree(c->d_g); (void)hipFree(c->d_dhist); (void)hipFree(c->d_out48); (void)hipFree(c->d_gc); (void)hipFree(c->d_h_odd); (void)hipFree(c->d_twist);
 	delete c;
 }
 
@@ -520,16 +493,65 @@ extern "C" int sonde_chan_create_dual(const uint8_t *types, uint32_t blocks_per_
 {
 	return chan_create(types, blocks_per_submit, n_streams, 1, device, out);
 }
+// Everything behind the argument checks: the decoder batch over all bins, the tables, the zeroed carried state and the events; on
+// failure chan_create destroys what has been built so far.
+static int chan_build(SondeChannelizer *c, const uint8_t *types, uint32_t blocks_per_submit)
+{
+	const uint32_t n_out = c->n_steps * RS_UP / RS_DN;
+	const size_t nb = (size_t)c->n_streams * CH_M;           // bins of all streams: the decoder batch's channels, stream-major
+	SondeBatchConfig cfg = SONDE_BATCH_CONFIG_INIT;
+	cfg.n_channels = (uint32_t)nb;
+	cfg.types = types;
+	cfg.max_samples = n_out;
+	cfg.input_kind = SONDE_INPUT_REAL;
+	cfg.device = c->device;
+	cfg.flags = 0;                                           // default completion: the bins decoder is one launch behind the filter bank, in the caller's stream
+	if (sonde_batch_create(&cfg, &c->batch) != 0) return -1;      // (the text is the batch's)
+	sd_batch_mark_channelizer(c->batch);
+	std::vector<float> h, tw, g;
+	make_tables(h, tw, g);
+	for (int i = 0; i < CH_L / 2; i++)      // the kernel keeps half of it
+		if (memcmp(&h[i], &h[CH_L - 1 - i], sizeof(float))) return sd_fail("sonde_chan_create: the window prototype is not symmetric bit for bit");
+	HIPCHK_IN("sonde_chan_create", c->d_hist.zeros((size_t)c->n_phys * CH_H));
+	HIPCHK_IN("sonde_chan_create", c->d_bins.zeros(nb * ((size_t)c->n_steps + PH_HEAD)));
+	if (blocks_per_submit <= 2) HIPCHK_IN("sonde_chan_create", c->d_out48.alloc(nb * n_out));
+	HIPCHK_IN("sonde_chan_create", c->d_h.upload(h.data(), CH_L));
+	HIPCHK_IN("sonde_chan_create", c->d_tw.upload((const float2 *)tw.data(), CH_M / 2));
+	HIPCHK_IN("sonde_chan_create", c->d_g.upload(g.data(), RS_UP * RS_TAPS));
+	HIPCHK_IN("sonde_chan_create", c->d_philast.zeros(nb));
+	HIPCHK_IN("sonde_chan_create", c->d_dhist.zeros(nb * RS_TAPS));
+	for (hipEvent_t &e : c->ev) HIPCHK_IN("sonde_chan_create", hipEventCreateWithFlags(&e, hipEventDisableSystemFence));     // timing only, same device
+	HIPCHK_IN("sonde_chan_create", hipEventCreateWithFlags(&c->ev_xs, hipEventDisableTiming | hipEventDisableSystemFence));
+	float gc[3 * SD_RS_KT_LD];
+	composite_rows(g, 4, gc);
+	for (float &v : gc) v *= 1.0f / 16384.0f;      // the bins decoder keeps the discriminator samples as 16-bit integers: the scale (a power of two: exact) sits in the taps
+	HIPCHK_IN("sonde_chan_create", c->d_gc.upload(gc, 3 * SD_RS_KT_LD));
+	if (c->dual) {                        // the odd-stacked bank's tables: taps of odd t negated, twist exp(-j pi r / 512)
+		std::vector<float> ho(h), wt(2 * CH_M);
+		for (int i = 0; i < CH_L; i++) if ((i / CH_M) & 1) ho[i] = -ho[i];
+		for (int r = 0; r < CH_M; r++) { wt[2 * r] = (float)cos(SD_PI * (double)r / (double)CH_M); wt[2 * r + 1] = (float)(-sin(SD_PI * (double)r / (double)CH_M)); }
+		HIPCHK_IN("sonde_chan_create", c->d_h_odd.upload(ho.data(), CH_L));
+		HIPCHK_IN("sonde_chan_create", c->d_twist.upload((const float2 *)wt.data(), CH_M));
+	}
+	// fused unless a bin's sonde type needs 48 kS/s rows (AFSK) or the host asks for the rows (sonde_chan_set_fused)
+	c->fused = sd_batch_bins_capable(c->batch);
+	if (!c->fused && blocks_per_submit > 2) return sd_fail("sonde_chan_create: bins with AFSK sondes take the three-kernel form: 1 or 2 blocks per submit");
+	return 0;
+}
+
 static int chan_create(const uint8_t *types, uint32_t blocks_per_submit, uint32_t n_phys, uint32_t dual, int device, SondeChannelizer **out)
 {
 	const uint32_t n_streams = n_phys * (dual ? 2u : 1u);
+	if (!out) return sd_fail("sonde_chan_create: null argument");
 	// up to 8 blocks per submit when the decoder takes the phases itself; the stand-alone discriminator + resampler kernel stages
 	// (16 + 2560 q) floats per bin in LDS: 1-2 blocks
-	if (!out || blocks_per_submit == 0 || blocks_per_submit > 8 || n_streams == 0 || n_streams > 64) return -1;
+	if (blocks_per_submit == 0 || blocks_per_submit > 8) return sd_fail("sonde_chan_create: blocks_per_submit must be 1 .. 8");
+	if (n_streams == 0 || n_streams > 64) return sd_fail("sonde_chan_create: 1 .. 64 streams (dual: 1 .. 32)");
 	*out = nullptr;
 	// an M10 / M20 channel is 50 kHz wide in the reference (/root/reference/src/main.hpp:48): it does not fit a 19.5 kHz bin
 	for (size_t i = 0; types && i < (size_t)n_streams * CH_M; i++)
-		if (types[i] == SONDE_M10) return sd_fail("sonde_chan_create: an M10 / M20 channel (50 kHz) does not fit a 19.5 kHz channelizer bin; use sonde_vfo_* at 50 kS/s", hipSuccess);
+		if (types[i] == SONDE_M10) return sd_fail("sonde_chan_create: an M10 / M20 channel (50 kHz) does not fit a 19.5 kHz channelizer bin; use sonde_vfo_* at 50 kS/s");
+	if (sd_select_device(device, "sonde_chan_create")) return -1;
 	SondeChannelizer *c = new SondeChannelizer;
 	c->device = device;
 	c->n_streams = n_streams;
@@ -538,56 +560,7 @@ static int chan_create(const uint8_t *types, uint32_t blocks_per_submit, uint32_
 	c->n_steps = 2560u * blocks_per_submit;                  // 2560 steps = 1.28 M wideband samples = 6144 samples at 48 kS/s
 	c->xcd_map = (c->n_steps / P_S) % 8 == 0 && (size_t)(c->n_steps / P_S) * n_streams > 1024;
 	if (c->xcd_map && !dual && n_streams % 8 == 0) c->xcd_map = 2;      // a stream per XCD (the two banks of a dual object share their samples: they stay together)
-	const uint32_t n_out = c->n_steps * RS_UP / RS_DN;
-	const size_t nb = (size_t)n_streams * CH_M;              // bins of all streams: the decoder batch's channels, stream-major
-	SondeBatchConfig cfg = SONDE_BATCH_CONFIG_INIT;
-	cfg.n_channels = (uint32_t)nb;
-	cfg.types = types;
-	cfg.max_samples = n_out;
-	cfg.input_kind = SONDE_INPUT_REAL;
-	cfg.device = device;
-	cfg.flags = 0;                                           // default completion: the bins decoder is one launch behind the filter bank, in the caller's stream
-	if (sonde_batch_create(&cfg, &c->batch) != 0) { delete c; return -1; }
-	sd_batch_mark_channelizer(c->batch);
-	std::vector<float> h, tw, g;
-	make_tables(h, tw, g);
-	const size_t hist_bytes = (size_t)n_phys * CH_H * sizeof(float2);
-	bool ok = hipMalloc((void **)&c->d_hist[0], hist_bytes) == hipSuccess && hipMalloc((void **)&c->d_hist[1], hist_bytes) == hipSuccess &&
-	          hipMalloc((void **)&c->d_bins, nb * ((size_t)c->n_steps + PH_HEAD) * sizeof(int16_t)) == hipSuccess &&
-	          (blocks_per_submit > 2 || hipMalloc((void **)&c->d_out48, nb * n_out * sizeof(float)) == hipSuccess) &&
-	          hipMalloc((void **)&c->d_h, CH_L * sizeof(float)) == hipSuccess &&
-	          hipMalloc((void **)&c->d_tw, CH_M * sizeof(float)) == hipSuccess &&
-	          hipMalloc((void **)&c->d_g, RS_UP * RS_TAPS * sizeof(float)) == hipSuccess &&
-	          hipMalloc((void **)&c->d_philast, nb * sizeof(int32_t)) == hipSuccess &&
-	          hipMalloc((void **)&c->d_dhist, nb * RS_TAPS * sizeof(float)) == hipSuccess;
-	ok = ok && hipMemset(c->d_hist[0], 0, hist_bytes) == hipSuccess && hipMemset(c->d_hist[1], 0, hist_bytes) == hipSuccess && hipMemset(c->d_philast, 0, nb * sizeof(int32_t)) == hipSuccess && hipMemset(c->d_bins, 0, nb * ((size_t)c->n_steps + PH_HEAD) * sizeof(int16_t)) == hipSuccess &&
-	     hipMemset(c->d_dhist, 0, nb * RS_TAPS * sizeof(float)) == hipSuccess &&
-	     [&] { for (int i = 0; i < CH_L / 2; i++) if (memcmp(&h[i], &h[CH_L - 1 - i], sizeof(float))) return false; return true; }() &&      // the kernel keeps half of it
-	     hipMemcpy(c->d_h, h.data(), CH_L * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(c->d_tw, tw.data(), CH_M * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(c->d_g, g.data(), RS_UP * RS_TAPS * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-	for (int i = 0; i < 3 && ok; i++) ok = hipEventCreateWithFlags(&c->ev[i], hipEventDisableSystemFence) == hipSuccess;     // timing only, same device
-	ok = ok && hipEventCreateWithFlags(&c->ev_xs, hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
-	if (ok) {
-		float gc[3 * SD_RS_KT_LD];
-		composite_rows(g, 4, gc);
-		for (float &v : gc) v *= 1.0f / 16384.0f;      // the bins decoder keeps the discriminator samples as 16-bit integers: the scale (a power of two: exact) sits in the taps
-		ok = hipMalloc((void **)&c->d_gc, sizeof(gc)) == hipSuccess && hipMemcpy(c->d_gc, gc, sizeof(gc), hipMemcpyHostToDevice) == hipSuccess;
-		if (ok && dual) {                     // the odd-stacked bank's tables: taps of odd t negated, twist exp(-j pi r / 512)
-			const double PI = 3.14159265358979323846;
-			std::vector<float> ho(h), wt(2 * CH_M);
-			for (int i = 0; i < CH_L; i++) if ((i / CH_M) & 1) ho[i] = -ho[i];
-			for (int r = 0; r < CH_M; r++) { wt[2 * r] = (float)cos(PI * (double)r / (double)CH_M); wt[2 * r + 1] = (float)(-sin(PI * (double)r / (double)CH_M)); }
-			ok = hipMalloc((void **)&c->d_h_odd, CH_L * sizeof(float)) == hipSuccess && hipMalloc((void **)&c->d_twist, CH_M * sizeof(float2)) == hipSuccess &&
-			     hipMemcpy(c->d_h_odd, ho.data(), CH_L * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-			     hipMemcpy(c->d_twist, wt.data(), CH_M * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess;
-		}
-		// fused unless a bin's sonde type needs 48 kS/s rows (AFSK) or the host asks for the rows (sonde_chan_set_fused)
-		c->fused = sd_batch_bins_capable(c->batch);
-		if (!c->fused && blocks_per_submit > 2) ok = false;      // (AFSK bins: the three-kernel form, 1-2 blocks per submit)
-		c->overlap = false;
-	}
-	if (!ok) { sonde_chan_destroy(c); return -1; }
+	if (chan_build(c, types, blocks_per_submit)) { sonde_chan_destroy(c); return -1; }       // (destroy leaves the error text alone)
 	*out = c;
 	return 0;
 }
@@ -603,7 +576,7 @@ extern "C" uint32_t sonde_chan_channels(const SondeChannelizer *c) { return c ? 
 // first submit only.  Returns the mode in force.
 extern "C" int sonde_chan_set_fused(SondeChannelizer *c, int on)
 {
-	if (!c) return -1;
+	if (!c) return sd_fail("sonde_chan_set_fused: null argument");
 	if (on < 0) return c->fused ? 1 : 0;       // query
 	if (c->n_blocks == 0 && (on || c->d_out48)) c->fused = on && sd_batch_bins_capable(c->batch);      // (> 2 blocks per submit: fused only)
 	return c->fused ? 1 : 0;
@@ -613,23 +586,21 @@ extern "C" int sonde_chan_set_fused(SondeChannelizer *c, int on)
 // (fused mode only); on = 0 (the default): both kernels in the caller's stream.  Before the first submit only.  Returns the mode.
 extern "C" int sonde_chan_set_overlap(SondeChannelizer *c, int on)
 {
-	if (!c) return -1;
+	if (!c) return sd_fail("sonde_chan_set_overlap: null argument");
 	if (c->n_blocks == 0) c->overlap = on && c->fused;
 	return c->overlap ? 1 : 0;
 }
 
-static bool chan_overlap_setup(SondeChannelizer *c)
+// the overlapped form's streams, events and second phase buffer (the layout of d_bins), at the first overlapped submit
+static int chan_overlap_setup(SondeChannelizer *c)
 {
-	if (c->s_pfb) return true;
-	const size_t nb = (size_t)c->n_streams * CH_M;
-	bool ok = hipStreamCreateWithFlags(&c->s_pfb, hipStreamNonBlocking) == hipSuccess && hipStreamCreateWithFlags(&c->s_dec, hipStreamNonBlocking) == hipSuccess &&
-	          hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess &&
-	          hipMalloc((void **)&c->d_bins_b, nb * ((size_t)c->n_steps + PH_HEAD) * sizeof(int16_t)) == hipSuccess &&      // the layout of d_bins: [PH_HEAD carried | n_steps] 16-bit phases
-	          hipMemset(c->d_bins_b, 0, nb * ((size_t)c->n_steps + PH_HEAD) * sizeof(int16_t)) == hipSuccess;
-	for (int i = 0; i < 2 && ok; i++)
-		ok = hipEventCreateWithFlags(&c->ev_pfb[i], hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess &&
-		     hipEventCreateWithFlags(&c->ev_dec[i], hipEventDisableTiming | hipEventDisableSystemFence) == hipSuccess;
-	return ok;
+	if (c->s_pfb) return 0;
+	HIPCHK_IN("sonde_chan_submit", hipStreamCreateWithFlags(&c->s_pfb, hipStreamNonBlocking));
+	HIPCHK_IN("sonde_chan_submit", hipStreamCreateWithFlags(&c->s_dec, hipStreamNonBlocking));
+	for (hipEvent_t *e : { &c->ev_in, &c->ev_pfb[0], &c->ev_pfb[1], &c->ev_dec[0], &c->ev_dec[1] })
+		HIPCHK_IN("sonde_chan_submit", hipEventCreateWithFlags(e, hipEventDisableTiming | hipEventDisableSystemFence));
+	HIPCHK_IN("sonde_chan_submit", c->d_bins_b.zeros((size_t)c->n_streams * CH_M * ((size_t)c->n_steps + PH_HEAD)));
+	return 0;
 }
 
 // What the wideband block holds: SONDE_INPUT_IQ (complex64, the default), SONDE_INPUT_IQ16 (int16 I, int16 Q: what a 10 MS/s
@@ -637,21 +608,22 @@ static bool chan_overlap_setup(SondeChannelizer *c)
 // kept in the input's format).  Returns the kind in force, or -1.
 extern "C" int sonde_chan_set_input(SondeChannelizer *c, int input_kind)
 {
-	if (!c) return -1;
-	if (c->n_blocks == 0 && sd_input_known(input_kind) && input_kind != SONDE_INPUT_REAL) c->input_kind = input_kind;
+	if (!c) return sd_fail("sonde_chan_set_input: null argument");
+	if (c->n_blocks == 0 && sd_input_complex(input_kind)) c->input_kind = input_kind;
 	return c->input_kind;
 }
 
 static void launch_pfb(SondeChannelizer *c, hipStream_t st, const void *iq_dev, size_t n_samples, int16_t *bins)
 {
 	const dim3 g(c->n_steps / P_S, c->n_streams), blk(P_NT);
-	const void *hin = c->d_hist[c->n_blocks & 1];
-	void *hout = c->d_hist[(c->n_blocks + 1) & 1];
+	const void *hin = c->d_hist.in();
+	void *hout = c->d_hist.out();
 	sd_input_dispatch(c->input_kind, [&](auto k) {
 		if constexpr (decltype(k)::value != SONDE_INPUT_REAL)      // (sonde_chan_set_input refuses REAL)
 			hipLaunchKernelGGL(sd_pfb_kernel<decltype(k)::value>, g, blk, 0, st, iq_dev, n_samples, hin, hout, c->d_h, c->d_tw, bins, c->n_steps, c->xcd_map, c->dual,
 				c->d_h_odd, c->d_twist);
 	});
+	c->d_hist.flip();      // the next submit reads the history this one writes
 }
 
 extern "C" uint32_t sonde_chan_samples_per_submit(const SondeChannelizer *c) { return c ? c->n_steps * CH_D : 0; }
@@ -659,9 +631,10 @@ extern "C" SondeBatch *sonde_chan_batch(SondeChannelizer *c) { return c ? c->bat
 
 extern "C" int sonde_chan_submit(SondeChannelizer *c, const void *iq_dev, size_t n_samples, void *stream_)
 {
-	if (!c || !iq_dev || n_samples != (size_t)c->n_steps * CH_D) return -1;
+	if (!c || !iq_dev) return sd_fail("sonde_chan_submit: null argument");
+	if (n_samples != (size_t)c->n_steps * CH_D) return sd_fail("sonde_chan_submit: n_samples must be sonde_chan_samples_per_submit()");
 	hipStream_t stream = (hipStream_t)stream_;
-	if (hipSetDevice(c->device) != hipSuccess) return -1;
+	HIPCHK_IN("sonde_chan_submit", hipSetDevice(c->device));
 	const uint32_t n_out = c->n_steps * RS_UP / RS_DN;
 	// fold the previous timed submit's events into the running sums (they have long completed)
 	if (c->ev_pending && hipEventQuery(c->ev[2]) == hipSuccess) {
@@ -673,47 +646,51 @@ extern "C" int sonde_chan_submit(SondeChannelizer *c, const void *iq_dev, size_t
 	}
 	const bool timed = !c->ev_pending && ((c->n_submits % 8) == 7 || c->n_blocks == 0);      // (as sonde_batch_submit: never the first submit behind a synchronize)
 	c->n_submits++;
-	if ((uintptr_t)iq_dev & 15u) return -1;       // 16-byte loads straight from the caller's block(s)
+	if ((uintptr_t)iq_dev & 15u) return sd_fail("sonde_chan_submit: the block must be 16-byte aligned");       // 16-byte loads straight from the caller's block(s)
 	c->overlap = c->overlap && c->fused;
 	if (c->overlap) {
-		if (!chan_overlap_setup(c)) return -1;
+		if (chan_overlap_setup(c)) return -1;
 		const int b = (int)(c->n_blocks & 1);
 		int16_t *bins = b ? c->d_bins_b : c->d_bins;
 		int16_t *bins_next = b ? c->d_bins : c->d_bins_b;      // the next submit's buffer takes this submit's last 16 phases
 		// the block is ready where the caller's stream stands now; bins[b] is free once the decoder of two submits ago is done
-		if (hipEventRecord(c->ev_in, stream) != hipSuccess || hipStreamWaitEvent(c->s_pfb, c->ev_in, 0) != hipSuccess) return -1;
-		if (c->n_blocks >= 2 && hipStreamWaitEvent(c->s_pfb, c->ev_dec[b], 0) != hipSuccess) return -1;
+		HIPCHK_IN("sonde_chan_submit", hipEventRecord(c->ev_in, stream));
+		HIPCHK_IN("sonde_chan_submit", hipStreamWaitEvent(c->s_pfb, c->ev_in, 0));
+		if (c->n_blocks >= 2) HIPCHK_IN("sonde_chan_submit", hipStreamWaitEvent(c->s_pfb, c->ev_dec[b], 0));
 		if (timed) (void)hipEventRecord(c->ev[0], c->s_pfb);
 		launch_pfb(c, c->s_pfb, iq_dev, n_samples, bins);
 		c->n_blocks++;
-		c->d_bins_last = bins;
+		c->bins_last = bins;
 		if (timed) { (void)hipEventRecord(c->ev[1], c->s_pfb); (void)hipEventRecord(c->ev[2], c->s_pfb); c->ev_pending = true; }
-		if (hipEventRecord(c->ev_pfb[b], c->s_pfb) != hipSuccess) return -1;
+		HIPCHK_IN("sonde_chan_submit", hipEventRecord(c->ev_pfb[b], c->s_pfb));
 		// the filter bank is the last reader of the caller's block: work queued on the caller's stream behind this submit may
 		// overwrite it; the decoder waits for the bins on its own stream
-		if (hipStreamWaitEvent(stream, c->ev_pfb[b], 0) != hipSuccess || hipStreamWaitEvent(c->s_dec, c->ev_pfb[b], 0) != hipSuccess) return -1;
-		if (hipGetLastError() != hipSuccess) return -1;
+		HIPCHK_IN("sonde_chan_submit", hipStreamWaitEvent(stream, c->ev_pfb[b], 0));
+		HIPCHK_IN("sonde_chan_submit", hipStreamWaitEvent(c->s_dec, c->ev_pfb[b], 0));
+		HIPCHK_IN("sonde_chan_submit", hipGetLastError());
 		c->last_stream = stream;
 		const SdBinsArgs ba = { bins, (size_t)c->n_steps + PH_HEAD, bins_next, (size_t)c->n_steps + PH_HEAD, c->d_gc };
-		if (sd_batch_submit_bins(c->batch, &ba, c->n_steps, (void *)c->s_dec) != 0) return -1;
-		return hipEventRecord(c->ev_dec[b], c->s_dec) == hipSuccess ? 0 : -1;
+		if (sd_batch_submit_bins(c->batch, &ba, c->n_steps, (void *)c->s_dec) != 0) return -1;      // (the text is the batch's)
+		HIPCHK_IN("sonde_chan_submit", hipEventRecord(c->ev_dec[b], c->s_dec));
+		return 0;
 	}
 	// the front-end kernels carry state too (window history, discriminator history): a submit on another stream waits for
 	// the previous one BEFORE the filter bank starts (sonde_batch_submit orders only the decoder behind them)
 	if (c->n_blocks && stream != c->last_stream) {
-		if (hipEventRecord(c->ev_xs, c->last_stream) != hipSuccess || hipStreamWaitEvent(stream, c->ev_xs, 0) != hipSuccess) return -1;
+		HIPCHK_IN("sonde_chan_submit", hipEventRecord(c->ev_xs, c->last_stream));
+		HIPCHK_IN("sonde_chan_submit", hipStreamWaitEvent(stream, c->ev_xs, 0));
 	}
 	c->last_stream = stream;
 	if (timed) (void)hipEventRecord(c->ev[0], stream);
 	launch_pfb(c, stream, iq_dev, n_samples, c->d_bins);
 	c->n_blocks++;
-	c->d_bins_last = c->d_bins;
+	c->bins_last = c->d_bins;
 	if (timed) (void)hipEventRecord(c->ev[1], stream);
 	if (!c->fused)
 		hipLaunchKernelGGL(sd_phase_resamp_kernel, dim3(CH_M * c->n_streams), dim3(256), (RS_TAPS + c->n_steps) * sizeof(float), stream,
 		                   c->d_bins, c->n_steps, c->d_g, c->d_philast, c->d_dhist, c->d_out48);
 	if (timed) { (void)hipEventRecord(c->ev[2], stream); c->ev_pending = true; }
-	if (hipGetLastError() != hipSuccess) return -1;
+	HIPCHK_IN("sonde_chan_submit", hipGetLastError());
 	if (c->fused) {
 		const SdBinsArgs ba = { c->d_bins, (size_t)c->n_steps + PH_HEAD, c->d_bins, (size_t)c->n_steps + PH_HEAD, c->d_gc };
 		return sd_batch_submit_bins(c->batch, &ba, c->n_steps, stream_);
@@ -725,8 +702,9 @@ extern "C" int sonde_chan_submit(SondeChannelizer *c, const void *iq_dev, size_t
 // (every 8th) since the previous call, then of the decoder behind them (sonde_batch_kernel_ms of the embedded batch).
 extern "C" int sonde_chan_kernel_ms(SondeChannelizer *c, float *pfb_ms, float *disc_resamp_ms, float *demod_ms, float *framer_ms)
 {
-	if (!c) return -1;
-	if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
+	if (!c) return sd_fail("sonde_chan_kernel_ms: null argument");
+	HIPCHK_IN("sonde_chan_kernel_ms", hipSetDevice(c->device));
+	HIPCHK_IN("sonde_chan_kernel_ms", hipDeviceSynchronize());
 	if (c->ev_pending) {
 		float a = 0.f, b = 0.f;
 		if (hipEventElapsedTime(&a, c->ev[0], c->ev[1]) == hipSuccess && hipEventElapsedTime(&b, c->ev[1], c->ev[2]) == hipSuccess) {
@@ -734,7 +712,7 @@ extern "C" int sonde_chan_kernel_ms(SondeChannelizer *c, float *pfb_ms, float *d
 		}
 		c->ev_pending = false;
 	}
-	if (c->n_timed == 0) return -1;
+	if (c->n_timed == 0) return sd_fail("sonde_chan_kernel_ms: no timed submit since the previous call");
 	if (pfb_ms) *pfb_ms = (float)(c->acc_ms[0] / c->n_timed);
 	if (disc_resamp_ms) *disc_resamp_ms = (float)(c->acc_ms[1] / c->n_timed);
 	c->acc_ms[0] = c->acc_ms[1] = 0.0;
@@ -746,19 +724,21 @@ extern "C" int sonde_chan_kernel_ms(SondeChannelizer *c, float *pfb_ms, float *d
 // introspection for the parity tests: copies of the intermediate products of the last submit
 extern "C" int sonde_chan_read(SondeChannelizer *c, float *bins /* [512][n_steps] phases (quadrants) or NULL */, float *out48 /* [512][n_out] or NULL */)
 {
-	if (!c) return -1;
-	if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
+	if (!c) return sd_fail("sonde_chan_read: null argument");
+	HIPCHK_IN("sonde_chan_read", hipSetDevice(c->device));
+	HIPCHK_IN("sonde_chan_read", hipDeviceSynchronize());
 	const uint32_t n_out = c->n_steps * RS_UP / RS_DN;
 	const size_t nb = (size_t)c->n_streams * CH_M;
 	if (bins) {           // the 16-bit phases as quadrants (q / 16384: exact), without the carried head of each row
 		const size_t prow = (size_t)c->n_steps + PH_HEAD;
 		std::vector<int16_t> tmp(nb * prow);
-		if (hipMemcpy(tmp.data(), c->d_bins_last ? c->d_bins_last : c->d_bins, tmp.size() * sizeof(int16_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+		HIPCHK_IN("sonde_chan_read", hipMemcpy(tmp.data(), c->bins_last ? c->bins_last : c->d_bins, tmp.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
 		for (size_t k = 0; k < nb; k++)
 			for (size_t m = 0; m < c->n_steps; m++) bins[k * c->n_steps + m] = (float)tmp[k * prow + PH_HEAD + m] * (1.0f / 16384.0f);
 	}
-	if (out48 && c->fused) return -1;      // the rows are never materialised in fused mode: sonde_chan_set_fused(c, 0) before the first submit
-	if (out48 && hipMemcpy(out48, c->d_out48, nb * n_out * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+	// the rows are never materialised in fused mode: sonde_chan_set_fused(c, 0) before the first submit
+	if (out48 && c->fused) return sd_fail("sonde_chan_read: no 48 kS/s rows in fused mode");
+	if (out48) HIPCHK_IN("sonde_chan_read", hipMemcpy(out48, c->d_out48, nb * n_out * sizeof(float), hipMemcpyDeviceToHost));
 	return 0;
 }
 

@@ -21,6 +21,8 @@
 #include "sd_rs41.h"
 #include "sd_fixed.h"
 #include "launch.h"
+#include "sd_host.h"
+#include "sd_devmem.h"
 #include "sd_tables.h"
 #include "sd_chanlist.h"
 #include "../../include/sonde_abi.h"
@@ -380,14 +382,14 @@ __global__ __launch_bounds__(DT_WG) void sd_detect_kernel(
 // theta_k: DESIGN 3.8's threshold table (the float64 reference over AWGN and over 30 dB signals of the other types)
 static const float k_theta[SONDE_NTYPES] = { 0.52f, 0.79f, 0.85f, 0.82f, 0.83f, 0.91f, 0.86f };
 
-struct SondeDetector {
+struct __attribute__((visibility("hidden"))) SondeDetector {
 	int device = 0, input_kind = 0;
 	uint32_t n_channels = 0, max_samples = 0, last_n = 0;
 	std::vector<uint8_t> mask;
-	SdDetState *d_state = nullptr;
-	int32_t *d_D = nullptr, *d_A = nullptr;
+	DevBuf<SdDetState> d_state;
+	DevBuf<int32_t> d_D, d_A;
 	size_t rowD = 0, rowA = 0;
-	float2 *d_wi = nullptr, *d_wc = nullptr;
+	DevBuf<float2> d_wi, d_wc;
 	hipStream_t last_stream = nullptr;
 	bool submitted = false;
 	SdChanLists restart_lists;              // sonde_detect_restart_channels
@@ -427,7 +429,6 @@ extern "C" void sonde_detect_destroy(SondeDetector *d)
 	(void)hipSetDevice(d->device);
 	if (d->submitted) (void)hipStreamSynchronize(d->last_stream);
 	d->restart_lists.destroy();
-	(void)hipFree(d->d_state); (void)hipFree(d->d_D); (void)hipFree(d->d_A); (void)hipFree(d->d_wi); (void)hipFree(d->d_wc);
 	delete d;
 }
 
@@ -443,33 +444,35 @@ static int dt_clear(SondeDetector *d)
 	return 0;
 }
 
+// Everything behind the argument checks: the mixer tables, the records and the carried streams, cleared as sonde_detect_reset clears
+// them; on failure sonde_detect_create destroys what has been built so far.
+static int dt_build(SondeDetector *d)
+{
+	float wi[2 * SD_AF_PER], wc[2 * SD_C50_PER];
+	make_mixer(wi, 17, SD_AF_PER);
+	make_mixer(wc, 19, SD_C50_PER);
+	HIPCHK(d->d_wi.upload((const float2 *)wi, SD_AF_PER));
+	HIPCHK(d->d_wc.upload((const float2 *)wc, SD_C50_PER));
+	HIPCHK(d->d_state.alloc(d->n_channels));
+	HIPCHK(d->d_D.alloc(d->n_channels * d->rowD));
+	HIPCHK(d->d_A.alloc(2 * (size_t)d->n_channels * d->rowA));
+	return dt_clear(d);
+}
+
 extern "C" int sonde_detect_create(uint32_t n_channels, uint32_t max_samples, int input_kind, const uint8_t *type_mask, int device, SondeDetector **out)
 {
 	if (!out) return sd_fail("sonde_detect_create: null argument");
 	*out = nullptr;
 	if (!n_channels || !max_samples || max_samples % SD_TILE) return sd_fail("sonde_detect_create: n_channels must be > 0 and max_samples a positive multiple of SONDE_TILE");
 	if (!sd_input_known(input_kind)) return sd_fail("sonde_detect_create: bad input kind");
-	int ndev = 0;
-	hipError_t e = hipGetDeviceCount(&ndev);
-	if (e != hipSuccess || device < 0 || device >= ndev) return sd_fail("sonde_detect_create: no such HIP device (this library has no CPU path)", e);
-	if ((e = hipSetDevice(device)) != hipSuccess) return sd_fail("hipSetDevice", e);
+	if (sd_select_device(device, "sonde_detect_create")) return -1;
 	SondeDetector *d = new SondeDetector;
 	d->device = device; d->n_channels = n_channels; d->max_samples = max_samples; d->input_kind = input_kind;
 	d->mask.assign(n_channels, 0x7F);
 	if (type_mask) for (uint32_t c = 0; c < n_channels; c++) d->mask[c] = type_mask[c] & 0x7F;
 	d->rowD = (DT_H24 + max_samples / 2 + 63) & ~(size_t)63;
 	d->rowA = (DT_H6 + max_samples / 8 + 63) & ~(size_t)63;
-	float wi[2 * SD_AF_PER], wc[2 * SD_C50_PER];
-	make_mixer(wi, 17, SD_AF_PER);
-	make_mixer(wc, 19, SD_C50_PER);
-	bool ok = hipMalloc((void **)&d->d_state, n_channels * sizeof(SdDetState)) == hipSuccess &&
-	          hipMalloc((void **)&d->d_D, n_channels * d->rowD * sizeof(int32_t)) == hipSuccess &&
-	          hipMalloc((void **)&d->d_A, 2 * (size_t)n_channels * d->rowA * sizeof(int32_t)) == hipSuccess &&
-	          hipMalloc((void **)&d->d_wi, sizeof(wi)) == hipSuccess && hipMalloc((void **)&d->d_wc, sizeof(wc)) == hipSuccess;
-	ok = ok && hipMemcpy(d->d_wi, wi, sizeof(wi), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(d->d_wc, wc, sizeof(wc), hipMemcpyHostToDevice) == hipSuccess;
-	if (!ok) { sonde_detect_destroy(d); return sd_fail("sonde_detect_create: device allocation failed"); }
-	if (dt_clear(d)) { sonde_detect_destroy(d); return -1; }
+	if (dt_build(d)) { sonde_detect_destroy(d); return -1; }       // (destroy leaves the error text alone)
 	*out = d;
 	return 0;
 }
@@ -481,14 +484,13 @@ extern "C" int sonde_detect_submit(SondeDetector *d, const void *samples, size_t
 	if (channel_stride < n_samples) return sd_fail("sonde_detect_submit: channel_stride < n_samples");
 	const size_t eb = sd_sample_bytes(d->input_kind);
 	if ((uintptr_t)samples % eb) return sd_fail("sonde_detect_submit: samples not aligned to the sample size");
-	hipError_t e = hipSetDevice(d->device);
-	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	HIPCHK(hipSetDevice(d->device));
 	hipStream_t s = (hipStream_t)stream;
 	sd_input_dispatch(d->input_kind, [&](auto k) {
 		hipLaunchKernelGGL(sd_detect_kernel<decltype(k)::value>, dim3(d->n_channels), dim3(DT_WG), 0, s, samples, channel_stride * eb, (uint32_t)n_samples,
 			d->d_state, d->d_D, d->rowD, d->d_A, d->rowA, d->d_wi, d->d_wc);
 	});
-	if ((e = hipGetLastError()) != hipSuccess) return sd_fail("sd_detect_kernel launch", e);
+	HIPCHK_IN("sonde_detect_submit", hipGetLastError());
 	d->last_stream = s;
 	d->last_n = (uint32_t)n_samples;
 	d->submitted = true;
@@ -553,14 +555,13 @@ extern "C" int sonde_detect_restart_channels(SondeDetector *d, const uint32_t *c
 	for (size_t i = 0; i < n; i++)
 		if (channels[i] >= d->n_channels) return sd_fail("sonde_detect_restart_channels: no such channel");
 	if (n == 0 || !d->submitted) return 0;      // nothing has run: the state is what create set
-	hipError_t e = hipSetDevice(d->device);
-	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	HIPCHK(hipSetDevice(d->device));
 	SdChanLists::Buf *lb = d->restart_lists.put(channels, n);
 	if (!lb) return sd_fail("sonde_detect_restart_channels: no pinned memory for the channel list");
 	// on the stream of the last submit: behind its kernel; a submit on another stream is the caller's to order, as between submits
 	hipLaunchKernelGGL(sd_detect_restart_kernel, dim3((unsigned)n), dim3(DT_WG), 0, d->last_stream, lb->dev, d->d_state, d->d_D, d->rowD, d->d_A, d->rowA);
-	if ((e = hipGetLastError()) != hipSuccess || (e = d->restart_lists.done(lb, d->last_stream)) != hipSuccess)
-		return sd_fail("sd_detect_restart_kernel launch", e);
+	HIPCHK_IN("sonde_detect_restart_channels", hipGetLastError());
+	HIPCHK_IN("sonde_detect_restart_channels", d->restart_lists.done(lb, d->last_stream));
 	return 0;
 }
 

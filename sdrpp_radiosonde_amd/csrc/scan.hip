@@ -17,6 +17,9 @@
 #include <string>
 #include <vector>
 #include "launch.h"
+#include "sd_host.h"
+#include "sd_devmem.h"
+#include "sd_design.h"
 #include "sd_input.h"
 #include "../../include/sonde_abi.h"
 
@@ -212,22 +215,20 @@ __global__ __launch_bounds__(256) void sd_scan_tail_kernel(const void *__restric
 }
 
 // ---------------------------------------------------------------- host
-struct SondeScanner {
+struct __attribute__((visibility("hidden"))) SondeScanner {
 	int device = 0, input_kind = SONDE_INPUT_IQ, log2n = 0;
 	uint32_t fs = 0, n = 0;
 	size_t max_in = 0;
 	int64_t total = 0;                  // samples since create / reset
 	int64_t segs = 0;                   // whole segments launched since create / reset
 	uint32_t tail_len = 0;              // raw samples carried: total - segs N / 2
-	unsigned parity = 0;
 	hipStream_t last = nullptr;
 	uint32_t max_rows = 0;              // power rows per launch pair
-	float *d_win = nullptr, *d_rows = nullptr;
-	float2 *d_tw = nullptr, *d_tail[2] = {};
-	double *d_acc = nullptr;
+	DevBuf<float> d_win, d_rows;
+	DevBuf<float2> d_tw;
+	DevPair<float2> d_tail;
+	DevBuf<double> d_acc;
 };
-
-static const double SC_PI = 3.14159265358979323846;
 
 static int sc_rate_ok(uint32_t fs, const char *fn)
 {
@@ -250,7 +251,7 @@ static uint32_t sc_auto_n(uint32_t fs)
 
 static void sc_window(uint32_t n, float *w)
 {
-	for (uint32_t i = 0; i < n; i++) w[i] = (float)(0.5 - 0.5 * cos(2.0 * SC_PI * (double)i / (double)n));
+	for (uint32_t i = 0; i < n; i++) w[i] = (float)(0.5 - 0.5 * cos(2.0 * SD_PI * (double)i / (double)n));
 }
 
 extern "C" int sonde_scan_window(uint32_t n, float *w, size_t cap)
@@ -274,32 +275,20 @@ extern "C" void sonde_scan_destroy(SondeScanner *s)
 {
 	if (!s) return;
 	(void)hipSetDevice(s->device);
-	(void)hipFree(s->d_win); (void)hipFree(s->d_rows); (void)hipFree(s->d_tw); (void)hipFree(s->d_tail[0]); (void)hipFree(s->d_tail[1]);
-	(void)hipFree(s->d_acc);
 	delete s;
 }
 
-extern "C" int sonde_scan_create(uint32_t rate_in, uint32_t fft_size, size_t max_in, int input_kind, int device, SondeScanner **out)
+// Everything behind the argument checks: the window, the twiddles, the power rows, the zeroed accumulator and tail; on failure
+// sonde_scan_create destroys what has been built so far.
+static int sc_build(SondeScanner *s)
 {
-	if (!out) return sd_fail("sonde_scan_create: bad argument");
-	if (sc_rate_ok(rate_in, "sonde_scan_create")) return -1;
-	const uint32_t n = fft_size ? fft_size : sc_auto_n(rate_in);
-	const int lg = sc_log2(n);
-	if (lg < 0) return sd_fail("sonde_scan_create: fft_size must be a power of two, 1024 .. 16384 (0 = by rate_in)");
-	if (input_kind != SONDE_INPUT_IQ && input_kind != SONDE_INPUT_IQ16 && input_kind != SONDE_INPUT_IQ8)
-		return sd_fail("sonde_scan_create: input_kind must be SONDE_INPUT_IQ, SONDE_INPUT_IQ16 or SONDE_INPUT_IQ8 (the scanner takes complex samples)");
-	if (!max_in || max_in >= ((size_t)1 << 31)) return sd_fail("sonde_scan_create: max_in must be 1 .. 2^31 - 1");
-	int ndev = 0;
-	hipError_t e = hipGetDeviceCount(&ndev);
-	if (e != hipSuccess || device < 0 || device >= ndev) return sd_fail("sonde_scan_create: no such HIP device (this library has no CPU path)", e);
-	if ((e = hipSetDevice(device)) != hipSuccess) return sd_fail("hipSetDevice", e);
-	SondeScanner *s = new SondeScanner;
-	s->device = device; s->input_kind = input_kind; s->log2n = lg; s->fs = rate_in; s->n = n; s->max_in = max_in;
+	const uint32_t n = s->n;
+	const int lg = s->log2n;
 	std::vector<float> w(n);
 	sc_window(n, w.data());
 	// the twiddles W_L^m = exp(-2 pi i m / L), double on the host, stored as float; exactly 1 at m = 0
 	const auto tw_of = [](uint64_t m, uint64_t L) {
-		const double a = -2.0 * SC_PI * (double)(m % L) / (double)L;
+		const double a = -2.0 * SD_PI * (double)(m % L) / (double)L;
 		return m % L ? make_float2((float)cos(a), (float)sin(a)) : make_float2(1.0f, 0.0f);
 	};
 	const size_t ntw = (size_t)sc_tw_off(lg, 2);
@@ -311,17 +300,30 @@ extern "C" int sonde_scan_create(uint32_t rate_in, uint32_t fft_size, size_t max
 		for (uint32_t p = 1; p <= 3; p++) for (uint32_t j = 0; j < q; j++) t[(p - 1) * q + j] = tw_of((uint64_t)p * j, (uint64_t)1 << l);
 	}
 	const size_t cap_rows = std::min<size_t>(SC_ROWS_MAX, SC_ROW_BYTES / (n * sizeof(float)));
-	const size_t max_rows = std::min<size_t>(cap_rows, (max_in + n - 1) / (n / 2) + 1);
+	const size_t max_rows = std::min<size_t>(cap_rows, (s->max_in + n - 1) / (n / 2) + 1);
 	s->max_rows = (uint32_t)max_rows;
-	const size_t tb = (size_t)n * sizeof(float2);
-	bool ok = hipMalloc((void **)&s->d_win, n * sizeof(float)) == hipSuccess && hipMalloc((void **)&s->d_tw, ntw * sizeof(float2)) == hipSuccess &&
-	          hipMalloc((void **)&s->d_rows, max_rows * n * sizeof(float)) == hipSuccess && hipMalloc((void **)&s->d_acc, n * sizeof(double)) == hipSuccess &&
-	          hipMalloc((void **)&s->d_tail[0], tb) == hipSuccess && hipMalloc((void **)&s->d_tail[1], tb) == hipSuccess;
-	ok = ok && hipMemcpy(s->d_win, w.data(), n * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(s->d_tw, tw.data(), ntw * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemset(s->d_acc, 0, n * sizeof(double)) == hipSuccess &&
-	     hipMemset(s->d_tail[0], 0, tb) == hipSuccess && hipMemset(s->d_tail[1], 0, tb) == hipSuccess;
-	if (!ok) { sonde_scan_destroy(s); return sd_fail("sonde_scan_create: device allocation failed"); }
+	HIPCHK(s->d_win.upload(w.data(), n));
+	HIPCHK(s->d_tw.upload(tw.data(), ntw));
+	HIPCHK(s->d_rows.alloc(max_rows * n));
+	HIPCHK(s->d_acc.zeros(n));
+	HIPCHK(s->d_tail.zeros(n));
+	return 0;
+}
+
+extern "C" int sonde_scan_create(uint32_t rate_in, uint32_t fft_size, size_t max_in, int input_kind, int device, SondeScanner **out)
+{
+	if (!out) return sd_fail("sonde_scan_create: bad argument");
+	if (sc_rate_ok(rate_in, "sonde_scan_create")) return -1;
+	const uint32_t n = fft_size ? fft_size : sc_auto_n(rate_in);
+	const int lg = sc_log2(n);
+	if (lg < 0) return sd_fail("sonde_scan_create: fft_size must be a power of two, 1024 .. 16384 (0 = by rate_in)");
+	if (!sd_input_complex(input_kind))
+		return sd_fail("sonde_scan_create: input_kind must be SONDE_INPUT_IQ, SONDE_INPUT_IQ16 or SONDE_INPUT_IQ8 (the scanner takes complex samples)");
+	if (!max_in || max_in >= ((size_t)1 << 31)) return sd_fail("sonde_scan_create: max_in must be 1 .. 2^31 - 1");
+	if (sd_select_device(device, "sonde_scan_create")) return -1;
+	SondeScanner *s = new SondeScanner;
+	s->device = device; s->input_kind = input_kind; s->log2n = lg; s->fs = rate_in; s->n = n; s->max_in = max_in;
+	if (sc_build(s)) { sonde_scan_destroy(s); return -1; }       // (destroy leaves the error text alone)
 	*out = s;
 	return 0;
 }
@@ -340,15 +342,14 @@ extern "C" int sonde_scan_submit(SondeScanner *s, const void *wide_dev, size_t n
 	if (!n_in || n_in > s->max_in) return sd_fail("sonde_scan_submit: n_in must be 1 .. max_in");
 	if (!wide_dev) return sd_fail("sonde_scan_submit: null argument");
 	if ((uintptr_t)wide_dev % sd_sample_bytes(s->input_kind)) return sd_fail("sonde_scan_submit: the block is not aligned to the sample size");
-	hipError_t e = hipSetDevice(s->device);
-	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	HIPCHK(hipSetDevice(s->device));
 	hipStream_t st = (hipStream_t)stream;
 	const int64_t N = s->n, half = N / 2;
 	const int64_t total = s->total + (int64_t)n_in;
 	const int64_t segs = total < N ? 0 : (total - N) / half + 1;          // whole segments since create / reset
 	const int64_t n_base = s->total;                                      // absolute index of the block's first sample
-	const float2 *t_in = s->d_tail[s->parity & 1];
-	float2 *t_out = s->d_tail[(s->parity + 1) & 1];
+	const float2 *t_in = s->d_tail.in();
+	float2 *t_out = s->d_tail.out();
 	const uint32_t tail_out = (uint32_t)(total - segs * half);            // < N
 	sd_input_dispatch(s->input_kind, [&](auto kk) {
 		constexpr int K = decltype(kk)::value;
@@ -370,8 +371,8 @@ extern "C" int sonde_scan_submit(SondeScanner *s, const void *wide_dev, size_t n
 					(uint64_t)s->tail_len + n_in - tail_out);
 		}
 	});
-	if ((e = hipGetLastError()) != hipSuccess) return sd_fail("sd_scan_kernel launch", e);
-	s->parity++;
+	HIPCHK_IN("sonde_scan_submit", hipGetLastError());
+	s->d_tail.flip();
 	s->total = total;
 	s->segs = segs;
 	s->tail_len = tail_out;
@@ -381,9 +382,9 @@ extern "C" int sonde_scan_submit(SondeScanner *s, const void *wide_dev, size_t n
 
 static int sc_sync(SondeScanner *s, const char *fn)
 {
-	hipError_t e = hipSetDevice(s->device);
-	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
-	if ((e = hipStreamSynchronize(s->last)) != hipSuccess) return sd_fail((std::string(fn) + ": hipStreamSynchronize").c_str(), e);
+	HIPCHK(hipSetDevice(s->device));
+	const hipError_t e = hipStreamSynchronize(s->last);
+	if (e != hipSuccess) return sd_fail((std::string(fn) + ": hipStreamSynchronize").c_str(), e);
 	return 0;
 }
 

@@ -9,6 +9,7 @@
 #include "../../include/sonde_abi.h"
 
 constexpr bool sd_input_known(int k) { return k == SONDE_INPUT_IQ || k == SONDE_INPUT_REAL || k == SONDE_INPUT_IQ16 || k == SONDE_INPUT_IQ8; }
+constexpr bool sd_input_complex(int k) { return k == SONDE_INPUT_IQ || k == SONDE_INPUT_IQ16 || k == SONDE_INPUT_IQ8; }      // what a mixer or a transform takes
 constexpr size_t sd_sample_bytes(int k) { return k == SONDE_INPUT_IQ ? 8 : (k == SONDE_INPUT_IQ8 ? 2 : 4); }
 
 // calls f(std::integral_constant<int, K>()) for the runtime kind K (the entry points refuse unknown kinds when they are created)

@@ -18,6 +18,9 @@
 #include <string>
 #include <vector>
 #include "launch.h"
+#include "sd_host.h"
+#include "sd_devmem.h"
+#include "sd_design.h"
 #include "../../include/sonde_abi.h"
 
 #define TK_WG     256
@@ -90,25 +93,31 @@ struct SdTrackPending { uint64_t seq, look; };
 struct SondeTracker {
 	int device = 0;
 	uint32_t n_rows = 0, rate = 0, max_samples = 0, L = 0, LB = 0, d = 0, ring_len = 0;
-	unsigned parity = 0;
 	hipStream_t last = nullptr;
 	std::vector<uint32_t> ph;           // blocks into the current look, per row
 	std::vector<uint8_t> fresh;         // the row starts at the next submit
 	std::vector<uint64_t> look, seq;    // index of the look in progress (from the last restart); looks finished since create
 	std::vector<std::deque<SdTrackPending>> pending;
 	std::vector<uint64_t> dropped;
-	float2 *d_hist[2] = {};
-	double *d_carry[2] = {}, *d_ring = nullptr;
+	DevPair<float2> d_hist;
+	DevPair<double> d_carry;
+	DevBuf<double> d_ring;
 };
-
-static const double TK_PI = 3.14159265358979323846;
 
 extern "C" void sonde_track_destroy(SondeTracker *t)
 {
 	if (!t) return;
 	(void)hipSetDevice(t->device);
-	(void)hipFree(t->d_hist[0]); (void)hipFree(t->d_hist[1]); (void)hipFree(t->d_carry[0]); (void)hipFree(t->d_carry[1]); (void)hipFree(t->d_ring);
 	delete t;
+}
+
+// Everything behind the argument checks; on failure sonde_track_create destroys what has been built so far.
+static int tk_build(SondeTracker *t)
+{
+	HIPCHK(t->d_hist.zeros((size_t)t->n_rows * TK_DMAX));
+	HIPCHK(t->d_carry.zeros((size_t)t->n_rows * 3));
+	HIPCHK(t->d_ring.zeros((size_t)t->n_rows * 3 * t->ring_len));
+	return 0;
 }
 
 extern "C" int sonde_track_defaults(uint32_t rate, uint32_t *look_samples, uint32_t *lag)
@@ -132,23 +141,14 @@ extern "C" int sonde_track_create(uint32_t n_rows, uint32_t rate, uint32_t max_s
 	if (d > TK_DMAX) return sd_fail("sonde_track_create: lag must be 1 .. 64 (0 = by rate)");
 	if (!max_samples || max_samples % TK_BLK || max_samples >= (1u << 30)) return sd_fail("sonde_track_create: max_samples must be a positive multiple of 256 below 2^30");
 	if ((max_samples / TK_BLK) / (L / TK_BLK) + 2 > 65535u) return sd_fail("sonde_track_create: max_samples holds more than 65 533 looks");
-	int ndev = 0;
-	hipError_t e = hipGetDeviceCount(&ndev);
-	if (e != hipSuccess || device < 0 || device >= ndev) return sd_fail("sonde_track_create: no such HIP device (this library has no CPU path)", e);
-	if ((e = hipSetDevice(device)) != hipSuccess) return sd_fail("hipSetDevice", e);
+	if (sd_select_device(device, "sonde_track_create")) return -1;
 	SondeTracker *t = new SondeTracker;
 	t->device = device; t->n_rows = n_rows; t->rate = rate; t->max_samples = max_samples; t->L = L; t->LB = L / TK_BLK; t->d = d;
 	const uint32_t per_submit = (max_samples / TK_BLK) / t->LB + 2;       // looks one submit can finish, and one more
 	t->ring_len = per_submit > 16u ? per_submit : 16u;
 	t->ph.assign(n_rows, 0); t->fresh.assign(n_rows, 1); t->look.assign(n_rows, 0); t->seq.assign(n_rows, 0);
 	t->pending.resize(n_rows); t->dropped.assign(n_rows, 0);
-	const size_t hb = (size_t)n_rows * TK_DMAX * sizeof(float2), cb = (size_t)n_rows * 3 * sizeof(double), rb = cb * t->ring_len;
-	bool ok = hipMalloc((void **)&t->d_hist[0], hb) == hipSuccess && hipMalloc((void **)&t->d_hist[1], hb) == hipSuccess &&
-	          hipMalloc((void **)&t->d_carry[0], cb) == hipSuccess && hipMalloc((void **)&t->d_carry[1], cb) == hipSuccess &&
-	          hipMalloc((void **)&t->d_ring, rb) == hipSuccess;
-	ok = ok && hipMemset(t->d_hist[0], 0, hb) == hipSuccess && hipMemset(t->d_hist[1], 0, hb) == hipSuccess &&
-	     hipMemset(t->d_carry[0], 0, cb) == hipSuccess && hipMemset(t->d_carry[1], 0, cb) == hipSuccess && hipMemset(t->d_ring, 0, rb) == hipSuccess;
-	if (!ok) { sonde_track_destroy(t); return sd_fail("sonde_track_create: device allocation failed"); }
+	if (tk_build(t)) { sonde_track_destroy(t); return -1; }       // (destroy leaves the error text alone)
 	*out = t;
 	return 0;
 }
@@ -164,14 +164,9 @@ extern "C" int sonde_track_submit(SondeTracker *t, const void *rows_dev, size_t 
 		return sd_fail("sonde_track_submit: n_samples must be a positive multiple of 256 and <= max_samples");
 	if (row_stride < n_samples) return sd_fail("sonde_track_submit: row_stride shorter than the row");
 	if ((uintptr_t)rows_dev & 7u) return sd_fail("sonde_track_submit: rows must be 8-byte aligned");
-	hipError_t e = hipSetDevice(t->device);
-	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	HIPCHK(hipSetDevice(t->device));
 	hipStream_t s = (hipStream_t)stream;
 	const uint32_t nb = (uint32_t)(n_samples / TK_BLK), LB = t->LB;
-	const float2 *h_in = t->d_hist[t->parity & 1];
-	float2 *h_out = t->d_hist[(t->parity + 1) & 1];
-	const double *c_in = t->d_carry[t->parity & 1];
-	double *c_out = t->d_carry[(t->parity + 1) & 1];
 	const dim3 wg(TK_WG);
 	for (uint32_t vb = 0; vb < t->n_rows; vb += TK_VMAX) {
 		const uint32_t nv = t->n_rows - vb < TK_VMAX ? t->n_rows - vb : TK_VMAX;
@@ -181,10 +176,10 @@ extern "C" int sonde_track_submit(SondeTracker *t, const void *rows_dev, size_t 
 			rs.slot[i] = (uint16_t)(t->seq[vb + i] % t->ring_len);
 		}
 		const dim3 grid((nb + LB - 1) / LB + 1, nv);
-		hipLaunchKernelGGL(sd_track_kernel, grid, wg, 0, s, (const float2 *)rows_dev, row_stride, nb, LB, t->d, rs, vb, h_in, h_out, c_in, c_out,
-			t->d_ring, t->ring_len);
+		hipLaunchKernelGGL(sd_track_kernel, grid, wg, 0, s, (const float2 *)rows_dev, row_stride, nb, LB, t->d, rs, vb, t->d_hist.in(), t->d_hist.out(),
+			t->d_carry.in(), t->d_carry.out(), t->d_ring, t->ring_len);
 	}
-	if ((e = hipGetLastError()) != hipSuccess) return sd_fail("sd_track_kernel launch", e);
+	HIPCHK_IN("sonde_track_submit", hipGetLastError());
 	for (uint32_t r = 0; r < t->n_rows; r++) {
 		const uint32_t tot = t->ph[r] + nb, fin = tot / LB;
 		for (uint32_t i = 0; i < fin; i++) {
@@ -194,7 +189,8 @@ extern "C" int sonde_track_submit(SondeTracker *t, const void *rows_dev, size_t 
 		t->ph[r] = tot % LB;
 		t->fresh[r] = 0;
 	}
-	t->parity++;
+	t->d_hist.flip();
+	t->d_carry.flip();
 	t->last = s;
 	return 0;
 }
@@ -213,9 +209,9 @@ extern "C" int sonde_track_results(SondeTracker *t, SondeTrackLook *out, size_t 
 	size_t count = 0;
 	for (uint32_t r = 0; r < t->n_rows; r++) count += t->pending[r].size();
 	if (cap < count) return sd_fail("sonde_track_results: the buffer is shorter than n_rows * sonde_track_ring()");
-	hipError_t e = hipSetDevice(t->device);
-	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
-	if ((e = hipStreamSynchronize(t->last)) != hipSuccess) return sd_fail("sonde_track_results: hipStreamSynchronize", e);
+	HIPCHK(hipSetDevice(t->device));
+	hipError_t e = hipStreamSynchronize(t->last);
+	if (e != hipSuccess) return sd_fail("sonde_track_results: hipStreamSynchronize", e);
 	std::vector<double> ring((size_t)t->n_rows * t->ring_len * 3);
 	if (count && (e = hipMemcpy(ring.data(), t->d_ring, ring.size() * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess)
 		return sd_fail("sonde_track_results: hipMemcpy", e);
@@ -236,7 +232,7 @@ extern "C" int sonde_track_results(SondeTracker *t, SondeTrackLook *out, size_t 
 // ---------------------------------------------------------------- the host conversions and the step rule (SPEC 3.11: pure host, double)
 extern "C" double sonde_track_err_hz(uint32_t rate, uint32_t lag, double a_re, double a_im)
 {
-	return (double)rate / (2.0 * TK_PI * (double)lag) * atan2(a_im, a_re);
+	return (double)rate / (2.0 * SD_PI * (double)lag) * atan2(a_im, a_re);
 }
 
 extern "C" double sonde_track_level_db(double p, uint32_t look_samples) { return 10.0 * log10(p / (double)look_samples); }

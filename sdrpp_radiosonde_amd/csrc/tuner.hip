@@ -21,6 +21,9 @@
 #include <string>
 #include <vector>
 #include "launch.h"
+#include "sd_host.h"
+#include "sd_devmem.h"
+#include "sd_design.h"
 #include "sd_input.h"
 #include "../../include/sonde_abi.h"
 
@@ -143,11 +146,11 @@ struct SondeTuner {
 	std::vector<uint8_t> set, active;   // per VFO (slot): its tap set, and whether it is tuned at all
 	std::map<uint32_t, uint32_t> set_of;        // listed bandwidth -> tap set (ascending bandwidth)
 	int64_t n_base = 0;                 // absolute input index of the next submit's first sample
-	unsigned parity = 0;
-	float *d_taps = nullptr;
-	uint64_t *d_tapoff = nullptr;
-	uint32_t *d_T = nullptr;
-	float2 *d_th = nullptr, *d_tl = nullptr, *d_hist[2] = {};
+	DevBuf<float> d_taps;
+	DevBuf<uint64_t> d_tapoff;
+	DevBuf<uint32_t> d_T;
+	DevBuf<float2> d_th, d_tl;
+	DevPair<float2> d_hist;
 };
 
 static uint64_t tn_gcd(uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; }
@@ -165,26 +168,10 @@ static int tn_ratio(uint32_t fs, uint32_t r, uint32_t *up, uint32_t *down, const
 
 static uint32_t tn_T(uint32_t fs, uint32_t b) { return 32u * ((fs + b - 1) / b); }
 
-// SPEC 3.9: the prototype of SPEC 3.7 (vfo.hip vfo_taps: Blackman-windowed sinc) with N = up T taps, cutoff B / 2 at Fs up; each
-// phase normalised to unit DC gain in double, g[p][t] = (float)(h[t up + p] / sum_t h[t up + p])
+// SPEC 3.9: the prototype of SPEC 3.7 (sd_design.h) with N = up T taps, cutoff B / 2 at Fs up, as `up` rows of unit DC gain
 static void tn_taps(uint32_t up, uint32_t T, double fs_up, double cutoff_hz, float *g)
 {
-	const double PI = 3.14159265358979323846;
-	const size_t N = (size_t)up * T;
-	const double fc = cutoff_hz / fs_up;
-	std::vector<double> tmp(N);
-	for (size_t i = 0; i < N; i++) {
-		const double t = (double)i - 0.5 * (double)(N - 1);
-		const double x = (double)i / (double)(N - 1);
-		const double w = 0.42 - 0.5 * cos(2.0 * PI * x) + 0.08 * cos(4.0 * PI * x);
-		const double s = (t == 0.0) ? 2.0 * fc : sin(2.0 * PI * fc * t) / (PI * t);
-		tmp[i] = s * w;
-	}
-	for (uint32_t p = 0; p < up; p++) {
-		double sum = 0.0;
-		for (uint32_t t = 0; t < T; t++) sum += tmp[(size_t)t * up + p];
-		for (uint32_t t = 0; t < T; t++) g[(size_t)p * T + t] = (float)(tmp[(size_t)t * up + p] / sum);
-	}
+	sd_design_rows(sd_design_prototype((size_t)up * T, cutoff_hz / fs_up), up, T, g);
 }
 
 extern "C" int sonde_tuner_ratio(uint32_t rate_in, uint32_t rate_out, int *up, int *down)
@@ -216,8 +203,6 @@ extern "C" void sonde_tuner_destroy(SondeTuner *t)
 {
 	if (!t) return;
 	(void)hipSetDevice(t->device);
-	(void)hipFree(t->d_taps); (void)hipFree(t->d_tapoff); (void)hipFree(t->d_T); (void)hipFree(t->d_th); (void)hipFree(t->d_tl);
-	(void)hipFree(t->d_hist[0]); (void)hipFree(t->d_hist[1]);
 	delete t;
 }
 
@@ -228,22 +213,11 @@ static int tn_check_offset(uint32_t fs, uint32_t b, int32_t f, const char *fn)
 	return 0;
 }
 
-// the object over n_slots idle slots and one tap set per listed bandwidth (ascending); H from the longest tap set (the narrowest bandwidth)
-static int tn_build(uint32_t rate_in, uint32_t rate_out, uint32_t up, uint32_t down, uint32_t n_slots, const std::map<uint32_t, uint32_t> &sets /* bandwidth -> T */,
-	size_t max_in, int input_kind, int device, const char *fn, SondeTuner **out)
+// Everything behind the argument checks: one tap set per listed bandwidth (ascending), the mixer tables and the zeroed history; on
+// failure tn_create destroys what has been built so far.
+static int tn_build(SondeTuner *t, const std::map<uint32_t, uint32_t> &sets /* bandwidth -> T */)
 {
-	uint32_t Tmax = 0;
-	for (auto &s : sets) Tmax = s.second > Tmax ? s.second : Tmax;
-	if (sets.size() > 255) return sd_fail((std::string(fn) + ": more than 255 distinct bandwidths").c_str());
-	if (max_in + Tmax >= (1u << 30) || (max_in / down) * up >= (1u << 30))
-		return sd_fail((std::string(fn) + ": max_in too large (window indices are 32-bit)").c_str());
-	int ndev = 0;
-	hipError_t e = hipGetDeviceCount(&ndev);
-	if (e != hipSuccess || device < 0 || device >= ndev) return sd_fail((std::string(fn) + ": no such HIP device (this library has no CPU path)").c_str(), e);
-	if ((e = hipSetDevice(device)) != hipSuccess) return sd_fail("hipSetDevice", e);
-	SondeTuner *t = new SondeTuner;
-	t->device = device; t->input_kind = input_kind; t->fs = rate_in; t->rate_out = rate_out; t->up = up; t->down = down;
-	t->n_vfos = n_slots; t->max_in = max_in; t->H = Tmax - 1;
+	const uint32_t rate_in = t->fs, up = t->up, n_slots = t->n_vfos;
 	// the tap sets, one per distinct bandwidth, back to back
 	const uint32_t n_sets = (uint32_t)sets.size();
 	std::vector<uint64_t> tapoff(n_sets);
@@ -259,30 +233,39 @@ static int tn_build(uint32_t rate_in, uint32_t rate_out, uint32_t up, uint32_t d
 	t->set.assign(n_slots, 0);
 	t->active.assign(n_slots, 0);
 	// the mixer tables (double on the host, stored as float): H[h] = exp(-2 pi i h 2^12 / Fs), D[l] = exp(-2 pi i l / Fs) - 1
-	const double PI = 3.14159265358979323846;
 	const uint32_t nh = (rate_in + (1u << TN_LOB) - 1) >> TN_LOB, nl = 1u << TN_LOB;
 	std::vector<float2> th(nh), tl(nl);
 	for (uint32_t h = 0; h < nh; h++) {
-		const double a = -2.0 * PI * (double)(((uint64_t)h << TN_LOB) % rate_in) / (double)rate_in;
+		const double a = -2.0 * SD_PI * (double)(((uint64_t)h << TN_LOB) % rate_in) / (double)rate_in;
 		th[h] = make_float2((float)cos(a), (float)sin(a));
 	}
 	for (uint32_t l = 0; l < nl; l++) {
-		const double a = -2.0 * PI * (double)l / (double)rate_in, s = sin(0.5 * a);
+		const double a = -2.0 * SD_PI * (double)l / (double)rate_in, s = sin(0.5 * a);
 		tl[l] = make_float2((float)(-2.0 * s * s), (float)sin(a));
 	}
-	const size_t hb = (size_t)t->H * sizeof(float2);
-	bool ok = hipMalloc((void **)&t->d_taps, total * sizeof(float)) == hipSuccess &&
-	          hipMalloc((void **)&t->d_tapoff, n_sets * sizeof(uint64_t)) == hipSuccess &&
-	          hipMalloc((void **)&t->d_T, n_sets * sizeof(uint32_t)) == hipSuccess &&
-	          hipMalloc((void **)&t->d_th, nh * sizeof(float2)) == hipSuccess && hipMalloc((void **)&t->d_tl, nl * sizeof(float2)) == hipSuccess &&
-	          hipMalloc((void **)&t->d_hist[0], hb) == hipSuccess && hipMalloc((void **)&t->d_hist[1], hb) == hipSuccess;
-	ok = ok && hipMemcpy(t->d_taps, g.data(), total * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(t->d_tapoff, tapoff.data(), n_sets * sizeof(uint64_t), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(t->d_T, T.data(), n_sets * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(t->d_th, th.data(), nh * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemcpy(t->d_tl, tl.data(), nl * sizeof(float2), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemset(t->d_hist[0], 0, hb) == hipSuccess && hipMemset(t->d_hist[1], 0, hb) == hipSuccess;
-	if (!ok) { sonde_tuner_destroy(t); return sd_fail((std::string(fn) + ": device allocation failed").c_str()); }
+	HIPCHK(t->d_taps.upload(g.data(), total));
+	HIPCHK(t->d_tapoff.upload(tapoff.data(), n_sets));
+	HIPCHK(t->d_T.upload(T.data(), n_sets));
+	HIPCHK(t->d_th.upload(th.data(), nh));
+	HIPCHK(t->d_tl.upload(tl.data(), nl));
+	HIPCHK(t->d_hist.zeros(t->H));
+	return 0;
+}
+
+// the object over n_slots idle slots; H from the longest tap set (the narrowest bandwidth)
+static int tn_create(uint32_t rate_in, uint32_t rate_out, uint32_t up, uint32_t down, uint32_t n_slots, const std::map<uint32_t, uint32_t> &sets /* bandwidth -> T */,
+	size_t max_in, int input_kind, int device, const char *fn, SondeTuner **out)
+{
+	uint32_t Tmax = 0;
+	for (auto &s : sets) Tmax = s.second > Tmax ? s.second : Tmax;
+	if (sets.size() > 255) return sd_fail((std::string(fn) + ": more than 255 distinct bandwidths").c_str());
+	if (max_in + Tmax >= (1u << 30) || (max_in / down) * up >= (1u << 30))
+		return sd_fail((std::string(fn) + ": max_in too large (window indices are 32-bit)").c_str());
+	if (sd_select_device(device, fn)) return -1;
+	SondeTuner *t = new SondeTuner;
+	t->device = device; t->input_kind = input_kind; t->fs = rate_in; t->rate_out = rate_out; t->up = up; t->down = down;
+	t->n_vfos = n_slots; t->max_in = max_in; t->H = Tmax - 1;
+	if (tn_build(t, sets)) { sonde_tuner_destroy(t); return -1; }       // (destroy leaves the error text alone)
 	*out = t;
 	return 0;
 }
@@ -290,7 +273,7 @@ static int tn_build(uint32_t rate_in, uint32_t rate_out, uint32_t up, uint32_t d
 static int tn_check_create(uint32_t rate_in, uint32_t rate_out, size_t max_in, int input_kind, uint32_t *up, uint32_t *down, const char *fn)
 {
 	if (tn_ratio(rate_in, rate_out, up, down, fn)) return -1;
-	if (input_kind != SONDE_INPUT_IQ && input_kind != SONDE_INPUT_IQ16 && input_kind != SONDE_INPUT_IQ8)
+	if (!sd_input_complex(input_kind))
 		return sd_fail((std::string(fn) + ": input_kind must be SONDE_INPUT_IQ, SONDE_INPUT_IQ16 or SONDE_INPUT_IQ8 (the tuner mixes complex samples)").c_str());
 	if (max_in < *down) return sd_fail((std::string(fn) + ": max_in must be at least the ratio's denominator").c_str());
 	return 0;
@@ -319,7 +302,7 @@ extern "C" int sonde_tuner_create(uint32_t rate_in, uint32_t rate_out, uint32_t 
 		if (tn_check_offset(rate_in, b, vfos[k].offset_hz, "sonde_tuner_create")) return -1;
 		sets[b] = tn_T(rate_in, b);
 	}
-	if (tn_build(rate_in, rate_out, up, down, n_vfos, sets, max_in, input_kind, device, "sonde_tuner_create", out)) return -1;
+	if (tn_create(rate_in, rate_out, up, down, n_vfos, sets, max_in, input_kind, device, "sonde_tuner_create", out)) return -1;
 	for (uint32_t k = 0; k < n_vfos; k++) tn_set(*out, k, vfos[k].offset_hz, vfos[k].bandwidth_hz ? vfos[k].bandwidth_hz : rate_out);
 	return 0;
 }
@@ -336,7 +319,7 @@ extern "C" int sonde_tuner_create_slots(uint32_t rate_in, uint32_t rate_out, uin
 		if (b < 5000u || b > rate_out) return sd_fail("sonde_tuner_create_slots: a bandwidth must be 5000 .. rate_out (0 = rate_out)");
 		sets[b] = tn_T(rate_in, b);
 	}
-	return tn_build(rate_in, rate_out, up, down, n_slots, sets, max_in, input_kind, device, "sonde_tuner_create_slots", out);
+	return tn_create(rate_in, rate_out, up, down, n_slots, sets, max_in, input_kind, device, "sonde_tuner_create_slots", out);
 }
 
 extern "C" int sonde_tuner_slot_set(SondeTuner *t, uint32_t slot, int32_t offset_hz, uint32_t bandwidth_hz)
@@ -404,11 +387,10 @@ extern "C" int sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n
 	if (out_stride < n_out) return sd_fail("sonde_tuner_process: out_stride shorter than the row");
 	if ((uintptr_t)wide_dev % sd_sample_bytes(t->input_kind)) return sd_fail("sonde_tuner_process: the block is not aligned to the sample size");
 	if ((uintptr_t)out_dev & 7u) return sd_fail("sonde_tuner_process: out must be 8-byte aligned");
-	hipError_t e = hipSetDevice(t->device);
-	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	HIPCHK(hipSetDevice(t->device));
 	hipStream_t s = (hipStream_t)stream;
-	const float2 *h_in = t->d_hist[t->parity & 1];
-	float2 *h_out = t->d_hist[(t->parity + 1) & 1];
+	const float2 *h_in = t->d_hist.in();
+	float2 *h_out = t->d_hist.out();
 	sd_input_dispatch(t->input_kind, [&](auto kk) {
 		constexpr int K = decltype(kk)::value;
 		if constexpr (K != SONDE_INPUT_REAL) {
@@ -445,8 +427,8 @@ extern "C" int sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n
 			hipLaunchKernelGGL(sd_tuner_hist_kernel<K>, dim3((t->H + TN_WG - 1) / TN_WG), dim3(TN_WG), 0, s, x, h_in, h_out, t->H, (uint32_t)n_in);
 		}
 	});
-	if ((e = hipGetLastError()) != hipSuccess) return sd_fail("sd_tuner_kernel launch", e);
-	t->parity++;
+	HIPCHK_IN("sonde_tuner_process", hipGetLastError());
+	t->d_hist.flip();
 	t->n_base += (int64_t)n_in;
 	return 0;
 }

@@ -14,11 +14,12 @@
 // race with the first chunk's read.  HBM traffic: 8 B in + (up/down) * 4 B out per input sample, read once.
 // Bit-exact against oracle/or_chan.c or_vfo_process.
 #include <hip/hip_runtime.h>
-#include <math.h>
-#include <string>
 #include <vector>
 #include "sd_math.h"
 #include "launch.h"
+#include "sd_host.h"
+#include "sd_devmem.h"
+#include "sd_design.h"
 #include "../../include/sonde_abi.h"
 
 #define VF_T      16          // taps per phase
@@ -76,16 +77,15 @@ __global__ __launch_bounds__(256) void sd_vfo_kernel(const float2 *__restrict__ 
 }
 
 // ---------------------------------------------------------------- host object
-struct SondeVfo {
+struct __attribute__((visibility("hidden"))) SondeVfo {      // (hidden: its implicit destructor stays out of the exported names)
 	int device = 0;
 	uint32_t n_channels = 0;
 	int rate_in = 0, up = 0, down = 0;
 	size_t max_in = 0;
-	float *d_g = nullptr;
-	SdVfoState *d_state[2] = {};
-	unsigned parity = 0;
-	float2 *d_stage = nullptr;      // sonde_vfo_process_host: staged input and the output rows
-	float *d_out = nullptr;
+	DevBuf<float> d_g;
+	DevPair<SdVfoState> d_state;
+	DevBuf<float2> d_stage;         // sonde_vfo_process_host: staged input and the output rows
+	DevBuf<float> d_out;
 };
 
 static int vfo_ratio(int rate_in, int *up, int *down, double *cutoff_hz)
@@ -102,23 +102,8 @@ static int vfo_ratio(int rate_in, int *up, int *down, double *cutoff_hz)
 
 static void vfo_taps(int up, double fs_up, double cutoff_hz, std::vector<float> &g)
 {
-	const double PI = 3.14159265358979323846;
-	const int N = up * VF_T;
-	const double fc = cutoff_hz / fs_up;
-	std::vector<double> tmp(N);
-	for (int i = 0; i < N; i++) {
-		const double t = (double)i - 0.5 * (double)(N - 1);
-		const double x = (double)i / (double)(N - 1);
-		const double w = 0.42 - 0.5 * cos(2.0 * PI * x) + 0.08 * cos(4.0 * PI * x);
-		const double s = (t == 0.0) ? 2.0 * fc : sin(2.0 * PI * fc * t) / (PI * t);
-		tmp[i] = s * w;
-	}
-	g.resize(N);
-	for (int p = 0; p < up; p++) {
-		double sum = 0.0;
-		for (int t = 0; t < VF_T; t++) sum += tmp[t * up + p];
-		for (int t = 0; t < VF_T; t++) g[p * VF_T + t] = (float)(tmp[t * up + p] / sum);
-	}
+	g.resize((size_t)up * VF_T);
+	sd_design_rows(sd_design_prototype(g.size(), cutoff_hz / fs_up), up, VF_T, g.data());
 }
 
 extern "C" int sonde_vfo_ratio(int rate_in, int *up, int *down)
@@ -146,8 +131,17 @@ extern "C" void sonde_vfo_destroy(SondeVfo *v)
 {
 	if (!v) return;
 	(void)hipSetDevice(v->device);
-	(void)hipFree(v->d_g); (void)hipFree(v->d_state[0]); (void)hipFree(v->d_state[1]); (void)hipFree(v->d_stage); (void)hipFree(v->d_out);
 	delete v;
+}
+
+// Everything behind the argument checks; on failure sonde_vfo_create destroys what has been built so far.
+static int vfo_build(SondeVfo *v, double cutoff_hz)
+{
+	std::vector<float> g;
+	vfo_taps(v->up, (double)v->rate_in * v->up, cutoff_hz, g);
+	HIPCHK(v->d_g.upload(g.data(), g.size()));
+	HIPCHK(v->d_state.zeros(v->n_channels));
+	return 0;
 }
 
 extern "C" int sonde_vfo_create(uint32_t n_channels, int rate_in, size_t max_in, int device, SondeVfo **out)
@@ -157,21 +151,10 @@ extern "C" int sonde_vfo_create(uint32_t n_channels, int rate_in, size_t max_in,
 	double fc;
 	if (vfo_ratio(rate_in, &up, &down, &fc)) return sd_fail("sonde_vfo_create: rate_in must be 10000, 15000, 20000, 40000 or 50000");
 	if (max_in % (size_t)down) return sd_fail("sonde_vfo_create: max_in must be a multiple of the ratio's denominator (5; 25 at 50 kS/s)");
-	int ndev = 0;
-	hipError_t e = hipGetDeviceCount(&ndev);
-	if (e != hipSuccess || device < 0 || device >= ndev) return sd_fail("sonde_vfo_create: no such HIP device (this library has no CPU path)", e);
-	if ((e = hipSetDevice(device)) != hipSuccess) return sd_fail("hipSetDevice", e);
+	if (sd_select_device(device, "sonde_vfo_create")) return -1;
 	SondeVfo *v = new SondeVfo;
 	v->device = device; v->n_channels = n_channels; v->rate_in = rate_in; v->up = up; v->down = down; v->max_in = max_in;
-	std::vector<float> g;
-	vfo_taps(up, (double)rate_in * up, fc, g);
-	bool ok = hipMalloc((void **)&v->d_g, g.size() * sizeof(float)) == hipSuccess &&
-	          hipMalloc((void **)&v->d_state[0], n_channels * sizeof(SdVfoState)) == hipSuccess &&
-	          hipMalloc((void **)&v->d_state[1], n_channels * sizeof(SdVfoState)) == hipSuccess;
-	ok = ok && hipMemcpy(v->d_g, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-	     hipMemset(v->d_state[0], 0, n_channels * sizeof(SdVfoState)) == hipSuccess &&
-	     hipMemset(v->d_state[1], 0, n_channels * sizeof(SdVfoState)) == hipSuccess;
-	if (!ok) { sonde_vfo_destroy(v); return sd_fail("sonde_vfo_create: device allocation failed"); }
+	if (vfo_build(v, fc)) { sonde_vfo_destroy(v); return -1; }       // (destroy leaves the error text alone)
 	*out = v;
 	return 0;
 }
@@ -184,13 +167,12 @@ extern "C" int sonde_vfo_process(SondeVfo *v, const void *iq_dev, size_t n_in, s
 	if (!n_in || n_in > v->max_in || n_in % (size_t)v->down) return sd_fail("sonde_vfo_process: n_in must be a multiple of the ratio's denominator and <= max_in");
 	if (channel_stride < n_in || out_stride < sonde_vfo_out_samples(v, n_in)) return sd_fail("sonde_vfo_process: stride shorter than the row");
 	if ((uintptr_t)iq_dev & 7u) return sd_fail("sonde_vfo_process: iq must be 8-byte aligned");
-	hipError_t e = hipSetDevice(v->device);
-	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	HIPCHK(hipSetDevice(v->device));
 	const dim3 grid((unsigned)((n_in + VF_CHUNK - 1) / VF_CHUNK), v->n_channels);
 	hipLaunchKernelGGL(sd_vfo_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float2 *)iq_dev, channel_stride, (uint32_t)n_in, v->up, v->down,
-		v->d_g, v->d_state[v->parity & 1], v->d_state[(v->parity + 1) & 1], out48_dev, out_stride);
-	if ((e = hipGetLastError()) != hipSuccess) return sd_fail("sd_vfo_kernel launch", e);
-	v->parity++;
+		v->d_g, v->d_state.in(), v->d_state.out(), out48_dev, out_stride);
+	HIPCHK_IN("sonde_vfo_process", hipGetLastError());
+	v->d_state.flip();
 	return 0;
 }
 
@@ -199,16 +181,14 @@ extern "C" int sonde_vfo_process(SondeVfo *v, const void *iq_dev, size_t n_in, s
 extern "C" int sonde_vfo_process_host(SondeVfo *v, const void *iq_host, size_t n_in, size_t channel_stride, const float **out48_dev, size_t *out_stride)
 {
 	if (!v || !iq_host || !out48_dev) return sd_fail("sonde_vfo_process_host: null argument");
-	hipError_t e = hipSetDevice(v->device);
-	if (e != hipSuccess) return sd_fail("hipSetDevice", e);
+	HIPCHK(hipSetDevice(v->device));
 	const size_t n_out_max = sonde_vfo_out_samples(v, v->max_in);
-	if (!v->d_stage) {
-		if ((e = hipMalloc((void **)&v->d_stage, (size_t)v->n_channels * v->max_in * sizeof(float2))) != hipSuccess ||
-		    (e = hipMalloc((void **)&v->d_out, (size_t)v->n_channels * n_out_max * sizeof(float))) != hipSuccess)
-			return sd_fail("sonde_vfo_process_host: device allocation failed", e);
+	if (!v->d_out) {
+		HIPCHK(v->d_stage.alloc((size_t)v->n_channels * v->max_in));
+		HIPCHK(v->d_out.alloc((size_t)v->n_channels * n_out_max));
 	}
 	if (!n_in || n_in > v->max_in || channel_stride < n_in) return sd_fail("sonde_vfo_process_host: bad n_in / stride");
-	e = hipMemcpy2DAsync(v->d_stage, v->max_in * sizeof(float2), iq_host, channel_stride * sizeof(float2), n_in * sizeof(float2), v->n_channels,
+	const hipError_t e = hipMemcpy2DAsync(v->d_stage, v->max_in * sizeof(float2), iq_host, channel_stride * sizeof(float2), n_in * sizeof(float2), v->n_channels,
 		hipMemcpyHostToDevice, nullptr);
 	if (e != hipSuccess) return sd_fail("sonde_vfo_process_host: upload", e);
 	if (sonde_vfo_process(v, v->d_stage, n_in, v->max_in, v->d_out, n_out_max, nullptr)) return -1;

@@ -233,6 +233,8 @@ def test_refusals():
     assert L.sonde_detect_create(4, 3000, 0, None, 0, C.byref(h)) < 0
     assert L.sonde_detect_create(0, 4096, 0, None, 0, C.byref(h)) < 0
     assert L.sonde_detect_create(4, 4096, 0, None, 0, None) < 0
+    with pytest.raises(SondeError, match="sonde_detect_create: no such HIP device"):
+        SondeDetector(4, 4096, device=torch.cuda.device_count())
     det = SondeDetector(4, 4096)
     x = torch.zeros((4, 8192, 2), device=DEV)
     p = C.c_void_p(x.data_ptr())

@@ -126,7 +126,7 @@ def test_refusals():
             SondeScanner(10_000_000, 1000, fft_size=n)
     with pytest.raises(SondeError, match="max_in"):
         SondeScanner(10_000_000, 0)
-    with pytest.raises(SondeError, match="device"):
+    with pytest.raises(SondeError, match="sonde_scan_create: no such HIP device"):
         SondeScanner(10_000_000, 1000, device=torch.cuda.device_count())
     sc = SondeScanner(10_000_000, 5000, fft_size=4096)
     blk = torch.zeros((5000, 2), device=DEV)

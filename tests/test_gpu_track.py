@@ -144,6 +144,8 @@ def test_refusals(rows):
         SondeTracker(3, 48_000, 1000)
     with pytest.raises(SondeError, match="rate"):
         SondeTracker(3, 1000, 2048)
+    with pytest.raises(SondeError, match="sonde_track_create: no such HIP device"):
+        SondeTracker(3, 48_000, 2048, device=torch.cuda.device_count())
     tr = SondeTracker(3, 48_000, 2048)
     with pytest.raises(SondeError, match="multiple of 256"):
         tr.submit(rows[:, :1000])

@@ -155,6 +155,8 @@ def test_refusals():
         SondeTuner(10_000_000, 10_000, [(0, 20_000)], 12500)
     with pytest.raises(SondeError, match="inside the band"):
         SondeTuner(10_000_000, 48_000, [(4_980_001, 40_000)], 12500)
+    with pytest.raises(SondeError, match="sonde_tuner_create: no such HIP device"):
+        SondeTuner(10_000_000, 48_000, [0], 12500, device=torch.cuda.device_count())
     tu = SondeTuner(10_000_000, 48_000, [0], 6250)
     blk = torch.zeros((6250, 2), device=DEV)
     with pytest.raises(SondeError, match="multiple"):
