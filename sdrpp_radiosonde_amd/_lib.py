@@ -101,7 +101,13 @@ FLAG_JOIN = 16           # accepted and ignored: joining at every submit is the 
 FLAG_LATE_JOIN = 32      # launch units joined into the caller's stream ONE SUBMIT LATE (SONDE_FLAG_LATE_JOIN; opt-in: round 5's default)
 FLAG_WIDE_AUTO = 8       # SONDE_FLAG_WIDE for the types whose reference channel is >= 20 kHz only (iMS-100, MRZ-N1, M10)
 FLAG_RS41_RESCUE = 64    # RS41: second pass over frames whose RS stage failed, block CRCs as erasure hints (SONDE_FLAG_RS41_RESCUE; opt-in)
-FRAME_RESCUED = 2        # SondeFrame.flags bit of a frame that pass filled in (SONDE_FRAME_RESCUED)
+FRAME_RESCUED = 2        # SondeFrame.flags bit of a frame a second pass completed (SONDE_FRAME_RESCUED)
+FLAG_MANCHESTER_RESCUE = 128   # M10 / M20 / MRZ-N1: second pass over frames whose check failed, Manchester violations as hints (SONDE_FLAG_MANCHESTER_RESCUE; opt-in)
+
+
+def frame_flips(flags):
+    """data bits SONDE_FLAG_MANCHESTER_RESCUE flipped in a rescued frame (SONDE_FRAME_FLIPS); an int or a numpy array of SondeFrame.flags"""
+    return (flags >> 8) & 0xF
 
 
 # every symbol include/sonde_abi.h declares; tests check the .so exports all of them
@@ -128,7 +134,7 @@ ABI_SYMBOLS = [
     "sonde_scan_spectrum", "sonde_scan_candidates", "sonde_scan_search", "sonde_scan_window", "sonde_scan_auto_fft_size",
     "sonde_tuner_create_slots", "sonde_tuner_slot_set", "sonde_tuner_slot_clear", "sonde_tuner_slot_active",
     "sonde_batch_restart_channels", "sonde_detect_restart_channels", "sonde_live_match",
-    "sonde_batch_test_rs255_erasures", "sonde_batch_rescue_info",
+    "sonde_batch_test_rs255_erasures", "sonde_batch_rescue_info", "sonde_batch_manchester_rescue_info",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -186,6 +192,8 @@ def load() -> C.CDLL:
     if hasattr(L, "sonde_batch_rescue_info"):             # absent only in older A/B builds loaded through SONDE_MI355_LIB
         L.sonde_batch_test_rs255_erasures.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp]
         L.sonde_batch_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(SondeRs41Layout), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "sonde_batch_manchester_rescue_info"):  # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        L.sonde_batch_manchester_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.sonde_get_taps.argtypes = [C.c_int, vp]
     L.sonde_parse_frame.argtypes = [vp, C.POINTER(SondeData), C.c_int]
     L.sonde_batch_poll.argtypes = [vp, C.POINTER(SondeData), C.POINTER(C.c_uint32), C.c_size_t]

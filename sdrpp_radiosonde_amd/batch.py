@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
+from ._lib import FLAG_MANCHESTER_RESCUE, FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
 
 
 class SondeError(RuntimeError):
@@ -176,6 +176,13 @@ class SondeBatch:
         self._chk(self.L.sonde_batch_rescue_info(self.h, channel, lay, C.byref(tried), C.byref(rescued)))
         layouts = {flen: [(int(l.offset[i]), int(l.type[i]), int(l.len[i])) for i in range(l.n_blocks)] for flen, l in ((320, lay[0]), (518, lay[1]))}
         return {"layouts": layouts, "tried": int(tried.value), "rescued": int(rescued.value)}
+
+    def manchester_rescue_info(self, channel: int) -> dict:
+        """FLAG_MANCHESTER_RESCUE: what the second pass has done on an M10 / M20 / MRZ-N1 channel (sonde_batch_manchester_rescue_info):
+        {'tried': frames whose check failed that reached the solver, 'rescued': frames it corrected}."""
+        tried, rescued = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.sonde_batch_manchester_rescue_info(self.h, channel, C.byref(tried), C.byref(rescued)))
+        return {"tried": int(tried.value), "rescued": int(rescued.value)}
 
     def test_rs255_erasures(self, cw_pairs: np.ndarray, erased: np.ndarray, n: int):
         """The errors-and-erasures RS(255,231) corrector alone (sonde_batch_test_rs255_erasures): cw_pairs, erased [P, 2, 256] uint8

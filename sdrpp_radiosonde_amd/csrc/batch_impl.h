@@ -10,6 +10,7 @@
 #include "launch.h"
 #include "parse.h"
 #include "sd_chanlist.h"
+#include "sd_devmem.h"
 #include "sd_host.h"
 #include "sd_tables.h"
 
@@ -152,4 +153,9 @@ struct SondeBatch {
 	// SONDE_FLAG_RS41_RESCUE (SPEC 3.3c): per-channel layouts and counters of the second pass (rescue_kernel.hip); null: the flag is
 	// off or the batch has no RS41 channel, and nothing of it is allocated or launched
 	SdRescueState *d_rescue = nullptr;
+	// SONDE_FLAG_MANCHESTER_RESCUE (SPEC 3.3f): per-channel counters of the second pass over M10 / M20 / MRZ-N1 records
+	// (check_rescue_kernel.hip) and MRZ-N1's column table; null: the flag is off or the batch has no such channel, and nothing of it
+	// is allocated or launched
+	DevBuf<SdManchesterState> d_mrescue;
+	DevBuf<uint16_t> d_mrztab;
 };

@@ -56,6 +56,19 @@ extern "C" int sonde_batch_rescue_info(SondeBatch *b, uint32_t channel, SondeRs4
 	return 0;
 }
 
+extern "C" int sonde_batch_manchester_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued)
+{
+	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_manchester_rescue_info: bad argument");
+	if (!b->d_mrescue) return sd_fail("sonde_batch_manchester_rescue_info: the batch was created without SONDE_FLAG_MANCHESTER_RESCUE (or has no M10 / M20 / MRZ-N1 channel)");
+	if (b->types[channel] != SONDE_M10 && b->types[channel] != SONDE_MRZN1) return sd_fail("sonde_batch_manchester_rescue_info: not an M10 / M20 / MRZ-N1 channel");
+	if (sonde_batch_sync(b) < 0) return -1;
+	SdManchesterState st;
+	HIPCHK(hipMemcpy(&st, b->d_mrescue + channel, sizeof(st), hipMemcpyDeviceToHost));
+	if (tried) *tried = st.tried;
+	if (rescued) *rescued = st.rescued;
+	return 0;
+}
+
 // wait for the last submit and fetch the channel's demodulator state
 static int fetch_state(SondeBatch *b, uint32_t channel, SdChanState *st)
 {

@@ -1,0 +1,200 @@
+// check_rescue_kernel.hip -- SONDE_FLAG_MANCHESTER_RESCUE (DESIGN SPEC 3.3f): the second pass over the M10 / M20 and MRZ-N1 frame
+// records of a submit.  These frames carry a 16-bit check and no FEC, but every data bit is a Manchester chip pair (a, !a): a pair
+// with two equal chips marks a bit that may be wrong.  A frame whose check fails with 1..8 such pairs is a linear system over GF(2)
+// -- 16 equations (the syndrome), one unknown per marked bit, the column of a bit being the change of the syndrome when it flips --
+// and is rescued iff exactly one subset of the marked bits explains the syndrome.
+//   one 64-lane wave per channel, four waves per workgroup; lanes load the headers of 64 records at once and the wave works on
+//   the candidates among them one by one: lane i reads 32 chips of the frame from the channel's bit ring (16 pairs), the marked
+//   bits are gathered into lanes 0..7, and the <= 255 subsets are tried across the wave, four per lane.  No LDS.
+// Runs behind whatever wrote the records, on the same stream, and rewrites them in place.  The records of a channel are
+// independent of each other (only the two counters are shared), so the result does not depend on the cut into submits.
+// Vector stores only.
+#include <hip/hip_runtime.h>
+#include "sonde_dev.h"
+#include "launch.h"
+
+#define MQ_WAVES 4
+#define MQ_MAX_HINTS 8         // SPEC 3.3f: at most this many marked bits (255 subsets)
+
+// CRC16 (reflected 0xA001) of the 43 zero bytes from 0xFFFF: the constant part of MRZ-N1's affine check
+static constexpr uint32_t mq_mrz_crc_of_zeros()
+{
+	uint32_t crc = 0xFFFFu;
+	for (int i = 0; i < 43 * 8; i++) crc = (crc & 1u) ? ((crc >> 1) ^ 0xA001u) : (crc >> 1);
+	return crc;
+}
+
+// the frame byte i of a record of n_cov covered bytes followed by the two stored check bytes: the eight columns of its bits (bit j
+// of the byte = LSB index j) as four dwords of two 16-bit columns each, like a row of m10tab.  hi_first: the stored check is big-endian.
+__device__ __forceinline__ uint4 mq_row(const uint16_t *__restrict__ tab, int n_cov, bool hi_first, int i)
+{
+	if (i < n_cov) return *reinterpret_cast<const uint4 *>(tab + 8 * (n_cov - 1 - i));
+	// a bit of the stored check flips that bit of the syndrome
+	const uint32_t sh = ((i == n_cov) == hi_first) ? 8u : 0u;
+	return make_uint4(0x00020001u << sh, 0x00080004u << sh, 0x00200010u << sh, 0x00800040u << sh);
+}
+__device__ __forceinline__ uint32_t mq_col(const uint4 row, int j)
+{
+	const uint32_t w = (j >> 1) == 0 ? row.x : ((j >> 1) == 1 ? row.y : ((j >> 1) == 2 ? row.z : row.w));
+	return (w >> (16 * (j & 1))) & 0xFFFFu;
+}
+// XOR of the columns of the bits set in byte b
+__device__ __forceinline__ uint32_t mq_byte_syndrome(const uint4 row, uint32_t b)
+{
+	uint32_t s = 0;
+#pragma unroll
+	for (int j = 0; j < 8; j++) if ((b >> j) & 1u) s ^= mq_col(row, j);
+	return s;
+}
+
+__global__ __launch_bounds__(64 * MQ_WAVES) void sd_manchester_rescue_kernel(
+	const uint16_t *__restrict__ m10tab /* [99][8] */, const uint16_t *__restrict__ mrztab /* [43][8] */,
+	const SdChanState *__restrict__ chan_states, const uint32_t *__restrict__ bitring, uint32_t ring_words,
+	SondeFrame *__restrict__ frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
+	const uint32_t *__restrict__ chlist, uint32_t n_list, SdManchesterState *__restrict__ states)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t li_ch = MQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
+	if (li_ch >= n_list) return;
+	const uint32_t ch = chlist[li_ch];
+	const uint32_t nfr = min(counts[ch], max_frames);
+	if (nfr == 0) return;
+	const uint64_t wpos = chan_states[ch].wpos;
+	const uint32_t *ring = bitring + (size_t)ch * ring_words;
+	const uint32_t mask = ring_words - 1;
+	SondeFrame *const chfr = frames + (size_t)ch * max_frames;
+	uint32_t tried = 0, rescued = 0;
+
+	for (uint32_t base = 0; base < nfr; base += 64) {
+		// the headers of records base .. base + 63, one per lane
+		int h_len = 0;
+		uint32_t h_type = 0, h_p_lo = 0, h_p_hi = 0;
+		bool cand = false;
+		if (base + (uint32_t)lane < nfr) {
+			const SondeFrame *f = chfr + base + lane;
+			h_type = f->type; h_len = f->len;
+			h_p_lo = (uint32_t)f->bitpos; h_p_hi = (uint32_t)(f->bitpos >> 32);
+			const bool known = (h_type == SONDE_M10 && (h_len == 101 || h_len == 70)) || (h_type == SONDE_MRZN1 && h_len == 45);
+			// nerr[1] is |V| (sd_fixed.h counts the same pairs): 0 or more than 8 of them never reach the solver
+			cand = known && f->nerr[0] == -1 && f->nerr[1] >= 1 && f->nerr[1] <= MQ_MAX_HINTS;
+		}
+		for (unsigned long long cm = __ballot(cand); cm; cm &= cm - 1ull) {
+			const int q = __builtin_ctzll(cm);
+			SondeFrame *fr = chfr + base + q;
+			const int len = __builtin_amdgcn_readlane(h_len, q);
+			const bool mrz = (uint32_t)__builtin_amdgcn_readlane((int)h_type, q) == SONDE_MRZN1;
+			const uint64_t p = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)h_p_lo, q) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)h_p_hi, q) << 32);
+			const int nbits = 8 * len;
+			const uint64_t c0 = p + (mrz ? 48u : 32u);              // the first data chip
+			// 2. the frame's chips must still be in the ring (always so for a record of this submit: DESIGN 3.3f)
+			if (wpos < c0 + 2ull * (uint64_t)nbits || wpos - p > 32ull * ring_words) continue;
+
+			// 1. V: lane i looks at the 16 pairs of frame bits 16 i .. 16 i + 15
+			uint32_t vm = 0;
+			if (16 * lane < nbits) {
+				const uint64_t cp = c0 + 32ull * (uint64_t)lane;
+				const uint32_t w = (uint32_t)(cp >> 5), sh = (uint32_t)cp & 31u;
+				const uint32_t r0 = ring[w & mask], r1 = ring[(w + 1) & mask];
+				const uint32_t x = (uint32_t)((((uint64_t)r1 << 32) | r0) >> sh);
+				uint32_t v = ~(x ^ (x >> 1)) & 0x55555555u;         // even positions: the pair's two chips are equal
+				v = (v | (v >> 1)) & 0x33333333u;
+				v = (v | (v >> 2)) & 0x0F0F0F0Fu;
+				v = (v | (v >> 4)) & 0x00FF00FFu;
+				v = (v | (v >> 8)) & 0x0000FFFFu;                   // bit q: pair q
+				const int left = nbits - 16 * lane;
+				vm = left >= 16 ? v : (v & ((1u << left) - 1u));
+			}
+			int nv = __popc(vm);
+#pragma unroll
+			for (int off = 32; off > 0; off >>= 1) nv += __shfl_xor(nv, off, 64);
+			if (nv == 0 || nv > MQ_MAX_HINTS) continue;
+			if (!mrz && (__builtin_amdgcn_readfirstlane((int)vm) & 0xFF)) continue;     // M10 / M20: the length byte decides the layout
+
+			// the marked bits, ascending, into lanes 0 .. nv - 1
+			int myk = 0, n = 0;
+			for (unsigned long long lm = __ballot(vm != 0u); lm; lm &= lm - 1ull) {
+				const int l = __builtin_ctzll(lm);
+				for (uint32_t bm = (uint32_t)__builtin_amdgcn_readlane((int)vm, l); bm; bm &= bm - 1u) {
+					if (lane == n) myk = 16 * l + __builtin_ctz(bm);
+					n++;
+				}
+			}
+
+			// 3. syndrome of the frame as recorded (bytes lane and lane + 64) and the column of this lane's marked bit
+			const uint16_t *tab = mrz ? mrztab : m10tab;
+			const int n_cov = len - 2;
+			const bool hi_first = !mrz;
+			uint32_t s = 0;
+#pragma unroll
+			for (int r = 0; r < 2; r++) {
+				const int i = lane + 64 * r;
+				if (i < len) s ^= mq_byte_syndrome(mq_row(tab, n_cov, hi_first, i), fr->data[i]);
+			}
+#pragma unroll
+			for (int off = 32; off > 0; off >>= 1) s ^= (uint32_t)__shfl_xor((int)s, off, 64);
+			if (mrz) s ^= mq_mrz_crc_of_zeros();
+			uint32_t col = 0;
+			if (lane < nv) col = mq_col(mq_row(tab, n_cov, hi_first, myk >> 3), 7 - (myk & 7));
+			tried++;
+
+			// 4. the subsets m = 1 .. 2^nv - 1 of the marked bits (bit j of m: lane j's), four per lane
+			uint32_t c[MQ_MAX_HINTS];
+#pragma unroll
+			for (int j = 0; j < MQ_MAX_HINTS; j++) c[j] = (uint32_t)__builtin_amdgcn_readlane((int)col, j);
+			int nhit = 0;
+			uint32_t U = 0;
+#pragma unroll
+			for (int it = 0; it < 4; it++) {
+				const uint32_t m = (uint32_t)(64 * it + lane);
+				uint32_t x = 0;
+#pragma unroll
+				for (int j = 0; j < MQ_MAX_HINTS; j++) if ((m >> j) & 1u) x ^= c[j];
+				const unsigned long long hm = __ballot(m != 0u && m < (1u << nv) && x == s);
+				nhit += __popcll(hm);
+				if (hm) U = (uint32_t)(64 * it + __builtin_ctzll(hm));
+			}
+			if (nhit != 1) continue;                                // none, or several: the frame stays
+
+			// 5. the record: every lane flips what falls into its two bytes
+#pragma unroll
+			for (int r = 0; r < 2; r++) {
+				const int i = lane + 64 * r;
+				uint32_t fm = 0;
+#pragma unroll
+				for (int j = 0; j < MQ_MAX_HINTS; j++) {
+					const int kj = __builtin_amdgcn_readlane(myk, j);
+					if (((U >> j) & 1u) && (kj >> 3) == i) fm ^= 0x80u >> (kj & 7);
+				}
+				if (fm) fr->data[i] = (uint8_t)(fr->data[i] ^ fm);
+			}
+			if (lane == 0) {
+				fr->nerr[0] = 0;
+				fr->flags |= SONDE_FRAME_RESCUED | ((uint32_t)__popc(U) << 8);
+			}
+			rescued++;
+		}
+	}
+	if (tried && lane == 0) {
+		states[ch].tried += tried;
+		states[ch].rescued += rescued;
+	}
+}
+
+void sd_launch_rescue_manchester(uint32_t n_list, hipStream_t stream, const uint16_t *m10tab, const uint16_t *mrztab, const SdChanState *chan_states,
+	const uint32_t *bitring, uint32_t ring_words, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist,
+	SdManchesterState *states)
+{
+	hipLaunchKernelGGL(sd_manchester_rescue_kernel, dim3((n_list + MQ_WAVES - 1) / MQ_WAVES), dim3(64 * MQ_WAVES), 0, stream,
+		m10tab, mrztab, chan_states, bitring, ring_words, frames, counts, max_frames, chlist, n_list, states);
+}
+
+// ---- the listed channels back to counters zero (sonde_batch_restart_channels)
+__global__ __launch_bounds__(64) void sd_manchester_clear_kernel(const uint32_t *__restrict__ list, uint32_t n, SdManchesterState *__restrict__ states)
+{
+	const uint32_t i = 64 * blockIdx.x + threadIdx.x;
+	if (i < n) { states[list[i]].tried = 0u; states[list[i]].rescued = 0u; }
+}
+void sd_launch_manchester_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdManchesterState *states)
+{
+	hipLaunchKernelGGL(sd_manchester_clear_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, list, n, states);
+}

@@ -95,5 +95,13 @@ void sd_launch_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list
 void sd_launch_rsee_unit(uint8_t *cw_io, const uint8_t *erased, uint32_t n_pairs, int n, int32_t *status, const uint8_t *gf_exp, const uint8_t *gf_log,
 	const uint32_t *gf_swar, hipStream_t stream);
 
+// SONDE_FLAG_MANCHESTER_RESCUE (check_rescue_kernel.hip, DESIGN SPEC 3.3f): per M10 / M20 / MRZ-N1 channel two counters (frames whose check
+// failed that reached the solver; frames rescued), carried from submit to submit.  chlist: never null.
+struct SdManchesterState { uint32_t tried, rescued; };
+void sd_launch_rescue_manchester(uint32_t n_list, hipStream_t stream, const uint16_t *m10tab, const uint16_t *mrztab, const SdChanState *chan_states,
+	const uint32_t *bitring, uint32_t ring_words, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist,
+	SdManchesterState *states);
+void sd_launch_manchester_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdManchesterState *states);
+
 // sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);

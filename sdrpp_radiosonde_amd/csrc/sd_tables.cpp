@@ -173,6 +173,19 @@ void fec_m10_table(uint16_t tab[99 * 8])
 	}
 }
 
+void fec_mrz_table(uint16_t tab[43 * 8])
+{
+	auto step = [](unsigned c, unsigned b) {
+		c ^= b;
+		for (int k = 0; k < 8; k++) c = (c & 1u) ? ((c >> 1) ^ 0xA001u) : (c >> 1);
+		return c;
+	};
+	for (int j = 0; j < 8; j++) {
+		unsigned c = step(0, 1u << j);
+		for (int k = 0; k < 43; k++) { tab[8 * k + j] = (uint16_t)c; c = step(c, 0); }
+	}
+}
+
 // ---------------------------------------------------------------- row layout
 extern "C" size_t sonde_sample_bytes(int input_kind)
 {

@@ -40,4 +40,7 @@ void fec_gf256_swar(uint32_t sw[24 * 8]);
 void fec_gf64_tables(uint8_t g64[192]);
 // M10 checksum: c' = f(c, b) is GF(2)-linear, c' = A c + B b; row k holds A^k B e_j for the eight unit bytes e_j (sd_fixed.h)
 void fec_m10_table(uint16_t tab[99 * 8]);
+// MRZ-N1 CRC16 (reflected 0xA001) as a GF(2) matrix, laid out like the M10 table: row k holds the CRC, run from 0, of the unit byte e_j
+// followed by k zero bytes (check_rescue_kernel.hip: the column of a frame bit, SPEC 3.3f)
+void fec_mrz_table(uint16_t tab[43 * 8]);
 #pragma GCC visibility pop
