@@ -103,8 +103,10 @@ enum { SONDE_INPUT_IQ = 0,      /* complex64 interleaved I,Q at 48 kS/s (vfo->ou
                                  * xGMI and HBM.  Batch / node API, all seven sonde types. */
 
 #define SONDE_FRAME_RESCUED 2u   /* SondeFrame.flags: a frame a second pass completed -- an RS41 frame SONDE_FLAG_RS41_RESCUE filled in, or an
-                                  * M10 / M20 / MRZ-N1 frame SONDE_FLAG_MANCHESTER_RESCUE corrected (then SONDE_FRAME_FLIPS says how many bits) */
+                                  * M10 / M20 / MRZ-N1 frame SONDE_FLAG_MANCHESTER_RESCUE corrected (then SONDE_FRAME_FLIPS says how many bits), or
+                                  * a DFM frame SONDE_FLAG_DFM_RESCUE completed (then SONDE_FRAME_WORDS says how many codewords) */
 #define SONDE_FRAME_FLIPS(f) (((f) >> 8) & 0xFu)   /* SondeFrame.flags bits 8..11: data bits SONDE_FLAG_MANCHESTER_RESCUE flipped (0..8) */
+#define SONDE_FRAME_WORDS(f) (((f) >> 8) & 0xFu)   /* the same bits for DFM: codewords SONDE_FLAG_DFM_RESCUE decoded with erasures (1..8) */
 #define SONDE_TILE       2048   /* samples; submit lengths are multiples of this */
 #define SONDE_FRAME_MAX  528
 
@@ -113,7 +115,7 @@ typedef struct {
 	uint32_t type;
 	int32_t  len;            /* bytes valid in data[] */
 	int32_t  nerr[2];        /* RS41: bytes corrected per RS codeword, -1 = uncorrectable */
-	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED; SONDE_FRAME_FLIPS */
+	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED; SONDE_FRAME_FLIPS / SONDE_FRAME_WORDS */
 	uint64_t bitpos;         /* absolute index (since create) of the first sync bit */
 	uint8_t  data[SONDE_FRAME_MAX];   /* de-whitened, error-corrected frame */
 } SondeFrame;
@@ -196,8 +198,21 @@ typedef struct {
  * A wrong bit whose pair is NOT marked (both chips wrong) can make a wrong subset fit, with probability about 2^(nerr[1] - 16);
  * measured: 2 wrong among 837 rescued M10 frames at Eb/N0 10 dB.  A host that wants fewer drops the rescued frames whose
  * nerr[1] exceeds its own limit.  One small launch more per launch with such channels, behind whatever wrote the records; no host
- * synchronisation.  Not for DFM (its violations would be erasures for Hamming(8,4)), iMS-100 or the batch behind a channelizer. */
+ * synchronisation.  Not for DFM (its violations are erasures for Hamming(8,4): SONDE_FLAG_DFM_RESCUE), iMS-100 or the batch behind a channelizer. */
 #define SONDE_FLAG_MANCHESTER_RESCUE 128u
+/* DFM06/09/17 channels: a second pass over the frames with a Hamming(8,4) word the first pass gave up on (nerr[1] >= 1), DESIGN SPEC
+ * 3.3g.  The framer takes each data bit from the first chip of its Manchester pair (a, !a) and decodes with hard decisions: one wrong
+ * bit per word is corrected, two are not, and DFM has no frame check, so hosts drop a frame with nerr[1] != 0.  A pair with two EQUAL
+ * chips is an erasure, and the extended Hamming code (distance 4) decodes any word with 2v + e <= 3 (v unknown errors, e erasures):
+ * the pass decodes each failed word with its 1..3 erasures, and rewrites the frame iff EVERY failed word decodes (at most 8 of them;
+ * otherwise, or with a word that has no erasure, more than 3, or too much damage, the frame stays as recorded).  A rescued frame
+ * carries data[] = the 33 codewords, nerr[0] raised by the words decoded here, nerr[1] = 0, SONDE_FRAME_RESCUED and SONDE_FRAME_WORDS =
+ * the words decoded here; every other record is, byte for byte, what it is without the flag, and words the first pass took as clean
+ * or corrected are never touched.  The result is right whenever 2v + e <= 3 truly holds; at e = 3 one unmarked error more still fits
+ * a codeword half of the time, and nothing behind the code can tell.  A host that wants fewer wrong frames drops the rescued DFM
+ * frames, or those whose SONDE_FRAME_WORDS exceeds its own limit.  One small launch more per launch with DFM channels, behind
+ * whatever wrote the records; no host synchronisation.  Not for iMS-100, no soft decisions, not the batch behind a channelizer. */
+#define SONDE_FLAG_DFM_RESCUE 256u
 
 typedef struct SondeBatch SondeBatch;
 
@@ -294,6 +309,13 @@ int      sonde_batch_rescue_info(SondeBatch *b, uint32_t channel, SondeRs41Layou
  * marked bits, none in an M10 length byte) and those it rescued, since create / the channel's restart.  Synchronises.  An error without
  * the flag or for a channel of another type. */
 int      sonde_batch_manchester_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued);
+/* SONDE_FLAG_DFM_RESCUE introspection: the frames of a DFM channel that reached the erasure decoder (1..8 failed words, chips at hand)
+ * and those it rescued, since create / the channel's restart.  Synchronises.  An error without the flag or for a channel that is not DFM. */
+int      sonde_batch_dfm_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued);
+/* SONDE_FLAG_DFM_RESCUE's word decoder alone (SPEC 3.3g step 4), on any batch: n received words and their erasure masks (0x80 >> j = bit
+ * j, the MSB first), decoded in place; status[i] = bits changed, -1 = no decode (no erasure, more than 3, or no codeword within
+ * 2v + e <= 3; the word is untouched). */
+int      sonde_batch_test_hamming84_erasures(SondeBatch *b, uint8_t *words, const uint8_t *erased, size_t n, int32_t *status);
 uint64_t sonde_batch_nbits(SondeBatch *b, uint32_t channel);
 int      sonde_batch_read_state(SondeBatch *b, uint32_t channel, int64_t *t_next, int32_t *period, float *bias, float *amp,
                                 float *afc_u /* the newest AFC state u of SPEC 3.0b (the carrier offset the channel is following: 2 atan u per

@@ -103,6 +103,12 @@ FLAG_WIDE_AUTO = 8       # SONDE_FLAG_WIDE for the types whose reference channel
 FLAG_RS41_RESCUE = 64    # RS41: second pass over frames whose RS stage failed, block CRCs as erasure hints (SONDE_FLAG_RS41_RESCUE; opt-in)
 FRAME_RESCUED = 2        # SondeFrame.flags bit of a frame a second pass completed (SONDE_FRAME_RESCUED)
 FLAG_MANCHESTER_RESCUE = 128   # M10 / M20 / MRZ-N1: second pass over frames whose check failed, Manchester violations as hints (SONDE_FLAG_MANCHESTER_RESCUE; opt-in)
+FLAG_DFM_RESCUE = 256         # DFM: second pass over frames with a Hamming word given up on, Manchester violations as erasures (SONDE_FLAG_DFM_RESCUE; opt-in)
+
+
+def frame_words(flags):
+    """codewords SONDE_FLAG_DFM_RESCUE decoded in a rescued DFM frame (SONDE_FRAME_WORDS); an int or a numpy array of SondeFrame.flags"""
+    return (flags >> 8) & 0xF
 
 
 def frame_flips(flags):
@@ -135,6 +141,7 @@ ABI_SYMBOLS = [
     "sonde_tuner_create_slots", "sonde_tuner_slot_set", "sonde_tuner_slot_clear", "sonde_tuner_slot_active",
     "sonde_batch_restart_channels", "sonde_detect_restart_channels", "sonde_live_match",
     "sonde_batch_test_rs255_erasures", "sonde_batch_rescue_info", "sonde_batch_manchester_rescue_info",
+    "sonde_batch_dfm_rescue_info", "sonde_batch_test_hamming84_erasures",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -194,6 +201,9 @@ def load() -> C.CDLL:
         L.sonde_batch_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(SondeRs41Layout), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     if hasattr(L, "sonde_batch_manchester_rescue_info"):  # absent only in older A/B builds loaded through SONDE_MI355_LIB
         L.sonde_batch_manchester_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    if hasattr(L, "sonde_batch_dfm_rescue_info"):         # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        L.sonde_batch_dfm_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.sonde_batch_test_hamming84_erasures.argtypes = [vp, vp, vp, C.c_size_t, vp]
     L.sonde_get_taps.argtypes = [C.c_int, vp]
     L.sonde_parse_frame.argtypes = [vp, C.POINTER(SondeData), C.c_int]
     L.sonde_batch_poll.argtypes = [vp, C.POINTER(SondeData), C.POINTER(C.c_uint32), C.c_size_t]

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FLAG_MANCHESTER_RESCUE, FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
+from ._lib import FLAG_DFM_RESCUE, FLAG_MANCHESTER_RESCUE, FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
 
 
 class SondeError(RuntimeError):
@@ -183,6 +183,24 @@ class SondeBatch:
         tried, rescued = C.c_uint32(), C.c_uint32()
         self._chk(self.L.sonde_batch_manchester_rescue_info(self.h, channel, C.byref(tried), C.byref(rescued)))
         return {"tried": int(tried.value), "rescued": int(rescued.value)}
+
+    def dfm_rescue_info(self, channel: int) -> dict:
+        """FLAG_DFM_RESCUE: what the second pass has done on a DFM channel (sonde_batch_dfm_rescue_info): {'tried': frames with a
+        failed Hamming word that reached the erasure decoder, 'rescued': frames it completed}."""
+        tried, rescued = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.sonde_batch_dfm_rescue_info(self.h, channel, C.byref(tried), C.byref(rescued)))
+        return {"tried": int(tried.value), "rescued": int(rescued.value)}
+
+    def test_hamming84_erasures(self, words: np.ndarray, erased: np.ndarray):
+        """FLAG_DFM_RESCUE's word decoder alone (sonde_batch_test_hamming84_erasures): words, erased [n] uint8 (erased: mask of the
+        erased bits, 0x80 = the first).  Returns (decoded words, status [n]): status = bits changed, -1 = no decode."""
+        w = np.ascontiguousarray(words, dtype=np.uint8).copy()
+        er = np.ascontiguousarray(erased, dtype=np.uint8)
+        assert w.ndim == 1 and er.shape == w.shape
+        status = np.zeros(len(w), dtype=np.int32)
+        self._chk(self.L.sonde_batch_test_hamming84_erasures(self.h, w.ctypes.data_as(C.c_void_p), er.ctypes.data_as(C.c_void_p), len(w),
+                                                             status.ctypes.data_as(C.c_void_p)))
+        return w, status
 
     def test_rs255_erasures(self, cw_pairs: np.ndarray, erased: np.ndarray, n: int):
         """The errors-and-erasures RS(255,231) corrector alone (sonde_batch_test_rs255_erasures): cw_pairs, erased [P, 2, 256] uint8

@@ -158,4 +158,7 @@ struct SondeBatch {
 	// is allocated or launched
 	DevBuf<SdManchesterState> d_mrescue;
 	DevBuf<uint16_t> d_mrztab;
+	// SONDE_FLAG_DFM_RESCUE (SPEC 3.3g): per-channel counters of the second pass over DFM records (dfm_rescue_kernel.hip); null: the
+	// flag is off or the batch has no DFM channel, and nothing of it is allocated or launched
+	DevBuf<SdDfmRescueState> d_drescue;
 };

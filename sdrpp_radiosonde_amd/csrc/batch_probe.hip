@@ -69,6 +69,38 @@ extern "C" int sonde_batch_manchester_rescue_info(SondeBatch *b, uint32_t channe
 	return 0;
 }
 
+extern "C" int sonde_batch_dfm_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued)
+{
+	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_dfm_rescue_info: bad argument");
+	if (b->behind_channelizer) return sd_fail("sonde_batch_dfm_rescue_info: SONDE_FLAG_DFM_RESCUE is not available for the batch behind a channelizer");
+	if (!b->d_drescue) return sd_fail("sonde_batch_dfm_rescue_info: the batch was created without SONDE_FLAG_DFM_RESCUE (or has no DFM channel)");
+	if (b->types[channel] != SONDE_DFM09) return sd_fail("sonde_batch_dfm_rescue_info: not a DFM channel");
+	if (sonde_batch_sync(b) < 0) return -1;
+	SdDfmRescueState st;
+	HIPCHK(hipMemcpy(&st, b->d_drescue + channel, sizeof(st), hipMemcpyDeviceToHost));
+	if (tried) *tried = st.tried;
+	if (rescued) *rescued = st.rescued;
+	return 0;
+}
+
+// Step 4 of SPEC 3.3g alone, through the kernel's own device function: n words and their erasure masks, decoded in place;
+// status[i] = bits changed, -1 = no decode (word untouched).
+extern "C" int sonde_batch_test_hamming84_erasures(SondeBatch *b, uint8_t *words, const uint8_t *erased, size_t n, int32_t *status)
+{
+	if (!b || !words || !erased || !status || !n || n > (1u << 24)) return sd_fail("sonde_batch_test_hamming84_erasures: bad argument");
+	HIPCHK(hipSetDevice(b->device));
+	DevBuf<uint8_t> d_w, d_e;
+	DevBuf<int32_t> d_st;
+	HIPCHK(d_w.upload(words, n));
+	HIPCHK(d_e.upload(erased, n));
+	HIPCHK(d_st.alloc(n));
+	sd_launch_hamming84_unit(d_w, d_e, (uint32_t)n, d_st, nullptr);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpy(words, d_w, n, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
 // wait for the last submit and fetch the channel's demodulator state
 static int fetch_state(SondeBatch *b, uint32_t channel, SdChanState *st)
 {

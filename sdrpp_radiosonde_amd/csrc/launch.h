@@ -103,5 +103,14 @@ void sd_launch_rescue_manchester(uint32_t n_list, hipStream_t stream, const uint
 	SdManchesterState *states);
 void sd_launch_manchester_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdManchesterState *states);
 
+// SONDE_FLAG_DFM_RESCUE (dfm_rescue_kernel.hip, DESIGN SPEC 3.3g): per DFM channel two counters (frames with a word the first pass gave
+// up on that reached the erasure decoder; frames rescued), carried from submit to submit.  chlist: never null.
+struct SdDfmRescueState { uint32_t tried, rescued; };
+void sd_launch_rescue_dfm(uint32_t n_list, hipStream_t stream, const SdChanState *chan_states, const uint32_t *bitring, uint32_t ring_words,
+	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist, SdDfmRescueState *states);
+void sd_launch_dfm_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdDfmRescueState *states);
+// step 4 of SPEC 3.3g alone: n words and their erasure masks (device memory), decoded in place; status = bits changed, -1 = no decode
+void sd_launch_hamming84_unit(uint8_t *words, const uint8_t *erased, uint32_t n, int32_t *status, hipStream_t stream);
+
 // sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);
