@@ -104,9 +104,11 @@ enum { SONDE_INPUT_IQ = 0,      /* complex64 interleaved I,Q at 48 kS/s (vfo->ou
 
 #define SONDE_FRAME_RESCUED 2u   /* SondeFrame.flags: a frame a second pass completed -- an RS41 frame SONDE_FLAG_RS41_RESCUE filled in, or an
                                   * M10 / M20 / MRZ-N1 frame SONDE_FLAG_MANCHESTER_RESCUE corrected (then SONDE_FRAME_FLIPS says how many bits), or
-                                  * a DFM frame SONDE_FLAG_DFM_RESCUE completed (then SONDE_FRAME_WORDS says how many codewords) */
+                                  * a DFM frame SONDE_FLAG_DFM_RESCUE completed (then SONDE_FRAME_WORDS says how many codewords), or an
+                                  * iMS-100 frame SONDE_FLAG_IMS_RESCUE completed (then SONDE_FRAME_BLOCKS says how many BCH blocks) */
 #define SONDE_FRAME_FLIPS(f) (((f) >> 8) & 0xFu)   /* SondeFrame.flags bits 8..11: data bits SONDE_FLAG_MANCHESTER_RESCUE flipped (0..8) */
 #define SONDE_FRAME_WORDS(f) (((f) >> 8) & 0xFu)   /* the same bits for DFM: codewords SONDE_FLAG_DFM_RESCUE decoded with erasures (1..8) */
+#define SONDE_FRAME_BLOCKS(f) (((f) >> 8) & 0xFu)  /* the same bits for iMS-100: BCH blocks SONDE_FLAG_IMS_RESCUE decoded (1..12) */
 #define SONDE_TILE       2048   /* samples; submit lengths are multiples of this */
 #define SONDE_FRAME_MAX  528
 
@@ -115,7 +117,7 @@ typedef struct {
 	uint32_t type;
 	int32_t  len;            /* bytes valid in data[] */
 	int32_t  nerr[2];        /* RS41: bytes corrected per RS codeword, -1 = uncorrectable */
-	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED; SONDE_FRAME_FLIPS / SONDE_FRAME_WORDS */
+	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED; SONDE_FRAME_FLIPS / SONDE_FRAME_WORDS / SONDE_FRAME_BLOCKS */
 	uint64_t bitpos;         /* absolute index (since create) of the first sync bit */
 	uint8_t  data[SONDE_FRAME_MAX];   /* de-whitened, error-corrected frame */
 } SondeFrame;
@@ -198,7 +200,8 @@ typedef struct {
  * A wrong bit whose pair is NOT marked (both chips wrong) can make a wrong subset fit, with probability about 2^(nerr[1] - 16);
  * measured: 2 wrong among 837 rescued M10 frames at Eb/N0 10 dB.  A host that wants fewer drops the rescued frames whose
  * nerr[1] exceeds its own limit.  One small launch more per launch with such channels, behind whatever wrote the records; no host
- * synchronisation.  Not for DFM (its violations are erasures for Hamming(8,4): SONDE_FLAG_DFM_RESCUE), iMS-100 or the batch behind a channelizer. */
+ * synchronisation.  Not for DFM (its violations are erasures for Hamming(8,4): SONDE_FLAG_DFM_RESCUE), iMS-100 (biphase-S marks a pair of
+ * bits, not one: SONDE_FLAG_IMS_RESCUE) or the batch behind a channelizer. */
 #define SONDE_FLAG_MANCHESTER_RESCUE 128u
 /* DFM06/09/17 channels: a second pass over the frames with a Hamming(8,4) word the first pass gave up on (nerr[1] >= 1), DESIGN SPEC
  * 3.3g.  The framer takes each data bit from the first chip of its Manchester pair (a, !a) and decodes with hard decisions: one wrong
@@ -211,8 +214,24 @@ typedef struct {
  * or corrected are never touched.  The result is right whenever 2v + e <= 3 truly holds; at e = 3 one unmarked error more still fits
  * a codeword half of the time, and nothing behind the code can tell.  A host that wants fewer wrong frames drops the rescued DFM
  * frames, or those whose SONDE_FRAME_WORDS exceeds its own limit.  One small launch more per launch with DFM channels, behind
- * whatever wrote the records; no host synchronisation.  Not for iMS-100, no soft decisions, not the batch behind a channelizer. */
+ * whatever wrote the records; no host synchronisation.  Not for iMS-100 (SONDE_FLAG_IMS_RESCUE), no soft decisions, not the batch
+ * behind a channelizer. */
 #define SONDE_FLAG_DFM_RESCUE 256u
+/* iMS-100 / RS-11G channels: a second pass over the frames with a BCH(46,34) block the first pass rejected (nerr[1] >= 1), DESIGN SPEC
+ * 3.3h.  Biphase-S carries a bit in whether the two chips of its cell are equal and makes a transition at every cell boundary; the
+ * framer reads the cells only.  A boundary WITHOUT a transition says that one of its two chips is wrong, so one of the two bits next
+ * to it is.  For each rejected block with 1..6 such boundaries the pass tries the 2^m ways of blaming the cell left or right of
+ * each, and the block decodes iff exactly one distinct flip pattern among them gives a codeword; the frame is rewritten iff EVERY
+ * rejected block decodes (otherwise, or when the record's nerr[1] is not what the chips say, it stays as recorded).  A rescued frame
+ * carries the 34 data bits of each decoded block, nerr[0] raised by the bits flipped, nerr[1] = 0, SONDE_FRAME_RESCUED and
+ * SONDE_FRAME_BLOCKS = the blocks decoded here; every other record is, byte for byte, what it is without the flag, and blocks the
+ * first pass took as clean or corrected are never touched.  With at most 4 violated boundaries inside a block the decode is unique,
+ * and right whenever every wrong chip is a lone one; a pair of wrong chips across a boundary marks nothing, and then a wrong pattern
+ * fits with probability about 2^m / 4096 -- iMS-100 has no frame check behind the code that could tell.  A host that wants fewer
+ * wrong frames drops the rescued iMS-100 frames, or those whose SONDE_FRAME_BLOCKS exceeds its own limit.  One small launch more per
+ * launch with iMS-100 channels, behind whatever wrote the records; no host synchronisation.  No soft decisions, not the batch behind
+ * a channelizer. */
+#define SONDE_FLAG_IMS_RESCUE 512u
 
 typedef struct SondeBatch SondeBatch;
 
@@ -316,6 +335,15 @@ int      sonde_batch_dfm_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *
  * j, the MSB first), decoded in place; status[i] = bits changed, -1 = no decode (no erasure, more than 3, or no codeword within
  * 2v + e <= 3; the word is untouched). */
 int      sonde_batch_test_hamming84_erasures(SondeBatch *b, uint8_t *words, const uint8_t *erased, size_t n, int32_t *status);
+/* SONDE_FLAG_IMS_RESCUE introspection: the frames of an iMS-100 channel that reached the block decoder (nerr[1] rejected blocks, found
+ * again in the chips at hand) and those it rescued, since create / the channel's restart.  Synchronises.  An error without the flag,
+ * behind a channelizer or for a channel that is not iMS-100. */
+int      sonde_batch_ims_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued);
+/* SONDE_FLAG_IMS_RESCUE's block decoder alone (SPEC 3.3h step 3), on any batch: n received blocks (bit b of the block, 0..45, is bit
+ * 45 - b of the word) and the masks of their violated boundaries (bit k = boundary k of the block, 0..46; boundary k lies between
+ * cell k - 1 and cell k), decoded in place; status[i] = bits flipped, -1 = no decode (no violation, more than 6, or not exactly one
+ * distinct pattern that gives a codeword; the block is untouched). */
+int      sonde_batch_test_ims_block(SondeBatch *b, size_t n, uint64_t *blocks, const uint64_t *viol, int32_t *status);
 uint64_t sonde_batch_nbits(SondeBatch *b, uint32_t channel);
 int      sonde_batch_read_state(SondeBatch *b, uint32_t channel, int64_t *t_next, int32_t *period, float *bias, float *amp,
                                 float *afc_u /* the newest AFC state u of SPEC 3.0b (the carrier offset the channel is following: 2 atan u per

@@ -104,6 +104,12 @@ FLAG_RS41_RESCUE = 64    # RS41: second pass over frames whose RS stage failed, 
 FRAME_RESCUED = 2        # SondeFrame.flags bit of a frame a second pass completed (SONDE_FRAME_RESCUED)
 FLAG_MANCHESTER_RESCUE = 128   # M10 / M20 / MRZ-N1: second pass over frames whose check failed, Manchester violations as hints (SONDE_FLAG_MANCHESTER_RESCUE; opt-in)
 FLAG_DFM_RESCUE = 256         # DFM: second pass over frames with a Hamming word given up on, Manchester violations as erasures (SONDE_FLAG_DFM_RESCUE; opt-in)
+FLAG_IMS_RESCUE = 512         # iMS-100: second pass over frames with a BCH block rejected, biphase-S boundary violations as hints (SONDE_FLAG_IMS_RESCUE; opt-in)
+
+
+def frame_blocks(flags):
+    """BCH blocks SONDE_FLAG_IMS_RESCUE decoded in a rescued iMS-100 frame (SONDE_FRAME_BLOCKS); an int or a numpy array of SondeFrame.flags"""
+    return (flags >> 8) & 0xF
 
 
 def frame_words(flags):
@@ -142,6 +148,7 @@ ABI_SYMBOLS = [
     "sonde_batch_restart_channels", "sonde_detect_restart_channels", "sonde_live_match",
     "sonde_batch_test_rs255_erasures", "sonde_batch_rescue_info", "sonde_batch_manchester_rescue_info",
     "sonde_batch_dfm_rescue_info", "sonde_batch_test_hamming84_erasures",
+    "sonde_batch_ims_rescue_info", "sonde_batch_test_ims_block",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -204,6 +211,9 @@ def load() -> C.CDLL:
     if hasattr(L, "sonde_batch_dfm_rescue_info"):         # absent only in older A/B builds loaded through SONDE_MI355_LIB
         L.sonde_batch_dfm_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.sonde_batch_test_hamming84_erasures.argtypes = [vp, vp, vp, C.c_size_t, vp]
+    if hasattr(L, "sonde_batch_ims_rescue_info"):         # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        L.sonde_batch_ims_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.sonde_batch_test_ims_block.argtypes = [vp, C.c_size_t, vp, vp, vp]
     L.sonde_get_taps.argtypes = [C.c_int, vp]
     L.sonde_parse_frame.argtypes = [vp, C.POINTER(SondeData), C.c_int]
     L.sonde_batch_poll.argtypes = [vp, C.POINTER(SondeData), C.POINTER(C.c_uint32), C.c_size_t]

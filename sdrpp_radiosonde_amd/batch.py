@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FLAG_DFM_RESCUE, FLAG_MANCHESTER_RESCUE, FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
+from ._lib import FLAG_DFM_RESCUE, FLAG_IMS_RESCUE, FLAG_MANCHESTER_RESCUE, FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
 
 
 class SondeError(RuntimeError):
@@ -201,6 +201,25 @@ class SondeBatch:
         self._chk(self.L.sonde_batch_test_hamming84_erasures(self.h, w.ctypes.data_as(C.c_void_p), er.ctypes.data_as(C.c_void_p), len(w),
                                                              status.ctypes.data_as(C.c_void_p)))
         return w, status
+
+    def ims_rescue_info(self, channel: int) -> dict:
+        """FLAG_IMS_RESCUE: what the second pass has done on an iMS-100 channel (sonde_batch_ims_rescue_info): {'tried': frames with a
+        rejected BCH block that reached the block decoder, 'rescued': frames it completed}."""
+        tried, rescued = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.sonde_batch_ims_rescue_info(self.h, channel, C.byref(tried), C.byref(rescued)))
+        return {"tried": int(tried.value), "rescued": int(rescued.value)}
+
+    def test_ims_block(self, blocks: np.ndarray, viol: np.ndarray):
+        """FLAG_IMS_RESCUE's block decoder alone (sonde_batch_test_ims_block): blocks, viol [n] uint64 (blocks: bit b of the block is bit
+        45 - b; viol: bit k = boundary k of the block is violated, 0..46).  Returns (decoded blocks, status [n]): status = bits flipped,
+        -1 = no decode."""
+        blk = np.ascontiguousarray(blocks, dtype=np.uint64).copy()
+        v = np.ascontiguousarray(viol, dtype=np.uint64)
+        assert blk.ndim == 1 and v.shape == blk.shape
+        status = np.zeros(len(blk), dtype=np.int32)
+        self._chk(self.L.sonde_batch_test_ims_block(self.h, len(blk), blk.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p),
+                                                    status.ctypes.data_as(C.c_void_p)))
+        return blk, status
 
     def test_rs255_erasures(self, cw_pairs: np.ndarray, erased: np.ndarray, n: int):
         """The errors-and-erasures RS(255,231) corrector alone (sonde_batch_test_rs255_erasures): cw_pairs, erased [P, 2, 256] uint8

@@ -161,4 +161,7 @@ struct SondeBatch {
 	// SONDE_FLAG_DFM_RESCUE (SPEC 3.3g): per-channel counters of the second pass over DFM records (dfm_rescue_kernel.hip); null: the
 	// flag is off or the batch has no DFM channel, and nothing of it is allocated or launched
 	DevBuf<SdDfmRescueState> d_drescue;
+	// SONDE_FLAG_IMS_RESCUE (SPEC 3.3h): per-channel counters of the second pass over iMS-100 records (ims_rescue_kernel.hip); null: the
+	// flag is off or the batch has no iMS-100 channel, and nothing of it is allocated or launched
+	DevBuf<SdImsRescueState> d_irescue;
 };

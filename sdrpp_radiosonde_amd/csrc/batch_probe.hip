@@ -101,6 +101,38 @@ extern "C" int sonde_batch_test_hamming84_erasures(SondeBatch *b, uint8_t *words
 	return 0;
 }
 
+extern "C" int sonde_batch_ims_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued)
+{
+	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_ims_rescue_info: bad argument");
+	if (b->behind_channelizer) return sd_fail("sonde_batch_ims_rescue_info: SONDE_FLAG_IMS_RESCUE is not available for the batch behind a channelizer");
+	if (!b->d_irescue) return sd_fail("sonde_batch_ims_rescue_info: the batch was created without SONDE_FLAG_IMS_RESCUE (or has no iMS-100 channel)");
+	if (b->types[channel] != SONDE_IMS100) return sd_fail("sonde_batch_ims_rescue_info: not an iMS-100 channel");
+	if (sonde_batch_sync(b) < 0) return -1;
+	SdImsRescueState st;
+	HIPCHK(hipMemcpy(&st, b->d_irescue + channel, sizeof(st), hipMemcpyDeviceToHost));
+	if (tried) *tried = st.tried;
+	if (rescued) *rescued = st.rescued;
+	return 0;
+}
+
+// Step 3 of SPEC 3.3h alone, through the kernel's own device function: n blocks (bit b of the block = bit 45 - b) and the masks of
+// their violated boundaries (bit k = boundary k, 0..46), decoded in place; status[i] = bits flipped, -1 = no decode (block untouched).
+extern "C" int sonde_batch_test_ims_block(SondeBatch *b, size_t n, uint64_t *blocks, const uint64_t *viol, int32_t *status)
+{
+	if (!b || !blocks || !viol || !status || !n || n > (1u << 24)) return sd_fail("sonde_batch_test_ims_block: bad argument");
+	HIPCHK(hipSetDevice(b->device));
+	DevBuf<uint64_t> d_b, d_v;
+	DevBuf<int32_t> d_st;
+	HIPCHK(d_b.upload(blocks, n));
+	HIPCHK(d_v.upload(viol, n));
+	HIPCHK(d_st.alloc(n));
+	sd_launch_ims_block_unit(b->fec.g64, d_b, d_v, (uint32_t)n, d_st, nullptr);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpy(blocks, d_b, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
 // wait for the last submit and fetch the channel's demodulator state
 static int fetch_state(SondeBatch *b, uint32_t channel, SdChanState *st)
 {

@@ -112,5 +112,16 @@ void sd_launch_dfm_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *
 // step 4 of SPEC 3.3g alone: n words and their erasure masks (device memory), decoded in place; status = bits changed, -1 = no decode
 void sd_launch_hamming84_unit(uint8_t *words, const uint8_t *erased, uint32_t n, int32_t *status, hipStream_t stream);
 
+// SONDE_FLAG_IMS_RESCUE (ims_rescue_kernel.hip, DESIGN SPEC 3.3h): per iMS-100 channel two counters (frames with a BCH block the first
+// pass rejected that reached the block decoder; frames rescued), carried from submit to submit.  chlist: never null.  g64: GF(2^6)
+// exp[128], log[64].
+struct SdImsRescueState { uint32_t tried, rescued; };
+void sd_launch_rescue_ims(uint32_t n_list, hipStream_t stream, const uint8_t *g64, const SdChanState *chan_states, const uint32_t *bitring,
+	uint32_t ring_words, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist, SdImsRescueState *states);
+void sd_launch_ims_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdImsRescueState *states);
+// step 3 of SPEC 3.3h alone: n blocks and the masks of their violated boundaries (device memory), decoded in place; status = bits
+// flipped, -1 = no decode
+void sd_launch_ims_block_unit(const uint8_t *g64, uint64_t *blocks, const uint64_t *viols, uint32_t n, int32_t *status, hipStream_t stream);
+
 // sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);
