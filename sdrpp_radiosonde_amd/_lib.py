@@ -105,6 +105,7 @@ FRAME_RESCUED = 2        # SondeFrame.flags bit of a frame a second pass complet
 FLAG_MANCHESTER_RESCUE = 128   # M10 / M20 / MRZ-N1: second pass over frames whose check failed, Manchester violations as hints (SONDE_FLAG_MANCHESTER_RESCUE; opt-in)
 FLAG_DFM_RESCUE = 256         # DFM: second pass over frames with a Hamming word given up on, Manchester violations as erasures (SONDE_FLAG_DFM_RESCUE; opt-in)
 FLAG_IMS_RESCUE = 512         # iMS-100: second pass over frames with a BCH block rejected, biphase-S boundary violations as hints (SONDE_FLAG_IMS_RESCUE; opt-in)
+FLAG_AFSK_RESCUE = 1024       # iMet / C50: second pass over packets whose check failed, one bit or an adjacent pair repaired (SONDE_FLAG_AFSK_RESCUE; opt-in)
 
 
 def frame_blocks(flags):
@@ -118,7 +119,8 @@ def frame_words(flags):
 
 
 def frame_flips(flags):
-    """data bits SONDE_FLAG_MANCHESTER_RESCUE flipped in a rescued frame (SONDE_FRAME_FLIPS); an int or a numpy array of SondeFrame.flags"""
+    """data bits SONDE_FLAG_MANCHESTER_RESCUE or SONDE_FLAG_AFSK_RESCUE flipped in a rescued frame (SONDE_FRAME_FLIPS); an int or a numpy
+    array of SondeFrame.flags"""
     return (flags >> 8) & 0xF
 
 
@@ -149,6 +151,7 @@ ABI_SYMBOLS = [
     "sonde_batch_test_rs255_erasures", "sonde_batch_rescue_info", "sonde_batch_manchester_rescue_info",
     "sonde_batch_dfm_rescue_info", "sonde_batch_test_hamming84_erasures",
     "sonde_batch_ims_rescue_info", "sonde_batch_test_ims_block",
+    "sonde_batch_afsk_rescue_info", "sonde_batch_test_afsk_repair",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -214,6 +217,9 @@ def load() -> C.CDLL:
     if hasattr(L, "sonde_batch_ims_rescue_info"):         # absent only in older A/B builds loaded through SONDE_MI355_LIB
         L.sonde_batch_ims_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.sonde_batch_test_ims_block.argtypes = [vp, C.c_size_t, vp, vp, vp]
+    if hasattr(L, "sonde_batch_afsk_rescue_info"):        # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        L.sonde_batch_afsk_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.sonde_batch_test_afsk_repair.argtypes = [vp, vp, C.c_size_t, vp]
     L.sonde_get_taps.argtypes = [C.c_int, vp]
     L.sonde_parse_frame.argtypes = [vp, C.POINTER(SondeData), C.c_int]
     L.sonde_batch_poll.argtypes = [vp, C.POINTER(SondeData), C.POINTER(C.c_uint32), C.c_size_t]

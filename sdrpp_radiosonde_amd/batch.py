@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FLAG_DFM_RESCUE, FLAG_IMS_RESCUE, FLAG_MANCHESTER_RESCUE, FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
+from ._lib import FLAG_AFSK_RESCUE, FLAG_DFM_RESCUE, FLAG_IMS_RESCUE, FLAG_MANCHESTER_RESCUE, FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
 
 
 class SondeError(RuntimeError):
@@ -220,6 +220,22 @@ class SondeBatch:
         self._chk(self.L.sonde_batch_test_ims_block(self.h, len(blk), blk.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p),
                                                     status.ctypes.data_as(C.c_void_p)))
         return blk, status
+
+    def afsk_rescue_info(self, channel: int) -> dict:
+        """FLAG_AFSK_RESCUE: what the second pass has done on an iMet / C50 channel (sonde_batch_afsk_rescue_info): {'tried': packets whose
+        check failed that reached the pattern search, 'rescued': packets it repaired}."""
+        tried, rescued = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.sonde_batch_afsk_rescue_info(self.h, channel, C.byref(tried), C.byref(rescued)))
+        return {"tried": int(tried.value), "rescued": int(rescued.value)}
+
+    def test_afsk_repair(self, records: np.ndarray):
+        """FLAG_AFSK_RESCUE's per-record routine alone (sonde_batch_test_afsk_repair): records [n] FRAME_DTYPE, caller-made.  Returns
+        (records after the routine, status [n]): status = 0 untouched, 1 rescued, 2 several patterns fit."""
+        rec = np.ascontiguousarray(records, dtype=FRAME_DTYPE).copy()
+        assert rec.ndim == 1
+        status = np.zeros(len(rec), dtype=np.int32)
+        self._chk(self.L.sonde_batch_test_afsk_repair(self.h, rec.ctypes.data_as(C.c_void_p), len(rec), status.ctypes.data_as(C.c_void_p)))
+        return rec, status
 
     def test_rs255_erasures(self, cw_pairs: np.ndarray, erased: np.ndarray, n: int):
         """The errors-and-erasures RS(255,231) corrector alone (sonde_batch_test_rs255_erasures): cw_pairs, erased [P, 2, 256] uint8

@@ -1,0 +1,176 @@
+// afsk_rescue_kernel.hip -- SONDE_FLAG_AFSK_RESCUE (DESIGN SPEC 3.3i): the second pass over the iMet-1/4 and SRS-C50 packet records of a
+// submit.  These packets carry a 16-bit check and nothing else: no FEC, no second chip per bit.  A packet whose check fails is
+// searched for ONE wrong bit, or TWO NEIGHBOURING wrong bits of one character (15 patterns per candidate byte), and is rescued iff
+// exactly one pattern makes the check pass.
+//   iMet: CRC16-CCITT is affine over GF(2).  The syndrome (computed CRC XOR stored CRC) is the XOR of the columns of the wrong bits,
+//   the column of a bit being the change of the syndrome when it flips: x^(16 + 8 k + j) mod 0x11021 for bit j of the byte with k
+//   covered bytes behind it, bit 8 + j / bit j of the syndrome itself for the two stored bytes.  Lane i owns byte i of the packet
+//   (at most 64), XORs the columns of its set bits into the wave's syndrome and compares its 15 patterns with it.
+//   C50: the two running byte sums are not linear over GF(2); lanes 2..8 recompute them over data XOR each of their 15 patterns.
+//   one 64-lane wave per channel, four waves per workgroup; lanes load the headers of 64 records at once and the wave works on
+//   the candidates among them one by one.  No LDS, no table in memory.
+// Runs behind sd_imet_kernel / sd_c50_kernel, on the same stream, and rewrites the records in place.  It reads the records only (not
+// the bit ring), and the records of a channel are independent of each other (only the two counters are shared), so the result
+// does not depend on the cut into submits.  Vector stores only.
+#include <hip/hip_runtime.h>
+#include "sonde_dev.h"
+#include "launch.h"
+
+#define AQ_WAVES 4
+#define AQ_IMET_MAXLEN 64      // sd_imet_kernel records nothing longer: one lane per packet byte
+#define AQ_C50_LEN 9
+
+// x^(16 + 8 k) mod (x^16 + x^12 + x^5 + 1), k = 0 .. 61: the column of bit 0 of the byte with k covered bytes behind it
+struct AqPow { uint16_t v[AQ_IMET_MAXLEN - 2]; };
+static constexpr uint32_t aq_mulx(uint32_t c) { return (c & 0x8000u) ? ((c << 1) ^ 0x1021u) & 0xFFFFu : (c << 1) & 0xFFFFu; }
+static constexpr AqPow aq_make_pow()
+{
+	AqPow t{};
+	uint32_t c = 0x1021u;                  // x^16
+	for (int k = 0; k < AQ_IMET_MAXLEN - 2; k++) {
+		t.v[k] = (uint16_t)c;
+		for (int s = 0; s < 8; s++) c = aq_mulx(c);
+	}
+	return t;
+}
+__device__ const AqPow aq_pow = aq_make_pow();
+
+// the change of the iMet syndrome when the bits `m` of this lane's byte flip; c0 = the column of its bit 0
+__device__ __forceinline__ uint32_t aq_imet_cols(uint32_t c0, uint32_t m)
+{
+	uint32_t s = 0, c = c0;
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		if ((m >> j) & 1u) s ^= c;
+		c = aq_mulx(c);
+	}
+	return s;
+}
+
+// pattern q = 0 .. 14 of SPEC 3.3i step 3: the single-bit masks 1 << q, then the adjacent-pair masks 3 << (q - 8)
+__device__ __forceinline__ uint32_t aq_pattern(int q) { return q < 8 ? 1u << q : 3u << (q - 8); }
+
+// Steps 1..5 of SPEC 3.3i for ONE record, by a whole wave (type, len, nerr0: the record's header, wave-uniform).
+// Returns -1: not eligible; 0: no pattern fits; 1: rescued (the record is rewritten); 2: several patterns fit.
+__device__ __forceinline__ int aq_repair(SondeFrame *__restrict__ fr, uint32_t type, int len, int nerr0, int lane)
+{
+	const bool imet = type == SONDE_IMET4 && len >= 5 && len <= AQ_IMET_MAXLEN;
+	const bool c50 = type == SONDE_C50 && len == AQ_C50_LEN;
+	if (!(imet || c50) || nerr0 != -1) return -1;
+	const uint32_t d = lane < len ? fr->data[lane] : 0u;
+	int first = 2;
+	uint32_t fit = 0;                       // bit q: pattern q of this lane's byte fits
+	if (imet) {
+		if ((uint32_t)__builtin_amdgcn_readlane((int)d, 1) == 3u) first = 3;     // XDATA: byte 2 decided len
+		// the start value 0x1D0F is an XOR into the first two bytes; columns of the covered bytes from the table, of the stored
+		// CRC (big-endian) the syndrome's own bits
+		const int n_cov = len - 2;
+		uint32_t c0 = 0;
+		if (lane < n_cov) c0 = aq_pow.v[n_cov - 1 - lane];
+		else if (lane < len) c0 = lane == n_cov ? 0x100u : 0x1u;
+		uint32_t s = aq_imet_cols(c0, d ^ (lane == 0 ? 0x1Du : (lane == 1 ? 0x0Fu : 0u)));
+#pragma unroll
+		for (int off = 32; off > 0; off >>= 1) s ^= (uint32_t)__shfl_xor((int)s, off, 64);
+		if (lane >= first && lane < len) {
+#pragma unroll
+			for (int q = 0; q < 15; q++) if (aq_imet_cols(c0, aq_pattern(q)) == s) fit |= 1u << q;
+		}
+	} else {
+		uint32_t b[AQ_C50_LEN];
+#pragma unroll
+		for (int i = 0; i < AQ_C50_LEN; i++) b[i] = (uint32_t)__builtin_amdgcn_readlane((int)d, i);
+		if (lane >= first && lane < len) {
+			for (int q = 0; q < 15; q++) {
+				const uint32_t m = aq_pattern(q);
+				uint32_t c1 = 0, c2 = 0;
+#pragma unroll
+				for (int i = 2; i < 7; i++) { c1 = (c1 + (b[i] ^ (i == lane ? m : 0u))) & 0xFFu; c2 = (c2 + c1) & 0xFFu; }
+				if (c1 == (b[7] ^ (lane == 7 ? m : 0u)) && c2 == (b[8] ^ (lane == 8 ? m : 0u))) fit |= 1u << q;
+			}
+		}
+	}
+	int nfit = __popc(fit);
+#pragma unroll
+	for (int off = 32; off > 0; off >>= 1) nfit += __shfl_xor(nfit, off, 64);
+	if (nfit != 1) return nfit ? 2 : 0;     // none, or several: the record stays
+	const unsigned long long who = __ballot(fit != 0u);
+	const uint32_t m = aq_pattern(__builtin_ctz(fit | 0x8000u));
+	if (fit) fr->data[lane] = (uint8_t)(d ^ m);
+	const uint32_t w = (uint32_t)__popc((uint32_t)__builtin_amdgcn_readlane((int)m, __builtin_ctzll(who)));
+	if (lane == 0) {
+		fr->nerr[0] = 0;
+		fr->flags |= SONDE_FRAME_RESCUED | (w << 8);
+	}
+	return 1;
+}
+
+__global__ __launch_bounds__(64 * AQ_WAVES) void sd_afsk_rescue_kernel(SondeFrame *__restrict__ frames, const uint32_t *__restrict__ counts,
+	uint32_t max_frames, const uint32_t *__restrict__ chlist, uint32_t n_list, SdAfskRescueState *__restrict__ states)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t li_ch = AQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
+	if (li_ch >= n_list) return;
+	const uint32_t ch = chlist[li_ch];
+	const uint32_t nfr = min(counts[ch], max_frames);
+	if (nfr == 0) return;
+	SondeFrame *const chfr = frames + (size_t)ch * max_frames;
+	uint32_t tried = 0, rescued = 0;
+
+	for (uint32_t base = 0; base < nfr; base += 64) {
+		// the headers of records base .. base + 63, one per lane
+		int h_len = 0;
+		uint32_t h_type = 0;
+		bool cand = false;
+		if (base + (uint32_t)lane < nfr) {
+			const SondeFrame *f = chfr + base + lane;
+			h_type = f->type; h_len = f->len;
+			cand = f->nerr[0] == -1 && ((h_type == SONDE_IMET4 && h_len >= 5 && h_len <= AQ_IMET_MAXLEN) || (h_type == SONDE_C50 && h_len == AQ_C50_LEN));
+		}
+		for (unsigned long long cm = __ballot(cand); cm; cm &= cm - 1ull) {
+			const int q = __builtin_ctzll(cm);
+			const int r = aq_repair(chfr + base + q, (uint32_t)__builtin_amdgcn_readlane((int)h_type, q), __builtin_amdgcn_readlane(h_len, q), -1, lane);
+			tried += r >= 0;
+			rescued += r == 1;
+		}
+	}
+	if (tried && lane == 0) {
+		states[ch].tried += tried;
+		states[ch].rescued += rescued;
+	}
+}
+
+void sd_launch_rescue_afsk(uint32_t n_list, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
+	const uint32_t *chlist, SdAfskRescueState *states)
+{
+	hipLaunchKernelGGL(sd_afsk_rescue_kernel, dim3((n_list + AQ_WAVES - 1) / AQ_WAVES), dim3(64 * AQ_WAVES), 0, stream,
+		frames, counts, max_frames, chlist, n_list, states);
+}
+
+// ---- the listed channels back to counters zero (sonde_batch_restart_channels)
+__global__ __launch_bounds__(64) void sd_afsk_rescue_clear_kernel(const uint32_t *__restrict__ list, uint32_t n, SdAfskRescueState *__restrict__ states)
+{
+	const uint32_t i = 64 * blockIdx.x + threadIdx.x;
+	if (i < n) { states[list[i]].tried = 0u; states[list[i]].rescued = 0u; }
+}
+void sd_launch_afsk_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdAfskRescueState *states)
+{
+	hipLaunchKernelGGL(sd_afsk_rescue_clear_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, list, n, states);
+}
+
+// ---- aq_repair alone over n caller-made records, one wave each (sonde_batch_test_afsk_repair): status 0 untouched, 1 rescued,
+// 2 several patterns fit
+__global__ __launch_bounds__(64 * AQ_WAVES) void sd_afsk_repair_unit_kernel(SondeFrame *__restrict__ records, uint32_t n, int32_t *__restrict__ status)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t i = AQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
+	if (i >= n) return;
+	SondeFrame *fr = records + i;
+	const uint32_t type = (uint32_t)__builtin_amdgcn_readfirstlane((int)fr->type);
+	const int len = __builtin_amdgcn_readfirstlane(fr->len), nerr0 = __builtin_amdgcn_readfirstlane(fr->nerr[0]);
+	const int r = aq_repair(fr, type, len, nerr0, lane);
+	if (lane == 0) status[i] = r < 0 ? 0 : r;
+}
+void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status, hipStream_t stream)
+{
+	hipLaunchKernelGGL(sd_afsk_repair_unit_kernel, dim3((n + AQ_WAVES - 1) / AQ_WAVES), dim3(64 * AQ_WAVES), 0, stream, records, n, status);
+}

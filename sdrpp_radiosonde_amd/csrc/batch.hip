@@ -185,6 +185,7 @@ static int build(SondeBatch *b, const SondeBatchConfig *cfg)
 	}
 	if ((cfg->flags & SONDE_FLAG_DFM_RESCUE) && !b->chlist[SONDE_DFM09].empty()) HIPCHK(b->d_drescue.zeros(C));
 	if ((cfg->flags & SONDE_FLAG_IMS_RESCUE) && !b->chlist[SONDE_IMS100].empty()) HIPCHK(b->d_irescue.zeros(C));
+	if ((cfg->flags & SONDE_FLAG_AFSK_RESCUE) && n_afsk) HIPCHK(b->d_arescue.zeros(C));
 	if (n_afsk) {
 		float wtab[2 * SD_AF_PER], wc[2 * SD_C50_PER];
 		make_mixer(wtab, 17, SD_AF_PER);         // iMet: 1700 Hz
@@ -325,6 +326,7 @@ int sd_batch_submit_bins(SondeBatch *b, const SdBinsArgs *ba, size_t n_steps, vo
 	if (b->d_mrescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_MANCHESTER_RESCUE is not available for the decoder batch behind a channelizer");
 	if (b->d_drescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_DFM_RESCUE is not available for the decoder batch behind a channelizer");
 	if (b->d_irescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_IMS_RESCUE is not available for the decoder batch behind a channelizer");
+	if (b->d_arescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_AFSK_RESCUE is not available for the decoder batch behind a channelizer");
 	const size_t n_out = n_steps / 5 * 12;
 	if (n_steps == 0 || n_steps % 2560 || n_out > b->max_samples || ba->row_stride < n_steps + 16)
 		return sd_fail("sd_batch_submit_bins: n_steps must be a multiple of 2560 within max_samples");
@@ -413,8 +415,8 @@ static int launch_framers(SondeBatch *b, SubmitCtx &cx, int t, hipStream_t sk, u
 // (SPEC 3.3c) over the same channels: directly behind the kernel that wrote the records (the demod kernel's epilogue, or
 // sd_rsdec_rs41_kernel), before anything joins that stream or records the submit's completion.  whole_batch: the launch covered
 // channels 0..n-1 of an all-RS41 batch, and the rescue pass needs no list.  Behind M10's and MRZ-N1's, in the same way, the pass of
-// SONDE_FLAG_MANCHESTER_RESCUE (SPEC 3.3f), behind DFM's that of SONDE_FLAG_DFM_RESCUE (SPEC 3.3g), and behind iMS-100's that of
-// SONDE_FLAG_IMS_RESCUE (SPEC 3.3h).
+// SONDE_FLAG_MANCHESTER_RESCUE (SPEC 3.3f), behind DFM's that of SONDE_FLAG_DFM_RESCUE (SPEC 3.3g), behind iMS-100's that of
+// SONDE_FLAG_IMS_RESCUE (SPEC 3.3h), and behind iMet's and C50's that of SONDE_FLAG_AFSK_RESCUE (SPEC 3.3i).
 static int launch_decoders(SondeBatch *b, SubmitCtx &cx, uint32_t types, hipStream_t sk, uint32_t off = 0, uint32_t nch = 0, bool whole_batch = false)
 {
 	for (int t = 0; t < SONDE_NTYPES; t++) {
@@ -435,6 +437,12 @@ static int launch_decoders(SondeBatch *b, SubmitCtx &cx, uint32_t types, hipStre
 		if (t == SONDE_IMS100 && b->d_irescue && !b->chlist[t].empty()) {
 			sd_launch_rescue_ims(nch ? nch : (uint32_t)b->chlist[t].size(), sk, b->fec.g64, b->d_states, b->d_bitring, b->ring_words,
 				cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_chlist[t] + off, b->d_irescue);
+			HIPCHK(hipGetLastError());
+			cx.framer_launched = true;
+		}
+		if ((t == SONDE_IMET4 || t == SONDE_C50) && b->d_arescue && !b->chlist[t].empty()) {
+			sd_launch_rescue_afsk(nch ? nch : (uint32_t)b->chlist[t].size(), sk, cx.slot->d_frames, cx.slot->d_counts, b->max_frames,
+				b->d_chlist[t] + off, b->d_arescue);
 			HIPCHK(hipGetLastError());
 			cx.framer_launched = true;
 		}
@@ -673,6 +681,10 @@ extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *chann
 	}
 	if (b->d_irescue) {                        // SPEC 3.3h: a restarted channel's counters are zero
 		sd_launch_ims_rescue_clear((uint32_t)n, s, lb->dev, b->d_irescue);
+		HIPCHK(hipGetLastError());
+	}
+	if (b->d_arescue) {                        // SPEC 3.3i: a restarted channel's counters are zero
+		sd_launch_afsk_rescue_clear((uint32_t)n, s, lb->dev, b->d_arescue);
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(b->restart_lists.done(lb, s));

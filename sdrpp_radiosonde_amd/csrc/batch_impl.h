@@ -164,4 +164,7 @@ struct SondeBatch {
 	// SONDE_FLAG_IMS_RESCUE (SPEC 3.3h): per-channel counters of the second pass over iMS-100 records (ims_rescue_kernel.hip); null: the
 	// flag is off or the batch has no iMS-100 channel, and nothing of it is allocated or launched
 	DevBuf<SdImsRescueState> d_irescue;
+	// SONDE_FLAG_AFSK_RESCUE (SPEC 3.3i): per-channel counters of the second pass over iMet and C50 records (afsk_rescue_kernel.hip);
+	// null: the flag is off or the batch has no iMet or C50 channel, and nothing of it is allocated or launched
+	DevBuf<SdAfskRescueState> d_arescue;
 };

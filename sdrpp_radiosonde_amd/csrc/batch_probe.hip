@@ -133,6 +133,37 @@ extern "C" int sonde_batch_test_ims_block(SondeBatch *b, size_t n, uint64_t *blo
 	return 0;
 }
 
+extern "C" int sonde_batch_afsk_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued)
+{
+	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_afsk_rescue_info: bad argument");
+	if (b->behind_channelizer) return sd_fail("sonde_batch_afsk_rescue_info: SONDE_FLAG_AFSK_RESCUE is not available for the batch behind a channelizer");
+	if (!b->d_arescue) return sd_fail("sonde_batch_afsk_rescue_info: the batch was created without SONDE_FLAG_AFSK_RESCUE (or has no iMet or C50 channel)");
+	if (b->types[channel] != SONDE_IMET4 && b->types[channel] != SONDE_C50) return sd_fail("sonde_batch_afsk_rescue_info: not an iMet or C50 channel");
+	if (sonde_batch_sync(b) < 0) return -1;
+	SdAfskRescueState st;
+	HIPCHK(hipMemcpy(&st, b->d_arescue + channel, sizeof(st), hipMemcpyDeviceToHost));
+	if (tried) *tried = st.tried;
+	if (rescued) *rescued = st.rescued;
+	return 0;
+}
+
+// Steps 1..5 of SPEC 3.3i alone, through the kernel's own device function: n caller-made records, rewritten in place where rescued;
+// status[i] = 0 untouched (not eligible, or no pattern fits), 1 rescued, 2 several patterns fit (untouched).
+extern "C" int sonde_batch_test_afsk_repair(SondeBatch *b, SondeFrame *records, size_t n, int32_t *status)
+{
+	if (!b || !records || !status || !n || n > (1u << 20)) return sd_fail("sonde_batch_test_afsk_repair: bad argument");
+	HIPCHK(hipSetDevice(b->device));
+	DevBuf<SondeFrame> d_r;
+	DevBuf<int32_t> d_st;
+	HIPCHK(d_r.upload(records, n));
+	HIPCHK(d_st.alloc(n));
+	sd_launch_afsk_repair_unit(d_r, (uint32_t)n, d_st, nullptr);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpy(records, d_r, n * sizeof(SondeFrame), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
 // wait for the last submit and fetch the channel's demodulator state
 static int fetch_state(SondeBatch *b, uint32_t channel, SdChanState *st)
 {

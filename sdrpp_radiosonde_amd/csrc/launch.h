@@ -123,5 +123,15 @@ void sd_launch_ims_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *
 // flipped, -1 = no decode
 void sd_launch_ims_block_unit(const uint8_t *g64, uint64_t *blocks, const uint64_t *viols, uint32_t n, int32_t *status, hipStream_t stream);
 
+// SONDE_FLAG_AFSK_RESCUE (afsk_rescue_kernel.hip, DESIGN SPEC 3.3i): per iMet / C50 channel two counters (packets whose check failed that
+// reached the pattern search; packets rescued), carried from submit to submit.  chlist: never null.
+struct SdAfskRescueState { uint32_t tried, rescued; };
+void sd_launch_rescue_afsk(uint32_t n_list, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
+	const uint32_t *chlist, SdAfskRescueState *states);
+void sd_launch_afsk_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdAfskRescueState *states);
+// steps 1..5 of SPEC 3.3i alone over n caller-made records (device memory), rewritten in place; status = 0 untouched, 1 rescued,
+// 2 several patterns fit
+void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status, hipStream_t stream);
+
 // sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);

@@ -217,7 +217,7 @@ class LiveReceiver:
     def __init__(self, rate_in: int, capacity, *, probes: int = 8, initial=(), input_kind: int = INPUT_IQ, device: int = 0, max_in: int | None = None,
                  scan_seconds: float = 1.0, probe_seconds: float = 2.0, lose_after: int = 3, max_probes: int = 3, track: bool = True,
                  track_params: dict | None = None, rescue: bool = False, manchester_rescue: bool = False,
-                 dfm_rescue: bool = False, ims_rescue: bool = False):
+                 dfm_rescue: bool = False, ims_rescue: bool = False, afsk_rescue: bool = False):
         import torch
         from .detect import SondeDetector
         from .scan import SondeScanner
@@ -241,10 +241,12 @@ class LiveReceiver:
         # rescue=True: FLAG_RS41_RESCUE, the second pass over RS41 frames whose RS stage failed (SPEC 3.3c); a slot's restart clears its layout;
         # manchester_rescue=True: FLAG_MANCHESTER_RESCUE, the one over M10 / M20 / MRZ-N1 frames whose check failed (SPEC 3.3f);
         # dfm_rescue=True: FLAG_DFM_RESCUE, the one over DFM frames with a Hamming word given up on (SPEC 3.3g);
-        # ims_rescue=True: FLAG_IMS_RESCUE, the one over iMS-100 frames with a BCH block rejected (SPEC 3.3h)
+        # ims_rescue=True: FLAG_IMS_RESCUE, the one over iMS-100 frames with a BCH block rejected (SPEC 3.3h);
+        # afsk_rescue=True: FLAG_AFSK_RESCUE, the one over iMet / C50 packets whose check failed (SPEC 3.3i)
         self.batch = SondeBatch(self.n_dec, n48, types=np.array(pol.slot_type, np.uint8), input_kind=INPUT_IQ, device=device,
                                 flags=(_lib.FLAG_RS41_RESCUE if rescue else 0) | (_lib.FLAG_MANCHESTER_RESCUE if manchester_rescue else 0) |
-                                (_lib.FLAG_DFM_RESCUE if dfm_rescue else 0) | (_lib.FLAG_IMS_RESCUE if ims_rescue else 0))
+                                (_lib.FLAG_DFM_RESCUE if dfm_rescue else 0) | (_lib.FLAG_IMS_RESCUE if ims_rescue else 0) |
+                                (_lib.FLAG_AFSK_RESCUE if afsk_rescue else 0))
         self.detector = SondeDetector(self.n_probes, n48, device=device)
         self.scanner = SondeScanner(fs, self.max_in, input_kind=input_kind, device=device)
         self.track = bool(track)

@@ -179,7 +179,8 @@ class WidebandReceiver:
 
     def __init__(self, rate_in: int, sondes, *, chain: str = "iq48", input_kind: int = INPUT_IQ, device: int = 0, max_in: int | None = None,
                  track: bool = False, track_params: dict | None = None, rescue: bool = False,
-                 manchester_rescue: bool = False, dfm_rescue: bool = False, ims_rescue: bool = False):
+                 manchester_rescue: bool = False, dfm_rescue: bool = False, ims_rescue: bool = False,
+                 afsk_rescue: bool = False):
         import torch
         if chain not in ("iq48", "reference"):
             raise SondeError('chain must be "iq48" or "reference"')
@@ -236,9 +237,11 @@ class WidebandReceiver:
         # rescue=True: FLAG_RS41_RESCUE, the second pass over RS41 frames whose RS stage failed (SPEC 3.3c); manchester_rescue=True:
         # FLAG_MANCHESTER_RESCUE, the one over M10 / M20 / MRZ-N1 frames whose check failed (SPEC 3.3f); dfm_rescue=True: FLAG_DFM_RESCUE,
         # the one over DFM frames with a Hamming word given up on (SPEC 3.3g); ims_rescue=True: FLAG_IMS_RESCUE, the one over iMS-100 frames
-        # with a BCH block rejected (SPEC 3.3h)
+        # with a BCH block rejected (SPEC 3.3h); afsk_rescue=True: FLAG_AFSK_RESCUE, the one over iMet / C50 packets whose check failed
+        # (SPEC 3.3i)
         flags = ((_lib.FLAG_RS41_RESCUE if rescue else 0) | (_lib.FLAG_MANCHESTER_RESCUE if manchester_rescue else 0) |
-                 (_lib.FLAG_DFM_RESCUE if dfm_rescue else 0) | (_lib.FLAG_IMS_RESCUE if ims_rescue else 0))
+                 (_lib.FLAG_DFM_RESCUE if dfm_rescue else 0) | (_lib.FLAG_IMS_RESCUE if ims_rescue else 0) |
+                 (_lib.FLAG_AFSK_RESCUE if afsk_rescue else 0))
         self.batch = SondeBatch(len(types), n48, types=bt, input_kind=kind, device=device, flags=flags)
         stride = int(_lib.load().sonde_row_stride(n48, kind))
         shape = (len(types), stride, 2) if kind == INPUT_IQ else (len(types), stride)
