@@ -111,6 +111,9 @@ enum { SONDE_INPUT_IQ = 0,      /* complex64 interleaved I,Q at 48 kS/s (vfo->ou
                                                     * iMet / C50 packet the bits SONDE_FLAG_AFSK_RESCUE flipped: 1, or 2 (an adjacent pair) */
 #define SONDE_FRAME_WORDS(f) (((f) >> 8) & 0xFu)   /* the same bits for DFM: codewords SONDE_FLAG_DFM_RESCUE decoded with erasures (1..8) */
 #define SONDE_FRAME_BLOCKS(f) (((f) >> 8) & 0xFu)  /* the same bits for iMS-100: BCH blocks SONDE_FLAG_IMS_RESCUE decoded (1..12) */
+#define SONDE_FRAME_COMBINED 4u  /* SondeFrame.flags: an RS41 frame sonde_batch_set_diversity put together from the copies of several receivers
+                                  * (always with SONDE_FRAME_RESCUED; then SONDE_FRAME_COPIES says from how many) */
+#define SONDE_FRAME_COPIES(f) (((f) >> 8) & 0xFu)  /* the same bits for a combined RS41 frame: the copies it was made from (2..4) */
 #define SONDE_TILE       2048   /* samples; submit lengths are multiples of this */
 #define SONDE_FRAME_MAX  528
 
@@ -119,7 +122,7 @@ typedef struct {
 	uint32_t type;
 	int32_t  len;            /* bytes valid in data[] */
 	int32_t  nerr[2];        /* RS41: bytes corrected per RS codeword, -1 = uncorrectable */
-	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED; SONDE_FRAME_FLIPS / SONDE_FRAME_WORDS / SONDE_FRAME_BLOCKS */
+	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED; SONDE_FRAME_COMBINED; SONDE_FRAME_FLIPS / _WORDS / _BLOCKS / _COPIES */
 	uint64_t bitpos;         /* absolute index (since create) of the first sync bit */
 	uint8_t  data[SONDE_FRAME_MAX];   /* de-whitened, error-corrected frame */
 } SondeFrame;
@@ -278,6 +281,32 @@ int  sonde_batch_submit_host(SondeBatch *b, const void *samples, size_t n_sample
  * nothing (stream order already says so); it is what a SONDE_FLAG_LATE_JOIN / SONDE_FLAG_PIPELINE host calls before it refills a
  * single buffer, and what any host calls to release the buffer on ANOTHER stream (a copy engine's).  0 = ok. */
 int  sonde_batch_wait_input(SondeBatch *b, void *stream);
+/* SEVERAL RECEIVERS OF ONE SONDE (DESIGN SPEC 3.3j).  A host that hears a sonde more than once -- two antennas or polarisations at one
+ * site, two sites of a network -- gives each receiver a channel and names the channels of one sonde a GROUP: group[ch] = -1 (none) or a
+ * group id 0..G-1 (no gaps), 2..4 SONDE_RS41 channels per group.  offset_bits[ch] is where channel ch's bit count (SondeFrame.bitpos)
+ * stands when the group's common clock reads 0 -- the host knows when it started each stream; NULL = zeros.  After every other pass
+ * of a submit one more kernel visits the group's frame records in the order of the common clock.  A frame with a failed codeword
+ * (nerr = -1) looks in every other member for the nearest record of the same length within window_bits (0 = 960, at most 1200) of
+ * its own time, among that member's records of this submit and the newest one it carried over from earlier submits.  If one of these
+ * partners is good, the record stays (removing duplicates is the host's business).  Otherwise the copies are combined: a codeword a
+ * partner decoded is taken whole; a block whose CRC passes in any copy is trusted; elsewhere a byte more than half of the copies agree
+ * on is taken; what is left is erased, and RS(255,231) fills up to 24 erasures per codeword.  The result is taken only if both
+ * codewords and every block CRC of its own chain pass.  A combined record carries the result, nerr[c] = the bytes of codeword c that
+ * changed, SONDE_FRAME_RESCUED | SONDE_FRAME_COMBINED and SONDE_FRAME_COPIES = the copies used; channel, type, len, bitpos and the
+ * polarity bit stay, and every other record is, byte for byte, what it is without the call.  One record per transmitted frame is
+ * rewritten -- the first visited copy that has a partner; which one that is depends on how the stream is cut into submits, the set of
+ * distinct good frames a group delivers does not.  Needs no learned layout (it works before a channel's first good frame) and reaches
+ * the 93-byte GPS-raw block and the XDATA block.  Limits: a block damaged in BOTH copies is voted byte by byte and limited by 24
+ * erasures per codeword; wrong bytes that are identical in all copies count as unknown errors; drift beyond window_bits (members
+ * idling on noise, cycle slips) loses partners silently.  RS41 only.
+ * Called once, before the first submit; if it is never called nothing is allocated or launched.  Refused: a second call, a call after a
+ * submit, a group of fewer than 2 or more than 4 members, a member that is not SONDE_RS41, group ids with gaps, window_bits > 1200, the
+ * batch behind a channelizer, and a batch created with SONDE_FLAG_LATE_JOIN or SONDE_FLAG_PIPELINE (those never join their launch
+ * units into one stream, and the pass needs all members' records).  One small launch more per submit; no host synchronisation.
+ * On a batch with groups sonde_batch_restart_channels takes all members of a group or none of them (their bit counts must stay
+ * together); a restarted group loses its carried records and its counters. */
+int  sonde_batch_set_diversity(SondeBatch *b, const int32_t *group /* n_channels entries */, const int64_t *offset_bits /* n_channels entries or NULL */,
+                               uint32_t window_bits);
 /* From the next submit on each listed channel decodes as a stream that begins there (DESIGN SPEC 3.12): demodulator, AFC, discriminator
  * history, bit ring and bit count (bitpos counts from the restart), framer, tone demodulator, time-slice progress and the poll parser
  * are what sonde_batch_create set for the channel's type, which stays.  One launch for any number of channels, ordered behind the
@@ -369,6 +398,14 @@ int      sonde_batch_afsk_rescue_info(SondeBatch *b, uint32_t channel, uint32_t 
 /* SONDE_FLAG_AFSK_RESCUE's per-record routine alone (SPEC 3.3i steps 1..5), on any batch: n caller-made records, rewritten in place
  * where rescued; status[i] = 0 untouched (not eligible, or no pattern fits), 1 rescued, 2 several patterns fit (untouched). */
 int      sonde_batch_test_afsk_repair(SondeBatch *b, SondeFrame *records, size_t n, int32_t *status);
+/* sonde_batch_set_diversity introspection: the failed frames of a group that found partners none of which was good, and those that were
+ * combined, since the call / the group's restart.  Synchronises.  An error if the batch has no groups or no such group. */
+int      sonde_batch_diversity_info(SondeBatch *b, uint32_t group, uint32_t *tried, uint32_t *combined);
+/* The combining rule alone (SPEC 3.3j steps 3 to 7), on any batch: n cases of 4 caller-made records each (copies[4 i + k]; n_copies[i] =
+ * 2..4 of them are used), copy 0 the record to rewrite: 320 or 518 bytes with a failed codeword, the other copies of the same length.
+ * out[i] = copy 0, rewritten or not; status[i] = the copies used, -1 (a codeword with more than 24 erasures), -2 (no decode) or -3
+ * (rejected by the accept step). */
+int      sonde_batch_test_rs41_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status);
 uint64_t sonde_batch_nbits(SondeBatch *b, uint32_t channel);
 int      sonde_batch_read_state(SondeBatch *b, uint32_t channel, int64_t *t_next, int32_t *period, float *bias, float *amp,
                                 float *afc_u /* the newest AFC state u of SPEC 3.0b (the carrier offset the channel is following: 2 atan u per

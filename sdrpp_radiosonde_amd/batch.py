@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FLAG_AFSK_RESCUE, FLAG_DFM_RESCUE, FLAG_IMS_RESCUE, FLAG_MANCHESTER_RESCUE, FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
+from ._lib import FRAME_COMBINED, FLAG_AFSK_RESCUE, FLAG_DFM_RESCUE, FLAG_IMS_RESCUE, FLAG_MANCHESTER_RESCUE, FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
 
 
 class SondeError(RuntimeError):
@@ -236,6 +236,45 @@ class SondeBatch:
         status = np.zeros(len(rec), dtype=np.int32)
         self._chk(self.L.sonde_batch_test_afsk_repair(self.h, rec.ctypes.data_as(C.c_void_p), len(rec), status.ctypes.data_as(C.c_void_p)))
         return rec, status
+
+    def set_diversity(self, groups, offsets=None, window_bits: int = 0):
+        """The receivers of one sonde (sonde_batch_set_diversity): groups = [[channel, ...], ...], 2..4 RS41 channels each; offsets[ch] =
+        the channel's bit count when the group's common clock reads 0 (None: zeros); window_bits: how far apart two copies of a frame may
+        lie on that clock (0: 960).  Once, before the first submit."""
+        gid = np.full(self.n_channels, -1, dtype=np.int32)
+        for g, members in enumerate(groups):
+            for ch in members:
+                if not 0 <= int(ch) < self.n_channels or gid[int(ch)] >= 0:
+                    raise SondeError(f"set_diversity: channel {ch} is out of range or in two groups")
+                gid[int(ch)] = g
+            if len(members) == 0:
+                raise SondeError("set_diversity: an empty group")
+        off = None
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, dtype=np.int64)
+            assert off.shape == (self.n_channels,)
+        self._chk(self.L.sonde_batch_set_diversity(self.h, gid.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p) if off is not None else None,
+                                                   int(window_bits)))
+
+    def diversity_info(self, g: int) -> dict:
+        """set_diversity: what the pass has done for group g (sonde_batch_diversity_info): {'tried': failed frames that found partners
+        none of which was good, 'combined': frames put together from the copies}."""
+        tried, combined = C.c_uint32(), C.c_uint32()
+        self._chk(self.L.sonde_batch_diversity_info(self.h, int(g), C.byref(tried), C.byref(combined)))
+        return {"tried": int(tried.value), "combined": int(combined.value)}
+
+    def test_rs41_combine(self, copies: np.ndarray, n_copies: np.ndarray):
+        """set_diversity's combining rule alone (sonde_batch_test_rs41_combine): copies [n, 4] FRAME_DTYPE, caller-made, copy 0 the record
+        to rewrite; n_copies [n] = 2..4.  Returns (copy 0 after the rule [n], status [n]): status = the copies used, -1 too many
+        erasures, -2 no decode, -3 rejected."""
+        cp = np.ascontiguousarray(copies, dtype=FRAME_DTYPE)
+        nc = np.ascontiguousarray(n_copies, dtype=np.uint32)
+        assert cp.ndim == 2 and cp.shape[1] == 4 and nc.shape == (len(cp),)
+        out = np.zeros(len(cp), dtype=FRAME_DTYPE)
+        status = np.zeros(len(cp), dtype=np.int32)
+        self._chk(self.L.sonde_batch_test_rs41_combine(self.h, len(cp), cp.ctypes.data_as(C.c_void_p), nc.ctypes.data_as(C.c_void_p),
+                                                       out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+        return out, status
 
     def test_rs255_erasures(self, cw_pairs: np.ndarray, erased: np.ndarray, n: int):
         """The errors-and-erasures RS(255,231) corrector alone (sonde_batch_test_rs255_erasures): cw_pairs, erased [P, 2, 256] uint8

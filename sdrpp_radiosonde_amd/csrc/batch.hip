@@ -327,6 +327,7 @@ int sd_batch_submit_bins(SondeBatch *b, const SdBinsArgs *ba, size_t n_steps, vo
 	if (b->d_drescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_DFM_RESCUE is not available for the decoder batch behind a channelizer");
 	if (b->d_irescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_IMS_RESCUE is not available for the decoder batch behind a channelizer");
 	if (b->d_arescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_AFSK_RESCUE is not available for the decoder batch behind a channelizer");
+	if (b->n_groups) return sd_fail("sd_batch_submit_bins: sonde_batch_set_diversity is not available for the decoder batch behind a channelizer");
 	const size_t n_out = n_steps / 5 * 12;
 	if (n_steps == 0 || n_steps % 2560 || n_out > b->max_samples || ba->row_stride < n_steps + 16)
 		return sd_fail("sd_batch_submit_bins: n_steps must be a multiple of 2560 within max_samples");
@@ -591,6 +592,17 @@ static int record_completion(SondeBatch *b, SubmitCtx &cx)
 	return 0;
 }
 
+// Behind every other kernel of the submit, where it completes (the launch units have joined there: set_diversity refuses the
+// late-joined modes): the pass over the groups of sonde_batch_set_diversity (SPEC 3.3j)
+static int launch_diversity(SondeBatch *b, SubmitCtx &cx)
+{
+	sd_launch_diversity(b->n_groups, cx.done, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, cx.slot->d_frames, cx.slot->d_counts, b->max_frames,
+		b->d_groups, b->div_window, b->d_carried, b->d_divcnt);
+	HIPCHK(hipGetLastError());
+	cx.framer_launched = true;
+	return 0;
+}
+
 // The launch plan of a submit: (1) order it behind the previous one, (2) launch the demodulators -- the one-launch mixed kernel, one
 // plain launch (or the bins decoder), or the launch units with their fork and join --, (3) the decoders behind each launch,
 // (4) record completion.
@@ -617,6 +629,7 @@ static int submit_impl(SondeBatch *b, const void *samples, size_t n_samples, siz
 	if (b->mixed_one && !bins_in) rc = launch_mixed(b, cx);
 	else if (b->units.empty()) rc = launch_plain(b, cx);
 	else rc = launch_units(b, cx);
+	if (!rc && b->n_groups) rc = launch_diversity(b, cx);
 	return rc ? -1 : record_completion(b, cx);
 }
 
@@ -649,6 +662,18 @@ extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *chann
 	for (size_t i = 0; i < n; i++)
 		if (channels[i] >= b->n_channels) return sd_fail("sonde_batch_restart_channels: no such channel");
 	if (n == 0) return 0;
+	if (b->n_groups) {      // SPEC 3.3j: the members of a group share a time base, so they restart together or not at all
+		std::vector<uint32_t> listed(b->n_groups, 0u);
+		for (size_t i = 0; i < n; i++) {
+			const int32_t slot = b->div_slot[channels[i]];
+			if (slot >= 0) listed[(size_t)slot / SD_DIV_MAX] |= 1u << (slot % SD_DIV_MAX);
+		}
+		std::vector<uint32_t> all(b->n_groups, 0u);
+		for (const int32_t slot : b->div_slot)
+			if (slot >= 0) all[(size_t)slot / SD_DIV_MAX] |= 1u << (slot % SD_DIV_MAX);
+		for (uint32_t g = 0; g < b->n_groups; g++)
+			if (listed[g] && listed[g] != all[g]) return sd_fail("sonde_batch_restart_channels: the list must hold all members of a diversity group or none of them");
+	}
 	// the poll parsers: an entry two submits old no longer separates anything a poll can still parse, so it is dropped (its parser
 	// replaced, if there is one) -- the list stays short for a host that never polls
 	while (!b->parser_restarts.empty() && b->parser_restarts.front().first + 2 <= b->tickets) {
@@ -687,11 +712,58 @@ extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *chann
 		sd_launch_afsk_rescue_clear((uint32_t)n, s, lb->dev, b->d_arescue);
 		HIPCHK(hipGetLastError());
 	}
+	if (b->n_groups) {                         // SPEC 3.3j: a restarted group has no carried records, and its counters are zero
+		sd_launch_diversity_clear((uint32_t)n, s, lb->dev, b->d_divslot, b->d_carried, b->d_divcnt);
+		HIPCHK(hipGetLastError());
+	}
 	HIPCHK(b->restart_lists.done(lb, s));
 	if (b->join_mode != 0) {
 		HIPCHK(hipEventRecord(b->ev_restart, s));
 		for (const SondeBatch::Unit &u : b->units) HIPCHK(hipStreamWaitEvent(u.st, b->ev_restart, 0));
 	}
+	return 0;
+}
+
+// The receivers of one sonde (include/sonde_abi.h, SPEC 3.3j): the group table, the carried records and the counters
+extern "C" int sonde_batch_set_diversity(SondeBatch *b, const int32_t *group, const int64_t *offset_bits, uint32_t window_bits)
+{
+	if (!b || !group) return sd_fail("sonde_batch_set_diversity: null argument");
+	if (b->n_groups) return sd_fail("sonde_batch_set_diversity: called twice");
+	if (b->tickets) return sd_fail("sonde_batch_set_diversity: must be called before the first submit");
+	if (b->behind_channelizer) return sd_fail("sonde_batch_set_diversity: not available for the batch behind a channelizer");
+	if (b->join_mode != 0)
+		return sd_fail("sonde_batch_set_diversity: not available with SONDE_FLAG_LATE_JOIN / SONDE_FLAG_PIPELINE (the launch units never join into one stream)");
+	if (window_bits > 1200) return sd_fail("sonde_batch_set_diversity: window_bits > 1200");
+	if (b->max_frames >= 0xFFFFu) return sd_fail("sonde_batch_set_diversity: too many frames per submit");
+	int32_t top = -1;
+	for (uint32_t c = 0; c < b->n_channels; c++) {
+		if (group[c] < -1 || (uint32_t)(group[c] + 1) > b->n_channels) return sd_fail("sonde_batch_set_diversity: bad group id");
+		top = std::max(top, group[c]);
+	}
+	if (top < 0) return sd_fail("sonde_batch_set_diversity: no group");
+	std::vector<SdDivGroup> gt((size_t)top + 1);
+	std::vector<int32_t> slot(b->n_channels, -1);
+	for (SdDivGroup &g : gt) g = SdDivGroup{};
+	for (uint32_t c = 0; c < b->n_channels; c++) {
+		if (group[c] < 0) continue;
+		SdDivGroup &g = gt[(size_t)group[c]];
+		if (b->types[c] != SONDE_RS41) return sd_fail("sonde_batch_set_diversity: a member that is not SONDE_RS41");
+		if (g.n == SD_DIV_MAX) return sd_fail("sonde_batch_set_diversity: a group with more than 4 members");
+		g.ch[g.n] = c;
+		g.off[g.n] = offset_bits ? offset_bits[c] : 0;
+		slot[c] = (int32_t)(SD_DIV_MAX * (uint32_t)group[c] + g.n);
+		g.n++;
+	}
+	for (const SdDivGroup &g : gt)
+		if (g.n < 2) return sd_fail(g.n ? "sonde_batch_set_diversity: a group with fewer than 2 members" : "sonde_batch_set_diversity: group ids with gaps");
+	HIPCHK(hipSetDevice(b->device));
+	HIPCHK(b->d_groups.upload(gt.data(), gt.size()));
+	HIPCHK(b->d_carried.zeros(gt.size() * SD_DIV_MAX));
+	HIPCHK(b->d_divcnt.zeros(gt.size() * 2));
+	HIPCHK(b->d_divslot.upload(slot.data(), slot.size()));
+	b->div_slot = slot;
+	b->div_window = window_bits ? window_bits : 960u;
+	b->n_groups = (uint32_t)gt.size();
 	return 0;
 }
 

@@ -167,4 +167,13 @@ struct SondeBatch {
 	// SONDE_FLAG_AFSK_RESCUE (SPEC 3.3i): per-channel counters of the second pass over iMet and C50 records (afsk_rescue_kernel.hip);
 	// null: the flag is off or the batch has no iMet or C50 channel, and nothing of it is allocated or launched
 	DevBuf<SdAfskRescueState> d_arescue;
+	// sonde_batch_set_diversity (SPEC 3.3j): the group table, per group SD_DIV_MAX carried records and two counters, the slot
+	// (SD_DIV_MAX * group + member, or -1) of every channel on both sides; null / empty: the call was never made, and nothing of it is
+	// allocated or launched
+	uint32_t n_groups = 0, div_window = 0;
+	DevBuf<SdDivGroup> d_groups;
+	DevBuf<SondeFrame> d_carried;
+	DevBuf<uint32_t> d_divcnt;
+	DevBuf<int32_t> d_divslot;
+	std::vector<int32_t> div_slot;
 };

@@ -164,6 +164,47 @@ extern "C" int sonde_batch_test_afsk_repair(SondeBatch *b, SondeFrame *records, 
 	return 0;
 }
 
+extern "C" int sonde_batch_diversity_info(SondeBatch *b, uint32_t group, uint32_t *tried, uint32_t *combined)
+{
+	if (!b) return sd_fail("sonde_batch_diversity_info: bad argument");
+	if (!b->n_groups) return sd_fail("sonde_batch_diversity_info: sonde_batch_set_diversity was not called");
+	if (group >= b->n_groups) return sd_fail("sonde_batch_diversity_info: no such group");
+	if (sonde_batch_sync(b) < 0) return -1;
+	uint32_t cnt[2];
+	HIPCHK(hipMemcpy(cnt, b->d_divcnt + 2 * (size_t)group, sizeof(cnt), hipMemcpyDeviceToHost));
+	if (tried) *tried = cnt[0];
+	if (combined) *combined = cnt[1];
+	return 0;
+}
+
+// Steps 3 to 7 of SPEC 3.3j alone, through the kernel's own device function: n cases of 4 caller-made copies (n_copies[i] in use, copy 0
+// the record to rewrite); out[i] = copy 0, rewritten or not; status[i] = copies used, -1 too many erasures, -2 no decode, -3 rejected.
+extern "C" int sonde_batch_test_rs41_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status)
+{
+	if (!b || !copies || !n_copies || !out || !status || !n || n > (1u << 16)) return sd_fail("sonde_batch_test_rs41_combine: bad argument");
+	for (size_t i = 0; i < n; i++) {
+		const SondeFrame *c = copies + SD_DIV_MAX * i;
+		if (n_copies[i] < 2 || n_copies[i] > SD_DIV_MAX) return sd_fail("sonde_batch_test_rs41_combine: n_copies must be 2..4");
+		if ((c[0].len != 320 && c[0].len != 518) || (c[0].nerr[0] >= 0 && c[0].nerr[1] >= 0))
+			return sd_fail("sonde_batch_test_rs41_combine: copy 0 must be a 320- or 518-byte record with a failed codeword");
+		for (uint32_t k = 1; k < n_copies[i]; k++)
+			if (c[k].len != c[0].len) return sd_fail("sonde_batch_test_rs41_combine: the copies of a case must have one length");
+	}
+	HIPCHK(hipSetDevice(b->device));
+	DevBuf<SondeFrame> d_c, d_o;
+	DevBuf<uint32_t> d_n;
+	DevBuf<int32_t> d_st;
+	HIPCHK(d_c.upload(copies, SD_DIV_MAX * n));
+	HIPCHK(d_n.upload(n_copies, n));
+	HIPCHK(d_o.alloc(n));
+	HIPCHK(d_st.alloc(n));
+	sd_launch_diversity_unit(d_c, d_n, (uint32_t)n, d_o, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpy(out, d_o, n * sizeof(SondeFrame), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
 // wait for the last submit and fetch the channel's demodulator state
 static int fetch_state(SondeBatch *b, uint32_t channel, SdChanState *st)
 {

@@ -133,5 +133,19 @@ void sd_launch_afsk_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t 
 // 2 several patterns fit
 void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status, hipStream_t stream);
 
+// sonde_batch_set_diversity (diversity_kernel.hip, DESIGN SPEC 3.3j): a group = 2..4 RS41 channels that hear the same sonde; ch[m] and
+// off[m] (offset_bits) per member.  carried: [n_groups][SD_DIV_MAX] records (len = 0: none), counters: [n_groups][2] (tried, combined);
+// both carried from submit to submit.  One launch behind every other kernel of the submit.
+#define SD_DIV_MAX 4
+struct SdDivGroup { uint32_t n; uint32_t ch[SD_DIV_MAX]; uint32_t pad; int64_t off[SD_DIV_MAX]; };
+void sd_launch_diversity(uint32_t n_groups, hipStream_t stream, const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar,
+	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, uint32_t window, SondeFrame *carried, uint32_t *counters);
+// the groups of the listed channels back to "no carried record, counters zero"; slot_of[channel] = SD_DIV_MAX * group + member or -1
+void sd_launch_diversity_clear(uint32_t n, hipStream_t stream, const uint32_t *list, const int32_t *slot_of, SondeFrame *carried, uint32_t *counters);
+// steps 3 to 7 of SPEC 3.3j alone: n cases of SD_DIV_MAX copies each (device memory; n_copies[i] of them in use, copy 0 the record to
+// rewrite); out[i] = copy 0, rewritten or not; status = copies used, -1 too many erasures, -2 no decode, -3 rejected
+void sd_launch_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
+	const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar, hipStream_t stream);
+
 // sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);

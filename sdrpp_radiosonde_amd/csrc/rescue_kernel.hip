@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include "sonde_dev.h"
 #include "sd_rsee.h"
+#include "sd_rs41_crc.h"          // rq_crc16, rq_block_ok
 #include "launch.h"
 
 #define RQ_WAVES 4
@@ -19,33 +20,6 @@ struct RescueLds {                 // one per wave: 3.3 KB
 	SdRescueState st;                              // the channel's layouts and counters, carried from submit to submit
 	SondeRs41Layout cand;                          // the chain of the clean frame in work
 };
-
-// CRC16-CCITT (0x1021, init 0xFFFF) of p[0..n), a byte per step: the eight bit steps of parse.cpp's sonde_crc16_ccitt folded
-__device__ __forceinline__ uint32_t rq_crc16(const uint8_t *p, int n)
-{
-	uint32_t crc = 0xFFFFu;
-	auto step = [&](uint32_t v) {
-		uint32_t t = (crc >> 8) ^ v;
-		t ^= t >> 4;
-		crc = ((crc << 8) ^ (t << 12) ^ (t << 5) ^ t) & 0xFFFFu;
-	};
-	int i = 0;
-	for (; i + 8 <= n; i += 8) {           // eight LDS reads in flight, then the eight dependent steps (the chain is what a lane waits for)
-		uint32_t v[8];
-#pragma unroll
-		for (int q = 0; q < 8; q++) v[q] = p[i + q];
-#pragma unroll
-		for (int q = 0; q < 8; q++) step(v[q]);
-	}
-	for (; i < n; i++) step(p[i]);
-	return crc;
-}
-// block (off, len) of the frame: does the CRC behind its body match?
-__device__ __forceinline__ bool rq_block_ok(const uint8_t *frame, int off, int len)
-{
-	const uint8_t *body = frame + off + 2;
-	return rq_crc16(body, len) == ((uint32_t)body[len] | ((uint32_t)body[len + 1] << 8));
-}
 
 // the record's data words into LDS (and a second copy)
 __device__ __forceinline__ void rq_load(const SondeFrame *__restrict__ fr, uint8_t *a, uint8_t *b, int flen, int lane)
