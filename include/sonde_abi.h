@@ -114,6 +114,8 @@ enum { SONDE_INPUT_IQ = 0,      /* complex64 interleaved I,Q at 48 kS/s (vfo->ou
 #define SONDE_FRAME_COMBINED 4u  /* SondeFrame.flags: an RS41 frame sonde_batch_set_diversity put together from the copies of several receivers
                                   * (always with SONDE_FRAME_RESCUED; then SONDE_FRAME_COPIES says from how many) */
 #define SONDE_FRAME_COPIES(f) (((f) >> 8) & 0xFu)  /* the same bits for a combined RS41 frame: the copies it was made from (2..4) */
+#define SONDE_FRAME_DUPLICATE 8u /* SondeFrame.flags: a good RS41 frame of which another receiver of its diversity group has delivered a copy
+                                  * (sonde_batch_set_diversity_auto with SONDE_DIVERSITY_MARK_DUPLICATES); sonde_batch_poll leaves its fragments out */
 #define SONDE_TILE       2048   /* samples; submit lengths are multiples of this */
 #define SONDE_FRAME_MAX  528
 
@@ -122,7 +124,7 @@ typedef struct {
 	uint32_t type;
 	int32_t  len;            /* bytes valid in data[] */
 	int32_t  nerr[2];        /* RS41: bytes corrected per RS codeword, -1 = uncorrectable */
-	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED; SONDE_FRAME_COMBINED; SONDE_FRAME_FLIPS / _WORDS / _BLOCKS / _COPIES */
+	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED; SONDE_FRAME_COMBINED; SONDE_FRAME_DUPLICATE; SONDE_FRAME_FLIPS / _WORDS / _BLOCKS / _COPIES */
 	uint64_t bitpos;         /* absolute index (since create) of the first sync bit */
 	uint8_t  data[SONDE_FRAME_MAX];   /* de-whitened, error-corrected frame */
 } SondeFrame;
@@ -307,6 +309,32 @@ int  sonde_batch_wait_input(SondeBatch *b, void *stream);
  * together); a restarted group loses its carried records and its counters. */
 int  sonde_batch_set_diversity(SondeBatch *b, const int32_t *group /* n_channels entries */, const int64_t *offset_bits /* n_channels entries or NULL */,
                                uint32_t window_bits);
+/* THE SAME WITHOUT KNOWING THE OFFSETS (DESIGN SPEC 3.3k).  mode = 0 is sonde_batch_set_diversity itself; else an OR of
+ *   SONDE_DIVERSITY_LEARN            the GPU finds offset_bits itself and keeps following it.  Two good records (len 320 or 518, both nerr
+ *                                    >= 0, rescued ones included) of two members whose bytes 8 .. len are identical are the same
+ *                                    transmitted frame -- an RS41 frame carries its number and the sonde's serial --, so the difference
+ *                                    of their bitpos is the difference of the members' offsets.  Before the combining pass of every
+ *                                    submit an align step looks for such pairs among each member's records of the submit and its
+ *                                    carried record, member pairs in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), per pair the
+ *                                    match that is latest in the higher member.  A member is LOCKED once it has an offset: two unlocked
+ *                                    members lock together (the lower keeps its offset, 0 if none was given), an unlocked one joins
+ *                                    a locked one, and of two locked members that disagree the higher is re-based.  Unlocked members
+ *                                    are to the combining pass members without records.  offset_bits NULL: nothing is known, every
+ *                                    member starts unlocked; else every member starts locked at what is given (good to within
+ *                                    window_bits or not: the first common good frame corrects it).
+ *   SONDE_DIVERSITY_MARK_DUPLICATES  a good record that is identical in bytes 8 .. len to the carried record of another member, or to a
+ *                                    good record of this submit of a member with a lower index, gets SONDE_FRAME_DUPLICATE; nothing
+ *                                    else of it changes.  One copy of a transmitted frame stays unmarked however the stream is cut,
+ *                                    as long as no copy arrives later than one frame period after the first (a later one goes unmarked).
+ * Limits: the two copies of a frame must be seen at once (records of one submit, or the other member's newest earlier record): the
+ * streams may be fed up to one frame period out of step, while the bit counts themselves may stand anywhere;
+ * a group locks at its first frame that is good in two members and not before; one that never has such a frame never locks,
+ * and then nothing of it changes; two different sondes in one group never lock; failed copies teach nothing; RS41 only.  Refused: any
+ * other mode bit, and everything sonde_batch_set_diversity refuses.  One more small launch per submit when mode != 0.
+ * sonde_batch_restart_channels puts a restarted group back to what this call set: unlocked or locked at offset_bits, counters zero. */
+#define SONDE_DIVERSITY_LEARN           1u
+#define SONDE_DIVERSITY_MARK_DUPLICATES 2u
+int  sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *group, const int64_t *offset_bits, uint32_t window_bits, uint32_t mode);
 /* From the next submit on each listed channel decodes as a stream that begins there (DESIGN SPEC 3.12): demodulator, AFC, discriminator
  * history, bit ring and bit count (bitpos counts from the restart), framer, tone demodulator, time-slice progress and the poll parser
  * are what sonde_batch_create set for the channel's type, which stays.  One launch for any number of channels, ordered behind the
@@ -406,6 +434,18 @@ int      sonde_batch_diversity_info(SondeBatch *b, uint32_t group, uint32_t *tri
  * out[i] = copy 0, rewritten or not; status[i] = the copies used, -1 (a codeword with more than 24 erasures), -2 (no decode) or -3
  * (rejected by the accept step). */
 int      sonde_batch_test_rs41_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status);
+/* sonde_batch_set_diversity_auto introspection: where each member of the group stands on the group's clock now (off[m], member m = the
+ * group's m-th channel in ascending order; unused entries 0), which members are locked (bit m), how many offsets the align step has
+ * set or changed and how many records it has marked SONDE_FRAME_DUPLICATE since the call / the group's restart.  Synchronises.  With
+ * mode 0 the offsets are the host's, every member is locked and the counters are 0. */
+int      sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t off[4], uint32_t *locked_mask, uint32_t *learned, uint32_t *duplicates);
+/* The align step alone (SPEC 3.3k), on any batch: n cases of 4 members with max_rec record slots each.  Case k: n_members[k] = 2..4;
+ * member m's records of the submit are records[(4 k + m) * max_rec + i], i < counts[4 k + m] <= max_rec, its carried record is
+ * carried[4 k + m] (len 0 = none); off[4 k + m] and locked[k] are the group's state, in and out; mode[k] as above (0 .. 3);
+ * learned[k] and duplicates[k] = what the step counted.  The records come back with their flags as the step left them. */
+int      sonde_batch_test_diversity_align(SondeBatch *b, size_t n, size_t max_rec, const uint32_t *n_members, SondeFrame *records, const uint32_t *counts,
+                                          const SondeFrame *carried, int64_t *off, uint32_t *locked, const uint32_t *mode, uint32_t *learned,
+                                          uint32_t *duplicates);
 uint64_t sonde_batch_nbits(SondeBatch *b, uint32_t channel);
 int      sonde_batch_read_state(SondeBatch *b, uint32_t channel, int64_t *t_next, int32_t *period, float *bias, float *amp,
                                 float *afc_u /* the newest AFC state u of SPEC 3.0b (the carrier offset the channel is following: 2 atan u per

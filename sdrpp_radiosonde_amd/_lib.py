@@ -103,6 +103,9 @@ FLAG_WIDE_AUTO = 8       # SONDE_FLAG_WIDE for the types whose reference channel
 FLAG_RS41_RESCUE = 64    # RS41: second pass over frames whose RS stage failed, block CRCs as erasure hints (SONDE_FLAG_RS41_RESCUE; opt-in)
 FRAME_RESCUED = 2        # SondeFrame.flags bit of a frame a second pass completed (SONDE_FRAME_RESCUED)
 FRAME_COMBINED = 4       # SondeFrame.flags bit of an RS41 frame set_diversity put together from several receivers' copies (SONDE_FRAME_COMBINED)
+FRAME_DUPLICATE = 8      # SondeFrame.flags bit of a good RS41 frame another receiver of its diversity group has delivered (SONDE_FRAME_DUPLICATE)
+DIVERSITY_LEARN = 1              # set_diversity modes (SONDE_DIVERSITY_LEARN, SONDE_DIVERSITY_MARK_DUPLICATES)
+DIVERSITY_MARK_DUPLICATES = 2
 FLAG_MANCHESTER_RESCUE = 128   # M10 / M20 / MRZ-N1: second pass over frames whose check failed, Manchester violations as hints (SONDE_FLAG_MANCHESTER_RESCUE; opt-in)
 FLAG_DFM_RESCUE = 256         # DFM: second pass over frames with a Hamming word given up on, Manchester violations as erasures (SONDE_FLAG_DFM_RESCUE; opt-in)
 FLAG_IMS_RESCUE = 512         # iMS-100: second pass over frames with a BCH block rejected, biphase-S boundary violations as hints (SONDE_FLAG_IMS_RESCUE; opt-in)
@@ -159,6 +162,7 @@ ABI_SYMBOLS = [
     "sonde_batch_ims_rescue_info", "sonde_batch_test_ims_block",
     "sonde_batch_afsk_rescue_info", "sonde_batch_test_afsk_repair",
     "sonde_batch_set_diversity", "sonde_batch_diversity_info", "sonde_batch_test_rs41_combine",
+    "sonde_batch_set_diversity_auto", "sonde_batch_diversity_offsets", "sonde_batch_test_diversity_align",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -231,6 +235,10 @@ def load() -> C.CDLL:
         L.sonde_batch_set_diversity.argtypes = [vp, vp, vp, C.c_uint32]
         L.sonde_batch_diversity_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.sonde_batch_test_rs41_combine.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
+    if hasattr(L, "sonde_batch_set_diversity_auto"):      # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        L.sonde_batch_set_diversity_auto.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
+        L.sonde_batch_diversity_offsets.argtypes = [vp, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.sonde_batch_test_diversity_align.argtypes = [vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sonde_get_taps.argtypes = [C.c_int, vp]
     L.sonde_parse_frame.argtypes = [vp, C.POINTER(SondeData), C.c_int]
     L.sonde_batch_poll.argtypes = [vp, C.POINTER(SondeData), C.POINTER(C.c_uint32), C.c_size_t]

@@ -237,10 +237,14 @@ class SondeBatch:
         self._chk(self.L.sonde_batch_test_afsk_repair(self.h, rec.ctypes.data_as(C.c_void_p), len(rec), status.ctypes.data_as(C.c_void_p)))
         return rec, status
 
-    def set_diversity(self, groups, offsets=None, window_bits: int = 0):
+    def set_diversity(self, groups, offsets=None, window_bits: int = 0, *, learn: bool = False, mark_duplicates: bool = False):
         """The receivers of one sonde (sonde_batch_set_diversity): groups = [[channel, ...], ...], 2..4 RS41 channels each; offsets[ch] =
         the channel's bit count when the group's common clock reads 0 (None: zeros); window_bits: how far apart two copies of a frame may
-        lie on that clock (0: 960).  Once, before the first submit."""
+        lie on that clock (0: 960).  Once, before the first submit.
+        learn=True (sonde_batch_set_diversity_auto, SONDE_DIVERSITY_LEARN): the GPU finds the offsets itself from frames that are good
+        in two members and keeps following them; offsets=None then means that nothing is known (every member starts unlocked), else
+        they are where the members start.  mark_duplicates=True (SONDE_DIVERSITY_MARK_DUPLICATES): all but one good copy of a
+        transmitted frame get FRAME_DUPLICATE, and poll() leaves their fragments out."""
         gid = np.full(self.n_channels, -1, dtype=np.int32)
         for g, members in enumerate(groups):
             for ch in members:
@@ -253,8 +257,41 @@ class SondeBatch:
         if offsets is not None:
             off = np.ascontiguousarray(offsets, dtype=np.int64)
             assert off.shape == (self.n_channels,)
-        self._chk(self.L.sonde_batch_set_diversity(self.h, gid.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p) if off is not None else None,
-                                                   int(window_bits)))
+        offp = off.ctypes.data_as(C.c_void_p) if off is not None else None
+        mode = (_lib.DIVERSITY_LEARN if learn else 0) | (_lib.DIVERSITY_MARK_DUPLICATES if mark_duplicates else 0)
+        if mode:
+            self._chk(self.L.sonde_batch_set_diversity_auto(self.h, gid.ctypes.data_as(C.c_void_p), offp, int(window_bits), mode))
+        else:
+            self._chk(self.L.sonde_batch_set_diversity(self.h, gid.ctypes.data_as(C.c_void_p), offp, int(window_bits)))
+
+    def diversity_offsets(self, g: int) -> dict:
+        """set_diversity: where group g stands (sonde_batch_diversity_offsets): {'offsets': [bit offset of each of the four member slots on
+        the group's clock], 'locked': a bit per member that has an offset, 'learned': offsets the align step set or changed,
+        'duplicates': records it marked FRAME_DUPLICATE}."""
+        off = np.zeros(4, dtype=np.int64)
+        locked, learned, dups = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.L.sonde_batch_diversity_offsets(self.h, int(g), off.ctypes.data_as(C.c_void_p), C.byref(locked), C.byref(learned), C.byref(dups)))
+        return {"offsets": [int(v) for v in off], "locked": int(locked.value), "learned": int(learned.value), "duplicates": int(dups.value)}
+
+    def test_diversity_align(self, records: np.ndarray, counts: np.ndarray, n_members: np.ndarray, carried: np.ndarray, off: np.ndarray,
+                             locked: np.ndarray, mode: np.ndarray):
+        """set_diversity's align step alone (sonde_batch_test_diversity_align): records [n, 4, R] FRAME_DTYPE, caller-made, counts [n, 4]
+        of them in use; n_members [n] = 2..4; carried [n, 4] (len 0: none); off [n, 4] int64, locked [n], mode [n].  Returns (records
+        with their flags as the step left them, off, locked, learned [n], duplicates [n])."""
+        rec = np.ascontiguousarray(records, dtype=FRAME_DTYPE).copy()
+        assert rec.ndim == 3 and rec.shape[1] == 4
+        n, R = rec.shape[0], rec.shape[2]
+        cnt = np.ascontiguousarray(counts, dtype=np.uint32)
+        nm = np.ascontiguousarray(n_members, dtype=np.uint32)
+        car = np.ascontiguousarray(carried, dtype=FRAME_DTYPE)
+        o = np.ascontiguousarray(off, dtype=np.int64).copy()
+        lk = np.ascontiguousarray(locked, dtype=np.uint32).copy()
+        md = np.ascontiguousarray(mode, dtype=np.uint32)
+        assert cnt.shape == (n, 4) and nm.shape == (n,) and car.shape == (n, 4) and o.shape == (n, 4) and lk.shape == (n,) and md.shape == (n,)
+        learned, dups = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        self._chk(self.L.sonde_batch_test_diversity_align(self.h, n, R, p(nm), p(rec), p(cnt), p(car), p(o), p(lk), p(md), p(learned), p(dups)))
+        return rec, o, lk, learned, dups
 
     def diversity_info(self, g: int) -> dict:
         """set_diversity: what the pass has done for group g (sonde_batch_diversity_info): {'tried': failed frames that found partners

@@ -596,8 +596,13 @@ static int record_completion(SondeBatch *b, SubmitCtx &cx)
 // late-joined modes): the pass over the groups of sonde_batch_set_diversity (SPEC 3.3j)
 static int launch_diversity(SondeBatch *b, SubmitCtx &cx)
 {
+	if (b->div_mode) {      // SPEC 3.3k: the align step first -- it sets the offsets and lock bits the pass reads, and marks duplicates
+		sd_launch_diversity_align(b->n_groups, cx.done, cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_groups, b->d_carried,
+			b->d_divstate, b->div_mode);
+		HIPCHK(hipGetLastError());
+	}
 	sd_launch_diversity(b->n_groups, cx.done, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, cx.slot->d_frames, cx.slot->d_counts, b->max_frames,
-		b->d_groups, b->div_window, b->d_carried, b->d_divcnt);
+		b->d_groups, b->d_divstate, b->div_window, b->d_carried, b->d_divcnt);
 	HIPCHK(hipGetLastError());
 	cx.framer_launched = true;
 	return 0;
@@ -713,7 +718,7 @@ extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *chann
 		HIPCHK(hipGetLastError());
 	}
 	if (b->n_groups) {                         // SPEC 3.3j: a restarted group has no carried records, and its counters are zero
-		sd_launch_diversity_clear((uint32_t)n, s, lb->dev, b->d_divslot, b->d_carried, b->d_divcnt);
+		sd_launch_diversity_clear((uint32_t)n, s, lb->dev, b->d_divslot, b->d_carried, b->d_divcnt, b->d_groups, b->d_divstate, b->div_unlocked);
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(b->restart_lists.done(lb, s));
@@ -724,10 +729,17 @@ extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *chann
 	return 0;
 }
 
-// The receivers of one sonde (include/sonde_abi.h, SPEC 3.3j): the group table, the carried records and the counters
+// The receivers of one sonde (include/sonde_abi.h, SPEC 3.3j and 3.3k): the group table, the carried records, the counters and the
+// align step's state.  mode 0 is sonde_batch_set_diversity.
 extern "C" int sonde_batch_set_diversity(SondeBatch *b, const int32_t *group, const int64_t *offset_bits, uint32_t window_bits)
 {
+	return sonde_batch_set_diversity_auto(b, group, offset_bits, window_bits, 0u);
+}
+
+extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *group, const int64_t *offset_bits, uint32_t window_bits, uint32_t mode)
+{
 	if (!b || !group) return sd_fail("sonde_batch_set_diversity: null argument");
+	if (mode & ~(SONDE_DIVERSITY_LEARN | SONDE_DIVERSITY_MARK_DUPLICATES)) return sd_fail("sonde_batch_set_diversity_auto: unknown mode bits");
 	if (b->n_groups) return sd_fail("sonde_batch_set_diversity: called twice");
 	if (b->tickets) return sd_fail("sonde_batch_set_diversity: must be called before the first submit");
 	if (b->behind_channelizer) return sd_fail("sonde_batch_set_diversity: not available for the batch behind a channelizer");
@@ -761,6 +773,17 @@ extern "C" int sonde_batch_set_diversity(SondeBatch *b, const int32_t *group, co
 	HIPCHK(b->d_carried.zeros(gt.size() * SD_DIV_MAX));
 	HIPCHK(b->d_divcnt.zeros(gt.size() * 2));
 	HIPCHK(b->d_divslot.upload(slot.data(), slot.size()));
+	// SPEC 3.3k: with SONDE_DIVERSITY_LEARN and no offsets nothing is known and every member starts unlocked; else all are locked
+	const bool unlocked = (mode & SONDE_DIVERSITY_LEARN) && !offset_bits;
+	std::vector<SdDivState> st(gt.size());
+	for (size_t g = 0; g < gt.size(); g++) {
+		st[g] = SdDivState{};
+		for (uint32_t m = 0; m < gt[g].n; m++) st[g].off[m] = gt[g].off[m];
+		st[g].locked = unlocked ? 0u : (1u << gt[g].n) - 1u;
+	}
+	HIPCHK(b->d_divstate.upload(st.data(), st.size()));
+	b->div_mode = mode;
+	b->div_unlocked = unlocked ? 1u : 0u;
 	b->div_slot = slot;
 	b->div_window = window_bits ? window_bits : 960u;
 	b->n_groups = (uint32_t)gt.size();

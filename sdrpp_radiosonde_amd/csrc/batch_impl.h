@@ -170,8 +170,11 @@ struct SondeBatch {
 	// sonde_batch_set_diversity (SPEC 3.3j): the group table, per group SD_DIV_MAX carried records and two counters, the slot
 	// (SD_DIV_MAX * group + member, or -1) of every channel on both sides; null / empty: the call was never made, and nothing of it is
 	// allocated or launched
-	uint32_t n_groups = 0, div_window = 0;
+	// div_mode: sonde_batch_set_diversity_auto's mode (SPEC 3.3k; 0: no align step is launched), div_unlocked: its groups start unlocked;
+	// d_divstate: per group the offsets and lock bits the combining pass reads, and the align step's counters
+	uint32_t n_groups = 0, div_window = 0, div_mode = 0, div_unlocked = 0;
 	DevBuf<SdDivGroup> d_groups;
+	DevBuf<SdDivState> d_divstate;
 	DevBuf<SondeFrame> d_carried;
 	DevBuf<uint32_t> d_divcnt;
 	DevBuf<int32_t> d_divslot;

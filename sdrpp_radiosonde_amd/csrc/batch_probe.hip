@@ -205,6 +205,64 @@ extern "C" int sonde_batch_test_rs41_combine(SondeBatch *b, size_t n, const Sond
 	return 0;
 }
 
+extern "C" int sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t off[4], uint32_t *locked_mask, uint32_t *learned, uint32_t *duplicates)
+{
+	if (!b) return sd_fail("sonde_batch_diversity_offsets: bad argument");
+	if (!b->n_groups) return sd_fail("sonde_batch_diversity_offsets: sonde_batch_set_diversity was not called");
+	if (group >= b->n_groups) return sd_fail("sonde_batch_diversity_offsets: no such group");
+	if (sonde_batch_sync(b) < 0) return -1;
+	if (b->tickets) HIPCHK(hipStreamSynchronize(b->last_stream));      // a restart queued behind the last submit has written the state too
+	SdDivState st;
+	HIPCHK(hipMemcpy(&st, b->d_divstate + (size_t)group, sizeof(st), hipMemcpyDeviceToHost));
+	for (int m = 0; off && m < SD_DIV_MAX; m++) off[m] = st.off[m];
+	if (locked_mask) *locked_mask = st.locked;
+	if (learned) *learned = st.learned;
+	if (duplicates) *duplicates = st.duplicates;
+	return 0;
+}
+
+// The align step of SPEC 3.3k alone, through the kernel's own device function (include/sonde_abi.h)
+extern "C" int sonde_batch_test_diversity_align(SondeBatch *b, size_t n, size_t max_rec, const uint32_t *n_members, SondeFrame *records, const uint32_t *counts,
+	const SondeFrame *carried, int64_t *off, uint32_t *locked, const uint32_t *mode, uint32_t *learned, uint32_t *duplicates)
+{
+	if (!b || !n_members || !records || !counts || !carried || !off || !locked || !mode || !learned || !duplicates || !n || n > (1u << 12) || !max_rec ||
+		max_rec > 1024)
+		return sd_fail("sonde_batch_test_diversity_align: bad argument");
+	std::vector<SdDivState> st(n);
+	for (size_t k = 0; k < n; k++) {
+		if (n_members[k] < 2 || n_members[k] > SD_DIV_MAX) return sd_fail("sonde_batch_test_diversity_align: n_members must be 2..4");
+		if (mode[k] & ~(SONDE_DIVERSITY_LEARN | SONDE_DIVERSITY_MARK_DUPLICATES)) return sd_fail("sonde_batch_test_diversity_align: unknown mode bits");
+		if (locked[k] >> n_members[k]) return sd_fail("sonde_batch_test_diversity_align: a lock bit of a member the case does not have");
+		st[k] = SdDivState{};
+		for (uint32_t m = 0; m < SD_DIV_MAX; m++) {
+			if (counts[SD_DIV_MAX * k + m] > max_rec) return sd_fail("sonde_batch_test_diversity_align: counts > max_rec");
+			st[k].off[m] = off[SD_DIV_MAX * k + m];
+		}
+		st[k].locked = locked[k];
+	}
+	HIPCHK(hipSetDevice(b->device));
+	DevBuf<SondeFrame> d_r, d_c;
+	DevBuf<uint32_t> d_cnt, d_nm, d_mode;
+	DevBuf<SdDivState> d_st;
+	HIPCHK(d_r.upload(records, SD_DIV_MAX * n * max_rec));
+	HIPCHK(d_c.upload(carried, SD_DIV_MAX * n));
+	HIPCHK(d_cnt.upload(counts, SD_DIV_MAX * n));
+	HIPCHK(d_nm.upload(n_members, n));
+	HIPCHK(d_mode.upload(mode, n));
+	HIPCHK(d_st.upload(st.data(), n));
+	sd_launch_diversity_align_unit((uint32_t)n, nullptr, d_r, d_cnt, (uint32_t)max_rec, d_nm, d_c, d_st, d_mode);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpy(records, d_r, SD_DIV_MAX * n * max_rec * sizeof(SondeFrame), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(st.data(), d_st, n * sizeof(SdDivState), hipMemcpyDeviceToHost));
+	for (size_t k = 0; k < n; k++) {
+		for (uint32_t m = 0; m < SD_DIV_MAX; m++) off[SD_DIV_MAX * k + m] = st[k].off[m];
+		locked[k] = st[k].locked;
+		learned[k] = st[k].learned;
+		duplicates[k] = st[k].duplicates;
+	}
+	return 0;
+}
+
 // wait for the last submit and fetch the channel's demodulator state
 static int fetch_state(SondeBatch *b, uint32_t channel, SdChanState *st)
 {

@@ -129,7 +129,8 @@ extern "C" long sonde_batch_poll(SondeBatch *b, SondeData *out, uint32_t *channe
 			if (c >= b->n_channels) continue;
 			if (!b->parsers[c]) b->parsers[c].reset(new SondeParser((int)b->types[c]));
 			v.clear();
-			b->parsers[c]->feed(fr[(size_t)i], v);
+			b->parsers[c]->feed(fr[(size_t)i], v);      // a duplicate too: the parser's calibration state keeps learning
+			if (fr[(size_t)i].flags & SONDE_FRAME_DUPLICATE) continue;      // SPEC 3.3k: another receiver of the group has delivered this frame
 			for (const SondeData &d : v) b->frags.emplace_back(c, d);
 		}
 		b->polled_ticket = t;

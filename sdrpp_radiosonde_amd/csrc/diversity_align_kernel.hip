@@ -1,0 +1,170 @@
+// diversity_align_kernel.hip -- sonde_batch_set_diversity_auto (DESIGN SPEC 3.3k): the align step in front of the combining pass of
+// diversity_kernel.hip.  Two good RS41 records of different members whose bytes 8 .. len are identical are the same transmitted frame
+// (the frame carries its number and the sonde's serial); from such pairs the step learns where each member's bit count stands on the
+// group's clock (SONDE_DIVERSITY_LEARN), and it marks all but one copy of a frame (SONDE_DIVERSITY_MARK_DUPLICATES).
+//   one 64-lane wave per group, a launch of its own in front of sd_diversity_kernel on the stream where the submit completes.  The
+//   lanes take one member's records (any number: the loops stride by 64) and each walks the other member's; a record's key is two
+//   words of its RS parity bytes, which differ between any two frames, so the byte compare runs for true matches only.
+// Writes: the group's SdDivState (lane 0) and the duplicate bit of records (each record by the one lane that owns it).  Nothing the
+// step reads of a record (len, nerr, bitpos, data) is written here, and the carried records are only read.  Vector stores only.
+#include <hip/hip_runtime.h>
+#include "sonde_dev.h"
+#include "launch.h"
+
+#define AL_U(x) __builtin_amdgcn_readfirstlane((int)(x))
+
+// a member's candidates: recs[0 .. cnt) are its records of this submit, index cnt is its carried record
+struct AlMember { SondeFrame *recs; const SondeFrame *carried; uint32_t cnt; };
+
+__device__ __forceinline__ const SondeFrame *al_cand(const AlMember &M, uint32_t i) { return i < M.cnt ? M.recs + i : M.carried; }
+__device__ __forceinline__ bool al_good(const SondeFrame *f) { return (f->len == 320 || f->len == 518) && f->nerr[0] >= 0 && f->nerr[1] >= 0; }
+__device__ __forceinline__ uint32_t al_key(const SondeFrame *f)
+{
+	const uint32_t *w = reinterpret_cast<const uint32_t *>(f->data);
+	return w[2] ^ w[8];                                // parity bytes of codeword 0 and of codeword 1
+}
+// two good records: the same length and data[8 .. len) identical (len is 320 or 518: whole words, and for 518 two bytes of word 129)
+__device__ __forceinline__ bool al_match(const SondeFrame *x, const SondeFrame *y)
+{
+	const int len = x->len;
+	if (y->len != len || al_key(x) != al_key(y)) return false;
+	const uint32_t *a = reinterpret_cast<const uint32_t *>(x->data), *b = reinterpret_cast<const uint32_t *>(y->data);
+	uint32_t diff = 0;
+	for (int i = 2; i < len / 4; i++) diff |= a[i] ^ b[i];
+	if (len & 3) diff |= (a[len / 4] ^ b[len / 4]) & ((1u << (8 * (len & 3))) - 1u);
+	return diff == 0;
+}
+
+__device__ __forceinline__ int64_t al_u64(int64_t v)
+{
+	return (int64_t)(((uint64_t)(uint32_t)AL_U((uint32_t)((uint64_t)v >> 32)) << 32) | (uint32_t)AL_U((uint32_t)(uint64_t)v));
+}
+
+// the learn rule for the pair (A, B): the match with the greatest bitpos in B (of several, the one with the greatest bitpos in A).
+// Returns true if there is a match; then d = bitpos_B - bitpos_A.  Wave-uniform result.
+__device__ bool al_pair(const AlMember &A, const AlMember &B, int lane, int64_t &d)
+{
+	int64_t bb = -1, ba = -1;                          // bitpos < 2^63
+	for (uint32_t j = (uint32_t)lane; j <= B.cnt; j += 64) {
+		const SondeFrame *fb = al_cand(B, j);
+		if (!al_good(fb)) continue;
+		const int64_t pb = (int64_t)fb->bitpos;
+		if (pb < bb) continue;
+		for (uint32_t i = 0; i <= A.cnt; i++) {
+			const SondeFrame *fa = al_cand(A, i);
+			if (!al_good(fa) || !al_match(fa, fb)) continue;
+			const int64_t pa = (int64_t)fa->bitpos;
+			if (pb > bb || pa > ba) { bb = pb; ba = pa; }
+		}
+	}
+#pragma unroll
+	for (int sh = 32; sh >= 1; sh >>= 1) {
+		const int64_t ob = __shfl_xor((long long)bb, sh, 64), oa = __shfl_xor((long long)ba, sh, 64);
+		if (ob > bb || (ob == bb && oa > ba)) { bb = ob; ba = oa; }
+	}
+	bb = al_u64(bb); ba = al_u64(ba);
+	d = bb - ba;
+	return bb >= 0;
+}
+
+// The align step of one group (SPEC 3.3k).  M[m], m < nm: the members; st: the group's state, read and written by this wave alone.
+__device__ void al_group(AlMember (&M)[SD_DIV_MAX], int nm, SdDivState *st, uint32_t mode, int lane)
+{
+	int64_t off[SD_DIV_MAX];
+#pragma unroll
+	for (int m = 0; m < SD_DIV_MAX; m++) off[m] = al_u64(st->off[m]);
+	uint32_t locked = (uint32_t)AL_U(st->locked), learned = 0, dups = 0;
+	if (mode & SONDE_DIVERSITY_LEARN) {
+#pragma unroll
+		for (int a = 0; a < SD_DIV_MAX - 1; a++) {
+#pragma unroll
+			for (int b = a + 1; b < SD_DIV_MAX; b++) {
+				if (b >= nm) continue;
+				int64_t d;
+				if (!al_pair(M[a], M[b], lane, d)) continue;
+				const bool la = (locked >> a) & 1u, lb = (locked >> b) & 1u;
+				if (lb && !la) { off[a] = off[b] - d; learned++; }
+				else if (!la || !lb || off[b] - off[a] != d) { off[b] = off[a] + d; learned++; }
+				locked |= (1u << a) | (1u << b);
+			}
+		}
+	}
+	if (mode & SONDE_DIVERSITY_MARK_DUPLICATES) {
+#pragma unroll
+		for (int b = 0; b < SD_DIV_MAX; b++) {
+			if (b >= nm) continue;
+			for (uint32_t j0 = 0; j0 < M[b].cnt; j0 += 64) {
+				const uint32_t j = j0 + (uint32_t)lane;
+				bool dup = false;
+				if (j < M[b].cnt && al_good(M[b].recs + j)) {
+					const SondeFrame *fb = M[b].recs + j;
+#pragma unroll
+					for (int a = 0; a < SD_DIV_MAX; a++) {
+						if (a >= nm || a == b || dup) continue;
+						if (al_good(M[a].carried) && al_match(M[a].carried, fb)) dup = true;
+						for (uint32_t i = 0; a < b && !dup && i < M[a].cnt; i++)
+							dup = al_good(M[a].recs + i) && al_match(M[a].recs + i, fb);
+					}
+					if (dup) M[b].recs[j].flags |= SONDE_FRAME_DUPLICATE;
+				}
+				dups += (uint32_t)__popcll(__ballot(dup));
+			}
+		}
+	}
+	if (lane == 0) {
+#pragma unroll
+		for (int m = 0; m < SD_DIV_MAX; m++) st->off[m] = off[m];
+		st->locked = locked;
+		st->learned += learned;
+		st->duplicates += dups;
+	}
+}
+
+__global__ __launch_bounds__(64) void sd_diversity_align_kernel(SondeFrame *frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
+	const SdDivGroup *__restrict__ groups, const SondeFrame *__restrict__ carried, SdDivState *states, uint32_t mode)
+{
+	const uint32_t g = blockIdx.x;
+	const int lane = (int)threadIdx.x;
+	const SdDivGroup *G = groups + g;
+	const int nm = AL_U(G->n);
+	AlMember M[SD_DIV_MAX];
+#pragma unroll
+	for (int m = 0; m < SD_DIV_MAX; m++) {
+		const uint32_t ch = m < nm ? (uint32_t)AL_U(G->ch[m]) : 0u;
+		M[m].recs = frames + (size_t)ch * max_frames;
+		M[m].cnt = m < nm ? (uint32_t)AL_U(min(counts[ch], max_frames)) : 0u;
+		M[m].carried = carried + (size_t)SD_DIV_MAX * g + m;
+	}
+	al_group(M, nm, states + g, mode, lane);
+}
+
+void sd_launch_diversity_align(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
+	const SdDivGroup *groups, const SondeFrame *carried, SdDivState *states, uint32_t mode)
+{
+	hipLaunchKernelGGL(sd_diversity_align_kernel, dim3(n_groups), dim3(64), 0, stream, frames, counts, max_frames, groups, carried, states, mode);
+}
+
+// ---- test introspection: the align step alone on caller-made records (sonde_batch_test_diversity_align).  One wave per case; case k
+// has SD_DIV_MAX members of max_rec record slots each (counts[4 k + m] <= max_rec in use), SD_DIV_MAX carried records, its state and
+// its mode; the host has checked n_members (2..4), the counts and the modes.
+__global__ __launch_bounds__(64) void sd_diversity_align_unit_kernel(SondeFrame *records, const uint32_t *__restrict__ counts, uint32_t max_rec,
+	const uint32_t *__restrict__ n_members, const SondeFrame *__restrict__ carried, SdDivState *states, const uint32_t *__restrict__ modes)
+{
+	const uint32_t k = blockIdx.x;
+	const int lane = (int)threadIdx.x;
+	const int nm = AL_U(n_members[k]);
+	AlMember M[SD_DIV_MAX];
+#pragma unroll
+	for (int m = 0; m < SD_DIV_MAX; m++) {
+		M[m].recs = records + ((size_t)SD_DIV_MAX * k + m) * max_rec;
+		M[m].cnt = m < nm ? (uint32_t)AL_U(min(counts[SD_DIV_MAX * k + m], max_rec)) : 0u;
+		M[m].carried = carried + (size_t)SD_DIV_MAX * k + m;
+	}
+	al_group(M, nm, states + k, (uint32_t)AL_U(modes[k]), lane);
+}
+
+void sd_launch_diversity_align_unit(uint32_t n, hipStream_t stream, SondeFrame *records, const uint32_t *counts, uint32_t max_rec,
+	const uint32_t *n_members, const SondeFrame *carried, SdDivState *states, const uint32_t *modes)
+{
+	hipLaunchKernelGGL(sd_diversity_align_unit_kernel, dim3(n), dim3(64), 0, stream, records, counts, max_rec, n_members, carried, states, modes);
+}

@@ -214,7 +214,8 @@ __device__ __forceinline__ uint32_t dv_wave_min(uint32_t v)
 __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(
 	const uint8_t *__restrict__ gf_exp, const uint8_t *__restrict__ gf_log, const uint32_t *__restrict__ gf_swar,
 	SondeFrame *frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const SdDivGroup *__restrict__ groups, uint32_t n_groups, uint32_t window, SondeFrame *carried, uint32_t *counters /* [n_groups][2] */)
+	const SdDivGroup *__restrict__ groups, const SdDivState *states, uint32_t n_groups, uint32_t window, SondeFrame *carried,
+	uint32_t *counters /* [n_groups][2] */)
 {
 	__shared__ __attribute__((aligned(16))) FramerTabs tabs;
 	__shared__ __attribute__((aligned(16))) DivLds wl[DV_WAVES];
@@ -226,15 +227,20 @@ __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(
 	DivLds &s = wl[w];
 	const SdDivGroup *G = groups + g;
 	const int nm = DV_U(G->n);
-	// the members: channel, offset, records of this submit (wave-uniform; the member loops below are unrolled over SD_DIV_MAX)
-	uint32_t ch[SD_DIV_MAX], cnt[SD_DIV_MAX], start[SD_DIV_MAX + 1];
+	// the members: channel, offset, records of this submit (wave-uniform; the member loops below are unrolled over SD_DIV_MAX).  The
+	// offsets and the lock bits are the align step's (SPEC 3.3k; an earlier launch, or as set_diversity left them): to steps 1 to 8 an
+	// unlocked member has no records (cnt), all[] is what the carried records are kept up to date from
+	const SdDivState *S = states + g;
+	const uint32_t lockmask = (uint32_t)DV_U(dv_load_fresh(&S->locked));
+	uint32_t ch[SD_DIV_MAX], cnt[SD_DIV_MAX], all[SD_DIV_MAX], start[SD_DIV_MAX + 1];
 	int64_t ofs[SD_DIV_MAX];
 	start[0] = 0;
 #pragma unroll
 	for (int m = 0; m < SD_DIV_MAX; m++) {
 		ch[m] = m < nm ? (uint32_t)DV_U(G->ch[m]) : 0u;
-		cnt[m] = m < nm ? (uint32_t)DV_U(min(counts[ch[m]], max_frames)) : 0u;
-		ofs[m] = m < nm ? dv_u64(G->off[m]) : 0;
+		all[m] = m < nm ? (uint32_t)DV_U(min(counts[ch[m]], max_frames)) : 0u;
+		cnt[m] = (lockmask >> m) & 1u ? all[m] : 0u;
+		ofs[m] = m < nm ? dv_u64((int64_t)__hip_atomic_load(reinterpret_cast<const uint64_t *>(&S->off[m]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0;
 		start[m + 1] = start[m] + cnt[m];
 	}
 	const uint32_t total = start[SD_DIV_MAX];
@@ -283,7 +289,7 @@ __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(
 		bool any_good = false;
 #pragma unroll
 		for (int b = 0; b < SD_DIV_MAX; b++) {
-			if (b >= nm || b == m_r || any_good) continue;
+			if (b >= nm || b == m_r || any_good || !((lockmask >> b) & 1u)) continue;
 			uint32_t best = 0xFFFFFFFFu;
 			const SondeFrame *cf = carried + (size_t)SD_DIV_MAX * g + b;
 			for (uint32_t j = (uint32_t)lane; j <= cnt_of(b); j += 64) {       // j = cnt: the carried record
@@ -328,7 +334,7 @@ __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(
 	for (int m = 0; m < SD_DIV_MAX; m++) {
 		if (m >= nm) continue;
 		uint32_t newest = 0;                           // record + 1
-		for (uint32_t j = (uint32_t)lane; j < cnt[m]; j += 64) {
+		for (uint32_t j = (uint32_t)lane; j < all[m]; j += 64) {
 			const int len = rec_of(m, j)->len;
 			if (len == 320 || len == 518) newest = j + 1u;
 		}
@@ -342,26 +348,38 @@ __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(
 }
 
 void sd_launch_diversity(uint32_t n_groups, hipStream_t stream, const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar,
-	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, uint32_t window, SondeFrame *carried, uint32_t *counters)
+	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, const SdDivState *states, uint32_t window,
+	SondeFrame *carried, uint32_t *counters)
 {
 	hipLaunchKernelGGL(sd_diversity_kernel, dim3((n_groups + DV_WAVES - 1) / DV_WAVES), dim3(64 * DV_WAVES), 0, stream,
-		gf_exp, gf_log, gf_swar, frames, counts, max_frames, groups, n_groups, window, carried, counters);
+		gf_exp, gf_log, gf_swar, frames, counts, max_frames, groups, states, n_groups, window, carried, counters);
 }
 
-// ---- a restarted group (sonde_batch_restart_channels lists all its members): no carried records, counters zero.  One workgroup per
-// listed channel; slot_of[channel] = SD_DIV_MAX * group + member, or -1 for a channel in no group.
+// ---- a restarted group (sonde_batch_restart_channels lists all its members): no carried records, counters zero, the align step's
+// state (SPEC 3.3k) as set_diversity left it.  One workgroup per listed channel; slot_of[channel] = SD_DIV_MAX * group + member, or -1
+// for a channel in no group.  The workgroups of a group's members write the same values to the group's words.
 __global__ __launch_bounds__(64) void sd_diversity_clear_kernel(const uint32_t *__restrict__ list, const int32_t *__restrict__ slot_of,
-	SondeFrame *__restrict__ carried, uint32_t *__restrict__ counters)
+	SondeFrame *__restrict__ carried, uint32_t *__restrict__ counters, const SdDivGroup *__restrict__ groups, SdDivState *__restrict__ states,
+	uint32_t unlocked_start)
 {
 	const int32_t slot = slot_of[list[blockIdx.x]];
 	if (slot < 0) return;
 	uint32_t *p = reinterpret_cast<uint32_t *>(carried + slot);
 	if ((int)threadIdx.x < DV_DATA_WORD0) p[threadIdx.x] = 0u;        // the header: len = 0 is "none"
 	if (threadIdx.x < 2) counters[2 * (slot / SD_DIV_MAX) + threadIdx.x] = 0u;
+	if (threadIdx.x == 2) {
+		const SdDivGroup *G = groups + slot / SD_DIV_MAX;
+		SdDivState *S = states + slot / SD_DIV_MAX;
+		S->off[slot % SD_DIV_MAX] = G->off[slot % SD_DIV_MAX];
+		S->locked = unlocked_start ? 0u : (1u << G->n) - 1u;
+		S->learned = 0u;
+		S->duplicates = 0u;
+	}
 }
-void sd_launch_diversity_clear(uint32_t n, hipStream_t stream, const uint32_t *list, const int32_t *slot_of, SondeFrame *carried, uint32_t *counters)
+void sd_launch_diversity_clear(uint32_t n, hipStream_t stream, const uint32_t *list, const int32_t *slot_of, SondeFrame *carried, uint32_t *counters,
+	const SdDivGroup *groups, SdDivState *states, uint32_t unlocked_start)
 {
-	hipLaunchKernelGGL(sd_diversity_clear_kernel, dim3(n), dim3(64), 0, stream, list, slot_of, carried, counters);
+	hipLaunchKernelGGL(sd_diversity_clear_kernel, dim3(n), dim3(64), 0, stream, list, slot_of, carried, counters, groups, states, unlocked_start);
 }
 
 // ---- test introspection: steps 3 to 7 alone on caller-made copies (sonde_batch_test_rs41_combine).  One wave per case; the host has

@@ -138,10 +138,25 @@ void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status
 // both carried from submit to submit.  One launch behind every other kernel of the submit.
 #define SD_DIV_MAX 4
 struct SdDivGroup { uint32_t n; uint32_t ch[SD_DIV_MAX]; uint32_t pad; int64_t off[SD_DIV_MAX]; };
+// What the align step (diversity_align_kernel.hip, DESIGN SPEC 3.3k) carries per group from submit to submit and the combining pass
+// reads: off[m] = where member m's bit count stands on the group's clock (SdDivGroup.off is its initial value), locked = a bit per
+// member (an unlocked member is to the combining pass a member without records), learned / duplicates = the step's counters.  Without
+// the step (mode 0) off is the host's and every member is locked, for good.
+struct SdDivState { int64_t off[SD_DIV_MAX]; uint32_t locked, learned, duplicates, pad; };
 void sd_launch_diversity(uint32_t n_groups, hipStream_t stream, const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar,
-	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, uint32_t window, SondeFrame *carried, uint32_t *counters);
-// the groups of the listed channels back to "no carried record, counters zero"; slot_of[channel] = SD_DIV_MAX * group + member or -1
-void sd_launch_diversity_clear(uint32_t n, hipStream_t stream, const uint32_t *list, const int32_t *slot_of, SondeFrame *carried, uint32_t *counters);
+	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, const SdDivState *states, uint32_t window,
+	SondeFrame *carried, uint32_t *counters);
+// the groups of the listed channels back to "no carried record, counters zero, offsets and locks as set_diversity left them"
+// (unlocked_start: the members of a group start unlocked); slot_of[channel] = SD_DIV_MAX * group + member or -1
+void sd_launch_diversity_clear(uint32_t n, hipStream_t stream, const uint32_t *list, const int32_t *slot_of, SondeFrame *carried, uint32_t *counters,
+	const SdDivGroup *groups, SdDivState *states, uint32_t unlocked_start);
+// the align step, one launch in front of sd_launch_diversity when mode != 0 (SONDE_DIVERSITY_LEARN | SONDE_DIVERSITY_MARK_DUPLICATES)
+void sd_launch_diversity_align(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
+	const SdDivGroup *groups, const SondeFrame *carried, SdDivState *states, uint32_t mode);
+// the align step alone: n cases of SD_DIV_MAX members with max_rec record slots each (records[(4 k + m) * max_rec + i], counts[4 k + m]
+// in use, n_members[k] = 2..4), carried[4 k + m] (len 0: none), states[k] in and out, modes[k]; all device memory
+void sd_launch_diversity_align_unit(uint32_t n, hipStream_t stream, SondeFrame *records, const uint32_t *counts, uint32_t max_rec,
+	const uint32_t *n_members, const SondeFrame *carried, SdDivState *states, const uint32_t *modes);
 // steps 3 to 7 of SPEC 3.3j alone: n cases of SD_DIV_MAX copies each (device memory; n_copies[i] of them in use, copy 0 the record to
 // rewrite); out[i] = copy 0, rewritten or not; status = copies used, -1 too many erasures, -2 no decode, -3 rejected
 void sd_launch_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,

@@ -34,9 +34,12 @@ def match(vfo_offsets, cand_offsets, match_hz: int = 0):
 def frame_ok(frames) -> np.ndarray:
     """which frames passed their own check, by the rule parse.cpp applies per sonde type: RS41 both codewords corrected; DFM and
     iMS-100 no uncorrectable block (nerr[1] == 0); M10 / M20, iMet-4, SRS-C50 and MRZ-N1 the checksum (nerr[0] == 0).  The batch
-    records frames that fail (a host may count them); a carrier that falls silent in mid-frame leaves one."""
+    records frames that fail (a host may count them); a carrier that falls silent in mid-frame leaves one.  A frame with
+    FRAME_DUPLICATE (set_diversity(mark_duplicates=True): another receiver of the group has delivered it) is left out like a failed
+    one; without that mode no record carries the flag."""
     t, e0, e1 = frames["type"], frames["nerr"][:, 0], frames["nerr"][:, 1]
-    return np.where(t == 0, (e0 >= 0) & (e1 >= 0), np.where((t == 1) | (t == 2), e1 == 0, e0 == 0))
+    ok = np.where(t == 0, (e0 >= 0) & (e1 >= 0), np.where((t == 1) | (t == 2), e1 == 0, e0 == 0))
+    return ok & ((frames["flags"] & _lib.FRAME_DUPLICATE) == 0)
 
 
 def _pools(capacity) -> dict:
