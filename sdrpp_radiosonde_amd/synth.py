@@ -1158,7 +1158,7 @@ SCENE_BAUD = {0: 4800.0, 1: 5000.0, 2: 4800.0, 3: 9600.0, 4: IMET_BAUD, 5: C50_B
 
 
 def make_wideband_scene(sondes, n_samples: int, *, fs: float = WB_FS, ebn0_db: float = 20.0, seed: int = 1, noise_sigma: float = 0.02,
-                        device: str | torch.device = "cpu", cfo_max_hz: float = 300.0, drift_hz_per_s=0.0, active=None):
+                        device: str | torch.device = "cpu", cfo_max_hz: float = 300.0, drift_hz_per_s=0.0, active=None, bits=None):
     """Transmitters of any sonde type at the given offsets, summed into one complex stream at fs [n_samples, 2] with ONE white noise
     floor (sigma per component): sondes = [(offset_hz, sonde type, m20), ...] (m20 optional: M20 frames for type 3).  Each carrier's
     amplitude sets its own Eb/N0 against that floor (GFSK), or its C/N in 48 kHz (iMet-4, SRS-C50) to ebn0_db; ebn0_db may be a
@@ -1166,7 +1166,8 @@ def make_wideband_scene(sondes, n_samples: int, *, fs: float = WB_FS, ebn0_db: f
     added to its phase, so that its offset at sample n is f + r n / fs.  active (None, or per sonde None or (first_sample, end_sample))
     puts a carrier on the air for that span only: it is gated before the noise is added, its frames and symbols stay those of the
     whole stream.  Returns (iq, frames, symbols): per sonde the list of (symbol offset, frame bytes) and the number of
-    on-air symbols the stream holds."""
+    on-air symbols the stream holds.  bits (None, or per sonde None or a symbol stream of the caller's, GFSK types only) replaces the
+    generator's frames of that sonde: it is modulated as it stands, and the sonde's frame list is empty."""
     ebn0 = list(ebn0_db) if np.ndim(ebn0_db) else [float(ebn0_db)] * len(sondes)
     drift = [float(r) for r in drift_hz_per_s] if np.ndim(drift_hz_per_s) else [float(drift_hz_per_s)] * len(sondes)
     total = torch.zeros((n_samples, 2), dtype=torch.float32, device=device)
@@ -1180,6 +1181,11 @@ def make_wideband_scene(sondes, n_samples: int, *, fs: float = WB_FS, ebn0_db: f
             a = noise_sigma * math.sqrt(2.0 * 10.0 ** (ebn0[i] / 10.0) * 48000.0 / fs)
             mk = make_imet_batch if t == 4 else make_c50_batch
             sb = mk(1, n_samples, seed=seed + 17 * i, snr_db=200.0, amp_range=(a, a), first_channel=i, **kw)
+        elif bits is not None and bits[i] is not None:
+            a = noise_sigma * math.sqrt(2.0 * 10.0 ** (ebn0[i] / 10.0) * SCENE_BAUD[t] / fs)
+            own = np.ascontiguousarray(bits[i], dtype=np.uint8)[None, :]
+            sb = SynthBatch(*gfsk_modulate(own, n_samples, SCENE_BAUD[t], seed=seed + 17 * i + 1000 * t, ebn0_db=200.0, amp_range=(a, a), **kw)[:1],
+                            [[]], own, None, None, None)
         else:
             a = noise_sigma * math.sqrt(2.0 * 10.0 ** (ebn0[i] / 10.0) * SCENE_BAUD[t] / fs)
             sb = make_batch(t, 1, n_samples, seed=seed + 17 * i, ebn0_db=200.0, amp_range=(a, a), first_channel=i, m20=m20, **kw)

@@ -1,6 +1,7 @@
-"""Stage 3 (sync search, Manchester / biphase decode, de-interleaving, FEC and checks) of the six non-RS41 sonde types in plain
-Python, written from DESIGN.md SPEC 3.3b-3.3e and 3.6: it imports neither the oracle nor the product and shares no arithmetic with
-them.  Hamming(8,4) is a nearest-codeword search over the 16 words of the null space; BCH(63,51) is the remainder of the block modulo
+"""Stage 3 (sync search, Manchester / biphase decode, de-interleaving, FEC and checks) of all seven sonde types in plain
+Python, written from DESIGN.md SPEC 3.3, 3.3b-3.3e and 3.6 (RS41: and SURVEY.md Appendix B.2): it imports neither the oracle nor the
+product and shares no arithmetic with them.  RS41 (type 0): its own header and mask constants, its own GF(2^8) tables, a textbook
+Berlekamp-Massey / exhaustive root search / Forney decoder (rs41_rs_decode).  Hamming(8,4) is a nearest-codeword search over the 16 words of the null space; BCH(63,51) is the remainder of the block modulo
 g(x) by long division, looked up in the table of the remainders of every error pattern of weight <= 2 over the full length 63 (no
 GF(2^6) anywhere); the CRCs are bit-serial divisions (iMet: binascii.crc_hqx); the M10 checksum is SPEC 3.3b's byte recurrence.
 
@@ -18,7 +19,7 @@ FRAME_MAX = 528
 FRAME_DTYPE = np.dtype([("channel", "<u4"), ("type", "<u4"), ("len", "<i4"), ("nerr", "<i4", (2,)),
                         ("flags", "<u4"), ("bitpos", "<u8"), ("data", "u1", (FRAME_MAX,))])
 
-DFM, IMS, M10, IMET, C50, MRZ = 1, 2, 3, 4, 5, 6
+RS41, DFM, IMS, M10, IMET, C50, MRZ = 0, 1, 2, 3, 4, 5, 6
 
 # every mutation keyword of reference() with the value that switches it on, and the sonde types it applies to
 MUTATIONS = {
@@ -47,6 +48,27 @@ MUTATIONS = {
     "XDATA length 4 + L": (dict(imet_xdata4=True), (IMET,)),
     "resume behind the stop bit": (dict(afsk_resume_behind=True), (IMET, C50)),
     "second sum not running": (dict(c50_plain_sum2=True), (C50,)),
+    # RS41 (SPEC 3.3)
+    "RS41 thr+1": (dict(thr_norm=+1), (RS41,)),
+    "RS41 thr-1": (dict(thr_norm=-1), (RS41,)),
+    "RS41 inverted thr+1": (dict(thr_inv=+1), (RS41,)),
+    "RS41 inverted thr-1": (dict(thr_inv=-1), (RS41,)),
+    "RS41 latest hit of 64 candidates": (dict(latest=True), (RS41,)),
+    "RS41 resume one bit early": (dict(resume=-1), (RS41,)),
+    "RS41 resume one bit late": (dict(resume=+1), (RS41,)),
+    "RS41 resume behind the sync": (dict(resume_in_frame=True), (RS41,)),
+    "RS41 tie goes to 518": (dict(tie_518=True), (RS41,)),
+    "RS41 length from an exact 0xF0": (dict(len_exact=True), (RS41,)),
+    "RS41 length byte not de-whitened": (dict(len_raw=True), (RS41,)),
+    "RS41 length byte polarity kept": (dict(len_pol=True), (RS41,)),
+    "RS41 mask aligned to the stream": (dict(mask_stream=True), (RS41,)),
+    "RS41 codeword parities swapped": (dict(swap_parity=True), (RS41,)),
+    "RS41 t = 11": (dict(t=11), (RS41,)),
+    "RS41 t = 13": (dict(t=13), (RS41,)),
+    "RS41 root in the padding accepted": (dict(pad_ok=True), (RS41,)),
+    "RS41 rejected codeword partly rewritten": (dict(partial=True), (RS41,)),
+    "RS41 bytes behind len not zeroed": (dict(tail_kept=True), (RS41,)),
+    "RS41 nerr off by one": (dict(nerr_plus=1), (RS41,)),
 }
 
 
@@ -347,13 +369,159 @@ def afsk_packets(stype: int, bits: np.ndarray, *, imet_no_stop=False, imet_xdata
     return out
 
 
+
+# ------------------------------------------------------------------------------------------------ RS41 (SPEC 3.3)
+RS41_HEADER = bytes.fromhex("10B6CA11229612F8")                         # on air, every byte least significant bit first
+RS41_MASK = bytes.fromhex("96833E51B1490898320559 0EF944C626 2160C2EA795D6DA15469470CDCE85CF1 F776827F0799A22C937C3063F5102E61"
+                          "D0BCB4B606AAF423786E3BAEBF7B4CC1".replace(" ", ""))
+assert len(RS41_MASK) == 64 and bytes(a ^ b for a, b in zip(RS41_HEADER, RS41_MASK)) == bytes.fromhex("8635F44093DF1A60")   # B.2's check
+RS41_HEADER_BITS = np.array([(RS41_HEADER[i >> 3] >> (i & 7)) & 1 for i in range(64)], dtype=np.uint8)
+
+GF_EXP, GF_LOG = [0] * 510, [0] * 256
+_v = 1
+for _i in range(255):
+    GF_EXP[_i] = GF_EXP[_i + 255] = _v
+    GF_LOG[_v] = _i
+    _v = (_v << 1) ^ (0x11D if _v & 0x80 else 0)
+
+
+def gf_mul(a: int, b: int) -> int:
+    return GF_EXP[GF_LOG[a] + GF_LOG[b]] if a and b else 0
+
+
+def gf_inv(a: int) -> int:
+    return GF_EXP[255 - GF_LOG[a]]
+
+
+def gf_poly_at(p, x: int) -> int:
+    """p[0] + p[1] x + p[2] x^2 + ..."""
+    r = 0
+    for c in reversed(p):
+        r = gf_mul(r, x) ^ c
+    return r
+
+
+def rs41_rs_decode(word, *, t=12, pad_ok=False, partial=False):
+    """RS(255,231) shortened to len(word), roots alpha^0..alpha^23, position k = the coefficient of x^k: (corrected bytes or -1, word).
+    SPEC 3.3: failure iff L > 12, deg Lambda != L, root count != L, a root in the padding, or a zero Forney denominator."""
+    w = [int(v) for v in word]
+    n = len(w)
+    S = [gf_poly_at(w, GF_EXP[j]) for j in range(24)]
+    if not any(S):
+        return 0, w
+    lam, B, L, m, b = [1], [1], 0, 1, 1                                  # Berlekamp-Massey, the textbook recurrence
+    for r in range(24):
+        d = S[r]
+        for i in range(1, min(L, len(lam) - 1) + 1):
+            d ^= gf_mul(lam[i], S[r - i])
+        if d == 0:
+            m += 1
+            continue
+        f = gf_mul(d, gf_inv(b))
+        new = lam + [0] * max(0, len(B) + m - len(lam))
+        for i, c in enumerate(B):
+            new[i + m] ^= gf_mul(f, c)
+        if 2 * L <= r:
+            L, B, b, m = r + 1 - L, lam, d, 1
+        else:
+            m += 1
+        lam = new
+    while len(lam) > 1 and lam[-1] == 0:
+        lam.pop()
+    if L > t or len(lam) - 1 != L:
+        return -1, w
+    roots = [k for k in range(255) if gf_poly_at(lam, GF_EXP[(255 - k) % 255]) == 0]
+    if len(roots) != L:
+        return -1, w
+    omega = [0] * 24
+    for i in range(24):
+        for k in range(min(i, L) + 1):
+            omega[i] ^= gf_mul(lam[k], S[i - k])
+    dlam = [lam[k] if k & 1 else 0 for k in range(1, L + 1)]           # the formal derivative: odd terms survive
+    vals = []
+    for k in roots:
+        xi = GF_EXP[(255 - k) % 255]
+        den = gf_poly_at(dlam, xi)
+        if den == 0:
+            return -1, w
+        vals.append(gf_mul(GF_EXP[k], gf_mul(gf_poly_at(omega, xi), gf_inv(den))))
+    out = list(w)
+    for k, v in zip(roots, vals):
+        if k < n:
+            out[k] ^= v
+    if any(k >= n for k in roots) and not pad_ok:
+        return -1, (out if partial else w)                               # (mutation `partial`: the valid positions rewritten all the same)
+    return L, out
+
+
+def _lsb_bytes(bits: np.ndarray) -> np.ndarray:
+    return np.packbits(bits[:len(bits) // 8 * 8].reshape(-1, 8), axis=1, bitorder="little")[:, 0]
+
+
+def rs41_frames(bits: np.ndarray, *, thr_norm=0, thr_inv=0, latest=False, resume=0, resume_in_frame=False, tie_518=False,
+                len_exact=False, len_raw=False, len_pol=False, info=None):
+    """[(fstart, inverted, frame bytes)] of every complete frame.  The earliest window within 6 bits of the header (58 or more: inverted)
+    wins; byte 56, polarity undone and de-whitened, decides the length (nearer to 0xF0 than to 0x0F: 518, else, a tie included,
+    320); a frame is emitted when all its bits exist; the search resumes at its last bit + 1.  info["pending"]: the start of a frame
+    that the end of the stream cut (found, but no record)."""
+    n = len(bits)
+    if n < 64:
+        return []
+    hd = (np.lib.stride_tricks.sliding_window_view(bits, 64) != RS41_HEADER_BITS[None, :]).sum(axis=1)
+    norm = hd <= 6 + thr_norm
+    inv = (hd >= 58 - thr_inv) & ~norm
+    hits = np.nonzero(norm | inv)[0]
+    out, pos = [], 0
+    while True:
+        k = np.searchsorted(hits, pos)
+        if k == len(hits):
+            break
+        p = int(hits[k])
+        if latest:                                                       # (mutation) the last match among the 64 candidates from p on
+            p = int(hits[np.searchsorted(hits, p + 64) - 1])
+        x = 0xFF if inv[p] else 0
+        if p + 8 * 57 > n:
+            if info is not None:
+                info["pending"] = p
+            break
+        tb = int(_lsb_bytes(bits[p + 448:p + 456])[0]) ^ (0 if len_pol else x) ^ (0 if len_raw else RS41_MASK[56])
+        d518, d320 = bin(tb ^ 0xF0).count("1"), bin(tb ^ 0x0F).count("1")
+        ext = tb == 0xF0 if len_exact else (d518 <= d320 if tie_518 else d518 < d320)
+        flen = 518 if ext else 320
+        if p + 8 * flen > n:
+            if info is not None:
+                info["pending"] = p
+            break
+        out.append((p, bool(inv[p]), flen))
+        pos = p + 64 if resume_in_frame else p + 8 * flen + resume
+    return out
+
+
+def rs41_record(bits: np.ndarray, p: int, inv: bool, flen: int, *, mask_stream=False, swap_parity=False, tail_kept=False, nerr_plus=0, **rs):
+    """(528 data bytes, nerr[2]): the frame de-whitened with the mask aligned to its start (the 8 header bytes too: as received),
+    then each codeword c: parity frame[8 + 24 c .. 32 + 24 c) at positions 0..23, frame[56 + 2 i + c] at 24 + i"""
+    have = min(FRAME_MAX if tail_kept else flen, (len(bits) - p) // 8)
+    raw = _lsb_bytes(bits[p:p + 8 * have]) ^ np.uint8(0xFF if inv else 0)
+    m0 = (p // 8) if mask_stream else 0
+    d = [int(raw[i]) ^ RS41_MASK[(i + m0) & 63] for i in range(have)] + [0] * (FRAME_MAX - have)
+    nerr = []
+    for c in (0, 1):
+        pc = 1 - c if swap_parity else c
+        word = d[8 + 24 * pc:32 + 24 * pc] + d[56 + c:flen:2]
+        ne, word = rs41_rs_decode(word, **rs)
+        d[8 + 24 * pc:32 + 24 * pc] = word[:24]
+        d[56 + c:flen:2] = word[24:]
+        nerr.append(ne + nerr_plus if ne > 0 else ne)
+    return d, nerr
+
 # ------------------------------------------------------------------------------------------------ records
 _FRAMER_KW = ("thr_norm", "thr_inv", "ims_inverted", "latest", "resume")
+_RS41_FRAMER_KW = ("thr_norm", "thr_inv", "latest", "resume", "resume_in_frame", "tie_518", "len_exact", "len_raw", "len_pol")
 
 
 def reference(stype: int, bits, channel: int, *, info=None, **mut) -> np.ndarray:
     """the frame records of one channel's whole chip / bit stream; `mut`: the keywords of MUTATIONS; info: a dict that receives
-    "pending" (fixed-length types) or "drops" (AFSK types)"""
+    "pending" (RS41 and the fixed-length types) or "drops" (AFSK types)"""
     bits = np.ascontiguousarray(bits, dtype=np.uint8)
     recs = []
 
@@ -364,7 +532,15 @@ def reference(stype: int, bits, channel: int, *, info=None, **mut) -> np.ndarray
         r["data"][:length] = np.frombuffer(bytes(data), dtype=np.uint8)[:length]
         recs.append(r)
 
-    if stype in (IMET, C50):
+    if stype == RS41:
+        fkw = {k: v for k, v in mut.items() if k in _RS41_FRAMER_KW}
+        dkw = {k: v for k, v in mut.items() if k not in _RS41_FRAMER_KW}
+        for p, inv, flen in rs41_frames(bits, info=info, **fkw):
+            data, nerr = rs41_record(bits, p, inv, flen, **dkw)
+            rec(flen, nerr[0], nerr[1], int(inv), p, data[:flen])
+            if dkw.get("tail_kept"):
+                recs[-1]["data"][:] = np.array(data, dtype=np.uint8)
+    elif stype in (IMET, C50):
         for c0, inv, pkt, ne in afsk_packets(stype, bits, info=info, **mut):
             rec(len(pkt), ne, 0, inv, c0, pkt)
     else:

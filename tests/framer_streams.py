@@ -1,4 +1,5 @@
-"""Designed inputs for the non-RS41 framers (tests/framer_reference.py): chip / bit streams from the generator's encoders with
+"""Designed inputs for the framers (tests/framer_reference.py; the six non-RS41 types first, RS41 in the second half of the file, in
+a list of its own: rs41_streams): chip / bit streams from the generator's encoders with
 errors planted chip by chip, so that every decision path of stage 3 is taken a known number of times, modulated at 40 dB so that the
 demodulator returns exactly what was planted.  Each builder returns a Designed: the IQ, the planted chips and a plan (per channel a
 list of cases: where the frame starts, what was planted, what must come out).  Seeds are fixed; nothing here is random at run time.
@@ -15,7 +16,7 @@ import torch
 
 from sdrpp_radiosonde_amd import synth
 
-DFM, IMS, M10, IMET, C50, MRZ = 1, 2, 3, 4, 5, 6
+RS41, DFM, IMS, M10, IMET, C50, MRZ = 0, 1, 2, 3, 4, 5, 6
 TILE = 2048
 NT = 144                     # tiles of every stream: 6.1 s, 18 granules of the AFSK front-end, so that all of them fit one batch
 THR = {DFM: 3, IMS: 2, M10: 3, MRZ: 4}
@@ -585,6 +586,8 @@ def align(d: Designed, c: int, bits: np.ndarray):
 
 def entry_span(d: Designed, e) -> int:
     """the chips of a plan entry that the demodulator must return as planted"""
+    if d.stype == RS41:
+        return e["span"]
     if d.stype in (IMET, C50):
         return 10 * e["len"] if e.get("found") else 0
     return FLEN[d.stype] if e.get("len") is not None else 0
@@ -609,6 +612,8 @@ def check_conditions(d: Designed, c: int, bits: np.ndarray):
 
 def check_plan(d: Designed, c: int, recs: np.ndarray, off: int, pol: int, cover: dict):
     """the plan's expectations on one channel's records; the decision paths taken are counted into `cover`"""
+    if d.stype == RS41:
+        return _check_plan_rs41(d, c, recs, off, cover)
     by_pos = {int(r["bitpos"]): r for r in recs}
     for e in d.plan[c]:
         r = by_pos.get(e["pos"] + e.get("lead", 0) + off)
@@ -644,7 +649,8 @@ def check_plan(d: Designed, c: int, recs: np.ndarray, off: int, pol: int, cover:
 
 
 def required_coverage(names) -> list:
-    """the keys that check_plan must have counted after the named streams"""
+    """the keys that check_plan must have counted after the named streams (of the six non-RS41 types; the RS41 streams are a list of their
+    own, rs41_streams, and so are their keys: required_coverage_rs41)"""
     req = []
     if "dfm-words" in names:
         req += [("dfm-word", i, w) for i in range(33) for w in range(256)]
@@ -682,3 +688,495 @@ def required_coverage(names) -> list:
 def required_drops() -> list:
     """every reason for which the packet framers drop a candidate (framer_reference.afsk_packets, info["drops"])"""
     return [(IMET, "drop", "framing"), (IMET, "drop", "type"), (IMET, "drop", "length"), (C50, "drop", "framing")]
+
+
+# ================================================================================================ RS41 (sonde type 0)
+# The designed streams of SPEC 3.3: per channel a lead-in of alternating bits, a first frame that no test looks at (it may fall into
+# acquisition), then items laid one behind the other: frames with planted header / length-byte / codeword errors, gaps of alternating
+# bits, decoy headers in those gaps.  The plan lists every planted header (the frames', the decoys', those inside payloads) with what
+# must become of it; whether a header is found and how long its frame is taken to be follows from walking the planted headers in stream
+# order (a header inside the span of a found frame is not looked at), which is the plan's own arithmetic, not the reference's.
+RS41_STREAM_BITS = int(NT * TILE * 4800 / synth.FS) + 16
+_HDR_BITS = synth.bytes_to_bits_lsb(synth.RS41_HEADER_AIR[None, :])[0]
+RS41_HEADER_DISTANCES = (0, 1, 5, 6, 7, 8, 32, 56, 57, 58, 59, 63, 64)
+RS41_GAPS = (0, 1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 204, 205, 206)
+RS41_CW_ERRORS = (0, 1, 2, 3, 11, 12, 13, 24)
+RS41_ORDERS = {"mixed": "CDCCDDCDCC", "all-clean": "CCCCCCCCCC", "all-dirty": "DDDDDDDDDD", "dirty-8th": "CCCCCCDCCC",
+               "dirty-9th": "CCCCCCCDCC", "dirty-11th": "CCCCCCCCCD"}       # frames 2..11 of the launch (the first is nobody's case)
+
+
+def _popc(v: int) -> int:
+    return bin(v).count("1")
+
+
+def _air(frame: np.ndarray) -> np.ndarray:
+    return synth.bytes_to_bits_lsb(synth.rs41_scramble(frame[None, :]))[0]
+
+
+def _unair(bits: np.ndarray) -> np.ndarray:
+    return synth.rs41_scramble(np.packbits(bits.reshape(-1, 8), axis=1, bitorder="little").T)[0]
+
+
+def _cw_byte(c: int, k: int) -> int:
+    """the frame byte of position k of codeword c"""
+    return 8 + 24 * c + k if k < 24 else 56 + 2 * (k - 24) + c
+
+
+def _gf_solve(A, y):
+    """x with A x = y over GF(2^8) (Gauss-Jordan; A square and regular)"""
+    n = len(y)
+    M = [[int(v) for v in row] + [int(y[i])] for i, row in enumerate(A)]
+    mul = lambda a, b: int(synth.gf_mul(a, b))
+    for col in range(n):
+        piv = next(r for r in range(col, n) if M[r][col])
+        M[col], M[piv] = M[piv], M[col]
+        inv = int(synth._GF_EXP[(255 - synth._GF_LOG[M[col][col]]) % 255])
+        M[col] = [mul(v, inv) for v in M[col]]
+        for r in range(n):
+            if r != col and M[r][col]:
+                f = M[r][col]
+                M[r] = [a ^ mul(f, b) for a, b in zip(M[r], M[col])]
+    return [M[r][n] for r in range(n)]
+
+
+@functools.lru_cache(None)
+def rs41_l13_parity_error(n: int, seed: int):
+    """24 parity-byte errors after which Berlekamp-Massey ends with L = 13 and a locator of degree 13 that HAS 13 distinct roots, all
+    inside a codeword of n bytes: a decoder without the test L <= 12 "corrects" 13 bytes.  Construction: 13 positions with
+    sum(X_i^-1) = 0 (the locator's x^12 coefficient vanishes), syndromes S_0..S_11 = 0, S_12 = the product of the X_i, S_13..S_23 from the
+    locator's recurrence; with twelve leading zeros the recurrence fixes coefficients 1..11 and BM leaves x^12 at 0 and sets x^13 to
+    S_12.  Returns (the 24 error bytes, the 13 positions)."""
+    rng = np.random.default_rng(seed)
+    E, Lg = synth._GF_EXP, synth._GF_LOG
+    mul = lambda a, b: int(synth.gf_mul(a, b))
+    while True:
+        pos = sorted(int(v) for v in rng.choice(n, size=12, replace=False))
+        s = 0
+        for p in pos:
+            s ^= int(E[(255 - p) % 255])
+        if s == 0:
+            continue
+        last = (255 - int(Lg[s])) % 255                                  # X^-1 = s
+        if last < n and last not in pos:
+            pos.append(last)
+            break
+    lam = [1]
+    for p in pos:                                                        # times (1 + X x)
+        X = int(E[p])
+        lam = [a ^ b for a, b in zip(lam + [0], [0] + [mul(X, v) for v in lam])]
+    assert len(lam) == 14 and lam[12] == 0 and lam[13] != 0
+    S = [0] * 12 + [lam[13]]
+    for j in range(13, 24):
+        v = 0
+        for k in range(1, 14):
+            v ^= mul(lam[k], S[j - k])
+        S.append(v)
+    A = [[int(E[(i * j) % 255]) for i in range(24)] for j in range(24)]
+    return tuple(_gf_solve(A, S)), tuple(pos)
+
+
+def _hdr_overlap_shifts(inv: bool):
+    """shifts D < 64 at which a decoy header (inverted: inv) D bits in front of an exact header differs from the pattern in <= 6 of the
+    bits the two share: [(D, wrong bits of the decoy)]"""
+    out = []
+    for D in range(33, 64):
+        m = int(((_HDR_BITS[D:] ^ int(inv)) != _HDR_BITS[:64 - D]).sum())
+        if m <= 6:
+            out.append((D, m))
+    return out
+
+
+class _Rs41Builder:
+    def __init__(self, name: str, seed: int, nchan: int, invert: bool = False):
+        self.name, self.seed, self.invert = name, seed, invert
+        self.rng = np.random.default_rng(9000 + seed)
+        self.rows = np.tile((np.arange(RS41_STREAM_BITS) & 1).astype(np.uint8), (nchan, 1))
+        self.heads = [[] for _ in range(nchan)]                          # planted headers: dict(pos, k wrong bits, entry)
+        self.at = [0] * nchan
+        self.nfr = [0] * nchan
+        ch = np.repeat(np.arange(nchan), 12)
+        fi = np.tile(np.arange(12), nchan)
+        self.pool = {False: synth.rs41_build_frames(seed, ch, fi, False).reshape(nchan, 12, 320),
+                     True: synth.rs41_build_frames(seed, ch, fi, True).reshape(nchan, 12, 518)}
+
+    def lead(self, c: int, nbits: int):
+        self.at[c] = nbits
+        self.frame(c, case=None)
+
+    def gap(self, c: int, nbits: int):
+        self.at[c] += nbits
+
+    def have(self, c: int, end: int) -> bool:
+        """does the demodulated stream hold the planted bits up to `end`?  It ends about 19 bits before the planted one."""
+        assert end <= RS41_STREAM_BITS - 60 or end > RS41_STREAM_BITS - 8, (self.name, c, end, "too close to the end of the stream to tell")
+        return end <= RS41_STREAM_BITS - 60
+
+    def room(self, c: int, nbits: int) -> bool:
+        return self.at[c] + nbits + 96 <= RS41_STREAM_BITS
+
+    def header(self, c: int, pos: int, k: int, inv: bool, case: str, at=None):
+        """a decoy: the header with k wrong bits (inverted: of the complemented header) at bit `pos`"""
+        bits = _HDR_BITS ^ np.uint8(inv)
+        bits[self.rng.choice(64, size=k, replace=False)] ^= 1
+        self.rows[c, pos:pos + 64] = bits
+        self.heads[c].append(dict(pos=pos, k=64 - k if inv else k, frame=None, case=case, at=at))
+
+    def frame(self, c: int, case, at=None, ext=False, hdr=0, lenflips=0, cw=(None, None), hdr_flips=0, inpay=(), pad=None, l13=None,
+              cut=False, tight=False, **extra):
+        """lay a frame at the channel's position.  hdr: wrong bits of the header against the true pattern (>= 58: the whole frame is sent
+        inverted); lenflips: bits of byte 56 flipped; cw[c]: (count, placement) of byte errors of codeword c; hdr_flips: bits of the header
+        flipped on top (a frame that is still found; the record shows them); inpay: [(byte, bit offset, inverted)] headers written into
+        the payload on the air, the parities recomputed; pad: (codeword, padding positions, extra errors); l13: codeword"""
+        rng = self.rng
+        flen = 518 if ext else 320
+        nmsg = (flen - 56) // 2
+        if not cut and not tight and not self.room(c, 8 * flen):
+            raise RuntimeError((self.name, c, case, "no room"))
+        d = self.pool[ext][c, self.nfr[c] % 12].copy()
+        self.nfr[c] += 1
+        pos = self.at[c]
+        if inpay:
+            air = _air(d)
+            for byte, bo, pinv in inpay:
+                q = 8 * byte + bo
+                air[q:q + 64] = _HDR_BITS ^ np.uint8(pinv)
+            d = _unair(air)
+            for k in (0, 1):
+                d[8 + 24 * k:32 + 24 * k] = synth.rs_parity(d[None, 56 + k::2])[0]
+        good = d.copy()
+        rx = d.copy()
+        errs = [set(), set()]
+        fails = [False, False]
+        if lenflips:
+            rx[56] ^= int(sum(1 << int(b) for b in rng.choice(8, size=lenflips, replace=False)))
+            errs[0].add(24)
+        for k in (0, 1):
+            if cw[k] is None:
+                continue
+            count, place = cw[k]
+            fixed = {"b56": [24], "last": [24 + nmsg - 1]}.get(place, [])
+            assert not (place == "b56" and k == 1) and not (place == "last" and k == 0)
+            pool = [i for i in (range(24) if place == "parity" else range(24 + nmsg)) if i not in fixed and not (k == 0 and i == 24)]
+            where = fixed + [int(v) for v in rng.choice(pool, size=count - len(fixed), replace=False)]
+            for i in where:
+                rx[_cw_byte(k, i)] ^= (1 << int(rng.integers(8))) if i == 24 and k == 0 else int(rng.integers(1, 256))
+                errs[k].add(i)
+        if pad is not None:                                              # the nearest codeword differs in the padding (and in `more` bytes)
+            k, npad, more = pad
+            assert not ext
+            full = np.zeros(231, dtype=np.uint8)
+            full[:nmsg] = d[56 + k::2]
+            for p in rng.choice(np.arange(nmsg, 231), size=npad, replace=False):
+                full[p] = rng.integers(1, 256)
+            rx[8 + 24 * k:32 + 24 * k] = synth.rs_parity(full[None, :])[0]
+            for i in rng.choice(np.arange(25, 24 + nmsg), size=more, replace=False):
+                rx[_cw_byte(k, int(i))] ^= int(rng.integers(1, 256))
+            fails[k] = True
+        if l13 is not None:
+            e, _ = rs41_l13_parity_error(24 + nmsg, 13 + l13 + 2 * ext)
+            rx[8 + 24 * l13:32 + 24 * l13] ^= np.array(e, dtype=np.uint8)
+            fails[l13] = True
+        air = _air(rx)
+        inv = hdr >= 58
+        if hdr:
+            air[:64] = _HDR_BITS
+            air[rng.choice(64, size=hdr, replace=False)] ^= 1
+            if inv:
+                air[64:] ^= 1
+        if hdr_flips:
+            air[rng.choice(64, size=hdr_flips, replace=False)] ^= 1
+        seen_hdr = _unair(np.concatenate([air[:64] ^ np.uint8(inv), air[64:128]]))[:8]
+        nerr = tuple(-1 if (fails[k] or len(errs[k]) > 12) else len(errs[k]) for k in (0, 1))
+        data = rx.copy()
+        for k in (0, 1):
+            if nerr[k] >= 0:
+                data[8 + 24 * k:32 + 24 * k] = good[8 + 24 * k:32 + 24 * k]
+                data[56 + k::2] = good[56 + k::2]
+        data[:8] = seen_hdr
+        nb = min(8 * flen, RS41_STREAM_BITS - pos)
+        self.rows[c, pos:pos + nb] = air[:nb]
+        if case is not None:
+            hk = hdr + hdr_flips if not inv else hdr - hdr_flips
+            self.heads[c].append(dict(pos=pos, k=hk, frame=dict(len=flen, data=data.tobytes(), nerr=nerr), case=case, at=at, cut=cut, **extra))
+            for byte, bo, pinv in inpay:
+                self.heads[c].append(dict(pos=pos + 8 * byte + bo, k=64 if pinv ^ inv else 0, frame=None, case="header-in-payload",
+                                          at=(int(pinv), int(ext), bo)))
+        else:
+            self.heads[c].append(dict(pos=pos, k=0, frame=dict(len=flen), case=None, at=None))
+        self.at[c] = pos + 8 * flen
+        return pos
+
+    def build(self) -> Designed:
+        plan = []
+        for c, heads in enumerate(self.heads):
+            row, busy, lst = self.rows[c], 0, []
+            for h in sorted(heads, key=lambda h: h["pos"]):
+                p, k = h["pos"], h["k"]
+                e = dict(pos=p, case=h["case"], at=h["at"], found=False, span=8 * h["frame"]["len"] if h["frame"] else 64,
+                         **{q: v for q, v in h.items() if q not in ("pos", "k", "frame", "case", "at", "cut")})
+                if h.get("cut"):                                         # the bits of it that the demodulated stream surely holds
+                    e["span"] = max(0, min(e["span"], RS41_STREAM_BITS - 60 - p))
+                if (k <= 6 or k >= 58) and p >= busy and self.have(c, p + 64):
+                    inv = k >= 58
+                    flen = 0
+                    if self.have(c, p + 456):
+                        tb = int(np.packbits(row[p + 448:p + 456], bitorder="little")[0]) ^ (0xFF if inv else 0) ^ int(synth.RS41_MASK[56])
+                        flen = 518 if _popc(tb ^ 0xF0) < _popc(tb ^ 0x0F) else 320
+                    if flen and self.have(c, p + 8 * flen):
+                        busy = p + 8 * flen
+                        e.update(found=True, len=flen, flags=int(inv), data=None, nerr=(None, None))
+                        if h["frame"] and h["frame"]["len"] == flen and "data" in h["frame"]:
+                            e.update(data=h["frame"]["data"], nerr=h["frame"]["nerr"])
+                    else:
+                        busy = RS41_STREAM_BITS                          # found, and the stream ends before its frame does
+                        e["pending"] = True
+                if h["case"] is not None:
+                    lst.append(e)
+            plan.append(lst)
+        d = _modulate(self.name, RS41, self.rows, NT * TILE, 7100 + self.seed, invert=self.invert, plan=plan)
+        return d
+
+
+def _pairs(vals):
+    return [(vals[i], vals[(i + 1) % len(vals)]) for i in range(len(vals))]
+
+
+def rs41_header_cases(invert: bool = False) -> Designed:
+    """0 .. 64 wrong header bits, twice each; 58 and more: the whole frame inverted.  invert: the stream sent with inverted polarity"""
+    cases = [k for k in RS41_HEADER_DISTANCES for _ in range(2)]
+    b = _Rs41Builder("rs41-header" + ("-inv" if invert else ""), 71, 4, invert)
+    for c in range(4):
+        b.lead(c, 650 + 37 * c)
+    for i, k in enumerate(cases):
+        c = i % 4
+        b.gap(c, 8 * (i % 5))
+        b.frame(c, "header-distance", at=k, hdr=k, ext=(i % 9 == 3))
+    return b.build()
+
+
+def rs41_decoy_cases() -> Designed:
+    """a decoy header D bits in front of a true frame: the decoy's frame is reported, the true one inside it is not"""
+    cases = []
+    for inv in (False, True):
+        ov = _hdr_overlap_shifts(inv)
+        assert ov, inv
+        cases += [(D, inv, m) for D, m in (ov[:1] + ov[-1:])]
+        cases += [(D, inv, k) for D, k in ((64, 0), (65, 6), (100, 3), (127, 0), (200, 6), (300, 1), (600, 0))]
+    b = _Rs41Builder("rs41-decoy", 72, 5)
+    for c in range(5):
+        b.lead(c, 640 + 53 * c)
+    for i, (D, inv, k) in enumerate(cases):
+        c = next(c for c in range(5) if b.room(c, D + 40 + 2 * 2560))
+        b.gap(c, D + 24 + 3 * i)
+        true_at = b.at[c]
+        b.frame(c, "behind-decoy", at=(D, int(inv)))
+        if D < 64:                                                       # the decoy keeps the bits it shares with the true header: k of them are wrong
+            save = b.rows[c, true_at:true_at + 64].copy()
+            b.header(c, true_at - D, 0, inv, "decoy", at=(D, int(inv)))
+            b.rows[c, true_at:true_at + 64] = save
+            b.heads[c][-1]["k"] = 64 - k if inv else k
+        else:
+            b.header(c, true_at - D, k, inv, "decoy", at=(D, int(inv)))
+        b.frame(c, "after-decoy", at=(D, int(inv)))
+    for inv in (False, True):                                            # a header whose first bit is the last bit of a frame: the search resumes one bit later
+        c = next(c for c in range(5) if b.room(c, 300 + 2 * 2560))
+        b.frame(c, "before-early-decoy", at=int(inv))
+        end = b.at[c]
+        last = b.rows[c, end - 1]
+        b.header(c, end - 1, 0, inv, "decoy-one-bit-early", at=int(inv))
+        b.heads[c][-1]["k"] = int(last != b.rows[c, end - 1]) if not inv else 64 - int(last != b.rows[c, end - 1])
+        b.rows[c, end - 1] = last
+        b.gap(c, 200)
+        b.frame(c, "behind-early-decoy", at=int(inv))
+    return b.build()
+
+
+def rs41_inpayload_cases() -> Designed:
+    """the header (true and inverted) inside the payload, at every bit offset, the next frame right behind: not searched for"""
+    b = _Rs41Builder("rs41-inpayload", 73, 3)
+    for c in range(3):
+        b.lead(c, 700 + 41 * c)
+    for ext in (False, True):
+        for j in range(8):
+            c = 0 if not ext else 1 + j // 4
+            b.frame(c, "carries-headers", at=(int(ext), j), ext=ext, inpay=[(80 + 9 * j, j, False), (200 + 11 * j, (j + 4) % 8, True)])
+    for c in range(3):
+        b.frame(c, "behind-carrier", at=c)
+    return b.build()
+
+
+def rs41_gap_cases() -> Designed:
+    """every gap of RS41_GAPS between two frames (alternating bits), and eight channels whose frames lie one bit further apart each
+    time, the channels 8 bits apart: record positions at every residue modulo 64"""
+    b = _Rs41Builder("rs41-gaps", 74, 10)
+    for c in range(2):
+        b.lead(c, 640 + 19 * c)
+        for g in RS41_GAPS[7 * c:7 * c + 7] + RS41_GAPS[:2]:
+            b.gap(c, g)
+            b.frame(c, "gap", at=g)
+    for j in range(8):
+        c = 2 + j
+        b.lead(c, 704 + 8 * j)
+        for i in range(10):
+            b.gap(c, 1)
+            b.frame(c, "gap", at=1)
+    return b.build()
+
+
+def rs41_length_cases() -> Designed:
+    """byte 56 = 0x0F / 0xF0 with 1..5 wrong bits in standard and extended frames, mixed in one channel; every other frame is a
+    plain one, found or lost as the misread lengths have it"""
+    cases = [(ext, k) for k in (1, 2, 3, 4, 5) for ext in (False, True)] * 2
+    b = _Rs41Builder("rs41-length", 75, 5)
+    for c in range(5):
+        b.lead(c, 650 + 29 * c)
+    for i, (ext, k) in enumerate(cases):
+        c = next(c for c in range(5) if b.room(c, 8 * (518 if ext else 320) + 2560))
+        b.frame(c, "length-byte", at=(int(ext), k), ext=ext, lenflips=k)
+        b.frame(c, "behind-length-byte", at=(int(ext), k), ext=(i % 4 == 1))
+    return b.build()
+
+
+def rs41_codeword_cases() -> Designed:
+    cases = []
+    for place in ("any", "parity"):
+        cases += [dict(cw=((a, place), (e, place)), at=(place, a, e)) for a, e in _pairs(RS41_CW_ERRORS)]
+    cases += [dict(cw=((a, "any"), (e, "any")), at=("ext", a, e), ext=True) for a, e in _pairs(RS41_CW_ERRORS)[::2] + [(12, 12), (13, 13)]]
+    cases += [dict(cw=((a, "b56"), (2, "any")), at=("b56", a, int(ext)), ext=ext) for a, ext in ((1, False), (12, False), (13, False), (3, True))]
+    cases += [dict(cw=((1, "any"), (e, "last")), at=("last", e, int(ext)), ext=ext) for e in (1, 12, 13) for ext in (False, True)]
+    cases += [dict(cw=((1, "any"), (2, "any")), at=("header", f), hdr_flips=f) for f in (1, 6)]
+    cases += [dict(l13=k, at=("L13", k, int(ext)), ext=ext, cw=((2, "any"), None) if k else (None, (2, "any"))) for k in (0, 1) for ext in (False, True)]
+    b = _Rs41Builder("rs41-codewords", 76, 5)
+    for c in range(5):
+        b.lead(c, 660 + 23 * c)
+    for kw in cases:
+        c = next(c for c in range(5) if b.room(c, 8 * (518 if kw.get("ext") else 320)))
+        b.frame(c, "codewords", **kw)
+    return b.build()
+
+
+def rs41_padding_cases() -> Designed:
+    """standard frames whose nearest codeword differs only in 1..3 padding bytes (and in 0..2 ordinary ones): rejected, untouched"""
+    b = _Rs41Builder("rs41-padding", 77, 1)
+    b.lead(0, 690)
+    for i, (npad, more) in enumerate(itertools.product((1, 2, 3), (0, 1, 2))):
+        b.frame(0, "padding", at=(npad, more), pad=(i % 2, npad, more))
+    return b.build()
+
+
+def rs41_order_cases() -> Designed:
+    """clean (C) and dirty (D) frames in the orders that make a decoder of the clean ones hand over and go on; the channel's frames are
+    the 2nd to 11th of a launch that takes the whole stream"""
+    b = _Rs41Builder("rs41-order", 78, len(RS41_ORDERS))
+    for c, (name, order) in enumerate(RS41_ORDERS.items()):
+        b.lead(c, 645 + 31 * c)
+        for i, ch in enumerate(order):
+            dirty = ch == "D"
+            b.frame(c, "order", at=(name, i + 2, ch), cw=((1 + i % 3, "any"), (i % 2, "any")) if dirty else (None, None))
+    return b.build()
+
+
+def rs41_end_cases() -> Designed:
+    """the stream ends inside a header, between the header and byte 56, between byte 56 and the end of the frame: no record"""
+    b = _Rs41Builder("rs41-end", 79, 3)
+    for c, (name, left) in enumerate((("in-header", 34), ("before-byte-56", 300), ("behind-byte-56", 1500))):
+        start = RS41_STREAM_BITS - 36 - left
+        nfull = (start - 640) // 2560 - 1
+        b.lead(c, start - 2560 * (nfull + 1))
+        for i in range(nfull):
+            b.frame(c, "before-the-end", at=name, tight=True)
+        assert b.at[c] == start
+        b.frame(c, "stream-end", at=name, cut=True)
+    return b.build()
+
+
+def rs41_streams():
+    """the designed RS41 streams by name (a list of their own: all_streams() is what the tests of the other six types select from)"""
+    return {
+        "rs41-header": lambda: rs41_header_cases(False),
+        "rs41-header-inv": lambda: rs41_header_cases(True),
+        "rs41-decoy": rs41_decoy_cases,
+        "rs41-inpayload": rs41_inpayload_cases,
+        "rs41-gaps": rs41_gap_cases,
+        "rs41-length": rs41_length_cases,
+        "rs41-codewords": rs41_codeword_cases,
+        "rs41-padding": rs41_padding_cases,
+        "rs41-order": rs41_order_cases,
+        "rs41-end": rs41_end_cases,
+    }
+
+
+def _check_plan_rs41(d: Designed, c: int, recs: np.ndarray, off: int, cover: dict):
+    by_pos = {int(r["bitpos"]): r for r in recs}
+    for e in d.plan[c]:
+        r = by_pos.get(e["pos"] + off)
+        tag = (d.name, c, e["case"], e["at"], e["pos"])
+        if not e["found"]:
+            assert r is None, tag
+        else:
+            assert r is not None, tag
+            assert r["len"] == e["len"] and r["flags"] == e["flags"] ^ int(d.invert), tag + (int(r["len"]), int(r["flags"]))
+            assert not r["data"][r["len"]:].any(), tag
+            if e["data"] is not None:
+                assert r["data"][:e["len"]].tobytes() == e["data"], tag
+            for k in range(2):
+                if e["nerr"][k] is not None:
+                    assert r["nerr"][k] == e["nerr"][k], tag + (k, int(r["nerr"][k]))
+            cover[(RS41, "bitpos mod 64", int(r["bitpos"]) % 64)] = 1
+            cover[(RS41, "bitpos mod 32", int(r["bitpos"]) % 32)] = 1
+        inv = int(d.invert)
+        cover[(RS41, e["case"], e["at"], inv)] = cover.get((RS41, e["case"], e["at"], inv), 0) + 1
+        cover[(RS41, e["case"], "found" if e["found"] else "not found", inv)] = 1
+        if e.get("pending"):
+            cover[(RS41, "pending", e["at"])] = 1
+        if e["case"] == "length-byte":
+            cover[(RS41, "length read", e["at"], e.get("len"))] = 1
+        if e["case"] == "header-distance" and e["found"]:
+            cover[(RS41, "found with flags", e["at"], e["flags"] ^ inv)] = 1
+
+
+def required_coverage_rs41(names) -> list:
+    """the keys that check_plan must have counted after the named RS41 streams"""
+    req = []
+    for inv in (0, 1):
+        if "rs41-header" + ("-inv" if inv else "") in names:
+            req += [(RS41, "header-distance", k, inv) for k in RS41_HEADER_DISTANCES]
+            req += [(RS41, "found with flags", k, inv) for k in (0, 1, 5, 6)] + [(RS41, "found with flags", k, 1 - inv) for k in (58, 59, 63, 64)]
+            req += [(RS41, "header-distance", "not found", inv), (RS41, "header-distance", "found", inv)]
+    if "rs41-decoy" in names:
+        for pinv in (0, 1):
+            ov = _hdr_overlap_shifts(bool(pinv))
+            for D in (ov[0][0], ov[-1][0], 64, 65, 100, 127, 200, 300, 600):
+                req += [(RS41, "decoy", (D, pinv), 0), (RS41, "behind-decoy", (D, pinv), 0)]
+        req += [(RS41, "decoy", "found", 0), (RS41, "behind-decoy", "not found", 0), (RS41, "after-decoy", "found", 0)]
+        req += [(RS41, "decoy-one-bit-early", pinv, 0) for pinv in (0, 1)]
+        req += [(RS41, "decoy-one-bit-early", "not found", 0), (RS41, "behind-early-decoy", "found", 0)]
+    if "rs41-inpayload" in names:
+        req += [(RS41, "header-in-payload", (p, e, bo), 0) for p in (0, 1) for e in (0, 1) for bo in range(8)]
+        req += [(RS41, "header-in-payload", "not found", 0), (RS41, "carries-headers", "found", 0), (RS41, "behind-carrier", "found", 0)]
+    if "rs41-gaps" in names:
+        req += [(RS41, "gap", g, 0) for g in RS41_GAPS] + [(RS41, "gap", "found", 0)]
+        req += [(RS41, "bitpos mod 64", r) for r in range(64)] + [(RS41, "bitpos mod 32", r) for r in range(32)]
+    if "rs41-length" in names:
+        for ext in (0, 1):
+            for k in (1, 2, 3, 4, 5):
+                true, other = (518, 320) if ext else (320, 518)
+                read = (518 if k <= 3 else 320) if ext else (320 if k <= 4 else 518)          # 4 wrong bits: a tie, which goes to 320
+                req += [(RS41, "length-byte", (ext, k), 0), (RS41, "length read", (ext, k), read)]
+        req += [(RS41, "behind-length-byte", "found", 0), (RS41, "behind-length-byte", "not found", 0)]
+    if "rs41-codewords" in names:
+        for place in ("any", "parity"):
+            req += [(RS41, "codewords", (place, a, e), 0) for a, e in _pairs(RS41_CW_ERRORS)]
+        req += [(RS41, "codewords", ("ext", a, e), 0) for a, e in _pairs(RS41_CW_ERRORS)[::2] + [(12, 12), (13, 13)]]
+        req += [(RS41, "codewords", ("b56", a, x), 0) for a, x in ((1, 0), (12, 0), (13, 0), (3, 1))]
+        req += [(RS41, "codewords", ("last", e, x), 0) for e in (1, 12, 13) for x in (0, 1)]
+        req += [(RS41, "codewords", ("header", f), 0) for f in (1, 6)]
+        req += [(RS41, "codewords", ("L13", k, x), 0) for k in (0, 1) for x in (0, 1)]
+    if "rs41-padding" in names:
+        req += [(RS41, "padding", (p, m), 0) for p in (1, 2, 3) for m in (0, 1, 2)]
+    if "rs41-order" in names:
+        req += [(RS41, "order", (name, i + 2, ch), 0) for name, order in RS41_ORDERS.items() for i, ch in enumerate(order)]
+    if "rs41-end" in names:
+        req += [(RS41, "stream-end", name, 0) for name in ("in-header", "before-byte-56", "behind-byte-56")]
+        req += [(RS41, "pending", name) for name in ("before-byte-56", "behind-byte-56")] + [(RS41, "stream-end", "not found", 0)]
+    return req

@@ -1,5 +1,5 @@
-"""The CPU oracle's stage 3 for the six non-RS41 sonde types (oracle/or_framers.c) against the independent reference of
-tests/framer_reference.py: unit by unit (BCH against the remainder table, Hamming on all 256 words in all 33 lanes, the checksums),
+"""The CPU oracle's stage 3 (oracle/or_framers.c for the six non-RS41 sonde types, oracle/or_fec.c for RS41) against the independent
+reference of tests/framer_reference.py: unit by unit (BCH against the remainder table, Hamming on all 256 words in all 33 lanes, the checksums),
 on every designed stream of tests/framer_streams.py and on noisy mixed scenes; the plan of every designed stream holds on the oracle's
 records and every decision path it was built for is counted; and every mutation of the reference is rejected by at least one designed
 stream, so the streams can see those bugs in a kernel (tests/test_gpu_framer_reference.py runs the same streams through the GPU)."""
@@ -21,7 +21,7 @@ _CACHE = {}
 def decoded(name: str):
     """(Designed, [bits per channel], [records per channel]) of a designed stream through the oracle, built once per session"""
     if name not in _CACHE:
-        d = S.all_streams()[name]()
+        d = (S.rs41_streams() if name in S.rs41_streams() else S.all_streams())[name]()
         x = d.iq.numpy()
         bits, recs = [], []
         for c in range(x.shape[0]):
@@ -35,6 +35,7 @@ def decoded(name: str):
 
 
 STREAMS = sorted(S.all_streams())
+RS41_STREAMS = sorted(S.rs41_streams())          # a list of their own: what the tests below select from STREAMS stays as it was
 
 
 # ------------------------------------------------------------------------------------------------ units
@@ -159,7 +160,78 @@ def test_designed_streams_cover_every_path(oracle):
           f"{pending} channels end inside a frame")
 
 
+# ------------------------------------------------------------------------------------------------ RS41: designed streams
+@pytest.mark.parametrize("name", RS41_STREAMS)
+def test_rs41_designed_stream(oracle, name):
+    """the conditions (the demodulator returns the planted bits of every planted frame and decoy), reference == oracle byte for byte,
+    the plan holds: every planted header is a case, only each channel's first frame is nobody's"""
+    d, bits, recs = decoded(name)
+    cover, nrec = {}, 0
+    for c in range(len(bits)):
+        assert d.plan[c], (name, c, "a channel without cases")
+        off, pol = S.check_conditions(d, c, bits[c])
+        ref = R.reference(R.RS41, bits[c], c)
+        assert len(ref) == len(recs[c]) and ref.tobytes() == recs[c].tobytes(), (name, c)
+        S.check_plan(d, c, ref, off, pol, cover)
+        assert name != "rs41-order" or len(ref) == 11, (name, c, len(ref))      # the first frame too: the cases are the 2nd .. 11th of the stream
+        nrec += len(ref)
+    print(f"FRAMER-REF stream {name}: {len(bits)} channels, {nrec} records, {sum(len(p) for p in d.plan)} planned cases")
+
+
+def test_rs41_designed_streams_cover_every_path(oracle):
+    cover, pending = {}, 0
+    for name in RS41_STREAMS:
+        d, bits, recs = decoded(name)
+        for c in range(len(bits)):
+            off, pol = S.align(d, c, bits[c])
+            S.check_plan(d, c, recs[c], off, pol, cover)
+            info = {}
+            R.reference(R.RS41, bits[c], c, info=info)
+            want = [e["pos"] + off for e in d.plan[c] if e.get("pending")]
+            assert ([info["pending"]] if "pending" in info else []) == want, (name, c, info, want)
+            pending += "pending" in info
+    req = S.required_coverage_rs41(RS41_STREAMS)
+    missing = [k for k in req if k not in cover]
+    assert not missing, (len(missing), missing[:10])
+    assert pending >= 2
+    print(f"FRAMER-REF RS41 coverage: {len(cover)} keys, none of the {len(req)} required ones missing; {pending} channels end inside a frame")
+
+
+@pytest.mark.parametrize("name", RS41_STREAMS)
+def test_rs41_designed_stream_behind_the_wide_modem(oracle, name):
+    """the conditions hold behind the 2:1 modem too (the GPU test runs these streams under SONDE_FLAG_WIDE)"""
+    d = S.rs41_streams()[name]()
+    L = oracle_lib.lib()
+    L.or_modem_set_decim(R.RS41, 2)
+    try:
+        x = d.iq.numpy()
+        for c in range(x.shape[0]):
+            ch = oracle_lib.Channel(R.RS41, c)
+            ch.feed(x[c])
+            bits = ch.bits()
+            off, pol = S.check_conditions(d, c, bits)
+            ref = R.reference(R.RS41, bits, c)
+            assert ref.tobytes() == ch.frames().tobytes(), (name, c)
+            S.check_plan(d, c, ref, off, pol, {})
+            del ch
+    finally:
+        L.or_modem_set_decim(R.RS41, 4)
+
+
+def test_rs41_l13_word_is_what_it_claims():
+    """the planted word of the `L13` case: Berlekamp-Massey ends with L = 13 and 13 roots inside the codeword (t = 13 would correct it)"""
+    for n in (24 + 132, 255):
+        e, pos = S.rs41_l13_parity_error(n, 13)
+        word = list(e) + [0] * (n - 24)
+        assert R.rs41_rs_decode(word)[0] == -1
+        ne, out = R.rs41_rs_decode(word, t=13)
+        assert ne == 13 and sorted(k for k in range(n) if out[k] != word[k]) == sorted(pos)
+
+
 # ------------------------------------------------------------------------------------------------ noisy scenes
+RS41_NOISY_EBN0 = (9.0, 12.0)
+
+
 @pytest.mark.parametrize("ebn0,seed", [(5.0, 1), (7.5, 2), (10.0, 3), (12.5, 4)])
 def test_noisy_mixed_scene(oracle, ebn0, seed):
     """the scenes of test_gpu_fuzz_parity.run_mixed (the non-RS41 types of it, plus M20 and the AFSK types)"""
@@ -176,7 +248,21 @@ def test_noisy_mixed_scene(oracle, ebn0, seed):
             assert R.reference(t, ch.bits(), c).tobytes() == fr.tobytes(), (t, kw, c)
             total += len(fr)
     assert total > 0
-    print(f"FRAMER-REF noisy {ebn0} dB: {total} records equal")
+    # RS41 at levels of its own (five channels each), so that clean, corrected and rejected codewords all occur in every one of the four
+    # scenes: a codeword of 156 bytes is clean only where almost none has 13 wrong bytes, so no single level shows all three
+    kinds = [0, 0, 0]
+    for k, level in enumerate(RS41_NOISY_EBN0):
+        sb = synth.make_batch(0, 5, n, seed=100 * seed + k, ebn0_db=level, cfo_max_hz=500.0, invert=seed % 2 == 0, extended=seed == 3)
+        x = sb.iq.numpy()
+        for c in range(x.shape[0]):
+            ch = oracle_lib.Channel(0, c)
+            ch.feed(x[c])
+            fr = ch.frames()
+            assert R.reference(0, ch.bits(), c).tobytes() == fr.tobytes(), (0, level, c)
+            kinds = [kinds[0] + int((fr["nerr"] == 0).sum()), kinds[1] + int((fr["nerr"] > 0).sum()), kinds[2] + int((fr["nerr"] < 0).sum())]
+            total += len(fr)
+    assert min(kinds) > 0, kinds
+    print(f"FRAMER-REF noisy {ebn0} dB: {total} records equal; RS41 at {RS41_NOISY_EBN0} dB: codewords clean / corrected / rejected {kinds}")
 
 
 def test_afsk_complemented_bit_streams(oracle):
@@ -196,7 +282,7 @@ MUT_CASES = [(m, t) for m, (kw, types) in R.MUTATIONS.items() for t in types]
 def test_mutation_is_rejected(oracle, mutation, stype):
     """the mutated reference must differ from the oracle on at least one designed stream of the type"""
     kw = R.MUTATIONS[mutation][0]
-    for name in STREAMS:
+    for name in (RS41_STREAMS if stype == R.RS41 else STREAMS):
         d, bits, recs = decoded(name)
         if d.stype != stype:
             continue
