@@ -112,6 +112,16 @@ FLAG_IMS_RESCUE = 512         # iMS-100: second pass over frames with a BCH bloc
 FLAG_AFSK_RESCUE = 1024       # iMet / C50: second pass over packets whose check failed, one bit or an adjacent pair repaired (SONDE_FLAG_AFSK_RESCUE; opt-in)
 
 
+def rescue_flags(rescue=False, manchester_rescue=False, dfm_rescue=False, ims_rescue=False, afsk_rescue=False) -> int:
+    """The batch flags of a receiver's rescue keywords: rescue=True: FLAG_RS41_RESCUE, the second pass over RS41 frames whose RS stage
+    failed (SPEC 3.3c; a channel's restart clears its layout); manchester_rescue: FLAG_MANCHESTER_RESCUE, the one over M10 / M20 / MRZ-N1
+    frames whose check failed (3.3f); dfm_rescue: FLAG_DFM_RESCUE, DFM frames with a Hamming word given up on (3.3g); ims_rescue:
+    FLAG_IMS_RESCUE, iMS-100 frames with a BCH block rejected (3.3h); afsk_rescue: FLAG_AFSK_RESCUE, iMet / C50 packets whose check
+    failed (3.3i)."""
+    return ((FLAG_RS41_RESCUE if rescue else 0) | (FLAG_MANCHESTER_RESCUE if manchester_rescue else 0) | (FLAG_DFM_RESCUE if dfm_rescue else 0) |
+            (FLAG_IMS_RESCUE if ims_rescue else 0) | (FLAG_AFSK_RESCUE if afsk_rescue else 0))
+
+
 def frame_blocks(flags):
     """BCH blocks SONDE_FLAG_IMS_RESCUE decoded in a rescued iMS-100 frame (SONDE_FRAME_BLOCKS); an int or a numpy array of SondeFrame.flags"""
     return (flags >> 8) & 0xF
@@ -220,17 +230,13 @@ def load() -> C.CDLL:
     if hasattr(L, "sonde_batch_rescue_info"):             # absent only in older A/B builds loaded through SONDE_MI355_LIB
         L.sonde_batch_test_rs255_erasures.argtypes = [vp, vp, C.c_size_t, C.c_int, vp, vp]
         L.sonde_batch_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(SondeRs41Layout), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    if hasattr(L, "sonde_batch_manchester_rescue_info"):  # absent only in older A/B builds loaded through SONDE_MI355_LIB
-        L.sonde_batch_manchester_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    if hasattr(L, "sonde_batch_dfm_rescue_info"):         # absent only in older A/B builds loaded through SONDE_MI355_LIB
-        L.sonde_batch_dfm_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.sonde_batch_test_hamming84_erasures.argtypes = [vp, vp, vp, C.c_size_t, vp]
-    if hasattr(L, "sonde_batch_ims_rescue_info"):         # absent only in older A/B builds loaded through SONDE_MI355_LIB
-        L.sonde_batch_ims_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.sonde_batch_test_ims_block.argtypes = [vp, C.c_size_t, vp, vp, vp]
-    if hasattr(L, "sonde_batch_afsk_rescue_info"):        # absent only in older A/B builds loaded through SONDE_MI355_LIB
-        L.sonde_batch_afsk_rescue_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.sonde_batch_test_afsk_repair.argtypes = [vp, vp, C.c_size_t, vp]
+    # the four counter passes: the counters query, and the entry that runs a step of the pass alone (Manchester has none)
+    for who, unit, unit_args in (("manchester", None, None), ("dfm", "hamming84_erasures", [vp, vp, vp, C.c_size_t, vp]),
+                                 ("ims", "ims_block", [vp, C.c_size_t, vp, vp, vp]), ("afsk", "afsk_repair", [vp, vp, C.c_size_t, vp])):
+        if hasattr(L, f"sonde_batch_{who}_rescue_info"):  # absent only in older A/B builds loaded through SONDE_MI355_LIB
+            getattr(L, f"sonde_batch_{who}_rescue_info").argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            if unit:
+                getattr(L, f"sonde_batch_test_{unit}").argtypes = unit_args
     if hasattr(L, "sonde_batch_set_diversity"):           # absent only in older A/B builds loaded through SONDE_MI355_LIB
         L.sonde_batch_set_diversity.argtypes = [vp, vp, vp, C.c_uint32]
         L.sonde_batch_diversity_info.argtypes = [vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]

@@ -177,19 +177,20 @@ class SondeBatch:
         layouts = {flen: [(int(l.offset[i]), int(l.type[i]), int(l.len[i])) for i in range(l.n_blocks)] for flen, l in ((320, lay[0]), (518, lay[1]))}
         return {"layouts": layouts, "tried": int(tried.value), "rescued": int(rescued.value)}
 
+    def _counters(self, query, channel: int) -> dict:
+        tried, rescued = C.c_uint32(), C.c_uint32()
+        self._chk(query(self.h, channel, C.byref(tried), C.byref(rescued)))
+        return {"tried": int(tried.value), "rescued": int(rescued.value)}
+
     def manchester_rescue_info(self, channel: int) -> dict:
         """FLAG_MANCHESTER_RESCUE: what the second pass has done on an M10 / M20 / MRZ-N1 channel (sonde_batch_manchester_rescue_info):
         {'tried': frames whose check failed that reached the solver, 'rescued': frames it corrected}."""
-        tried, rescued = C.c_uint32(), C.c_uint32()
-        self._chk(self.L.sonde_batch_manchester_rescue_info(self.h, channel, C.byref(tried), C.byref(rescued)))
-        return {"tried": int(tried.value), "rescued": int(rescued.value)}
+        return self._counters(self.L.sonde_batch_manchester_rescue_info, channel)
 
     def dfm_rescue_info(self, channel: int) -> dict:
         """FLAG_DFM_RESCUE: what the second pass has done on a DFM channel (sonde_batch_dfm_rescue_info): {'tried': frames with a
         failed Hamming word that reached the erasure decoder, 'rescued': frames it completed}."""
-        tried, rescued = C.c_uint32(), C.c_uint32()
-        self._chk(self.L.sonde_batch_dfm_rescue_info(self.h, channel, C.byref(tried), C.byref(rescued)))
-        return {"tried": int(tried.value), "rescued": int(rescued.value)}
+        return self._counters(self.L.sonde_batch_dfm_rescue_info, channel)
 
     def test_hamming84_erasures(self, words: np.ndarray, erased: np.ndarray):
         """FLAG_DFM_RESCUE's word decoder alone (sonde_batch_test_hamming84_erasures): words, erased [n] uint8 (erased: mask of the
@@ -205,9 +206,7 @@ class SondeBatch:
     def ims_rescue_info(self, channel: int) -> dict:
         """FLAG_IMS_RESCUE: what the second pass has done on an iMS-100 channel (sonde_batch_ims_rescue_info): {'tried': frames with a
         rejected BCH block that reached the block decoder, 'rescued': frames it completed}."""
-        tried, rescued = C.c_uint32(), C.c_uint32()
-        self._chk(self.L.sonde_batch_ims_rescue_info(self.h, channel, C.byref(tried), C.byref(rescued)))
-        return {"tried": int(tried.value), "rescued": int(rescued.value)}
+        return self._counters(self.L.sonde_batch_ims_rescue_info, channel)
 
     def test_ims_block(self, blocks: np.ndarray, viol: np.ndarray):
         """FLAG_IMS_RESCUE's block decoder alone (sonde_batch_test_ims_block): blocks, viol [n] uint64 (blocks: bit b of the block is bit
@@ -224,9 +223,7 @@ class SondeBatch:
     def afsk_rescue_info(self, channel: int) -> dict:
         """FLAG_AFSK_RESCUE: what the second pass has done on an iMet / C50 channel (sonde_batch_afsk_rescue_info): {'tried': packets whose
         check failed that reached the pattern search, 'rescued': packets it repaired}."""
-        tried, rescued = C.c_uint32(), C.c_uint32()
-        self._chk(self.L.sonde_batch_afsk_rescue_info(self.h, channel, C.byref(tried), C.byref(rescued)))
-        return {"tried": int(tried.value), "rescued": int(rescued.value)}
+        return self._counters(self.L.sonde_batch_afsk_rescue_info, channel)
 
     def test_afsk_repair(self, records: np.ndarray):
         """FLAG_AFSK_RESCUE's per-record routine alone (sonde_batch_test_afsk_repair): records [n] FRAME_DTYPE, caller-made.  Returns

@@ -105,7 +105,7 @@ __device__ __forceinline__ int aq_repair(SondeFrame *__restrict__ fr, uint32_t t
 }
 
 __global__ __launch_bounds__(64 * AQ_WAVES) void sd_afsk_rescue_kernel(SondeFrame *__restrict__ frames, const uint32_t *__restrict__ counts,
-	uint32_t max_frames, const uint32_t *__restrict__ chlist, uint32_t n_list, SdAfskRescueState *__restrict__ states)
+	uint32_t max_frames, const uint32_t *__restrict__ chlist, uint32_t n_list, SdRescueCounters *__restrict__ states)
 {
 	const int lane = threadIdx.x & 63;
 	const uint32_t li_ch = AQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
@@ -139,22 +139,10 @@ __global__ __launch_bounds__(64 * AQ_WAVES) void sd_afsk_rescue_kernel(SondeFram
 	}
 }
 
-void sd_launch_rescue_afsk(uint32_t n_list, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
-	const uint32_t *chlist, SdAfskRescueState *states)
+void sd_launch_rescue_afsk(const SdRescueArgs &a)
 {
-	hipLaunchKernelGGL(sd_afsk_rescue_kernel, dim3((n_list + AQ_WAVES - 1) / AQ_WAVES), dim3(64 * AQ_WAVES), 0, stream,
-		frames, counts, max_frames, chlist, n_list, states);
-}
-
-// ---- the listed channels back to counters zero (sonde_batch_restart_channels)
-__global__ __launch_bounds__(64) void sd_afsk_rescue_clear_kernel(const uint32_t *__restrict__ list, uint32_t n, SdAfskRescueState *__restrict__ states)
-{
-	const uint32_t i = 64 * blockIdx.x + threadIdx.x;
-	if (i < n) { states[list[i]].tried = 0u; states[list[i]].rescued = 0u; }
-}
-void sd_launch_afsk_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdAfskRescueState *states)
-{
-	hipLaunchKernelGGL(sd_afsk_rescue_clear_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, list, n, states);
+	hipLaunchKernelGGL(sd_afsk_rescue_kernel, dim3((a.n_list + AQ_WAVES - 1) / AQ_WAVES), dim3(64 * AQ_WAVES), 0, a.stream,
+		a.frames, a.counts, a.max_frames, a.chlist, a.n_list, (SdRescueCounters *)a.states);
 }
 
 // ---- aq_repair alone over n caller-made records, one wave each (sonde_batch_test_afsk_repair): status 0 untouched, 1 rescued,

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <algorithm>
+#include <string>
 #include <vector>
 #include "batch_impl.h"
 #include "sd_devmem.h"
@@ -38,7 +39,7 @@ extern "C" void sonde_batch_destroy(SondeBatch *b)
 	if (b->ev_xs) (void)hipEventDestroy(b->ev_xs);
 	if (b->ev_restart) (void)hipEventDestroy(b->ev_restart);
 	b->restart_lists.destroy();
-	(void)hipFree(b->d_taps); (void)hipFree(b->d_modems); (void)hipFree(b->d_prog); (void)hipFree(b->d_rescue);
+	(void)hipFree(b->d_taps); (void)hipFree(b->d_modems); (void)hipFree(b->d_prog);
 	(void)hipFree(b->d_astates); (void)hipFree(b->d_wtab); (void)hipFree(b->d_wtab_c50); (void)hipFree(b->d_afq);
 	for (auto &u : b->units) { if (u.st) (void)hipStreamDestroy(u.st); for (int k = 0; k < 2; k++) if (u.ev_join[k]) (void)hipEventDestroy(u.ev_join[k]); }
 	for (int k = 0; k < 4; k++) (void)hipFree(b->d_cls[k]);
@@ -174,18 +175,17 @@ static int build(SondeBatch *b, const SondeBatchConfig *cfg)
 	HIPCHK(dev_zeros(b->d_hist, C * SD_HIST * sizeof(float)));
 	HIPCHK(dev_zeros(b->d_bitring, C * (size_t)b->ring_words * sizeof(uint32_t)));
 	HIPCHK(dev_zeros(b->d_prog, (C + 1) * sizeof(uint32_t)));
-	if ((cfg->flags & SONDE_FLAG_RS41_RESCUE) && !b->chlist[SONDE_RS41].empty()) {
-		HIPCHK(dev_zeros(b->d_rescue, C * sizeof(SdRescueState)));       // no layout, counters zero
+	uint32_t types_present = 0;
+	for (int t = 0; t < SONDE_NTYPES; t++) types_present |= (uint32_t)!b->chlist[t].empty() << t;
+	for (int k = 0; k < SD_N_PASSES; k++) {      // the rescue passes asked for that have a channel to work on: no layout, counters zero
+		const SdRescuePass &p = k_rescue_passes[k];
+		if ((cfg->flags & p.flag) && (types_present & p.types)) HIPCHK(b->d_pass[k].zeros(C * p.words));
 	}
-	if ((cfg->flags & SONDE_FLAG_MANCHESTER_RESCUE) && !(b->chlist[SONDE_M10].empty() && b->chlist[SONDE_MRZN1].empty())) {
+	if (b->d_pass[SD_PASS_MANCHESTER]) {
 		uint16_t mrz[43 * 8];
 		fec_mrz_table(mrz);
-		HIPCHK(b->d_mrescue.zeros(C));
 		HIPCHK(b->d_mrztab.upload(mrz, 43 * 8));
 	}
-	if ((cfg->flags & SONDE_FLAG_DFM_RESCUE) && !b->chlist[SONDE_DFM09].empty()) HIPCHK(b->d_drescue.zeros(C));
-	if ((cfg->flags & SONDE_FLAG_IMS_RESCUE) && !b->chlist[SONDE_IMS100].empty()) HIPCHK(b->d_irescue.zeros(C));
-	if ((cfg->flags & SONDE_FLAG_AFSK_RESCUE) && n_afsk) HIPCHK(b->d_arescue.zeros(C));
 	if (n_afsk) {
 		float wtab[2 * SD_AF_PER], wc[2 * SD_C50_PER];
 		make_mixer(wtab, 17, SD_AF_PER);         // iMet: 1700 Hz
@@ -322,11 +322,9 @@ int sd_batch_submit_bins(SondeBatch *b, const SdBinsArgs *ba, size_t n_steps, vo
 	if (!b || !ba || !ba->phases || !ba->carry_rows || !ba->g_comp || !sd_batch_bins_capable(b)) return sd_fail("sd_batch_submit_bins: bad argument");
 	//  the launch-unit path knows nothing of phase rows: it would read them as float rows without an error
 	if (!b->units.empty()) return sd_fail("sd_batch_submit_bins: the decoder batch behind a channelizer must be one plain launch (no launch units)");
-	if (b->d_rescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_RS41_RESCUE is not available for the decoder batch behind a channelizer");
-	if (b->d_mrescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_MANCHESTER_RESCUE is not available for the decoder batch behind a channelizer");
-	if (b->d_drescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_DFM_RESCUE is not available for the decoder batch behind a channelizer");
-	if (b->d_irescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_IMS_RESCUE is not available for the decoder batch behind a channelizer");
-	if (b->d_arescue) return sd_fail("sd_batch_submit_bins: SONDE_FLAG_AFSK_RESCUE is not available for the decoder batch behind a channelizer");
+	for (int k = 0; k < SD_N_PASSES; k++)
+		if (b->d_pass[k])
+			return sd_fail((std::string("sd_batch_submit_bins: ") + k_rescue_passes[k].flag_name + " is not available for the decoder batch behind a channelizer").c_str());
 	if (b->n_groups) return sd_fail("sd_batch_submit_bins: sonde_batch_set_diversity is not available for the decoder batch behind a channelizer");
 	const size_t n_out = n_steps / 5 * 12;
 	if (n_steps == 0 || n_steps % 2560 || n_out > b->max_samples || ba->row_stride < n_steps + 16)
@@ -412,47 +410,22 @@ static int launch_framers(SondeBatch *b, SubmitCtx &cx, int t, hipStream_t sk, u
 }
 
 // What follows a demod launch on its stream sk: the frame decoders of the sonde types it covered (a bit mask), each over the piece
-// [off, off + nch) of its type's channel list (nch = 0: the whole list), and behind RS41's the rescue pass of SONDE_FLAG_RS41_RESCUE
-// (SPEC 3.3c) over the same channels: directly behind the kernel that wrote the records (the demod kernel's epilogue, or
-// sd_rsdec_rs41_kernel), before anything joins that stream or records the submit's completion.  whole_batch: the launch covered
-// channels 0..n-1 of an all-RS41 batch, and the rescue pass needs no list.  Behind M10's and MRZ-N1's, in the same way, the pass of
-// SONDE_FLAG_MANCHESTER_RESCUE (SPEC 3.3f), behind DFM's that of SONDE_FLAG_DFM_RESCUE (SPEC 3.3g), behind iMS-100's that of
-// SONDE_FLAG_IMS_RESCUE (SPEC 3.3h), and behind iMet's and C50's that of SONDE_FLAG_AFSK_RESCUE (SPEC 3.3i).
+// [off, off + nch) of its type's channel list (nch = 0: the whole list), and behind each type's decoders the rescue passes the batch
+// has for that type over the same channels: directly behind the kernel that wrote the records, before anything joins that stream or
+// records the submit's completion.  whole_batch: the launch covered channels 0..n-1 of an all-RS41 batch, and the pass needs no list.
 static int launch_decoders(SondeBatch *b, SubmitCtx &cx, uint32_t types, hipStream_t sk, uint32_t off = 0, uint32_t nch = 0, bool whole_batch = false)
 {
 	for (int t = 0; t < SONDE_NTYPES; t++) {
 		if (!(types >> t & 1u)) continue;
 		if (launch_framers(b, cx, t, sk, off, nch)) return -1;
-		if ((t == SONDE_M10 || t == SONDE_MRZN1) && b->d_mrescue && !b->chlist[t].empty()) {
-			sd_launch_rescue_manchester(nch ? nch : (uint32_t)b->chlist[t].size(), sk, b->fec.m10tab, b->d_mrztab, b->d_states, b->d_bitring, b->ring_words,
-				cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_chlist[t] + off, b->d_mrescue);
+		const uint32_t n = nch ? nch : (uint32_t)b->chlist[t].size();
+		for (int k = 0; k < SD_N_PASSES; k++) {
+			if (!(k_rescue_passes[k].types >> t & 1u) || !b->d_pass[k] || !n) continue;
+			k_rescue_passes[k].launch({ n, sk, b->fec, b->d_mrztab, b->d_states, b->d_bitring, b->ring_words, cx.slot->d_frames, cx.slot->d_counts,
+				b->max_frames, whole_batch ? nullptr : b->d_chlist[t] + off, b->d_pass[k] });
 			HIPCHK(hipGetLastError());
 			cx.framer_launched = true;
 		}
-		if (t == SONDE_DFM09 && b->d_drescue && !b->chlist[t].empty()) {
-			sd_launch_rescue_dfm(nch ? nch : (uint32_t)b->chlist[t].size(), sk, b->d_states, b->d_bitring, b->ring_words,
-				cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_chlist[t] + off, b->d_drescue);
-			HIPCHK(hipGetLastError());
-			cx.framer_launched = true;
-		}
-		if (t == SONDE_IMS100 && b->d_irescue && !b->chlist[t].empty()) {
-			sd_launch_rescue_ims(nch ? nch : (uint32_t)b->chlist[t].size(), sk, b->fec.g64, b->d_states, b->d_bitring, b->ring_words,
-				cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_chlist[t] + off, b->d_irescue);
-			HIPCHK(hipGetLastError());
-			cx.framer_launched = true;
-		}
-		if ((t == SONDE_IMET4 || t == SONDE_C50) && b->d_arescue && !b->chlist[t].empty()) {
-			sd_launch_rescue_afsk(nch ? nch : (uint32_t)b->chlist[t].size(), sk, cx.slot->d_frames, cx.slot->d_counts, b->max_frames,
-				b->d_chlist[t] + off, b->d_arescue);
-			HIPCHK(hipGetLastError());
-			cx.framer_launched = true;
-		}
-		const uint32_t n_rescue = nch ? nch : (uint32_t)b->chlist[SONDE_RS41].size();
-		if (t != SONDE_RS41 || !b->d_rescue || !n_rescue) continue;
-		sd_launch_rescue_rs41(n_rescue, sk, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, cx.slot->d_frames, cx.slot->d_counts, b->max_frames,
-			whole_batch ? nullptr : b->d_chlist[SONDE_RS41] + off, b->d_rescue);
-		HIPCHK(hipGetLastError());
-		cx.framer_launched = true;
 	}
 	return 0;
 }
@@ -658,6 +631,18 @@ __global__ __launch_bounds__(256) void sd_batch_restart_kernel(const uint32_t *_
 	}
 }
 
+// The state of a rescue pass, `words` dwords per channel, back to zero for the n listed channels (every word of every listed state:
+// one thread each)
+__global__ __launch_bounds__(64) void sd_rescue_clear_kernel(const uint32_t *__restrict__ list, uint32_t n, uint32_t *__restrict__ states, uint32_t words)
+{
+	const uint32_t i = 64 * blockIdx.x + threadIdx.x;
+	if (i < n * words) states[(size_t)list[i / words] * words + i % words] = 0u;
+}
+static void sd_launch_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, uint32_t *states, uint32_t words)
+{
+	hipLaunchKernelGGL(sd_rescue_clear_kernel, dim3((n * words + 63) / 64), dim3(64), 0, stream, list, n, states, words);
+}
+
 void sd_batch_mark_channelizer(SondeBatch *b) { if (b) b->behind_channelizer = true; }
 
 extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *channels, size_t n)
@@ -697,24 +682,9 @@ extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *chann
 	hipLaunchKernelGGL(sd_batch_restart_kernel, dim3((unsigned)n), dim3(256), 0, s, lb->dev, b->d_states, b->d_fstates, b->d_hist, b->d_bitring,
 		b->ring_words, b->d_astates, b->d_prog, b->d_modems);
 	HIPCHK(hipGetLastError());
-	if (b->d_rescue) {                         // SPEC 3.3c: a restarted channel has no layout
-		sd_launch_rescue_clear((uint32_t)n, s, lb->dev, b->d_rescue);
-		HIPCHK(hipGetLastError());
-	}
-	if (b->d_mrescue) {                        // SPEC 3.3f: a restarted channel's counters are zero
-		sd_launch_manchester_clear((uint32_t)n, s, lb->dev, b->d_mrescue);
-		HIPCHK(hipGetLastError());
-	}
-	if (b->d_drescue) {                        // SPEC 3.3g: a restarted channel's counters are zero
-		sd_launch_dfm_rescue_clear((uint32_t)n, s, lb->dev, b->d_drescue);
-		HIPCHK(hipGetLastError());
-	}
-	if (b->d_irescue) {                        // SPEC 3.3h: a restarted channel's counters are zero
-		sd_launch_ims_rescue_clear((uint32_t)n, s, lb->dev, b->d_irescue);
-		HIPCHK(hipGetLastError());
-	}
-	if (b->d_arescue) {                        // SPEC 3.3i: a restarted channel's counters are zero
-		sd_launch_afsk_rescue_clear((uint32_t)n, s, lb->dev, b->d_arescue);
+	for (int k = 0; k < SD_N_PASSES; k++) {     // SPEC 3.3c .. 3.3i: a restarted channel has no layout, and its counters are zero
+		if (!b->d_pass[k]) continue;
+		sd_launch_rescue_clear((uint32_t)n, s, lb->dev, b->d_pass[k], k_rescue_passes[k].words);
 		HIPCHK(hipGetLastError());
 	}
 	if (b->n_groups) {                         // SPEC 3.3j: a restarted group has no carried records, and its counters are zero

@@ -23,13 +23,26 @@
 #define SD_EV_ORDER  (hipEventDisableTiming | SD_EV_FLAGS)
 
 #pragma GCC visibility push(hidden)       // private types: their inline members are not among the library's exported symbols
-// The FEC tables of the frame decoders (sd_tables.h), each its own allocation
-struct SdFecTables {
-	uint8_t *gfexp = nullptr;              // zero-absorbing antilog table of the RS decoder (GF_EXP2 in framer_kernel.hip)
-	uint8_t *gflog = nullptr;              // 256 x u16 logarithms, log 0 = 768
-	uint32_t *gfswar = nullptr;            // byte-slice tables of the 24 syndrome multipliers alpha^(4j), framer_kernel.hip
-	uint8_t *g64 = nullptr;                // GF(2^6): iMS-100's BCH(63,51)
-	uint16_t *m10tab = nullptr;            // Meteomodem checksum as a GF(2) matrix product: rows A^k B, sd_fixed.h
+// The rescue passes (launch.h, DESIGN "what a rescue pass plugs into"), one row each: what create, submit, restart and the info
+// entries need to know about a pass
+struct SdRescuePass {
+	uint32_t flag; const char *flag_name;  // SONDE_FLAG_*_RESCUE and its name
+	uint32_t types;                        // bit t: the pass follows the frame decoders of sonde type t
+	uint32_t words;                        // dwords of state per channel (the counters are the last two)
+	void (*launch)(const SdRescueArgs &);
+	const char *info;                      // its introspection entry, sonde_batch_*_rescue_info
+	const char *article, *kind;            // "has no <kind> channel", "not <article> <kind> channel"
+};
+enum { SD_PASS_RS41, SD_PASS_MANCHESTER, SD_PASS_DFM, SD_PASS_IMS, SD_PASS_AFSK, SD_N_PASSES };
+static const SdRescuePass k_rescue_passes[SD_N_PASSES] = {
+	{ SONDE_FLAG_RS41_RESCUE, "SONDE_FLAG_RS41_RESCUE", 1u << SONDE_RS41, sizeof(SdRescueState) / 4, sd_launch_rescue_rs41,
+	  "sonde_batch_rescue_info", "an", "RS41" },
+	{ SONDE_FLAG_MANCHESTER_RESCUE, "SONDE_FLAG_MANCHESTER_RESCUE", 1u << SONDE_M10 | 1u << SONDE_MRZN1, 2, sd_launch_rescue_manchester,
+	  "sonde_batch_manchester_rescue_info", "an", "M10 / M20 / MRZ-N1" },
+	{ SONDE_FLAG_DFM_RESCUE, "SONDE_FLAG_DFM_RESCUE", 1u << SONDE_DFM09, 2, sd_launch_rescue_dfm, "sonde_batch_dfm_rescue_info", "a", "DFM" },
+	{ SONDE_FLAG_IMS_RESCUE, "SONDE_FLAG_IMS_RESCUE", 1u << SONDE_IMS100, 2, sd_launch_rescue_ims, "sonde_batch_ims_rescue_info", "an", "iMS-100" },
+	{ SONDE_FLAG_AFSK_RESCUE, "SONDE_FLAG_AFSK_RESCUE", 1u << SONDE_IMET4 | 1u << SONDE_C50, 2, sd_launch_rescue_afsk,
+	  "sonde_batch_afsk_rescue_info", "an", "iMet or C50" },
 };
 
 // Timing events.  An event record is a bubble of a few microseconds in the command stream (three of them cost a 0.29 ms step 3 %), so
@@ -82,7 +95,7 @@ struct SondeBatch {
 	float *d_taps = nullptr;
 	SdModem *d_modems = nullptr;
 	SdModem h_modems[SONDE_NTYPES] = {};   // host copy: the bins decoder takes the table by value
-	SdFecTables fec;
+	SdFecTables fec = {};
 	uint32_t fuse_fec = 1;                 // RS41 FEC in the demod kernel's epilogue (default) or as its own kernel (SONDE_FLAG_SPLIT_FEC)
 	uint32_t fixed_epi = 1;                // the fixed-length framers' frames decoded in the demod kernel's epilogue too (round 6; not behind a channelizer: bins_kernel.hip)
 	void *d_descs = nullptr;
@@ -150,23 +163,10 @@ struct SondeBatch {
 	hipEvent_t ev_restart = nullptr;
 	std::deque<std::pair<uint64_t, uint32_t>> parser_restarts;
 	bool behind_channelizer = false;
-	// SONDE_FLAG_RS41_RESCUE (SPEC 3.3c): per-channel layouts and counters of the second pass (rescue_kernel.hip); null: the flag is
-	// off or the batch has no RS41 channel, and nothing of it is allocated or launched
-	SdRescueState *d_rescue = nullptr;
-	// SONDE_FLAG_MANCHESTER_RESCUE (SPEC 3.3f): per-channel counters of the second pass over M10 / M20 / MRZ-N1 records
-	// (check_rescue_kernel.hip) and MRZ-N1's column table; null: the flag is off or the batch has no such channel, and nothing of it
-	// is allocated or launched
-	DevBuf<SdManchesterState> d_mrescue;
+	// the rescue passes (k_rescue_passes): per pass [n_channels][words] of state; null: its flag is off or the batch has no channel of its
+	// types, and nothing of it is allocated or launched.  d_mrztab: MRZ-N1's column table, with the Manchester pass
+	DevBuf<uint32_t> d_pass[SD_N_PASSES];
 	DevBuf<uint16_t> d_mrztab;
-	// SONDE_FLAG_DFM_RESCUE (SPEC 3.3g): per-channel counters of the second pass over DFM records (dfm_rescue_kernel.hip); null: the
-	// flag is off or the batch has no DFM channel, and nothing of it is allocated or launched
-	DevBuf<SdDfmRescueState> d_drescue;
-	// SONDE_FLAG_IMS_RESCUE (SPEC 3.3h): per-channel counters of the second pass over iMS-100 records (ims_rescue_kernel.hip); null: the
-	// flag is off or the batch has no iMS-100 channel, and nothing of it is allocated or launched
-	DevBuf<SdImsRescueState> d_irescue;
-	// SONDE_FLAG_AFSK_RESCUE (SPEC 3.3i): per-channel counters of the second pass over iMet and C50 records (afsk_rescue_kernel.hip);
-	// null: the flag is off or the batch has no iMet or C50 channel, and nothing of it is allocated or launched
-	DevBuf<SdAfskRescueState> d_arescue;
 	// sonde_batch_set_diversity (SPEC 3.3j): the group table, per group SD_DIV_MAX carried records and two counters, the slot
 	// (SD_DIV_MAX * group + member, or -1) of every channel on both sides; null / empty: the call was never made, and nothing of it is
 	// allocated or launched

@@ -1,6 +1,7 @@
 // batch_probe.hip -- introspection for the staged parity tests and the bench: the RS correctors alone, a channel's state and bits,
 // what the rescue pass has learned, and the HBM read probe.  Not on the product path.
 #include <hip/hip_runtime.h>
+#include <string>
 #include <vector>
 #include "batch_impl.h"
 
@@ -41,46 +42,45 @@ extern "C" int sonde_batch_test_rs255_erasures(SondeBatch *b, uint8_t *cw_pairs,
 	return test_rs255("sonde_batch_test_rs255_erasures", b, cw_pairs, n_pairs, n, erased, status);
 }
 
+// What a rescue pass (k_rescue_passes) has counted on a channel: the last two words of the channel's state
+static int rescue_info(SondeBatch *b, int pass, uint32_t channel, uint32_t *tried, uint32_t *rescued)
+{
+	const SdRescuePass &p = k_rescue_passes[pass];
+	const std::string who = std::string(p.info) + ": ";
+	if (!b || channel >= b->n_channels) return sd_fail((who + "bad argument").c_str());
+	if (b->behind_channelizer) return sd_fail((who + p.flag_name + " is not available for the batch behind a channelizer").c_str());
+	if (!b->d_pass[pass]) return sd_fail((who + "the batch was created without " + p.flag_name + " (or has no " + p.kind + " channel)").c_str());
+	if (!(p.types >> b->types[channel] & 1u)) return sd_fail((who + "not " + p.article + " " + p.kind + " channel").c_str());
+	if (sonde_batch_sync(b) < 0) return -1;
+	SdRescueCounters cnt;
+	HIPCHK(hipMemcpy(&cnt, b->d_pass[pass] + ((size_t)channel + 1) * p.words - 2, sizeof(cnt), hipMemcpyDeviceToHost));
+	if (tried) *tried = cnt.tried;
+	if (rescued) *rescued = cnt.rescued;
+	return 0;
+}
+
 extern "C" int sonde_batch_rescue_info(SondeBatch *b, uint32_t channel, SondeRs41Layout out[2], uint32_t *tried, uint32_t *rescued)
 {
-	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_rescue_info: bad argument");
-	if (b->behind_channelizer) return sd_fail("sonde_batch_rescue_info: SONDE_FLAG_RS41_RESCUE is not available for the batch behind a channelizer");
-	if (!b->d_rescue) return sd_fail("sonde_batch_rescue_info: the batch was created without SONDE_FLAG_RS41_RESCUE (or has no RS41 channel)");
-	if (b->types[channel] != SONDE_RS41) return sd_fail("sonde_batch_rescue_info: not an RS41 channel");
-	if (sonde_batch_sync(b) < 0) return -1;
-	SdRescueState st;
-	HIPCHK(hipMemcpy(&st, b->d_rescue + channel, sizeof(st), hipMemcpyDeviceToHost));
-	if (out) { out[0] = st.lay[0]; out[1] = st.lay[1]; }
-	if (tried) *tried = st.tried;
-	if (rescued) *rescued = st.rescued;
+	if (rescue_info(b, SD_PASS_RS41, channel, tried, rescued)) return -1;
+	const SdRescueState *st = (const SdRescueState *)(uint32_t *)b->d_pass[SD_PASS_RS41] + channel;
+	if (out) HIPCHK(hipMemcpy(out, st->lay, sizeof(st->lay), hipMemcpyDeviceToHost));
 	return 0;
 }
-
 extern "C" int sonde_batch_manchester_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued)
 {
-	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_manchester_rescue_info: bad argument");
-	if (!b->d_mrescue) return sd_fail("sonde_batch_manchester_rescue_info: the batch was created without SONDE_FLAG_MANCHESTER_RESCUE (or has no M10 / M20 / MRZ-N1 channel)");
-	if (b->types[channel] != SONDE_M10 && b->types[channel] != SONDE_MRZN1) return sd_fail("sonde_batch_manchester_rescue_info: not an M10 / M20 / MRZ-N1 channel");
-	if (sonde_batch_sync(b) < 0) return -1;
-	SdManchesterState st;
-	HIPCHK(hipMemcpy(&st, b->d_mrescue + channel, sizeof(st), hipMemcpyDeviceToHost));
-	if (tried) *tried = st.tried;
-	if (rescued) *rescued = st.rescued;
-	return 0;
+	return rescue_info(b, SD_PASS_MANCHESTER, channel, tried, rescued);
 }
-
 extern "C" int sonde_batch_dfm_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued)
 {
-	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_dfm_rescue_info: bad argument");
-	if (b->behind_channelizer) return sd_fail("sonde_batch_dfm_rescue_info: SONDE_FLAG_DFM_RESCUE is not available for the batch behind a channelizer");
-	if (!b->d_drescue) return sd_fail("sonde_batch_dfm_rescue_info: the batch was created without SONDE_FLAG_DFM_RESCUE (or has no DFM channel)");
-	if (b->types[channel] != SONDE_DFM09) return sd_fail("sonde_batch_dfm_rescue_info: not a DFM channel");
-	if (sonde_batch_sync(b) < 0) return -1;
-	SdDfmRescueState st;
-	HIPCHK(hipMemcpy(&st, b->d_drescue + channel, sizeof(st), hipMemcpyDeviceToHost));
-	if (tried) *tried = st.tried;
-	if (rescued) *rescued = st.rescued;
-	return 0;
+	return rescue_info(b, SD_PASS_DFM, channel, tried, rescued);
+}
+extern "C" int sonde_batch_ims_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued)
+{
+	return rescue_info(b, SD_PASS_IMS, channel, tried, rescued);
+}
+extern "C" int sonde_batch_afsk_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued)
+{
+	return rescue_info(b, SD_PASS_AFSK, channel, tried, rescued);
 }
 
 // Step 4 of SPEC 3.3g alone, through the kernel's own device function: n words and their erasure masks, decoded in place;
@@ -101,20 +101,6 @@ extern "C" int sonde_batch_test_hamming84_erasures(SondeBatch *b, uint8_t *words
 	return 0;
 }
 
-extern "C" int sonde_batch_ims_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued)
-{
-	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_ims_rescue_info: bad argument");
-	if (b->behind_channelizer) return sd_fail("sonde_batch_ims_rescue_info: SONDE_FLAG_IMS_RESCUE is not available for the batch behind a channelizer");
-	if (!b->d_irescue) return sd_fail("sonde_batch_ims_rescue_info: the batch was created without SONDE_FLAG_IMS_RESCUE (or has no iMS-100 channel)");
-	if (b->types[channel] != SONDE_IMS100) return sd_fail("sonde_batch_ims_rescue_info: not an iMS-100 channel");
-	if (sonde_batch_sync(b) < 0) return -1;
-	SdImsRescueState st;
-	HIPCHK(hipMemcpy(&st, b->d_irescue + channel, sizeof(st), hipMemcpyDeviceToHost));
-	if (tried) *tried = st.tried;
-	if (rescued) *rescued = st.rescued;
-	return 0;
-}
-
 // Step 3 of SPEC 3.3h alone, through the kernel's own device function: n blocks (bit b of the block = bit 45 - b) and the masks of
 // their violated boundaries (bit k = boundary k, 0..46), decoded in place; status[i] = bits flipped, -1 = no decode (block untouched).
 extern "C" int sonde_batch_test_ims_block(SondeBatch *b, size_t n, uint64_t *blocks, const uint64_t *viol, int32_t *status)
@@ -130,20 +116,6 @@ extern "C" int sonde_batch_test_ims_block(SondeBatch *b, size_t n, uint64_t *blo
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpy(blocks, d_b, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-	return 0;
-}
-
-extern "C" int sonde_batch_afsk_rescue_info(SondeBatch *b, uint32_t channel, uint32_t *tried, uint32_t *rescued)
-{
-	if (!b || channel >= b->n_channels) return sd_fail("sonde_batch_afsk_rescue_info: bad argument");
-	if (b->behind_channelizer) return sd_fail("sonde_batch_afsk_rescue_info: SONDE_FLAG_AFSK_RESCUE is not available for the batch behind a channelizer");
-	if (!b->d_arescue) return sd_fail("sonde_batch_afsk_rescue_info: the batch was created without SONDE_FLAG_AFSK_RESCUE (or has no iMet or C50 channel)");
-	if (b->types[channel] != SONDE_IMET4 && b->types[channel] != SONDE_C50) return sd_fail("sonde_batch_afsk_rescue_info: not an iMet or C50 channel");
-	if (sonde_batch_sync(b) < 0) return -1;
-	SdAfskRescueState st;
-	HIPCHK(hipMemcpy(&st, b->d_arescue + channel, sizeof(st), hipMemcpyDeviceToHost));
-	if (tried) *tried = st.tried;
-	if (rescued) *rescued = st.rescued;
 	return 0;
 }
 

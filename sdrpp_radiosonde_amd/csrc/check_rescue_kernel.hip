@@ -51,7 +51,7 @@ __global__ __launch_bounds__(64 * MQ_WAVES) void sd_manchester_rescue_kernel(
 	const uint16_t *__restrict__ m10tab /* [99][8] */, const uint16_t *__restrict__ mrztab /* [43][8] */,
 	const SdChanState *__restrict__ chan_states, const uint32_t *__restrict__ bitring, uint32_t ring_words,
 	SondeFrame *__restrict__ frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const uint32_t *__restrict__ chlist, uint32_t n_list, SdManchesterState *__restrict__ states)
+	const uint32_t *__restrict__ chlist, uint32_t n_list, SdRescueCounters *__restrict__ states)
 {
 	const int lane = threadIdx.x & 63;
 	const uint32_t li_ch = MQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
@@ -180,21 +180,8 @@ __global__ __launch_bounds__(64 * MQ_WAVES) void sd_manchester_rescue_kernel(
 	}
 }
 
-void sd_launch_rescue_manchester(uint32_t n_list, hipStream_t stream, const uint16_t *m10tab, const uint16_t *mrztab, const SdChanState *chan_states,
-	const uint32_t *bitring, uint32_t ring_words, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist,
-	SdManchesterState *states)
+void sd_launch_rescue_manchester(const SdRescueArgs &a)
 {
-	hipLaunchKernelGGL(sd_manchester_rescue_kernel, dim3((n_list + MQ_WAVES - 1) / MQ_WAVES), dim3(64 * MQ_WAVES), 0, stream,
-		m10tab, mrztab, chan_states, bitring, ring_words, frames, counts, max_frames, chlist, n_list, states);
-}
-
-// ---- the listed channels back to counters zero (sonde_batch_restart_channels)
-__global__ __launch_bounds__(64) void sd_manchester_clear_kernel(const uint32_t *__restrict__ list, uint32_t n, SdManchesterState *__restrict__ states)
-{
-	const uint32_t i = 64 * blockIdx.x + threadIdx.x;
-	if (i < n) { states[list[i]].tried = 0u; states[list[i]].rescued = 0u; }
-}
-void sd_launch_manchester_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdManchesterState *states)
-{
-	hipLaunchKernelGGL(sd_manchester_clear_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, list, n, states);
+	hipLaunchKernelGGL(sd_manchester_rescue_kernel, dim3((a.n_list + MQ_WAVES - 1) / MQ_WAVES), dim3(64 * MQ_WAVES), 0, a.stream,
+		a.fec.m10tab, a.mrztab, a.chan_states, a.bitring, a.ring_words, a.frames, a.counts, a.max_frames, a.chlist, a.n_list, (SdRescueCounters *)a.states);
 }

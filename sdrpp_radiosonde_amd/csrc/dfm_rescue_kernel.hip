@@ -56,7 +56,7 @@ __device__ __forceinline__ uint32_t dq_chip(const uint32_t *__restrict__ ring, u
 __global__ __launch_bounds__(64 * DQ_WAVES) void sd_dfm_rescue_kernel(
 	const SdChanState *__restrict__ chan_states, const uint32_t *__restrict__ bitring, uint32_t ring_words,
 	SondeFrame *__restrict__ frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const uint32_t *__restrict__ chlist, uint32_t n_list, SdDfmRescueState *__restrict__ states)
+	const uint32_t *__restrict__ chlist, uint32_t n_list, SdRescueCounters *__restrict__ states)
 {
 	const int lane = threadIdx.x & 63;
 	const uint32_t li_ch = DQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
@@ -132,22 +132,10 @@ __global__ __launch_bounds__(64 * DQ_WAVES) void sd_dfm_rescue_kernel(
 	}
 }
 
-void sd_launch_rescue_dfm(uint32_t n_list, hipStream_t stream, const SdChanState *chan_states, const uint32_t *bitring, uint32_t ring_words,
-	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist, SdDfmRescueState *states)
+void sd_launch_rescue_dfm(const SdRescueArgs &a)
 {
-	hipLaunchKernelGGL(sd_dfm_rescue_kernel, dim3((n_list + DQ_WAVES - 1) / DQ_WAVES), dim3(64 * DQ_WAVES), 0, stream,
-		chan_states, bitring, ring_words, frames, counts, max_frames, chlist, n_list, states);
-}
-
-// ---- the listed channels back to counters zero (sonde_batch_restart_channels)
-__global__ __launch_bounds__(64) void sd_dfm_rescue_clear_kernel(const uint32_t *__restrict__ list, uint32_t n, SdDfmRescueState *__restrict__ states)
-{
-	const uint32_t i = 64 * blockIdx.x + threadIdx.x;
-	if (i < n) { states[list[i]].tried = 0u; states[list[i]].rescued = 0u; }
-}
-void sd_launch_dfm_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdDfmRescueState *states)
-{
-	hipLaunchKernelGGL(sd_dfm_rescue_clear_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, list, n, states);
+	hipLaunchKernelGGL(sd_dfm_rescue_kernel, dim3((a.n_list + DQ_WAVES - 1) / DQ_WAVES), dim3(64 * DQ_WAVES), 0, a.stream,
+		a.chan_states, a.bitring, a.ring_words, a.frames, a.counts, a.max_frames, a.chlist, a.n_list, (SdRescueCounters *)a.states);
 }
 
 // ---- test introspection: step 4 alone on caller-supplied (word, erasure mask) pairs (sonde_batch_test_hamming84_erasures)

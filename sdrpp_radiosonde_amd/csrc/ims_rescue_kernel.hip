@@ -108,7 +108,7 @@ __device__ __forceinline__ bool iq_decode_block(uint32_t s1, uint32_t s3, uint64
 __global__ __launch_bounds__(64 * IQ_WAVES) void sd_ims_rescue_kernel(
 	const uint8_t *__restrict__ g64, const SdChanState *__restrict__ chan_states, const uint32_t *__restrict__ bitring, uint32_t ring_words,
 	SondeFrame *__restrict__ frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const uint32_t *__restrict__ chlist, uint32_t n_list, SdImsRescueState *__restrict__ states)
+	const uint32_t *__restrict__ chlist, uint32_t n_list, SdRescueCounters *__restrict__ states)
 {
 	const int lane = threadIdx.x & 63;
 	const uint32_t li_ch = IQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
@@ -215,22 +215,10 @@ __global__ __launch_bounds__(64 * IQ_WAVES) void sd_ims_rescue_kernel(
 	}
 }
 
-void sd_launch_rescue_ims(uint32_t n_list, hipStream_t stream, const uint8_t *g64, const SdChanState *chan_states, const uint32_t *bitring,
-	uint32_t ring_words, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist, SdImsRescueState *states)
+void sd_launch_rescue_ims(const SdRescueArgs &a)
 {
-	hipLaunchKernelGGL(sd_ims_rescue_kernel, dim3((n_list + IQ_WAVES - 1) / IQ_WAVES), dim3(64 * IQ_WAVES), 0, stream,
-		g64, chan_states, bitring, ring_words, frames, counts, max_frames, chlist, n_list, states);
-}
-
-// ---- the listed channels back to counters zero (sonde_batch_restart_channels)
-__global__ __launch_bounds__(64) void sd_ims_rescue_clear_kernel(const uint32_t *__restrict__ list, uint32_t n, SdImsRescueState *__restrict__ states)
-{
-	const uint32_t i = 64 * blockIdx.x + threadIdx.x;
-	if (i < n) { states[list[i]].tried = 0u; states[list[i]].rescued = 0u; }
-}
-void sd_launch_ims_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdImsRescueState *states)
-{
-	hipLaunchKernelGGL(sd_ims_rescue_clear_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, list, n, states);
+	hipLaunchKernelGGL(sd_ims_rescue_kernel, dim3((a.n_list + IQ_WAVES - 1) / IQ_WAVES), dim3(64 * IQ_WAVES), 0, a.stream,
+		a.fec.g64, a.chan_states, a.bitring, a.ring_words, a.frames, a.counts, a.max_frames, a.chlist, a.n_list, (SdRescueCounters *)a.states);
 }
 
 // ---- test introspection: step 3 alone on caller-supplied (block, violation mask) pairs (sonde_batch_test_ims_block); one wave per

@@ -86,51 +86,45 @@ void sd_launch_framer_other(int type, uint32_t n_list, hipStream_t stream,
 void sd_launch_rs255_unit(uint8_t *cw_io, uint32_t n_pairs, int n, int32_t *status, const uint8_t *gf_exp, const uint8_t *gf_log,
 	const uint32_t *gf_swar, hipStream_t stream);
 
-// SONDE_FLAG_RS41_RESCUE (rescue_kernel.hip, DESIGN SPEC 3.3c): per RS41 channel the learned block layouts of the two frame lengths
-// (320, 518) and two counters (frames with a failed codeword that had a layout to try; frames rescued), carried from submit to submit
+// The FEC tables of the frame decoders (sd_tables.h), each its own allocation
+struct SdFecTables {
+	uint8_t *gfexp;                        // zero-absorbing antilog table of the RS decoder (GF_EXP2 in framer_kernel.hip)
+	uint8_t *gflog;                        // 256 x u16 logarithms, log 0 = 768
+	uint32_t *gfswar;                      // byte-slice tables of the 24 syndrome multipliers alpha^(4j), framer_kernel.hip
+	uint8_t *g64;                          // GF(2^6): iMS-100's BCH(63,51); exp[128], log[64]
+	uint16_t *m10tab;                      // Meteomodem checksum as a GF(2) matrix product: rows A^k B, sd_fixed.h
+};
+
+// THE RESCUE PASSES (DESIGN "what a rescue pass plugs into"): opt-in second passes over a submit's frame records, each behind the
+// frame decoders of its sonde types on their stream.  Every pass carries per channel two counters from submit to submit -- records
+// that reached its decoder, records rescued -- as the LAST two words of its state; RS41's state has its learned block layouts of the
+// two frame lengths (320, 518) in front of them, the other four have nothing else.
+struct SdRescueCounters { uint32_t tried, rescued; };
 struct SdRescueState { SondeRs41Layout lay[2]; uint32_t tried, rescued; };
-void sd_launch_rescue_rs41(uint32_t n_list, hipStream_t stream, const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar,
-	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist, SdRescueState *states);
-void sd_launch_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdRescueState *states);
+// what a pass launcher may need; each picks what its kernel takes
+struct SdRescueArgs {
+	uint32_t n_list; hipStream_t stream;
+	SdFecTables fec;
+	const uint16_t *mrztab;                // MRZ-N1's column table (SONDE_FLAG_MANCHESTER_RESCUE only, else null)
+	const SdChanState *chan_states; const uint32_t *bitring; uint32_t ring_words;
+	SondeFrame *frames; const uint32_t *counts; uint32_t max_frames;
+	const uint32_t *chlist;                // null (RS41 only): channels 0..n_list-1
+	void *states;                          // [n_channels] of the pass's state
+};
+void sd_launch_rescue_rs41(const SdRescueArgs &a);            // SONDE_FLAG_RS41_RESCUE (rescue_kernel.hip, DESIGN SPEC 3.3c)
+void sd_launch_rescue_manchester(const SdRescueArgs &a);      // SONDE_FLAG_MANCHESTER_RESCUE (check_rescue_kernel.hip, 3.3f): M10 / M20 / MRZ-N1
+void sd_launch_rescue_dfm(const SdRescueArgs &a);             // SONDE_FLAG_DFM_RESCUE (dfm_rescue_kernel.hip, 3.3g)
+void sd_launch_rescue_ims(const SdRescueArgs &a);             // SONDE_FLAG_IMS_RESCUE (ims_rescue_kernel.hip, 3.3h)
+void sd_launch_rescue_afsk(const SdRescueArgs &a);            // SONDE_FLAG_AFSK_RESCUE (afsk_rescue_kernel.hip, 3.3i): iMet / C50
+// test introspection, each a step of its pass alone over caller-made cases (device memory), in place:
+// the errors-and-erasures corrector of 3.3c on codeword pairs
 void sd_launch_rsee_unit(uint8_t *cw_io, const uint8_t *erased, uint32_t n_pairs, int n, int32_t *status, const uint8_t *gf_exp, const uint8_t *gf_log,
 	const uint32_t *gf_swar, hipStream_t stream);
-
-// SONDE_FLAG_MANCHESTER_RESCUE (check_rescue_kernel.hip, DESIGN SPEC 3.3f): per M10 / M20 / MRZ-N1 channel two counters (frames whose check
-// failed that reached the solver; frames rescued), carried from submit to submit.  chlist: never null.
-struct SdManchesterState { uint32_t tried, rescued; };
-void sd_launch_rescue_manchester(uint32_t n_list, hipStream_t stream, const uint16_t *m10tab, const uint16_t *mrztab, const SdChanState *chan_states,
-	const uint32_t *bitring, uint32_t ring_words, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist,
-	SdManchesterState *states);
-void sd_launch_manchester_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdManchesterState *states);
-
-// SONDE_FLAG_DFM_RESCUE (dfm_rescue_kernel.hip, DESIGN SPEC 3.3g): per DFM channel two counters (frames with a word the first pass gave
-// up on that reached the erasure decoder; frames rescued), carried from submit to submit.  chlist: never null.
-struct SdDfmRescueState { uint32_t tried, rescued; };
-void sd_launch_rescue_dfm(uint32_t n_list, hipStream_t stream, const SdChanState *chan_states, const uint32_t *bitring, uint32_t ring_words,
-	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist, SdDfmRescueState *states);
-void sd_launch_dfm_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdDfmRescueState *states);
-// step 4 of SPEC 3.3g alone: n words and their erasure masks (device memory), decoded in place; status = bits changed, -1 = no decode
+// step 4 of 3.3g: n words and their erasure masks; status = bits changed, -1 = no decode
 void sd_launch_hamming84_unit(uint8_t *words, const uint8_t *erased, uint32_t n, int32_t *status, hipStream_t stream);
-
-// SONDE_FLAG_IMS_RESCUE (ims_rescue_kernel.hip, DESIGN SPEC 3.3h): per iMS-100 channel two counters (frames with a BCH block the first
-// pass rejected that reached the block decoder; frames rescued), carried from submit to submit.  chlist: never null.  g64: GF(2^6)
-// exp[128], log[64].
-struct SdImsRescueState { uint32_t tried, rescued; };
-void sd_launch_rescue_ims(uint32_t n_list, hipStream_t stream, const uint8_t *g64, const SdChanState *chan_states, const uint32_t *bitring,
-	uint32_t ring_words, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist, SdImsRescueState *states);
-void sd_launch_ims_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdImsRescueState *states);
-// step 3 of SPEC 3.3h alone: n blocks and the masks of their violated boundaries (device memory), decoded in place; status = bits
-// flipped, -1 = no decode
+// step 3 of 3.3h: n blocks and the masks of their violated boundaries; status = bits flipped, -1 = no decode
 void sd_launch_ims_block_unit(const uint8_t *g64, uint64_t *blocks, const uint64_t *viols, uint32_t n, int32_t *status, hipStream_t stream);
-
-// SONDE_FLAG_AFSK_RESCUE (afsk_rescue_kernel.hip, DESIGN SPEC 3.3i): per iMet / C50 channel two counters (packets whose check failed that
-// reached the pattern search; packets rescued), carried from submit to submit.  chlist: never null.
-struct SdAfskRescueState { uint32_t tried, rescued; };
-void sd_launch_rescue_afsk(uint32_t n_list, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
-	const uint32_t *chlist, SdAfskRescueState *states);
-void sd_launch_afsk_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdAfskRescueState *states);
-// steps 1..5 of SPEC 3.3i alone over n caller-made records (device memory), rewritten in place; status = 0 untouched, 1 rescued,
-// 2 several patterns fit
+// steps 1..5 of 3.3i: n records; status = 0 untouched, 1 rescued, 2 several patterns fit
 void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status, hipStream_t stream);
 
 // sonde_batch_set_diversity (diversity_kernel.hip, DESIGN SPEC 3.3j): a group = 2..4 RS41 channels that hear the same sonde; ch[m] and

@@ -198,22 +198,10 @@ __global__ __launch_bounds__(64 * RQ_WAVES) void sd_rs41_rescue_kernel(
 	if (dirty && lane < ST_WORDS) gst32[lane] = st32[lane];
 }
 
-void sd_launch_rescue_rs41(uint32_t n_list, hipStream_t stream, const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar,
-	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const uint32_t *chlist, SdRescueState *states)
+void sd_launch_rescue_rs41(const SdRescueArgs &a)
 {
-	hipLaunchKernelGGL(sd_rs41_rescue_kernel, dim3((n_list + RQ_WAVES - 1) / RQ_WAVES), dim3(64 * RQ_WAVES), 0, stream,
-		gf_exp, gf_log, gf_swar, frames, counts, max_frames, chlist, n_list, states);
-}
-
-// ---- the listed channels back to "no layout, counters zero" (sonde_batch_restart_channels)
-__global__ __launch_bounds__(64) void sd_rescue_clear_kernel(const uint32_t *__restrict__ list, SdRescueState *__restrict__ states)
-{
-	uint32_t *p = reinterpret_cast<uint32_t *>(states + list[blockIdx.x]);
-	if (threadIdx.x < sizeof(SdRescueState) / 4) p[threadIdx.x] = 0u;
-}
-void sd_launch_rescue_clear(uint32_t n, hipStream_t stream, const uint32_t *list, SdRescueState *states)
-{
-	hipLaunchKernelGGL(sd_rescue_clear_kernel, dim3(n), dim3(64), 0, stream, list, states);
+	hipLaunchKernelGGL(sd_rs41_rescue_kernel, dim3((a.n_list + RQ_WAVES - 1) / RQ_WAVES), dim3(64 * RQ_WAVES), 0, a.stream,
+		a.fec.gfexp, a.fec.gflog, a.fec.gfswar, a.frames, a.counts, a.max_frames, a.chlist, a.n_list, (SdRescueState *)a.states);
 }
 
 // ---- test introspection: the errors-and-erasures corrector alone on caller-supplied codeword pairs (sonde_batch_test_rs255_erasures).

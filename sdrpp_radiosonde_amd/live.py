@@ -241,15 +241,8 @@ class LiveReceiver:
         self._bw = {t: min(VFO_RATE[t], IQ48_MAX_BW) for t in pol.pools}
         self.tuner = SondeTuner.slots(fs, 48000, self.n_dec + self.n_probes, sorted(set(self._bw.values()) | {PROBE_BW}), self.max_in,
                                       input_kind=input_kind, device=device)
-        # rescue=True: FLAG_RS41_RESCUE, the second pass over RS41 frames whose RS stage failed (SPEC 3.3c); a slot's restart clears its layout;
-        # manchester_rescue=True: FLAG_MANCHESTER_RESCUE, the one over M10 / M20 / MRZ-N1 frames whose check failed (SPEC 3.3f);
-        # dfm_rescue=True: FLAG_DFM_RESCUE, the one over DFM frames with a Hamming word given up on (SPEC 3.3g);
-        # ims_rescue=True: FLAG_IMS_RESCUE, the one over iMS-100 frames with a BCH block rejected (SPEC 3.3h);
-        # afsk_rescue=True: FLAG_AFSK_RESCUE, the one over iMet / C50 packets whose check failed (SPEC 3.3i)
         self.batch = SondeBatch(self.n_dec, n48, types=np.array(pol.slot_type, np.uint8), input_kind=INPUT_IQ, device=device,
-                                flags=(_lib.FLAG_RS41_RESCUE if rescue else 0) | (_lib.FLAG_MANCHESTER_RESCUE if manchester_rescue else 0) |
-                                (_lib.FLAG_DFM_RESCUE if dfm_rescue else 0) | (_lib.FLAG_IMS_RESCUE if ims_rescue else 0) |
-                                (_lib.FLAG_AFSK_RESCUE if afsk_rescue else 0))
+                                flags=_lib.rescue_flags(rescue, manchester_rescue, dfm_rescue, ims_rescue, afsk_rescue))
         self.detector = SondeDetector(self.n_probes, n48, device=device)
         self.scanner = SondeScanner(fs, self.max_in, input_kind=input_kind, device=device)
         self.track = bool(track)

@@ -234,14 +234,7 @@ class WidebandReceiver:
             c0 += len(idx)
         bt = np.array([types[i] for i in self.order], dtype=np.uint8)
         kind = INPUT_IQ if chain == "iq48" else INPUT_REAL
-        # rescue=True: FLAG_RS41_RESCUE, the second pass over RS41 frames whose RS stage failed (SPEC 3.3c); manchester_rescue=True:
-        # FLAG_MANCHESTER_RESCUE, the one over M10 / M20 / MRZ-N1 frames whose check failed (SPEC 3.3f); dfm_rescue=True: FLAG_DFM_RESCUE,
-        # the one over DFM frames with a Hamming word given up on (SPEC 3.3g); ims_rescue=True: FLAG_IMS_RESCUE, the one over iMS-100 frames
-        # with a BCH block rejected (SPEC 3.3h); afsk_rescue=True: FLAG_AFSK_RESCUE, the one over iMet / C50 packets whose check failed
-        # (SPEC 3.3i)
-        flags = ((_lib.FLAG_RS41_RESCUE if rescue else 0) | (_lib.FLAG_MANCHESTER_RESCUE if manchester_rescue else 0) |
-                 (_lib.FLAG_DFM_RESCUE if dfm_rescue else 0) | (_lib.FLAG_IMS_RESCUE if ims_rescue else 0) |
-                 (_lib.FLAG_AFSK_RESCUE if afsk_rescue else 0))
+        flags = _lib.rescue_flags(rescue, manchester_rescue, dfm_rescue, ims_rescue, afsk_rescue)
         self.batch = SondeBatch(len(types), n48, types=bt, input_kind=kind, device=device, flags=flags)
         stride = int(_lib.load().sonde_row_stride(n48, kind))
         shape = (len(types), stride, 2) if kind == INPUT_IQ else (len(types), stride)

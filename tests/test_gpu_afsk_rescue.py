@@ -4,12 +4,15 @@ byte, and they are the twin's over the CPU oracle; afsk_rescue_info reports the 
 oracle's and the entry point refuses.  The result does not depend on how the stream is cut into submits, on where the frame decoders
 run or on the completion mode; in a mixed batch with all five rescue flags only iMet / C50 records differ from the four-flag run; a
 restarted channel counts from zero; poll() delivers a rescued packet's fields."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import afsk_rescue_reference as ar
 import afsk_rescue_scenes as sc
+from rescue_gpu_harness import check_info, run
 from sdrpp_radiosonde_amd import _lib
 from sdrpp_radiosonde_amd.batch import SondeBatch, SondeError
 
@@ -19,6 +22,8 @@ RESCUE = _lib.FLAG_AFSK_RESCUE
 KINDS = ["imet", "c50"]
 AFSK_MIN = 16384             # the shortest submit of a batch with iMet or C50 channels
 _dev_cache = {}
+_run = functools.partial(run, tile=AFSK_MIN)
+_check_info = functools.partial(check_info, method="afsk_rescue_info", new_state=ar.new_state)
 
 
 def _iq(kind, clean=False):
@@ -28,40 +33,13 @@ def _iq(kind, clean=False):
     return _dev_cache[key]
 
 
-def _sorted(parts):
-    fr = np.concatenate(parts)
-    return fr[np.lexsort((fr["bitpos"], fr["channel"]))]
-
-
 def _types(kind):
     s = sc.scene_of(kind)
     return np.full(s.C, s.type, dtype=np.uint8)
 
 
-def _run(iq, flags, cuts=1, via_ticket=False, keep=False, **kw):
-    C_, n = iq.shape[0], iq.shape[1]
-    assert n % (cuts * AFSK_MIN) == 0
-    step = n // cuts
-    b = SondeBatch(C_, step, flags=flags, **kw)
-    parts = []
-    for k in range(cuts):
-        b.submit(iq[:, k * step:(k + 1) * step])
-        parts.append(b.frames_of(b.ticket()) if via_ticket else b.frames())
-    out = _sorted(parts)
-    if keep:
-        return out, b
-    b.close()
-    return out
-
-
 def _oracle_twin(kind):
     return ar.rescue(sc.oracle_run(kind))
-
-
-def _check_info(b, state, channels):
-    for c in channels:
-        st = state.get(c, ar.new_state())
-        assert b.afsk_rescue_info(c) == st, (c, st)
 
 
 @pytest.mark.parametrize("kind", KINDS)

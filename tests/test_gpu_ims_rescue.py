@@ -5,12 +5,15 @@ reports the twin's counters.  Without the flag the records are the oracle's and 
 on how the stream is cut into submits, on time slices, on where the frame decoders run, on the completion mode or (given that run's
 own chips) on SONDE_FLAG_WIDE; in a mixed batch with all four rescue flags only iMS-100 records differ from the three-flag run; a
 restarted channel counts from zero; poll() delivers a rescued frame's fragments and LiveReceiver's validity rule takes it."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import ims_rescue_reference as ir
 import ims_rescue_scenes as ims
+from rescue_gpu_harness import check_info, gpu_chips as _gpu_chips, run
 from sdrpp_radiosonde_amd import _lib
 from sdrpp_radiosonde_amd.batch import SondeBatch, SondeError
 
@@ -18,6 +21,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 RESCUE = _lib.FLAG_IMS_RESCUE
 _dev_cache = {}
+_run = functools.partial(run, tile=ims.TILE, default_type=ims.IMS)
+_check_info = functools.partial(check_info, method="ims_rescue_info", new_state=ir.new_state)
 
 
 def _iq(name="designed", clean=False):
@@ -27,44 +32,9 @@ def _iq(name="designed", clean=False):
     return _dev_cache[key]
 
 
-def _sorted(parts):
-    fr = np.concatenate(parts)
-    return fr[np.lexsort((fr["bitpos"], fr["channel"]))]
-
-
-def _run(iq, flags, cuts=1, via_ticket=False, keep=False, **kw):
-    C_, n = iq.shape[0], iq.shape[1]
-    assert (n // ims.TILE) % cuts == 0
-    step = n // cuts
-    kw.setdefault("types", np.full(C_, ims.IMS, dtype=np.uint8))
-    b = SondeBatch(C_, step, flags=flags, **kw)
-    parts = []
-    for k in range(cuts):
-        b.submit(iq[:, k * step:(k + 1) * step])
-        parts.append(b.frames_of(b.ticket()) if via_ticket else b.frames())
-    out = _sorted(parts)
-    if keep:
-        return out, b
-    b.close()
-    return out
-
-
-def _gpu_chips(b):
-    """a chips getter over the batch's bit rings (the whole stream is still there after ONE submit: the ring holds a submit and a frame)"""
-    def get(channel, start, count):
-        return b.read_bits(channel, start, count)
-    return get
-
-
 def _oracle_twin(name):
     fr, streams = ims.oracle_run(name)
     return ir.rescue(fr, ir.chips_of_streams(streams))
-
-
-def _check_info(b, state, channels):
-    for c in channels:
-        st = state.get(c, ir.new_state())
-        assert b.ims_rescue_info(c) == st, (c, st)
 
 
 def test_block_decoder_on_designed_random_and_ambiguous_pairs():

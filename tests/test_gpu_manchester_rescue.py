@@ -5,12 +5,15 @@ the twin's counters.  Without the flag the records are the oracle's and the entr
 the stream is cut into submits, on time slices, on where the frame decoders run or on the completion mode; in a mixed batch only
 M10 / M20 / MRZ-N1 records change, and the RS41 pass works beside it; a restarted channel counts from zero; poll() delivers a rescued
 frame's fragments."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import manchester_rescue_reference as mr
 import manchester_rescue_scenes as ms
+from rescue_gpu_harness import check_info, gpu_chips as _gpu_chips, run
 from sdrpp_radiosonde_amd import _lib, synth
 from sdrpp_radiosonde_amd.batch import SondeBatch, SondeError
 
@@ -19,6 +22,8 @@ DEV = "cuda:0"
 RESCUE = _lib.FLAG_MANCHESTER_RESCUE
 KINDS = ["m10", "m20", "mrz"]
 _dev_cache = {}
+_run = functools.partial(run, tile=ms.TILE)
+_check_info = functools.partial(check_info, method="manchester_rescue_info", new_state=mr.new_state)
 
 
 def _iq(kind, clean=False):
@@ -29,34 +34,6 @@ def _iq(kind, clean=False):
     return _dev_cache[key]
 
 
-def _sorted(parts):
-    fr = np.concatenate(parts)
-    return fr[np.lexsort((fr["bitpos"], fr["channel"]))]
-
-
-def _run(iq, flags, cuts=1, via_ticket=False, keep=False, **kw):
-    C_, n = iq.shape[0], iq.shape[1]
-    assert (n // ms.TILE) % cuts == 0
-    step = n // cuts
-    b = SondeBatch(C_, step, flags=flags, **kw)
-    parts = []
-    for k in range(cuts):
-        b.submit(iq[:, k * step:(k + 1) * step])
-        parts.append(b.frames_of(b.ticket()) if via_ticket else b.frames())
-    out = _sorted(parts)
-    if keep:
-        return out, b
-    b.close()
-    return out
-
-
-def _gpu_chips(b):
-    """a chips getter over the batch's bit rings (the whole stream is still there after ONE submit: the ring holds a submit and a frame)"""
-    def get(channel, start, count):
-        return b.read_bits(channel, start, count)
-    return get
-
-
 def _oracle_twin(kind):
     fr, streams = ms.oracle_run(kind)
     return mr.rescue(fr, mr.chips_of_streams(streams))
@@ -64,12 +41,6 @@ def _oracle_twin(kind):
 
 def _types(kind):
     return np.full(ms.scene(kind).C if kind != "noisy" else ms.noisy_scene().C, ms.KINDS[kind][0] if kind != "noisy" else ms.M10, dtype=np.uint8)
-
-
-def _check_info(b, state, channels):
-    for c in channels:
-        st = state.get(c, mr.new_state())
-        assert b.manchester_rescue_info(c) == st, (c, st)
 
 
 @pytest.mark.parametrize("kind", KINDS)

@@ -3,12 +3,15 @@ tests/test_rescue_reference.py: with the flag the records are the twin's over th
 rescue_info reports the twin's layouts and counters; without it they are the oracle's; a clean scene does not change; the result
 does not depend on how the stream is cut into submits, on time slices, on where the RS stage runs or on the completion mode; in
 a mixed batch only RS41 records change; a restarted channel starts without a layout; poll() delivers the rescued block."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import rescue_reference as rr
 import rescue_scenes as rs
+from rescue_gpu_harness import run, sorted_frames as _sorted
 from sdrpp_radiosonde_amd import _lib, synth
 from sdrpp_radiosonde_amd.batch import SondeBatch, SondeError
 
@@ -16,6 +19,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 RESCUE = _lib.FLAG_RS41_RESCUE
 _dev_cache = {}
+_run = functools.partial(run, tile=rs.TILE)
 
 
 def _iq(extended=False, clean=False):
@@ -23,27 +27,6 @@ def _iq(extended=False, clean=False):
     if key not in _dev_cache:
         _dev_cache[key] = torch.from_numpy(rs.scene(extended, clean).iq).to(DEV)
     return _dev_cache[key]
-
-
-def _sorted(parts):
-    fr = np.concatenate(parts)
-    return fr[np.lexsort((fr["bitpos"], fr["channel"]))]
-
-
-def _run(iq, flags, cuts=1, via_ticket=False, keep=False, **kw):
-    C_, n = iq.shape[0], iq.shape[1]
-    assert (n // rs.TILE) % cuts == 0
-    step = n // cuts
-    b = SondeBatch(C_, step, flags=flags, **kw)
-    parts = []
-    for k in range(cuts):
-        b.submit(iq[:, k * step:(k + 1) * step])
-        parts.append(b.frames_of(b.ticket()) if via_ticket else b.frames())
-    out = _sorted(parts)
-    if keep:
-        return out, b
-    b.close()
-    return out
 
 
 def _layouts(st):
