@@ -7,13 +7,14 @@
 //
 // This file: create / destroy, the launch plan of a submit (submit_impl) and the restart of single channels.  The object is
 // batch_impl.h; the tables it uploads are sd_tables.h; frames, poll and the timing queries are batch_results.cpp.
+// Its device memory, pinned list buffers, events and streams are members that release themselves (sd_devmem.h): destroy selects the
+// device, waits for the batch's own work and deletes; a create that fails half-way deletes the same way.
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <algorithm>
 #include <string>
 #include <vector>
 #include "batch_impl.h"
-#include "sd_devmem.h"
 #include "sd_input.h"
 
 static uint32_t pow2ceil(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
@@ -29,32 +30,26 @@ static __host__ __device__ inline SdChanState chan_state_init(int32_t type, int3
 	return st;
 }
 
+// What destroy waits for: the streams on which the batch may still have work.  last_stream is where the last submit completes and
+// where a restart's kernels follow it: the caller's stream (join mode 0, or no launch units), else done_stream, which has joined
+// every unit's last kernel.  In the late-joined modes the unit streams may hold a restart's ev_restart wait behind that, so they are
+// waited for too.  Nothing else of the batch's can be unfinished then: what a submit leaves on the caller's stream in those modes
+// (the timing start, ev_fork, join mode 1's waits for the previous submit's ev_join) precedes what the unit streams have completed.
+// After the wait no member is in use, and the order in which they are released does not matter.
 extern "C" void sonde_batch_destroy(SondeBatch *b)
 {
 	if (!b) return;
 	(void)hipSetDevice(b->device);
 	if (b->pending) (void)hipStreamSynchronize(b->last_stream);
-	(void)hipFree(b->d_states); (void)hipFree(b->d_fstates); (void)hipFree(b->d_hist); (void)hipFree(b->d_bitring);
-	for (SondeBatch::Slot &s : b->slot) { (void)hipFree(s.d_frames); (void)hipFree(s.d_counts); (void)hipFree(s.d_fo); if (s.ev_done) (void)hipEventDestroy(s.ev_done); }
-	if (b->ev_xs) (void)hipEventDestroy(b->ev_xs);
-	if (b->ev_restart) (void)hipEventDestroy(b->ev_restart);
-	b->restart_lists.destroy();
-	(void)hipFree(b->d_taps); (void)hipFree(b->d_modems); (void)hipFree(b->d_prog);
-	(void)hipFree(b->d_astates); (void)hipFree(b->d_wtab); (void)hipFree(b->d_wtab_c50); (void)hipFree(b->d_afq);
-	for (auto &u : b->units) { if (u.st) (void)hipStreamDestroy(u.st); for (int k = 0; k < 2; k++) if (u.ev_join[k]) (void)hipEventDestroy(u.ev_join[k]); }
-	for (int k = 0; k < 4; k++) (void)hipFree(b->d_cls[k]);
-	if (b->done_stream) (void)hipStreamDestroy(b->done_stream);
-	if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
-	(void)hipFree(b->fec.gfexp); (void)hipFree(b->fec.gflog); (void)hipFree(b->fec.gfswar); (void)hipFree(b->fec.g64); (void)hipFree(b->fec.m10tab);
-	(void)hipFree(b->d_descs); (void)hipFree(b->d_stage);
-	for (int t = 0; t < SONDE_NTYPES; t++) (void)hipFree(b->d_chlist[t]);
-	for (SdTiming::Submit &s : b->timing.submit) for (hipEvent_t e : s.ev) if (e) (void)hipEventDestroy(e);
-	for (hipEvent_t e : b->timing.unit) if (e) (void)hipEventDestroy(e);
+	if (b->join_mode != 0) {
+		for (const SondeBatch::Unit &u : b->units) (void)hipStreamSynchronize(u.st);
+		if (b->done_stream) (void)hipStreamSynchronize(b->done_stream);
+	}
 	delete b;
 }
 
 // ---------------------------------------------------------------- create
-static int upload_fec_tables(SdFecTables &f)
+static int upload_fec_tables(SondeBatch *b)
 {
 	uint8_t exp2[SD_GFEXP_BYTES];
 	uint16_t log2[256];
@@ -65,11 +60,12 @@ static int upload_fec_tables(SdFecTables &f)
 	fec_gf256_swar(swar);
 	fec_gf64_tables(g64);
 	fec_m10_table(m10);
-	HIPCHK(dev_upload(f.gfexp, exp2, sizeof(exp2)));
-	HIPCHK(dev_upload(f.gflog, log2, sizeof(log2)));
-	HIPCHK(dev_upload(f.gfswar, swar, sizeof(swar)));
-	HIPCHK(dev_upload(f.g64, g64, sizeof(g64)));
-	HIPCHK(dev_upload(f.m10tab, m10, sizeof(m10)));
+	HIPCHK(b->d_gfexp.upload(exp2, sizeof(exp2)));
+	HIPCHK(b->d_gflog.upload((const uint8_t *)log2, sizeof(log2)));
+	HIPCHK(b->d_gfswar.upload(swar, 24 * 8));
+	HIPCHK(b->d_g64.upload(g64, sizeof(g64)));
+	HIPCHK(b->d_m10tab.upload(m10, 99 * 8));
+	b->fec = { b->d_gfexp, b->d_gflog, b->d_gfswar, b->d_g64, b->d_m10tab };
 	return 0;
 }
 
@@ -170,11 +166,11 @@ static int build(SondeBatch *b, const SondeBatchConfig *cfg)
 	modem_fill(md, modems);
 	memcpy(b->h_modems, modems, sizeof(modems));
 	for (size_t c = 0; c < C; c++) st[c] = chan_state_init(b->types[c], modems[b->types[c]].period0);
-	HIPCHK(dev_upload(b->d_states, st.data(), C * sizeof(SdChanState)));
-	HIPCHK(dev_zeros(b->d_fstates, C * sizeof(SdFramerState)));
-	HIPCHK(dev_zeros(b->d_hist, C * SD_HIST * sizeof(float)));
-	HIPCHK(dev_zeros(b->d_bitring, C * (size_t)b->ring_words * sizeof(uint32_t)));
-	HIPCHK(dev_zeros(b->d_prog, (C + 1) * sizeof(uint32_t)));
+	HIPCHK(b->d_states.upload(st.data(), C));
+	HIPCHK(b->d_fstates.zeros(C));
+	HIPCHK(b->d_hist.zeros(C * SD_HIST));
+	HIPCHK(b->d_bitring.zeros(C * (size_t)b->ring_words));
+	HIPCHK(b->d_prog.zeros(C + 1));
 	uint32_t types_present = 0;
 	for (int t = 0; t < SONDE_NTYPES; t++) types_present |= (uint32_t)!b->chlist[t].empty() << t;
 	for (int k = 0; k < SD_N_PASSES; k++) {      // the rescue passes asked for that have a channel to work on: no layout, counters zero
@@ -190,40 +186,40 @@ static int build(SondeBatch *b, const SondeBatchConfig *cfg)
 		float wtab[2 * SD_AF_PER], wc[2 * SD_C50_PER];
 		make_mixer(wtab, 17, SD_AF_PER);         // iMet: 1700 Hz
 		make_mixer(wc, 19, SD_C50_PER);          // C50: 3800 Hz, midway between the 2900 / 4700 Hz tones
-		HIPCHK(dev_upload(b->d_wtab, wtab, sizeof(wtab)));
-		HIPCHK(dev_upload(b->d_wtab_c50, wc, sizeof(wc)));
-		HIPCHK(dev_zeros(b->d_astates, C * sizeof(SdAfskState)));
-		HIPCHK(dev_alloc(b->d_afq, n_afsk * (size_t)(cfg->max_samples / SD_AF_DEC) * sizeof(float)));
+		HIPCHK(b->d_wtab.upload(wtab, 2 * SD_AF_PER));
+		HIPCHK(b->d_wtab_c50.upload(wc, 2 * SD_C50_PER));
+		HIPCHK(b->d_astates.zeros(C));
+		HIPCHK(b->d_afq.alloc(n_afsk * (size_t)(cfg->max_samples / SD_AF_DEC)));
 	}
 
 	// ---- tables and channel lists
 	std::vector<float> taps((size_t)SONDE_NTYPES * SD_NPHASE * SD_NTAPS);
 	for (int t = 0; t < SONDE_NTYPES; t++) make_taps(md, t, &taps[(size_t)t * SD_NPHASE * SD_NTAPS]);
-	HIPCHK(dev_upload(b->d_taps, taps.data(), taps.size() * sizeof(float)));
-	HIPCHK(dev_upload(b->d_modems, modems, sizeof(modems)));
-	if (upload_fec_tables(b->fec)) return -1;
-	HIPCHK(dev_alloc(b->d_descs, C * (size_t)b->max_frames * SD_DESC_BYTES));
+	HIPCHK(b->d_taps.upload(taps.data(), taps.size()));
+	HIPCHK(b->d_modems.upload(modems, SONDE_NTYPES));
+	if (upload_fec_tables(b)) return -1;
+	HIPCHK(b->d_descs.alloc(C * (size_t)b->max_frames * SD_DESC_BYTES));
 	for (int t = 0; t < SONDE_NTYPES; t++)
-		if (!b->chlist[t].empty()) HIPCHK(dev_upload(b->d_chlist[t], b->chlist[t].data(), b->chlist[t].size() * sizeof(uint32_t)));
+		if (!b->chlist[t].empty()) HIPCHK(b->d_chlist[t].upload(b->chlist[t].data(), b->chlist[t].size()));
 
 	// ---- the two slot sets
 	for (SondeBatch::Slot &s : b->slot) {
-		HIPCHK(dev_alloc(s.d_frames, C * (size_t)b->max_frames * sizeof(SondeFrame)));
-		HIPCHK(dev_zeros(s.d_counts, C * sizeof(uint32_t)));
+		HIPCHK(s.d_frames.alloc(C * (size_t)b->max_frames));
+		HIPCHK(s.d_counts.zeros(C));
 		s.h_fo = { b->d_fstates, b->d_descs, s.d_counts, b->max_frames, b->fuse_fec, /* loop_fec_max_wg = */ b->residency, b->fec.gfexp, b->fec.gflog, b->fec.gfswar,
 		           b->fec.g64, s.d_frames, b->fec.m10tab, b->fixed_epi };
-		HIPCHK(dev_upload(s.d_fo, &s.h_fo, sizeof(s.h_fo)));
-		HIPCHK(hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming));
+		HIPCHK(s.d_fo.upload(&s.h_fo, 1));
+		HIPCHK(s.ev_done.create(hipEventDisableTiming));
 		s.h_counts.assign(C, 0);
 	}
-	HIPCHK(hipEventCreateWithFlags(&b->ev_xs, SD_EV_ORDER));
-	HIPCHK(hipEventCreateWithFlags(&b->ev_restart, SD_EV_ORDER));
+	HIPCHK(b->ev_xs.create(SD_EV_ORDER));
+	HIPCHK(b->ev_restart.create(SD_EV_ORDER));
 	b->timing.submit.resize(SdTiming::kSlots);
-	for (SdTiming::Submit &s : b->timing.submit) for (hipEvent_t &e : s.ev) HIPCHK(hipEventCreateWithFlags(&e, SD_EV_TIMING));
+	for (SdTiming::Submit &s : b->timing.submit) for (DevEvent &e : s.ev) HIPCHK(e.create(SD_EV_TIMING));
 	if (!need_lists) return 0;
 
 	// ---- launch units
-	HIPCHK(hipEventCreateWithFlags(&b->ev_fork, SD_EV_ORDER));
+	HIPCHK(b->ev_fork.create(SD_EV_ORDER));
 	if (b->join_mode != 0) {
 		// per type; pieces per type: one (2-8 pieces of every type of a mixed batch measured 6-70 % slower, profiles/r3_notes.md); a one-type batch: two
 		const int R = one_class_units;
@@ -233,21 +229,21 @@ static int build(SondeBatch *b, const SondeBatchConfig *cfg)
 			for (int t : order) {
 				const size_t nt = b->chlist[t].size();
 				const size_t lo = nt * (size_t)j / (size_t)R, hi = nt * (size_t)(j + 1) / (size_t)R;
-				if (hi > lo) b->units.push_back({ t, modem_class(md, t), (uint32_t)lo, (uint32_t)(hi - lo), 0, 1u << t, nullptr, { nullptr, nullptr } });
+				if (hi > lo) b->units.push_back({ t, modem_class(md, t), (uint32_t)lo, (uint32_t)(hi - lo), 0, 1u << t });
 			}
 	} else {
 		// per class; class order: the class with the longest-running workgroups (M10: twice the symbols per tile) first, then the 4:1
 		// class (whose RS41 workgroups end with the FEC epilogue): best of all orders in round 2 (profiles/r2_notes.md)
 		for (int k : { 3, 0, 2, 1 }) {
 			if (!b->n_cls[k]) continue;
-			HIPCHK(dev_upload(b->d_cls[k], cls[k].data(), cls[k].size() * sizeof(uint32_t)));
-			b->units.push_back({ -1, k, 0, b->n_cls[k], 0, class_types(b, k), nullptr, { nullptr, nullptr } });
+			HIPCHK(b->d_cls[k].upload(cls[k].data(), cls[k].size()));
+			b->units.push_back({ -1, k, 0, b->n_cls[k], 0, class_types(b, k) });
 		}
 	}
 	size_t row0 = 0;
 	for (int t : { SONDE_IMET4, SONDE_C50 }) {       // AFSK chains: tone demodulator -> 6 kS/s rows -> demod -> framer, one unit per type
 		if (b->chlist[t].empty()) continue;
-		b->units.push_back({ t, 0, 0, (uint32_t)b->chlist[t].size(), row0, 1u << t, nullptr, { nullptr, nullptr } });
+		b->units.push_back({ t, 0, 0, (uint32_t)b->chlist[t].size(), row0, 1u << t });
 		row0 += b->chlist[t].size();
 	}
 	if (b->join_mode == 0 && n_afsk == 0 && b->n_classes == 2 && b->n_cls[2] && b->n_cls[3] && b->fuse_fec && b->fixed_epi) {
@@ -255,12 +251,12 @@ static int build(SondeBatch *b, const SondeBatchConfig *cfg)
 		b->units.clear();              // (d_cls[2], d_cls[3] stay: the kernel's two channel lists)
 	}
 	for (auto &u : b->units) {
-		HIPCHK(hipStreamCreateWithFlags(&u.st, hipStreamNonBlocking));
-		for (int k = 0; k < 2; k++) HIPCHK(hipEventCreateWithFlags(&u.ev_join[k], SD_EV_ORDER));
+		HIPCHK(u.st.create());
+		for (DevEvent &e : u.ev_join) HIPCHK(e.create(SD_EV_ORDER));
 	}
-	b->timing.unit.assign(2 * b->units.size() * SdTiming::kSlots, nullptr);
-	for (hipEvent_t &e : b->timing.unit) HIPCHK(hipEventCreateWithFlags(&e, SD_EV_TIMING));
-	if (b->join_mode != 0) HIPCHK(hipStreamCreateWithFlags(&b->done_stream, hipStreamNonBlocking));
+	b->timing.unit.resize(2 * b->units.size() * SdTiming::kSlots);
+	for (DevEvent &e : b->timing.unit) HIPCHK(e.create(SD_EV_TIMING));
+	if (b->join_mode != 0) HIPCHK(b->done_stream.create());
 	return 0;
 }
 
@@ -522,7 +518,7 @@ static int launch_units(SondeBatch *b, SubmitCtx &cx)
 	for (size_t ui = 0; ui < b->units.size(); ui++) {
 		const SondeBatch::Unit &u = b->units[ui];
 		HIPCHK(hipStreamWaitEvent(u.st, b->ev_fork, 0));
-		hipEvent_t *ec = cx.timed ? b->timing.unit_pair(b->units.size(), b->timing.unit_used % SdTiming::kSlots, ui) : nullptr;
+		DevEvent *ec = cx.timed ? b->timing.unit_pair(b->units.size(), b->timing.unit_used % SdTiming::kSlots, ui) : nullptr;
 		if (ec) HIPCHK(hipEventRecord(ec[0], u.st));
 		if (launch_unit_demod(b, cx, u)) return -1;
 		if (ec) HIPCHK(hipEventRecord(ec[1], u.st));
@@ -679,19 +675,20 @@ extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *chann
 	// stream of the late-joined modes, which waits for every unit's last kernel.  The next submit follows it there (or through
 	// ev_xs from another stream); launch units that are not joined keep their own streams from submit to submit, so each waits.
 	hipStream_t s = b->last_stream;
-	hipLaunchKernelGGL(sd_batch_restart_kernel, dim3((unsigned)n), dim3(256), 0, s, lb->dev, b->d_states, b->d_fstates, b->d_hist, b->d_bitring,
+	hipLaunchKernelGGL(sd_batch_restart_kernel, dim3((unsigned)n), dim3(256), 0, s, lb->list.dev(), b->d_states, b->d_fstates, b->d_hist, b->d_bitring,
 		b->ring_words, b->d_astates, b->d_prog, b->d_modems);
 	HIPCHK(hipGetLastError());
 	for (int k = 0; k < SD_N_PASSES; k++) {     // SPEC 3.3c .. 3.3i: a restarted channel has no layout, and its counters are zero
 		if (!b->d_pass[k]) continue;
-		sd_launch_rescue_clear((uint32_t)n, s, lb->dev, b->d_pass[k], k_rescue_passes[k].words);
+		sd_launch_rescue_clear((uint32_t)n, s, lb->list.dev(), b->d_pass[k], k_rescue_passes[k].words);
 		HIPCHK(hipGetLastError());
 	}
 	if (b->n_groups) {                         // SPEC 3.3j: a restarted group has no carried records, and its counters are zero
-		sd_launch_diversity_clear((uint32_t)n, s, lb->dev, b->d_divslot, b->d_carried, b->d_divcnt, b->d_groups, b->d_divstate, b->div_unlocked);
+		sd_launch_diversity_clear((uint32_t)n, s, lb->list.dev(), b->d_divslot, b->d_carried, b->d_divcnt, b->d_groups, b->d_divstate, b->div_unlocked);
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(b->restart_lists.done(lb, s));
+	b->pending = true;                         // (sonde_batch_destroy, sonde_batch_submit_host: last_stream holds work again)
 	if (b->join_mode != 0) {
 		HIPCHK(hipEventRecord(b->ev_restart, s));
 		for (const SondeBatch::Unit &u : b->units) HIPCHK(hipStreamWaitEvent(u.st, b->ev_restart, 0));
@@ -799,10 +796,8 @@ extern "C" int sonde_batch_submit_host(SondeBatch *b, const void *samples, size_
 	const size_t dstride = sonde_row_stride(n_samples, b->input_kind);            // rows on the recommended stride
 	const size_t need = (size_t)b->n_channels * sonde_row_stride(b->max_samples, b->input_kind) * elem;
 	if (b->stage_bytes < need) {
-		(void)hipFree(b->d_stage);
-		b->d_stage = nullptr;
 		b->stage_bytes = 0;
-		HIPCHK(hipMalloc(&b->d_stage, need));
+		HIPCHK(b->d_stage.alloc(need));
 		b->stage_bytes = need;
 	}
 	if (b->pending) HIPCHK(hipStreamSynchronize(b->last_stream));

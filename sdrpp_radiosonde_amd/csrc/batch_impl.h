@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <deque>
 #include <memory>
+#include <type_traits>
 #include <vector>
 #include "sonde_dev.h"
 #include "../../include/sonde_abi.h"
@@ -49,20 +50,22 @@ static const SdRescuePass k_rescue_passes[SD_N_PASSES] = {
 // only every `every`-th submit is timed (0: none), into the next of kSlots slots; all events are created with the batch.
 struct SdTiming {
 	static const int kSlots = 128;         // submits timed between two sonde_batch_kernel_ms() calls
-	struct Submit { hipEvent_t ev[3] = {}; bool has_framer = false; };      // start, behind the demodulators, behind the frame decoders (if any ran behind)
+	struct Submit { DevEvent ev[3]; bool has_framer = false; };      // start, behind the demodulators, behind the frame decoders (if any ran behind)
 	std::vector<Submit> submit;            // [kSlots]
 	int used = 0;
 	// batches of launch units: the same for each unit's demod kernel alone, on the unit's stream (sonde_batch_class_ms)
-	std::vector<hipEvent_t> unit;          // [kSlots][units][2]
+	std::vector<DevEvent> unit;            // [kSlots][units][2]
 	int unit_used = 0;
 	int every = 8;
 	unsigned long n_submits = 0;           // since sonde_batch_set_timing
 
 	Submit &slot() { return submit[(size_t)(used % kSlots)]; }
-	hipEvent_t *unit_pair(size_t n_units, int slot, size_t ui) { return &unit[2 * (n_units * (size_t)slot + ui)]; }
+	DevEvent *unit_pair(size_t n_units, int slot, size_t ui) { return &unit[2 * (n_units * (size_t)slot + ui)]; }
 };
-#pragma GCC visibility pop
 
+// The object owns its device memory, events and streams through the members of sd_devmem.h: sonde_batch_destroy waits for the batch's
+// work and deletes, and a build() that fails half-way leaves an object that deletes the same way.  Launchers and kernels take plain
+// pointers: the members convert.
 struct SondeBatch {
 	uint32_t n_channels = 0, max_samples = 0;
 	int input_kind = 0, device = 0;
@@ -72,39 +75,42 @@ struct SondeBatch {
 	std::vector<uint32_t> chlist[SONDE_NTYPES];
 	ModemDef md[SONDE_NTYPES];             // this batch's modem table (k_modems, with the configuration flags applied)
 
-	SdChanState *d_states = nullptr;
-	SdFramerState *d_fstates = nullptr;
-	float *d_hist = nullptr;
-	uint32_t *d_bitring = nullptr;
+	DevBuf<SdChanState> d_states;
+	DevBuf<SdFramerState> d_fstates;
+	DevBuf<float> d_hist;
+	DevBuf<uint32_t> d_bitring;
 	// frame slots, per-channel frame counts and the demod kernel's framer descriptor exist TWICE: submit number t (1-based) uses
 	// slot[(t - 1) & 1], so the frames of submit t stay readable while submit t + 1 is queued or running (sonde_batch_frames_of)
 	struct Slot {
-		SondeFrame *d_frames = nullptr;
-		uint32_t *d_counts = nullptr;
-		SdFramerOut *d_fo = nullptr;       // where the demod kernel's in-kernel sync search keeps its state and lists frames (device copy)
+		DevBuf<SondeFrame> d_frames;
+		DevBuf<uint32_t> d_counts;
+		DevBuf<SdFramerOut> d_fo;          // where the demod kernel's in-kernel sync search keeps its state and lists frames (device copy)
 		SdFramerOut h_fo = {};             // host copy: the bins decoder takes the descriptor by value (bins_kernel.hip)
-		hipEvent_t ev_done = nullptr;      // recorded behind the last kernel of the submit once the host works with tickets
+		DevEvent ev_done;                  // recorded behind the last kernel of the submit once the host works with tickets
 		bool ev_valid = false;             // (an event record is a bubble in the command stream: not paid by hosts that sync every submit)
 		bool have_counts = false;          // h_counts, n_frames, n_overflow hold this submit's
 		std::vector<uint32_t> h_counts;
 		long n_frames = 0, n_overflow = 0;
 	} slot[2];
 	bool ticketing = false;
-	hipEvent_t ev_xs = nullptr;            // orders a submit behind the previous one when the host changes streams
+	DevEvent ev_xs;                        // orders a submit behind the previous one when the host changes streams
 	uint64_t tickets = 0;                  // submits so far
-	float *d_taps = nullptr;
-	SdModem *d_modems = nullptr;
+	DevBuf<float> d_taps;
+	DevBuf<SdModem> d_modems;
 	SdModem h_modems[SONDE_NTYPES] = {};   // host copy: the bins decoder takes the table by value
+	DevBuf<uint8_t> d_gfexp, d_gflog, d_g64;      // the FEC tables, and what launchers and kernels take: the view `fec` of them
+	DevBuf<uint32_t> d_gfswar;
+	DevBuf<uint16_t> d_m10tab;
 	SdFecTables fec = {};
 	uint32_t fuse_fec = 1;                 // RS41 FEC in the demod kernel's epilogue (default) or as its own kernel (SONDE_FLAG_SPLIT_FEC)
 	uint32_t fixed_epi = 1;                // the fixed-length framers' frames decoded in the demod kernel's epilogue too (round 6; not behind a channelizer: bins_kernel.hip)
-	void *d_descs = nullptr;
-	uint32_t *d_chlist[SONDE_NTYPES] = {};
-	void *d_stage = nullptr;               // sonde_batch_submit_host's device rows
+	DevBuf<uint8_t> d_descs;
+	DevBuf<uint32_t> d_chlist[SONDE_NTYPES];
+	DevBuf<uint8_t> d_stage;               // sonde_batch_submit_host's device rows
 	size_t stage_bytes = 0;
 	// AFSK sondes (iMet): tone-demodulator state, mixer table, 6 kS/s scratch rows; the other channels' list for kernel A
-	SdAfskState *d_astates = nullptr;
-	float *d_wtab = nullptr, *d_wtab_c50 = nullptr, *d_afq = nullptr;
+	DevBuf<SdAfskState> d_astates;
+	DevBuf<float> d_wtab, d_wtab_c50, d_afq;
 	// kernel A is instantiated per (decimation, taps) class (k_cls_*).  One class in the batch = one plain launch over all
 	// channels.  Several (or AFSK channels) = LAUNCH UNITS: every sonde type's channel list is cut into n_chunks pieces, a unit is
 	// (type, piece): its demod launch (the type's class) and its frame decoder behind it on the unit's OWN stream, so that the
@@ -122,25 +128,25 @@ struct SondeBatch {
 	struct Unit {
 		int type, cls; uint32_t off, n; size_t row0;
 		uint32_t types;                    // bit t: the frame decoders of sonde type t follow this unit's demod launch
-		hipStream_t st; hipEvent_t ev_join[2];      // ev_join[submit parity]
+		DevStream st; DevEvent ev_join[2];          // ev_join[submit parity]; created once the units are known (build)
 	};
 	std::vector<Unit> units;
-	uint32_t *d_cls[4] = {};               // joined batches: the channel list of each class
+	DevBuf<uint32_t> d_cls[4];             // joined batches: the channel list of each class
 	int n_chunks = 1;
-	hipEvent_t ev_fork = nullptr;
+	DevEvent ev_fork;
 	// How a submit of several launch units completes (include/sonde_abi.h): 0 (default): the unit streams are joined into the
 	// caller's stream before sonde_batch_submit returns; 1 SONDE_FLAG_LATE_JOIN: one submit late -- submit t joins the units of submit
 	// t - 1 into the caller's stream, so that a unit's submit t + 1 may start beside the other units' submit t; 2 SONDE_FLAG_PIPELINE:
 	// never.  In modes 1 and 2 done_stream collects the unit streams for completion (sonde_batch_sync, tickets).
 	int join_mode = 0;
-	hipStream_t done_stream = nullptr;
+	DevStream done_stream;
 	uint32_t granule = SONDE_TILE;         // submit sizes must be a multiple of this
 	// one residency of the GPU: the demod workgroups it holds at once, 4 (39.7 KB of LDS, 8 waves each) per CU.  The launch-unit
 	// rule, the in-loop FEC bound (SdFramerOut.loop_fec_max_wg) and the time-slice policy all work with it.
 	uint32_t residency = 0;
 	// time slices (launch.h SdSlice): per-channel segment counters, the value they hold before the next sliced launch and the knob
 	// (SondeBatchConfig.time_slices; 0: the library's choice)
-	uint32_t *d_prog = nullptr;
+	DevBuf<uint32_t> d_prog;
 	uint32_t seg_base = 0;
 	int seg_force = 0;
 	bool sliced_once = false;
@@ -160,7 +166,7 @@ struct SondeBatch {
 	// sonde_batch_restart_channels (SPEC 3.12): the channel lists on their way to the reset kernel, the event that orders the next
 	// submit's launch units behind it, and (submits so far, channel): the channel's parser is replaced before a later submit is parsed
 	SdChanLists restart_lists;
-	hipEvent_t ev_restart = nullptr;
+	DevEvent ev_restart;
 	std::deque<std::pair<uint64_t, uint32_t>> parser_restarts;
 	bool behind_channelizer = false;
 	// the rescue passes (k_rescue_passes): per pass [n_channels][words] of state; null: its flag is off or the batch has no channel of its
@@ -180,3 +186,7 @@ struct SondeBatch {
 	DevBuf<int32_t> d_divslot;
 	std::vector<int32_t> div_slot;
 };
+static_assert(!std::is_copy_constructible<SondeBatch>::value && !std::is_copy_constructible<SondeBatch::Unit>::value, "owners of device resources");
+static_assert(!std::is_copy_constructible<DevBuf<uint8_t>>::value && !std::is_copy_constructible<PinnedBuf<uint32_t>>::value &&
+	!std::is_copy_constructible<DevEvent>::value && !std::is_copy_constructible<DevStream>::value, "owners of device resources");
+#pragma GCC visibility pop

@@ -9,26 +9,23 @@
 // status[2 * i + c]: 0 clean, > 0 corrected byte errors, -1 uncorrectable (word left as received).
 // erased = null: errors only (sd_rsdec.h); else the errors-and-erasures corrector of SONDE_FLAG_RS41_RESCUE (sd_rsee.h), with
 // erased[i][c][k] != 0 marking position k.
+#define RSCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return sd_fail(who, e_); } while (0)      // (the text is the entry's name, as it always was)
 static int test_rs255(const char *who, SondeBatch *b, uint8_t *cw_pairs, size_t n_pairs, int n, const uint8_t *erased, int32_t *status)
 {
 	HIPCHK(hipSetDevice(b->device));
-	uint8_t *d_cw = nullptr, *d_er = nullptr;
-	int32_t *d_st = nullptr;
-	hipError_t e = hipMalloc((void **)&d_cw, n_pairs * 512);
-	if (e == hipSuccess && erased) e = hipMalloc((void **)&d_er, n_pairs * 512);
-	if (e == hipSuccess) e = hipMalloc((void **)&d_st, n_pairs * 2 * sizeof(int32_t));
-	if (e == hipSuccess) e = hipMemcpy(d_cw, cw_pairs, n_pairs * 512, hipMemcpyHostToDevice);
-	if (e == hipSuccess && erased) e = hipMemcpy(d_er, erased, n_pairs * 512, hipMemcpyHostToDevice);
-	if (e == hipSuccess) {
-		if (erased) sd_launch_rsee_unit(d_cw, d_er, (uint32_t)n_pairs, n, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
-		else sd_launch_rs255_unit(d_cw, (uint32_t)n_pairs, n, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpy(cw_pairs, d_cw, n_pairs * 512, hipMemcpyDeviceToHost);
-	if (e == hipSuccess) e = hipMemcpy(status, d_st, n_pairs * 2 * sizeof(int32_t), hipMemcpyDeviceToHost);
-	(void)hipFree(d_cw); (void)hipFree(d_er); (void)hipFree(d_st);
-	return e == hipSuccess ? 0 : sd_fail(who, e);
+	DevBuf<uint8_t> d_cw, d_er;
+	DevBuf<int32_t> d_st;
+	RSCHK(d_cw.upload(cw_pairs, n_pairs * 512));
+	if (erased) RSCHK(d_er.upload(erased, n_pairs * 512));
+	RSCHK(d_st.alloc(n_pairs * 2));
+	if (erased) sd_launch_rsee_unit(d_cw, d_er, (uint32_t)n_pairs, n, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
+	else sd_launch_rs255_unit(d_cw, (uint32_t)n_pairs, n, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
+	RSCHK(hipGetLastError());
+	RSCHK(hipMemcpy(cw_pairs, d_cw, n_pairs * 512, hipMemcpyDeviceToHost));
+	RSCHK(hipMemcpy(status, d_st, n_pairs * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
+	return 0;
 }
+#undef RSCHK
 
 extern "C" int sonde_batch_test_rs255(SondeBatch *b, uint8_t *cw_pairs, size_t n_pairs, int n, int32_t *status)
 {
@@ -307,11 +304,11 @@ __global__ __launch_bounds__(256) void sd_read_probe_kernel(const sd_u32x4 *__re
 extern "C" int sonde_hbm_read_probe(const void *d_buf, size_t bytes, int reps, float *gbs_out)
 {
 	if (!d_buf || bytes < 16 || reps < 1 || !gbs_out) return sd_fail("sonde_hbm_read_probe: bad argument");
-	uint32_t *sink = nullptr;
-	HIPCHK(hipMalloc(&sink, 4));
-	hipEvent_t e0, e1;
-	HIPCHK(hipEventCreate(&e0));
-	HIPCHK(hipEventCreate(&e1));
+	DevBuf<uint32_t> sink;
+	DevEvent e0, e1;
+	HIPCHK(sink.alloc(1));
+	HIPCHK(e0.create(hipEventDefault));
+	HIPCHK(e1.create(hipEventDefault));
 	const size_t n16 = bytes / 16;
 	float best = 1e30f;
 	for (int grid = 256 * 4; grid <= 256 * 32; grid *= 2) {      // best over a few occupancies
@@ -327,9 +324,6 @@ extern "C" int sonde_hbm_read_probe(const void *d_buf, size_t bytes, int reps, f
 		}
 	}
 	const hipError_t err = hipGetLastError();
-	(void)hipEventDestroy(e0);
-	(void)hipEventDestroy(e1);
-	(void)hipFree(sink);
 	if (err != hipSuccess) return sd_fail("sonde_hbm_read_probe", err);
 	*gbs_out = (float)((double)(n16 * 16) / ((double)best * 1e-3) / 1e9);
 	return 0;

@@ -198,7 +198,7 @@ extern "C" int sonde_batch_class_ms(SondeBatch *b, float out[4])
 			const SondeBatch::Unit &u = b->units[ui];
 			if (u.type == SONDE_IMET4 || u.type == SONDE_C50 || u.cls != k) continue;
 			for (int i = 0; i < n; i++) {
-				const hipEvent_t *ec = tm.unit_pair(nu, i, ui);
+				const DevEvent *ec = tm.unit_pair(nu, i, ui);
 				float x = 0.0f;
 				HIPCHK(hipEventElapsedTime(&x, ec[0], ec[1]));
 				acc += x;

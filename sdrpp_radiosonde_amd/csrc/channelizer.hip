@@ -406,7 +406,7 @@ struct __attribute__((visibility("hidden"))) SondeChannelizer {
 	DevBuf<float> d_h_odd; DevBuf<float2> d_twist;
 	bool fused = false;                    // the decoder kernel takes the bins themselves (discriminator + resampler in its load path): two launches per submit
 	hipStream_t last_stream = nullptr;     // a submit on another stream waits for the previous one (the state is carried)
-	hipEvent_t ev_xs = nullptr;
+	DevEvent ev_xs;
 	// overlapped form (an OPTION: sonde_chan_set_overlap(c, 1); fused mode only): the filter bank runs on
 	// s_pfb, the decoder on s_dec, the bins are double-buffered, so that the filter bank of submit k+1 may run beside the decoder
 	// of submit k.  Measured (profiles/r3_notes.md): no gain at one stream (43.9 -> 48.9 us per block: the two kernels do not
@@ -414,8 +414,8 @@ struct __attribute__((visibility("hidden"))) SondeChannelizer {
 	// The caller's stream only waits for the filter bank (the last reader of its block); results come with sonde_batch_sync.
 	uint32_t xcd_map = 0;                  // 8-step filter bank: XCD-aware step-group order (from two generations of workgroups on)
 	bool overlap = false;
-	hipStream_t s_pfb = nullptr, s_dec = nullptr;
-	hipEvent_t ev_in = nullptr, ev_pfb[2] = {}, ev_dec[2] = {};
+	DevStream s_pfb, s_dec;                // (with their events and d_bins_b: created at the first overlapped submit)
+	DevEvent ev_in, ev_pfb[2], ev_dec[2];
 	DevBuf<int16_t> d_bins_b;              // the second phase buffer (allocated at the first overlapped submit)
 	const int16_t *bins_last = nullptr;    // the phases of the last submit (sonde_chan_read): d_bins or d_bins_b
 	SondeBatch *batch = nullptr;
@@ -425,7 +425,7 @@ struct __attribute__((visibility("hidden"))) SondeChannelizer {
 	DevBuf<int32_t> d_philast;             // unfused mode: per bin, the last phase of the previous block
 	DevBuf<float> d_h, d_g, d_gc, d_dhist, d_out48;
 	// kernel timing (HIP events on the submit stream), sampled: every 8th submit
-	hipEvent_t ev[3] = {};
+	DevEvent ev[3];
 	unsigned long n_submits = 0, n_blocks = 0;
 	double acc_ms[2] = { 0.0, 0.0 };
 	int n_timed = 0;
@@ -472,13 +472,7 @@ extern "C" void sonde_chan_destroy(SondeChannelizer *c)
 {
 	if (!c) return;
 	(void)hipSetDevice(c->device);
-	sonde_batch_destroy(c->batch);
-	for (int i = 0; i < 3; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-	if (c->ev_xs) (void)hipEventDestroy(c->ev_xs);
-	if (c->ev_in) (void)hipEventDestroy(c->ev_in);
-	for (int i = 0; i < 2; i++) { if (c->ev_pfb[i]) (void)hipEventDestroy(c->ev_pfb[i]); if (c->ev_dec[i]) (void)hipEventDestroy(c->ev_dec[i]); }
-	if (c->s_pfb) (void)hipStreamDestroy(c->s_pfb);
-	if (c->s_dec) (void)hipStreamDestroy(c->s_dec);
+	sonde_batch_destroy(c->batch);          // waits for the decoder, which every submit queues behind the filter bank: nothing of c's is in use after it
 	delete c;
 }
 
@@ -520,8 +514,8 @@ static int chan_build(SondeChannelizer *c, const uint8_t *types, uint32_t blocks
 	HIPCHK_IN("sonde_chan_create", c->d_g.upload(g.data(), RS_UP * RS_TAPS));
 	HIPCHK_IN("sonde_chan_create", c->d_philast.zeros(nb));
 	HIPCHK_IN("sonde_chan_create", c->d_dhist.zeros(nb * RS_TAPS));
-	for (hipEvent_t &e : c->ev) HIPCHK_IN("sonde_chan_create", hipEventCreateWithFlags(&e, hipEventDisableSystemFence));     // timing only, same device
-	HIPCHK_IN("sonde_chan_create", hipEventCreateWithFlags(&c->ev_xs, hipEventDisableTiming | hipEventDisableSystemFence));
+	for (DevEvent &e : c->ev) HIPCHK_IN("sonde_chan_create", e.create(hipEventDisableSystemFence));     // timing only, same device
+	HIPCHK_IN("sonde_chan_create", c->ev_xs.create(hipEventDisableTiming | hipEventDisableSystemFence));
 	float gc[3 * SD_RS_KT_LD];
 	composite_rows(g, 4, gc);
 	for (float &v : gc) v *= 1.0f / 16384.0f;      // the bins decoder keeps the discriminator samples as 16-bit integers: the scale (a power of two: exact) sits in the taps
@@ -595,10 +589,10 @@ extern "C" int sonde_chan_set_overlap(SondeChannelizer *c, int on)
 static int chan_overlap_setup(SondeChannelizer *c)
 {
 	if (c->s_pfb) return 0;
-	HIPCHK_IN("sonde_chan_submit", hipStreamCreateWithFlags(&c->s_pfb, hipStreamNonBlocking));
-	HIPCHK_IN("sonde_chan_submit", hipStreamCreateWithFlags(&c->s_dec, hipStreamNonBlocking));
-	for (hipEvent_t *e : { &c->ev_in, &c->ev_pfb[0], &c->ev_pfb[1], &c->ev_dec[0], &c->ev_dec[1] })
-		HIPCHK_IN("sonde_chan_submit", hipEventCreateWithFlags(e, hipEventDisableTiming | hipEventDisableSystemFence));
+	HIPCHK_IN("sonde_chan_submit", c->s_pfb.create());
+	HIPCHK_IN("sonde_chan_submit", c->s_dec.create());
+	for (DevEvent *e : { &c->ev_in, &c->ev_pfb[0], &c->ev_pfb[1], &c->ev_dec[0], &c->ev_dec[1] })
+		HIPCHK_IN("sonde_chan_submit", e->create(hipEventDisableTiming | hipEventDisableSystemFence));
 	HIPCHK_IN("sonde_chan_submit", c->d_bins_b.zeros((size_t)c->n_streams * CH_M * ((size_t)c->n_steps + PH_HEAD)));
 	return 0;
 }

@@ -428,7 +428,6 @@ extern "C" void sonde_detect_destroy(SondeDetector *d)
 	if (!d) return;
 	(void)hipSetDevice(d->device);
 	if (d->submitted) (void)hipStreamSynchronize(d->last_stream);
-	d->restart_lists.destroy();
 	delete d;
 }
 
@@ -559,7 +558,7 @@ extern "C" int sonde_detect_restart_channels(SondeDetector *d, const uint32_t *c
 	SdChanLists::Buf *lb = d->restart_lists.put(channels, n);
 	if (!lb) return sd_fail("sonde_detect_restart_channels: no pinned memory for the channel list");
 	// on the stream of the last submit: behind its kernel; a submit on another stream is the caller's to order, as between submits
-	hipLaunchKernelGGL(sd_detect_restart_kernel, dim3((unsigned)n), dim3(DT_WG), 0, d->last_stream, lb->dev, d->d_state, d->d_D, d->rowD, d->d_A, d->rowA);
+	hipLaunchKernelGGL(sd_detect_restart_kernel, dim3((unsigned)n), dim3(DT_WG), 0, d->last_stream, lb->list.dev(), d->d_state, d->d_D, d->rowD, d->d_A, d->rowA);
 	HIPCHK_IN("sonde_detect_restart_channels", hipGetLastError());
 	HIPCHK_IN("sonde_detect_restart_channels", d->restart_lists.done(lb, d->last_stream));
 	return 0;
