@@ -446,6 +446,22 @@ int      sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t of
 int      sonde_batch_test_diversity_align(SondeBatch *b, size_t n, size_t max_rec, const uint32_t *n_members, SondeFrame *records, const uint32_t *counts,
                                           const SondeFrame *carried, int64_t *off, uint32_t *locked, const uint32_t *mode, uint32_t *learned,
                                           uint32_t *duplicates);
+/* STREAM AGE, test introspection only -- NOT FOR HOSTS (DESIGN "Stream age").  Each listed channel becomes "the same stream, begun
+ * samples[i] input samples and bits_added[i] bits earlier": the call adds to every absolute position the batch carries for the channel
+ * and leaves everything relative as it is, so that the tests can put a channel just below 2^31, 2^32, 2^37, 2^48 ... without feeding
+ * hours of samples.  Shifted: SdChanState n0 (by samples[i] / the channel's class decimation; 8 behind the tone front-end), t_next (that
+ * << 16) and wpos; SdFramerState rpos and fstart; SdAfskState n (by samples[i]); the bitpos of the record the diversity pass carries for
+ * the channel.  Nothing else the batch carries is a position: the rescue passes keep layouts and counters, the diversity offsets are
+ * differences of bit counts, frame slots and descriptors are written anew by every submit (batch.hip lists the state).  The bit shift
+ * is ring_turns[i] * 32 * ring_words, returned in bits_added[i]: a whole number of ring turns leaves every ring index, and so the
+ * ring's contents, where they are.  samples[i] must be a multiple of 30720 = lcm(2048, 480): tile phase and both tone-mixer phases
+ * stay.  Ordered exactly like sonde_batch_restart_channels (behind the last submit's kernels, before the next submit's, in every
+ * completion mode, no host synchronisation); sonde_batch_nbits / _read_bits / _read_state / _frames / _poll and the *_info calls then
+ * simply see the aged channel.  Refused: any other samples[i], a channel listed twice, a call before the first submit, the batch
+ * behind a channelizer, a diversity group listed in part, members of one group given different shifts (their common clock is bitpos -
+ * offset: an equal shift keeps it). */
+int      sonde_batch_test_shift_age(SondeBatch *b, const uint32_t *channels, size_t n, const uint64_t *samples, const uint32_t *ring_turns,
+                                    uint64_t *bits_added);
 uint64_t sonde_batch_nbits(SondeBatch *b, uint32_t channel);
 int      sonde_batch_read_state(SondeBatch *b, uint32_t channel, int64_t *t_next, int32_t *period, float *bias, float *amp,
                                 float *afc_u /* the newest AFC state u of SPEC 3.0b (the carrier offset the channel is following: 2 atan u per
@@ -582,6 +598,11 @@ int  sonde_detect_restart_channels(SondeDetector *d, const uint32_t *channels, s
 int  sonde_detect_thresholds(float out[SONDE_NTYPES]);
 /* test introspection: the last submit's quantised streams of one channel; returns that submit's n_samples */
 int  sonde_detect_read(SondeDetector *d, uint32_t channel, int32_t *D /* n/2 */, int32_t *a_imet /* n/8 */, int32_t *a_c50 /* n/8 */);
+/* STREAM AGE, test introspection only -- NOT FOR HOSTS (DESIGN "Stream age"): each listed channel becomes "the same stream, begun
+ * samples[i] input samples earlier": added to the channel's sample count and to every pos[k] that is set (best[k] > 0).  samples[i] a
+ * multiple of 30720 (both tone-mixer phases and every decimation stay); ordered as sonde_detect_restart_channels; refused before the
+ * first submit and for a channel listed twice. */
+int  sonde_detect_test_shift_age(SondeDetector *d, const uint32_t *channels, size_t n, const uint64_t *samples);
 int  sonde_detect_templates(int type, int8_t *s, int cap);    /* returns L; writes min(L, cap) values of +-1 (s may be NULL) */
 
 /* ------------------------------------------------------------------ wideband tuner (DESIGN SPEC 3.9)
@@ -622,6 +643,10 @@ int    sonde_tuner_slot_clear(SondeTuner *t, uint32_t slot);
 int    sonde_tuner_slot_active(const SondeTuner *t, uint32_t slot);      /* 1 active, 0 idle */
 /* wide_dev: DEVICE pointer to n_in samples (a multiple of down, <= max_in); out_dev: VFO k's n_out complex64 samples at
  * element k * out_stride (complex samples; sonde_row_stride(n_out, SONDE_INPUT_IQ) writes straight into a SondeBatch input buffer) */
+/* STREAM AGE, test introspection only -- NOT FOR HOSTS (DESIGN "Stream age"): the absolute input index of the next process's first
+ * sample, for a tuner that has not processed or been retuned yet (its history is zeros: "tuned since create, silence until n_base").
+ * 0 <= n_base <= 2^62, a multiple of the ratio's denominator `down`. */
+int    sonde_tuner_test_set_base(SondeTuner *t, int64_t n_base);
 int    sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n_in,
                            void *out_dev /* complex64 rows */, size_t out_stride /* complex samples */, void *stream);
 

@@ -199,6 +199,7 @@ struct OrDemod {
 	float af_b[OR_AF_WIN - 1][2];   /* the four block sums before the current one, oldest first */
 	float af_z[2];                  /* previous boxcar output */
 	uint64_t af_n;                  /* input samples consumed (mixer phase = af_n mod 480) */
+	int af_wrap32;                  /* test mutation (or_demod_test_set_af_n): the count is cut to 32 bits before the mod */
 	int64_t t_next;      /* Q16 absolute on-time instant of the next symbol */
 	int32_t period;      /* Q16 samples per symbol */
 	float bias, amp;
@@ -387,7 +388,9 @@ static void afsk_front(OrDemod *d, const float *src, size_t n_in, int is_iq, flo
 		else memcpy(dv, src + OR_AF_DEC * m, sizeof(dv));
 		float br = 0.0f, bi = 0.0f;
 		for (int i = 0; i < OR_AF_DEC; i++) {
-			const unsigned k = (unsigned)((d->af_n + OR_AF_DEC * m + (size_t)i) % per);
+			uint64_t n_abs = d->af_n + OR_AF_DEC * m + (size_t)i;
+			if (d->af_wrap32) n_abs = (uint32_t)n_abs;
+			const unsigned k = (unsigned)(n_abs % per);
 			br = fmaf(dv[i], W[2 * k], br);
 			bi = fmaf(dv[i], W[2 * k + 1], bi);
 		}
@@ -514,6 +517,9 @@ void or_demod_feed(OrDemod *d, const float *src, size_t n, int is_iq)
 }
 
 uint64_t or_demod_nbits(const OrDemod *d) { return d->nbits; }
+/* stream-age tests: the tone front-end's absolute sample count (the stream "began n samples earlier"); wrap32 != 0 makes this
+ * demodulator take the mixer phase from the low 32 bits of the count -- the bug the tests' comparisons must reject */
+void or_demod_test_set_af_n(OrDemod *d, uint64_t n, int wrap32) { d->af_n = n; d->af_wrap32 = wrap32; }
 
 void or_demod_getbits(const OrDemod *d, uint64_t from, size_t count, uint8_t *out)
 {

@@ -87,6 +87,7 @@ void     or_demod_free(OrDemod *d);
 /* n must be a multiple of OR_TILE.  is_iq: src is interleaved I,Q (2n floats); else n real discriminator samples */
 void     or_demod_feed(OrDemod *d, const float *src, size_t n, int is_iq);
 uint64_t or_demod_nbits(const OrDemod *d);
+void     or_demod_test_set_af_n(OrDemod *d, uint64_t n, int wrap32);   /* stream-age tests: the tone front-end's sample count; wrap32: the 32-bit bug */
 /* copy bits [from, from+count) one per byte */
 void     or_demod_getbits(const OrDemod *d, uint64_t from, size_t count, uint8_t *out);
 /* debug taps for staged parity tests */

@@ -173,6 +173,7 @@ ABI_SYMBOLS = [
     "sonde_batch_afsk_rescue_info", "sonde_batch_test_afsk_repair",
     "sonde_batch_set_diversity", "sonde_batch_diversity_info", "sonde_batch_test_rs41_combine",
     "sonde_batch_set_diversity_auto", "sonde_batch_diversity_offsets", "sonde_batch_test_diversity_align",
+    "sonde_batch_test_shift_age", "sonde_detect_test_shift_age", "sonde_tuner_test_set_base",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -370,6 +371,10 @@ def load() -> C.CDLL:
         L.sonde_batch_restart_channels.argtypes = [vp, vp, C.c_size_t]
         L.sonde_detect_restart_channels.argtypes = [vp, vp, C.c_size_t]
         L.sonde_live_match.argtypes = [vp, u32, vp, u32, u32, vp, vp]
+    if hasattr(L, "sonde_batch_test_shift_age"):          # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        L.sonde_batch_test_shift_age.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+        L.sonde_detect_test_shift_age.argtypes = [vp, vp, C.c_size_t, vp]
+        L.sonde_tuner_test_set_base.argtypes = [vp, C.c_int64]
     f = C.c_float
     L.sonde_gpx_open.restype = vp
     L.sonde_gpx_open.argtypes = [C.c_char_p]

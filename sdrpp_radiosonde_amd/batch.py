@@ -104,6 +104,18 @@ class SondeBatch:
         ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
         self._chk(self.L.sonde_batch_restart_channels(self.h, ch.ctypes.data_as(C.c_void_p), len(ch)))
 
+    def test_shift_age(self, channels, samples, ring_turns) -> np.ndarray:
+        """Test introspection, not for hosts (sonde_batch_test_shift_age): the listed channels become the same streams, begun
+        samples[i] input samples (a multiple of 30720) and ring_turns[i] whole turns of the bit ring earlier.  Ordered like
+        restart_channels.  Returns the bits added per channel."""
+        ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
+        sm = np.ascontiguousarray(np.broadcast_to(np.asarray(samples, dtype=np.uint64), ch.shape))
+        tr = np.ascontiguousarray(np.broadcast_to(np.asarray(ring_turns, dtype=np.uint32), ch.shape))
+        added = np.zeros(len(ch), dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+        self._chk(self.L.sonde_batch_test_shift_age(self.h, p(ch), len(ch), p(sm), p(tr), p(added)))
+        return added
+
     def sync(self) -> int:
         return self._chk(self.L.sonde_batch_sync(self.h))
 

@@ -696,6 +696,98 @@ extern "C" int sonde_batch_restart_channels(SondeBatch *b, const uint32_t *chann
 	return 0;
 }
 
+// ---------------------------------------------------------------- test introspection: stream age (DESIGN "Stream age")
+// The listed channels become "the same stream, begun earlier": one thread per entry adds to every ABSOLUTE position the batch carries
+// for the channel and touches nothing relative.  The list below is sd_batch_restart_kernel's list of the state that exists, read for
+// what counts from the stream's origin:
+//   SdChanState     n0 (+ dn0 internal-rate samples), t_next (+ dn0 << 16), wpos (+ dbits); period, nstat, bias, amp, iq_last, afc: relative
+//   SdFramerState   rpos, fstart (+ dbits; fstart is read only while collecting, and is then a position); collecting, inv, flen: relative
+//   SdAfskState     n (+ samples; the tone mixers' phases are n mod 480 and n mod 240); iq_last, b, z: relative
+//   hist, bit ring  contents only; dbits is a whole number of ring turns, so every ring index stays where it is
+//   prog            a segment count of the launch plan, not a stream position
+//   rescue passes   (k_rescue_passes) RS41: learned block layouts and two counters; the other four: two counters.  No position: the
+//                   passes take every position from the records' bitpos and the channel's wpos
+//   diversity       the carried record of the channel's slot: bitpos (+ dbits, if there is a record).  SdDivGroup.off / SdDivState.off
+//                   are differences of bit counts against the group's clock: members shifted alike keep them
+//   frame slots, descriptors   written anew by every submit; the records of earlier submits keep the positions they were given
+// entry i of the list: 8 words { channel, 0, dn0 lo, hi, samples lo, hi, dbits lo, hi }.  Plain loads and stores.
+__global__ __launch_bounds__(64) void sd_batch_shift_age_kernel(const uint32_t *__restrict__ list, uint32_t n, SdChanState *__restrict__ states,
+	SdFramerState *__restrict__ fstates, SdAfskState *__restrict__ astates, const int32_t *__restrict__ divslot, SondeFrame *__restrict__ carried)
+{
+	const uint32_t i = 64 * blockIdx.x + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t *e = list + 8 * (size_t)i;
+	const uint32_t c = e[0];
+	const uint64_t dn0 = (uint64_t)e[2] | (uint64_t)e[3] << 32, samples = (uint64_t)e[4] | (uint64_t)e[5] << 32, dbits = (uint64_t)e[6] | (uint64_t)e[7] << 32;
+	states[c].n0 += (int64_t)dn0;
+	states[c].t_next += (int64_t)(dn0 << 16);
+	states[c].wpos += dbits;
+	fstates[c].rpos += dbits;
+	fstates[c].fstart += dbits;
+	const int32_t type = states[c].type;
+	if (astates && (type == SONDE_IMET4 || type == SONDE_C50)) astates[c].n += samples;
+	if (divslot && divslot[c] >= 0 && carried[divslot[c]].len != 0) carried[divslot[c]].bitpos += dbits;
+}
+
+#define SD_AGE_QUANTUM 30720u      // lcm(SONDE_TILE, SD_AF_PER) (and a multiple of SD_C50_PER and of every decimation): tile and mixer phases stay
+
+extern "C" int sonde_batch_test_shift_age(SondeBatch *b, const uint32_t *channels, size_t n, const uint64_t *samples, const uint32_t *ring_turns,
+	uint64_t *bits_added)
+{
+	if (!b || !channels || !samples || !ring_turns || !bits_added || !n) return sd_fail("sonde_batch_test_shift_age: null argument");
+	if (b->behind_channelizer) return sd_fail("sonde_batch_test_shift_age: the batch sits behind a channelizer (its bins carry state the batch does not own)");
+	if (b->tickets == 0) return sd_fail("sonde_batch_test_shift_age: nothing has run yet (shift after the first submit)");
+	const uint64_t ring_bits = 32ull * b->ring_words;
+	std::vector<int64_t> at(b->n_channels, -1);        // channel -> its entry
+	for (size_t i = 0; i < n; i++) {
+		if (channels[i] >= b->n_channels) return sd_fail("sonde_batch_test_shift_age: no such channel");
+		if (at[channels[i]] >= 0) return sd_fail("sonde_batch_test_shift_age: a channel listed twice");
+		if (samples[i] % SD_AGE_QUANTUM) return sd_fail("sonde_batch_test_shift_age: samples must be a multiple of 30720 (tile phase and both tone-mixer phases stay)");
+		if (samples[i] >> 62 || (uint64_t)ring_turns[i] * ring_bits >> 62) return sd_fail("sonde_batch_test_shift_age: shift too large");
+		at[channels[i]] = (int64_t)i;
+	}
+	if (b->n_groups) {      // SPEC 3.3j: the members of a group share the clock bitpos - offset: all of them, by one amount, or none
+		std::vector<int64_t> first(b->n_groups, -1);
+		std::vector<uint32_t> listed(b->n_groups, 0u), all(b->n_groups, 0u);
+		for (uint32_t c = 0; c < b->n_channels; c++) {
+			const int32_t slot = b->div_slot[c];
+			if (slot < 0) continue;
+			const size_t g = (size_t)slot / SD_DIV_MAX;
+			all[g] |= 1u << (slot % SD_DIV_MAX);
+			if (at[c] < 0) continue;
+			listed[g] |= 1u << (slot % SD_DIV_MAX);
+			if (first[g] < 0) first[g] = at[c];
+			if (samples[at[c]] != samples[first[g]] || ring_turns[at[c]] != ring_turns[first[g]])
+				return sd_fail("sonde_batch_test_shift_age: the members of a diversity group must be shifted by the same amount");
+		}
+		for (uint32_t g = 0; g < b->n_groups; g++)
+			if (listed[g] && listed[g] != all[g]) return sd_fail("sonde_batch_test_shift_age: the list must hold all members of a diversity group or none of them");
+	}
+	std::vector<uint32_t> words(8 * n);
+	for (size_t i = 0; i < n; i++) {
+		const int t = b->types[channels[i]];
+		const uint64_t dn0 = samples[i] / (uint64_t)modem_div(b->md, t);      // the class decimation; 8 behind the tone front-end
+		bits_added[i] = (uint64_t)ring_turns[i] * ring_bits;
+		const uint64_t v[4] = { channels[i], dn0, samples[i], bits_added[i] };
+		for (int k = 0; k < 4; k++) { words[8 * i + 2 * k] = (uint32_t)v[k]; words[8 * i + 2 * k + 1] = (uint32_t)(v[k] >> 32); }
+	}
+	HIPCHK(hipSetDevice(b->device));
+	SdChanLists::Buf *lb = b->restart_lists.put(words.data(), words.size());
+	if (!lb) return sd_fail("sonde_batch_test_shift_age: no pinned memory for the list");
+	// ordered as sonde_batch_restart_channels orders its kernel: behind the last submit where it completes, in front of the next one
+	hipStream_t s = b->last_stream;
+	hipLaunchKernelGGL(sd_batch_shift_age_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, lb->list.dev(), (uint32_t)n, b->d_states, b->d_fstates,
+		b->d_astates, b->d_divslot, b->d_carried);
+	HIPCHK(hipGetLastError());
+	HIPCHK(b->restart_lists.done(lb, s));
+	b->pending = true;
+	if (b->join_mode != 0) {
+		HIPCHK(hipEventRecord(b->ev_restart, s));
+		for (const SondeBatch::Unit &u : b->units) HIPCHK(hipStreamWaitEvent(u.st, b->ev_restart, 0));
+	}
+	return 0;
+}
+
 // The receivers of one sonde (include/sonde_abi.h, SPEC 3.3j and 3.3k): the group table, the carried records, the counters and the
 // align step's state.  mode 0 is sonde_batch_set_diversity.
 extern "C" int sonde_batch_set_diversity(SondeBatch *b, const int32_t *group, const int64_t *offset_bits, uint32_t window_bits)

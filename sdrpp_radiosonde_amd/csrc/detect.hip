@@ -564,6 +564,45 @@ extern "C" int sonde_detect_restart_channels(SondeDetector *d, const uint32_t *c
 	return 0;
 }
 
+// test introspection (DESIGN "Stream age"): the listed channels become "the same stream, begun samples[i] input samples earlier".
+// SdDetState's absolute positions are n and the pos[k] of the types that have a match (best[k] > 0; a type without one keeps pos 0);
+// the front-end state, the records' values and signs and the carried streams are relative.  entry i of the list: 4 words
+// { channel, 0, samples lo, hi }.
+__global__ __launch_bounds__(64) void sd_detect_shift_age_kernel(const uint32_t *__restrict__ list, uint32_t n, SdDetState *__restrict__ state)
+{
+	const uint32_t i = 64 * blockIdx.x + threadIdx.x;
+	if (i >= n) return;
+	SdDetState *st = state + list[4 * (size_t)i];
+	const uint64_t samples = (uint64_t)list[4 * (size_t)i + 2] | (uint64_t)list[4 * (size_t)i + 3] << 32;
+	st->n += samples;
+	for (int k = 0; k < SONDE_NTYPES; k++)
+		if (st->best[k] > 0.0) st->pos[k] += samples;
+}
+
+extern "C" int sonde_detect_test_shift_age(SondeDetector *d, const uint32_t *channels, size_t n, const uint64_t *samples)
+{
+	if (!d || !channels || !samples || !n) return sd_fail("sonde_detect_test_shift_age: null argument");
+	if (!d->submitted) return sd_fail("sonde_detect_test_shift_age: nothing has run yet (shift after the first submit)");
+	std::vector<uint8_t> seen(d->n_channels, 0);
+	std::vector<uint32_t> words(4 * n, 0u);
+	for (size_t i = 0; i < n; i++) {
+		if (channels[i] >= d->n_channels) return sd_fail("sonde_detect_test_shift_age: no such channel");
+		if (seen[channels[i]]) return sd_fail("sonde_detect_test_shift_age: a channel listed twice");
+		if (samples[i] % 30720u || samples[i] >> 62)
+			return sd_fail("sonde_detect_test_shift_age: samples must be a multiple of 30720 (tile phase and both tone-mixer phases stay) below 2^62");
+		seen[channels[i]] = 1;
+		words[4 * i] = channels[i]; words[4 * i + 2] = (uint32_t)samples[i]; words[4 * i + 3] = (uint32_t)(samples[i] >> 32);
+	}
+	HIPCHK(hipSetDevice(d->device));
+	SdChanLists::Buf *lb = d->restart_lists.put(words.data(), words.size());
+	if (!lb) return sd_fail("sonde_detect_test_shift_age: no pinned memory for the list");
+	// ordered as sonde_detect_restart_channels orders its kernel: on the stream of the last submit, behind its kernel
+	hipLaunchKernelGGL(sd_detect_shift_age_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, d->last_stream, lb->list.dev(), (uint32_t)n, d->d_state);
+	HIPCHK_IN("sonde_detect_test_shift_age", hipGetLastError());
+	HIPCHK_IN("sonde_detect_test_shift_age", d->restart_lists.done(lb, d->last_stream));
+	return 0;
+}
+
 extern "C" int sonde_detect_read(SondeDetector *d, uint32_t channel, int32_t *D, int32_t *a_imet, int32_t *a_c50)
 {
 	if (!d || !D || !a_imet || !a_c50) return sd_fail("sonde_detect_read: null argument");

@@ -146,6 +146,7 @@ struct SondeTuner {
 	std::vector<uint8_t> set, active;   // per VFO (slot): its tap set, and whether it is tuned at all
 	std::map<uint32_t, uint32_t> set_of;        // listed bandwidth -> tap set (ascending bandwidth)
 	int64_t n_base = 0;                 // absolute input index of the next submit's first sample
+	bool started = false;               // it has processed or been retuned (sonde_tuner_test_set_base refuses it then)
 	DevBuf<float> d_taps;
 	DevBuf<uint64_t> d_tapoff;
 	DevBuf<uint32_t> d_T;
@@ -358,6 +359,7 @@ extern "C" int sonde_tuner_retune(SondeTuner *t, uint32_t vfo, int32_t offset_hz
 	if (tn_check_offset(t->fs, t->bw[vfo], offset_hz, "sonde_tuner_retune")) return -1;
 	t->offset[vfo] = offset_hz;
 	t->theta[vfo] = 0;
+	t->started = true;
 	return 0;
 }
 
@@ -376,6 +378,19 @@ extern "C" int sonde_tuner_retune_continuous(SondeTuner *t, uint32_t vfo, int32_
 	const uint64_t n0 = tn_mod(t->n_base - (int64_t)(tn_T(t->fs, t->bw[vfo]) / 2), t->fs);
 	t->theta[vfo] = (uint32_t)((t->theta[vfo] + df * n0 % t->fs) % t->fs);
 	t->offset[vfo] = offset_hz;
+	t->started = true;
+	return 0;
+}
+
+// test introspection (DESIGN "Stream age"): the absolute input index of the first sample the tuner will see.  Its history is zeros, so
+// the tuner is one that was "tuned since create, with silence until n_base".  Only before the first process and the first retune.
+extern "C" int sonde_tuner_test_set_base(SondeTuner *t, int64_t n_base)
+{
+	if (!t) return sd_fail("sonde_tuner_test_set_base: null argument");
+	if (t->started) return sd_fail("sonde_tuner_test_set_base: the tuner has processed or been retuned already");
+	if (n_base < 0 || n_base > ((int64_t)1 << 62) || n_base % (int64_t)t->down)
+		return sd_fail("sonde_tuner_test_set_base: n_base must be 0 .. 2^62 and a multiple of the ratio's denominator");
+	t->n_base = n_base;
 	return 0;
 }
 
@@ -430,5 +445,6 @@ extern "C" int sonde_tuner_process(SondeTuner *t, const void *wide_dev, size_t n
 	HIPCHK_IN("sonde_tuner_process", hipGetLastError());
 	t->d_hist.flip();
 	t->n_base += (int64_t)n_in;
+	t->started = true;
 	return 0;
 }

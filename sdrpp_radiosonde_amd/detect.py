@@ -113,6 +113,13 @@ class SondeDetector:
         ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
         _chk(self.L.sonde_detect_restart_channels(self.h, ch.ctypes.data_as(C.c_void_p), len(ch)))
 
+    def test_shift_age(self, channels, samples):
+        """Test introspection, not for hosts (sonde_detect_test_shift_age): the listed channels become the same streams, begun
+        samples[i] input samples (a multiple of 30720) earlier; ordered like restart_channels."""
+        ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
+        sm = np.ascontiguousarray(np.broadcast_to(np.asarray(samples, dtype=np.uint64), ch.shape))
+        _chk(self.L.sonde_detect_test_shift_age(self.h, ch.ctypes.data_as(C.c_void_p), len(ch), sm.ctypes.data_as(C.c_void_p)))
+
     def read(self, channel: int):
         """the last submit's quantised streams of one channel: D [n/2], A_imet [n/8], A_c50 [n/8] (int32)"""
         D = np.zeros(self.max_samples // 2, np.int32)

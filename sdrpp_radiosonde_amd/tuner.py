@@ -111,6 +111,11 @@ class SondeTuner:
         _chk((self.L.sonde_tuner_retune_continuous if continuous else self.L.sonde_tuner_retune)(self.h, int(k), int(hz)))
         self.offsets[k] = int(hz)
 
+    def test_set_base(self, n_base: int):
+        """Test introspection, not for hosts (sonde_tuner_test_set_base): the absolute input index of the first sample, for a tuner
+        that has not processed or been retuned yet; a multiple of `down`, 0 .. 2^62."""
+        _chk(self.L.sonde_tuner_test_set_base(self.h, int(n_base)))
+
     def process(self, block, out=None, stream: int | None = None):
         import torch
         want = {INPUT_IQ16: torch.int16, INPUT_IQ8: torch.int8}.get(self.input_kind, torch.float32)

@@ -50,6 +50,7 @@ def lib():
     L.or_demod_nbits.restype = C.c_uint64
     L.or_demod_nbits.argtypes = [C.c_void_p]
     L.or_demod_getbits.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, u8p]
+    L.or_demod_test_set_af_n.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
     L.or_demod_state.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32), f32p, f32p, f32p]
     L.or_gf256_mul.restype = C.c_uint8
     L.or_gf256_mul.argtypes = [C.c_uint8, C.c_uint8]

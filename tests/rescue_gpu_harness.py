@@ -12,9 +12,10 @@ def sorted_frames(parts):
     return fr[np.lexsort((fr["bitpos"], fr["channel"]))]
 
 
-def run(iq, flags, cuts=1, via_ticket=False, keep=False, *, tile, default_type=None, **kw):
+def run(iq, flags, cuts=1, via_ticket=False, keep=False, *, tile, default_type=None, after_submit=None, **kw):
     """iq through a batch in `cuts` equal submits (each a multiple of `tile`); default_type: the sonde type of every channel unless
-    types= says otherwise (None: the batch's default, RS41)"""
+    types= says otherwise (None: the batch's default, RS41); after_submit(b, k): called behind submit k's frames (the stream-age
+    tests shift the batch there)"""
     C_, n = iq.shape[0], iq.shape[1]
     assert n % (cuts * tile) == 0
     step = n // cuts
@@ -25,6 +26,8 @@ def run(iq, flags, cuts=1, via_ticket=False, keep=False, *, tile, default_type=N
     for k in range(cuts):
         b.submit(iq[:, k * step:(k + 1) * step])
         parts.append(b.frames_of(b.ticket()) if via_ticket else b.frames())
+        if after_submit is not None:
+            after_submit(b, k)
     out = sorted_frames(parts)
     if keep:
         return out, b

@@ -65,26 +65,35 @@ def response_db(g: np.ndarray, fs: int, freqs_hz: np.ndarray) -> np.ndarray:
     return 20.0 * np.log10(np.maximum(np.interp(np.abs(freqs_hz), f, H), 1e-30))
 
 
-def phase(f_hz: int, n: np.ndarray, fs: int) -> np.ndarray:
-    """phi(n) = (f n) mod Fs, exact: both factors reduced mod Fs first, the product in 64-bit integers"""
-    return ((np.int64(f_hz) % fs) * (np.asarray(n, np.int64) % fs)) % fs
+def phase(f_hz: int, n: np.ndarray, fs: int, start: int = 0) -> np.ndarray:
+    """phi(n) = (f (start + n)) mod Fs, exact at any stream age: n and start are reduced mod Fs in integers BEFORE anything is added
+    or multiplied (start as a Python integer, so that it may be 2^62 and beyond), both factors are then below Fs <= 2e7 and the
+    product fits 64-bit integers with room to spare"""
+    fs = int(fs)
+    n_mod = (np.asarray(n, np.int64) % fs + np.int64(int(start) % fs)) % fs
+    return (np.int64(int(f_hz) % fs) * n_mod) % fs
 
 
 def tuner_ref(x: np.ndarray, fs: int, r: int, g: np.ndarray, offsets, submits, *, j_range=None,
-              flip_sign=False, tap_shift=0, phase_shift=0, drop_history=False, local_mixer=False):
+              flip_sign=False, tap_shift=0, phase_shift=0, drop_history=False, local_mixer=False, start: int = 0, thetas=None):
     """SPEC 3.9 for one VFO.  x: the whole stream (complex, absolute index 0 ..), g: [up, T] taps (float64 values), offsets: one
     offset per submit (a retune applies from the submit on), submits: the n_in of each submit.  Returns (y, A): the outputs of the
-    submits (or those with absolute index in j_range) and A = sum_t |g| (|Re x| + |Im x|) per output (for the error bound)."""
+    submits (or those with absolute index in j_range) and A = sum_t |g| (|Re x| + |Im x|) per output (for the error bound).
+    start (a multiple of down): x[0] has the absolute index `start` and the stream before it is silence; everything but the mixer's
+    phase is relative to it (start up / down is an integer, so the filter phase (j down) mod up is that of the relative index), and
+    j_range counts from it.  thetas: the mixer's phase offset of each submit (a continuous retune's theta; default zeros)."""
     up, down = ratio(fs, r)
+    assert int(start) % down == 0 and start >= 0
+    thetas = [0] * len(submits) if thetas is None else thetas
     T = g.shape[1]
     x = np.asarray(x, np.complex128)
     ys, As, n_base = [], [], 0
-    for f, n_in in zip(offsets, submits):
+    for f, n_in, theta in zip(offsets, submits, thetas):
         assert n_in % down == 0
         f = -f if flip_sign else f
         lo = max(0, n_base - (T - 1) - abs(tap_shift))
         idx = np.arange(lo, n_base + n_in)
-        ph = phase(f, idx - n_base if local_mixer else idx, fs)
+        ph = (phase(f, idx - n_base, fs) if local_mixer else phase(f, idx, fs, start)) + np.int64(int(theta) % fs)
         v = x[lo:n_base + n_in] * np.exp(-2j * np.pi * ph.astype(np.float64) / fs)
         if drop_history:
             v[idx < n_base] = 0.0
