@@ -740,6 +740,54 @@ double sonde_track_quality(double a_re, double a_im, double p);
 int  sonde_track_step(int32_t offset_hz, uint32_t bandwidth_hz, uint32_t rate_in, uint32_t rate, uint32_t lag, const SondeTrackLook *look,
                       const SondeTrackParams *p, int32_t *new_offset);
 
+/* ------------------------------------------------------------------ coherent antenna combiner (DESIGN SPEC 3.14)
+ * Pre-detection combining: the K antennas' complex64 rows of one sonde at `rate` (what K tuners with the same VFO list write) are
+ * added with complex weights that align their phases and favour the stronger ones, y[m] = sum_a conj(w_a) x_a[m], |w| = 1; one row
+ * per sonde goes to the decoder, whatever the sonde type.  Row a * n_sondes + i of the input is sonde i on antenna a.
+ * COHERENCE CONDITION: the K antennas share ONE sample clock and their streams START TOGETHER (one coherent SDR: two polarisations,
+ * a small array), so that sample m of every row is the same instant.  Streams that do not start together stay the business of the
+ * frame-level pass (sonde_batch_set_diversity_auto).  Equal noise floors are assumed: unequal ones are the host's to equalise first.
+ * Per sonde and per block of `block` samples counted from the sonde's last restart: M = sum_m x[m] x[m]^H in the carrier meter's
+ * arithmetic (float32 products, each aligned 256-sample block summed in a fixed order, the block sums added into doubles in
+ * ascending order), the weights by sonde_combine_weights from M and the previous block's weights, applied as their float32
+ * rounding.  No samples are carried across submits, only each sonde's last weights; the combiner holds no absolute position.  The
+ * output is bit-identical however the stream is cut into submits.  Three launches per submit on the caller's stream, ordinary stream
+ * semantics (as sonde_track_submit), one stream per combiner; nothing synchronises before sonde_combine_readout. */
+#define SONDE_COMBINE_MAX_ANTENNAS 4
+#define SONDE_COMBINE_BLOCK 1024          /* block = 0: about 21 ms at 48 kHz */
+typedef struct SondeCombiner SondeCombiner;
+typedef struct {
+	uint32_t sonde, reserved;
+	uint64_t block;                   /* index of the block, counted from the sonde's last restart (or create) */
+	double   m[16];                   /* M: m[a] = sum |x_a|^2 (a = 0..3); then (re, im) of sum x_a conj(x_c) for
+	                                     (a, c) = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); entries of antennas >= K are 0 */
+	double   w[8];                    /* the block's weights (re, im) per antenna, as carried; antennas >= K: 0 */
+	float    wf[8];                   /* the float32 roundings that were applied */
+} SondeCombineBlock;
+/* pure host: the default block length for rows at `rate` (SONDE_COMBINE_BLOCK) */
+int  sonde_combine_defaults(uint32_t rate, uint32_t *block);
+/* antennas: 2 .. 4; block: a multiple of 256 (0 = default); max_samples: a positive multiple of block; input_kind: SONDE_INPUT_IQ
+ * (anything else is refused: the combiner takes the tuner's complex64 rows).  No CPU path: a device is required. */
+int  sonde_combine_create(uint32_t n_sondes, uint32_t antennas, uint32_t rate, uint32_t max_samples, uint32_t block, int input_kind,
+                          int device, SondeCombiner **out);
+void sonde_combine_destroy(SondeCombiner *c);
+int  sonde_combine_block(const SondeCombiner *c);
+/* rows_dev: DEVICE pointer, antennas * n_sondes rows, row r at element r * row_stride (complex samples); out_dev: n_sondes rows
+ * out_stride apart, which must not overlap the input (a SondeBatch input buffer will do); n: a positive multiple of the block
+ * length, <= max_samples */
+int  sonde_combine_process(SondeCombiner *c, const void *rows_dev, size_t n, size_t row_stride, void *out_dev, size_t out_stride, void *stream);
+/* the sonde's next block starts a stream of its own (block index 0, no previous weights): after a retune or a slot reuse */
+int  sonde_combine_restart(SondeCombiner *c, uint32_t sonde);
+/* synchronises; writes the blocks of the LAST submit, sonde by sonde, oldest first (n_sondes * n / block records); returns the count */
+int  sonde_combine_readout(SondeCombiner *c, SondeCombineBlock *out, size_t cap);
+/* pure host, double, exactly reproducible (the routine the kernel runs): from m (layout of SondeCombineBlock.m) and the previous
+ * block's weights w_prev (2 * antennas doubles; NULL = after a restart): start from w_prev (after a restart: the unit vector of the
+ * largest m[a], lowest a on ties), four power iterations v <- M v each normalised to unit length (a zero norm keeps the start
+ * vector), then the phase rule rho = w_prev^H v, v <- v conj(rho) / |rho| if |rho| > 0.  w: 2 * antennas doubles */
+int  sonde_combine_weights(uint32_t antennas, const double *m, const double *w_prev, double *w);
+/* pure host: antenna a's share |w_a|^2 of the weights w */
+double sonde_combine_share(const double *w, uint32_t a);
+
 /* ------------------------------------------------------------------ live receiver: the matching rule (DESIGN SPEC 3.12)
  * Pure host, integers, exactly reproducible: which scan candidate belongs to which live VFO.  Each candidate goes to the nearest VFO no
  * further than match_hz away (0 = the scanner's min_sep_hz default, 10000; a tie: the lower VFO index); a VFO keeps only the nearest of

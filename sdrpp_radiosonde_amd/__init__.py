@@ -5,7 +5,9 @@
     detect    SondeDetector: the sonde type of each channel (sync-template correlation on the GPU); detect, then build the batch
     tuner     SondeTuner (VFOs at any offset over one wideband stream), WidebandReceiver (wideband stream -> tuner -> decoders)
     scan      SondeScanner (where in a wideband stream the carriers are: averaged power spectrum on the GPU, candidate search), survey
-    diversity DiversityReceiver (K antennas' wideband streams -> one frame list per RS41 sonde: the diversity pass with learned offsets)
+    diversity DiversityReceiver (K antennas' wideband streams -> one frame list per RS41 sonde: the diversity pass with learned offsets;
+              combine="coherent": the antennas' rows added before detection, any sonde type)
+    combine   SondeCombiner (the K antennas' IQ rows of each sonde -> one row: weights per block from the block's own statistics)
     live      LiveReceiver (a wideband receiver left running: sondes that appear are probed, typed and decoded, those that vanish dropped), LivePolicy
     node      SondeNode: the one-process node-level host (libsonde_rccl.so, include/sonde_node.h): one batch per GPU, RCCL scatter of IQ rows
     shard     channel sharding for a rank-per-GPU host on plain torch.distributed (range arithmetic, scatter, frame gather)
@@ -21,4 +23,7 @@ def __getattr__(name):          # `from sdrpp_radiosonde_amd import LiveReceiver
     if name == "DiversityReceiver":
         from . import diversity
         return diversity.DiversityReceiver
+    if name == "SondeCombiner":
+        from . import combine
+        return combine.SondeCombiner
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -79,6 +79,16 @@ assert LOOK_DTYPE.itemsize == C.sizeof(SondeTrackLook)
 TRACK_DEADBAND_HZ, TRACK_MAX_STEP_HZ = 400, 4000          # SONDE_TRACK_DEADBAND_HZ, SONDE_TRACK_MAX_STEP_HZ
 
 
+class SondeCombineBlock(C.Structure):
+    _fields_ = [("sonde", C.c_uint32), ("reserved", C.c_uint32), ("block", C.c_uint64), ("m", C.c_double * 16), ("w", C.c_double * 8),
+                ("wf", C.c_float * 8)]
+
+
+COMBINE_DTYPE = np.dtype([("sonde", "<u4"), ("reserved", "<u4"), ("block", "<u8"), ("m", "<f8", (16,)), ("w", "<f8", (8,)), ("wf", "<f4", (8,))])
+assert COMBINE_DTYPE.itemsize == C.sizeof(SondeCombineBlock)
+COMBINE_MAX_ANTENNAS, COMBINE_BLOCK = 4, 1024          # SONDE_COMBINE_MAX_ANTENNAS, SONDE_COMBINE_BLOCK
+
+
 CANDIDATE_DTYPE = np.dtype([("offset_hz", "<i4"), ("bandwidth_hz", "<u4"), ("cn0_dbhz", "<f4"), ("excess_db", "<f4"), ("bin", "<u4")])
 assert CANDIDATE_DTYPE.itemsize == C.sizeof(SondeScanCandidate)
 
@@ -174,6 +184,8 @@ ABI_SYMBOLS = [
     "sonde_batch_set_diversity", "sonde_batch_diversity_info", "sonde_batch_test_rs41_combine",
     "sonde_batch_set_diversity_auto", "sonde_batch_diversity_offsets", "sonde_batch_test_diversity_align",
     "sonde_batch_test_shift_age", "sonde_detect_test_shift_age", "sonde_tuner_test_set_base",
+    "sonde_combine_defaults", "sonde_combine_create", "sonde_combine_destroy", "sonde_combine_block", "sonde_combine_process",
+    "sonde_combine_restart", "sonde_combine_readout", "sonde_combine_weights", "sonde_combine_share",
 ] + [f"{x}_{fn}" for x in ("rs41", "dfm09", "ims100", "m10", "imet4", "c50", "mrzn1")
      for fn in ("decoder_init", "decoder_deinit", "decode")]
 
@@ -375,6 +387,19 @@ def load() -> C.CDLL:
         L.sonde_batch_test_shift_age.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
         L.sonde_detect_test_shift_age.argtypes = [vp, vp, C.c_size_t, vp]
         L.sonde_tuner_test_set_base.argtypes = [vp, C.c_int64]
+    if hasattr(L, "sonde_combine_create"):                # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        u32 = C.c_uint32
+        L.sonde_combine_defaults.argtypes = [u32, C.POINTER(u32)]
+        L.sonde_combine_create.argtypes = [u32, u32, u32, u32, u32, C.c_int, C.c_int, C.POINTER(vp)]
+        L.sonde_combine_destroy.argtypes = [vp]
+        L.sonde_combine_destroy.restype = None
+        L.sonde_combine_block.argtypes = [vp]
+        L.sonde_combine_process.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]
+        L.sonde_combine_restart.argtypes = [vp, u32]
+        L.sonde_combine_readout.argtypes = [vp, vp, C.c_size_t]
+        L.sonde_combine_weights.argtypes = [u32, vp, vp, vp]
+        L.sonde_combine_share.argtypes = [vp, u32]
+        L.sonde_combine_share.restype = C.c_double
     f = C.c_float
     L.sonde_gpx_open.restype = vp
     L.sonde_gpx_open.argtypes = [C.c_char_p]
