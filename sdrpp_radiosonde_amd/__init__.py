@@ -1,6 +1,8 @@
 """MI355X-native radiosonde demod + FEC path: ctypes binding of libsonde_mi355.so (include/sonde_abi.h).
 
-    _lib      the raw C ABI (argtypes / restypes), constants, structures
+    _lib      the raw C ABI (argtypes / restypes), constants, structures, SondeError
+    _handle   private: what the object wrappers share (the error check, the handle with close(), the checks of the tensors they take)
+    _chain    private: what the three receivers share (block arithmetic, iq48 bandwidths, batch and row buffer, the tracking loop)
     batch     SondeBatch (many 48 kS/s channels), SondeChannelizer (10 MS/s -> 512 bins), SondeVfo (VFO-rate front-end)
     detect    SondeDetector: the sonde type of each channel (sync-template correlation on the GPU); detect, then build the batch
     tuner     SondeTuner (VFOs at any offset over one wideband stream), WidebandReceiver (wideband stream -> tuner -> decoders)

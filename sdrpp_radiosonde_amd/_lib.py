@@ -22,6 +22,10 @@ PROCEED, PARSED = 0, 1
 DATA_SEQ, DATA_POS, DATA_SPEED, DATA_TIME, DATA_PTU, DATA_SERIAL, DATA_SHUTDOWN, DATA_OZONE = (1 << i for i in range(8))
 
 
+class SondeError(RuntimeError):
+    """what every refusal of this package raises: the library's sonde_last_error() text, or the Python face's own (batch.SondeError)"""
+
+
 class SondeFrame(C.Structure):
     _fields_ = [("channel", C.c_uint32), ("type", C.c_uint32), ("len", C.c_int32), ("nerr", C.c_int32 * 2),
                 ("flags", C.c_uint32), ("bitpos", C.c_uint64), ("data", C.c_uint8 * FRAME_MAX)]

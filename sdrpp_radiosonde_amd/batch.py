@@ -7,22 +7,20 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._handle import Handle, channel_rows, chk, current_stream
+from ._lib import SondeError  # noqa: F401  (batch.SondeError: where hosts and tests import it from)
 from ._lib import FRAME_COMBINED, FLAG_AFSK_RESCUE, FLAG_DFM_RESCUE, FLAG_IMS_RESCUE, FLAG_MANCHESTER_RESCUE, FLAG_RS41_RESCUE, FRAME_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE  # noqa: F401
 
 
-class SondeError(RuntimeError):
-    pass
-
-
-class SondeBatch:
+class SondeBatch(Handle):
     """Many independent 48 kS/s channels on one GPU; one HIP workgroup per channel.
 
     submit() takes a device tensor (torch, any object with data_ptr()) shaped
     [C, n, 2] float32 (IQ) or [C, n] float32 (discriminator samples), n % 2048 == 0.
     """
+    DESTROY = "sonde_batch_destroy"
 
     def __init__(self, n_channels: int, max_samples: int, *, types=None, input_kind: int = INPUT_IQ, device: int = 0, flags: int = 0, time_slices: int = 0):
-        self.L = _lib.load()
         self.n_channels = int(n_channels)
         self.max_samples = int(max_samples)
         self.input_kind = input_kind
@@ -40,47 +38,13 @@ class SondeBatch:
         cfg.time_slices = time_slices          # 0: the library's choice (SondeBatchConfig.time_slices)
         cfg.input_kind = input_kind
         cfg.device = device
-        h = C.c_void_p()
-        if self.L.sonde_batch_create(C.byref(cfg), C.byref(h)) != 0:
-            raise SondeError(_lib.last_error())
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.sonde_batch_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        self._create("sonde_batch_create", C.byref(cfg))
 
     def _chk(self, rc):
-        if rc < 0:
-            raise SondeError(_lib.last_error())
-        return rc
+        return chk(rc)
 
     def submit(self, samples, stream: int | None = None):
-        shape = tuple(samples.shape)
-        n = shape[1]
-        if shape[0] != self.n_channels:
-            raise SondeError("first dimension must be n_channels")
-        is_iq = self.input_kind in (INPUT_IQ, INPUT_IQ16, INPUT_IQ8)
-        if is_iq and (len(shape) != 3 or shape[2] != 2):
-            raise SondeError("IQ input must be [C, n, 2] (float32; int16 for INPUT_IQ16, int8 for INPUT_IQ8)")
-        if not is_iq and len(shape) != 2:
-            raise SondeError("real input must be [C, n] float32")
-        # the C side sees only a pointer: check what it cannot (dtype, device, inner layout)
-        dt = str(getattr(samples, "dtype", ""))
-        want = {INPUT_IQ16: "int16", INPUT_IQ8: "int8"}.get(self.input_kind, "float32")
-        if not dt.endswith(want) or dt.endswith("u" + want):
-            raise SondeError(f"samples must be {want}, got {dt}")
-        dev = getattr(samples, "device", None)
-        if dev is None or getattr(dev, "type", "") != "cuda":
-            raise SondeError("samples must be a device (HIP) tensor; use submit_host() for host memory")
-        if dev.index is not None and dev.index != self.device:
-            raise SondeError(f"samples live on device {dev.index}, the batch on device {self.device}")
-        st = tuple(samples.stride())
-        if (is_iq and st[1:] != (2, 1)) or (not is_iq and st[1] != 1):
-            raise SondeError("samples must be contiguous inside a channel (only the channel stride may be padded)")
-        stride = samples.stride(0) // (2 if is_iq else 1)
+        n, stride = channel_rows(samples, self.input_kind, self.n_channels, self.device, "batch")
         # keep the device buffers of the last two submits alive (Python-side lifetime only): with SONDE_FLAG_LATE_JOIN / _PIPELINE the
         # buffer of submit t may be read until submit t + 1 is queued (include/sonde_abi.h); with default flags stream order covers it
         self._keep = (samples, getattr(self, "_keep", (None, None))[0])
@@ -370,17 +334,17 @@ def strided_rows(x, stride: int | None = None):
     return buf[:, :n]
 
 
-class SondeChannelizer:
+class SondeChannelizer(Handle):
     """Wideband front-end (BASELINE config 4): n_streams x 10 MS/s complex IQ -> 512 bins each (20 kS/s, one phase sample per
     step) -> per-bin decode; every stage is one launch over all streams.  submit() takes [samples_per_submit, 2] (one stream) or
     [n_streams, samples_per_submit, 2].  Bins carry the 12 kS/s sondes (RS41, DFM, iMS-100, MRZ-N1) and, unfused, the AFSK
     sondes; an M10 channel (50 kHz wide) does not fit a 19.5 kHz bin: use SondeVfo for those."""
+    DESTROY = "sonde_chan_destroy"
 
     def __init__(self, types=None, blocks_per_submit: int = 1, device: int = 0, n_streams: int = 1, fused: bool | None = None, overlap: bool | None = None,
                  dual: bool = False, input_kind: int = INPUT_IQ):
         """dual: both stackings of every stream (SPEC 3.5c): 1024 channels per stream, 1024 p + k = even bin k (centre k x 19531.25 Hz),
         1024 p + 512 + k = odd bin k (centre (k + 1/2) x 19531.25 Hz): every carrier lies within 4.9 kHz of a bin centre."""
-        self.L = _lib.load()
         self._types = None
         self.n_streams = int(n_streams)
         self.dual = bool(dual)
@@ -390,11 +354,7 @@ class SondeChannelizer:
             self._types = np.ascontiguousarray(types, dtype=np.uint8)
             assert self._types.shape == (self.n_channels,)
             tp = self._types.ctypes.data_as(C.c_void_p)
-        h = C.c_void_p()
-        create = self.L.sonde_chan_create_dual if dual else self.L.sonde_chan_create_multi
-        if create(tp, blocks_per_submit, self.n_streams, device, C.byref(h)) != 0:
-            raise SondeError(_lib.last_error())
-        self.h = h
+        self._create("sonde_chan_create_dual" if dual else "sonde_chan_create_multi", tp, blocks_per_submit, self.n_streams, device)
         # fused (default where possible): discriminator + resampler inside the decoder kernel; fused=False keeps the 48 kS/s rows
         # (read()); fused=None leaves the library's choice alone
         self.fused = bool(self.L.sonde_chan_set_fused(self.h, 1 if fused else 0)) if fused is not None else bool(self.L.sonde_chan_set_fused(self.h, -1))
@@ -419,8 +379,7 @@ class SondeChannelizer:
         if not str(iq.dtype).endswith(want) or str(iq.dtype).endswith("u" + want):
             raise SondeError(f"wideband block must be {want}, got {iq.dtype}")
         self._keep = iq
-        if self.L.sonde_chan_submit(self.h, C.c_void_p(iq.data_ptr()), self.samples_per_submit, C.c_void_p(stream or 0)) != 0:
-            raise SondeError(_lib.last_error())
+        chk(self.L.sonde_chan_submit(self.h, C.c_void_p(iq.data_ptr()), self.samples_per_submit, C.c_void_p(stream or 0)))
 
     def frames(self) -> np.ndarray:
         return SondeBatch.frames(self.batch)
@@ -428,31 +387,25 @@ class SondeChannelizer:
     def kernel_ms(self):
         """(filter bank, discriminator + resampler, demodulator, framers) average ms over the timed submits."""
         v = [C.c_float() for _ in range(4)]
-        if self.L.sonde_chan_kernel_ms(self.h, *[C.byref(x) for x in v]) != 0:
-            raise SondeError(_lib.last_error())
+        chk(self.L.sonde_chan_kernel_ms(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
     def read(self):
         """(phases [bins, n_steps] in quadrants, 48 kS/s rows [bins, n_steps * 12 / 5] or None in fused mode) of the last submit."""
         bins = np.zeros((self.n_channels, self.n_steps), dtype=np.float32)
         out48 = None if self.fused else np.zeros((self.n_channels, self.n_steps * 12 // 5), dtype=np.float32)
-        if self.L.sonde_chan_read(self.h, bins.ctypes.data_as(C.c_void_p), out48.ctypes.data_as(C.c_void_p) if out48 is not None else None) != 0:
-            raise SondeError(_lib.last_error())
+        chk(self.L.sonde_chan_read(self.h, bins.ctypes.data_as(C.c_void_p), out48.ctypes.data_as(C.c_void_p) if out48 is not None else None))
         return bins, out48
 
     def close(self):
-        if getattr(self, "h", None):
-            self.batch.h = None
-            self.L.sonde_chan_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        if self.h:
+            self.batch.h = None          # the borrowed view first: the embedded batch goes with the channelizer
+        super().close()
 
 
 def get_taps(sonde_type: int) -> np.ndarray:
     out = np.zeros((32, 32), dtype=np.float32)
-    if _lib.load().sonde_get_taps(sonde_type, out.ctypes.data_as(C.c_void_p)) != 0:
-        raise SondeError(_lib.last_error())
+    chk(_lib.load().sonde_get_taps(sonde_type, out.ctypes.data_as(C.c_void_p)))
     return out
 
 
@@ -460,16 +413,13 @@ def get_taps(sonde_type: int) -> np.ndarray:
 VFO_RATE = {0: 10000, 1: 15000, 2: 20000, 3: 50000, 4: 20000, 5: 20000, 6: 20000}
 
 
-class SondeVfo:
+class SondeVfo(Handle):
     """VFO front-end (SURVEY 8 a1 + a2): IQ at the sonde type's VFO rate -> discriminator -> rational resampler -> 48 kS/s
     FM audio rows for a SondeBatch created with INPUT_REAL (/root/reference/src/main.cpp:55-60)."""
+    DESTROY = "sonde_vfo_destroy"
 
     def __init__(self, n_channels: int, rate_in: int, max_in: int, device: int = 0):
-        self.L = _lib.load()
-        h = C.c_void_p()
-        if self.L.sonde_vfo_create(n_channels, rate_in, max_in, device, C.byref(h)) != 0:
-            raise SondeError(_lib.last_error())
-        self.h = h
+        self._create("sonde_vfo_create", n_channels, rate_in, max_in, device)
         self.n_channels, self.rate_in, self.max_in = n_channels, rate_in, max_in
         up, down = C.c_int(), C.c_int()
         self.L.sonde_vfo_ratio(rate_in, C.byref(up), C.byref(down))
@@ -487,26 +437,13 @@ class SondeVfo:
         if out is None:
             out = torch.empty((self.n_channels, n_out), dtype=torch.float32, device=iq.device)
         if stream is None:
-            stream = torch.cuda.current_stream(iq.device).cuda_stream
-        if self.L.sonde_vfo_process(self.h, C.c_void_p(iq.data_ptr()), n_in, iq.stride(0) // 2, C.c_void_p(out.data_ptr()), out.stride(0),
-                                    C.c_void_p(stream)) != 0:
-            raise SondeError(_lib.last_error())
+            stream = current_stream(iq.device)
+        chk(self.L.sonde_vfo_process(self.h, C.c_void_p(iq.data_ptr()), n_in, iq.stride(0) // 2, C.c_void_p(out.data_ptr()), out.stride(0),
+                                     C.c_void_p(stream)))
         return out
 
     def taps(self) -> np.ndarray:
         g = np.zeros((self.up, 16), dtype=np.float32)
-        if self.L.sonde_vfo_taps(self.rate_in, g.ctypes.data_as(C.c_void_p)) != 0:
-            raise SondeError(_lib.last_error())
+        chk(self.L.sonde_vfo_taps(self.rate_in, g.ctypes.data_as(C.c_void_p)))
         return g
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.sonde_vfo_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 

@@ -15,20 +15,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import COMBINE_DTYPE, INPUT_IQ
-from .batch import SondeError
-
-
-def _chk(rc):
-    if rc < 0:
-        raise SondeError(_lib.last_error())
-    return rc
+from ._handle import Handle, chk, complex_rows, complex_stride, current_stream
+from ._lib import COMBINE_DTYPE, INPUT_IQ, SondeError
 
 
 def defaults(rate: int) -> int:
     """the block length the combiner picks for rows at `rate` (sonde_combine_defaults)"""
     b = C.c_uint32()
-    _chk(_lib.load().sonde_combine_defaults(int(rate), C.byref(b)))
+    chk(_lib.load().sonde_combine_defaults(int(rate), C.byref(b)))
     return b.value
 
 
@@ -46,7 +40,7 @@ def weights(m, w_prev=None, antennas: int | None = None) -> np.ndarray:
         wp = np.ascontiguousarray(w_prev, dtype=np.complex128)
         K, prev = len(wp), wp.ctypes.data_as(C.c_void_p)
     w = np.zeros(max(K, 1), dtype=np.complex128)
-    _chk(_lib.load().sonde_combine_weights(K, m.ctypes.data_as(C.c_void_p), prev, w.ctypes.data_as(C.c_void_p)))
+    chk(_lib.load().sonde_combine_weights(K, m.ctypes.data_as(C.c_void_p), prev, w.ctypes.data_as(C.c_void_p)))
     return w[:K]
 
 
@@ -58,65 +52,41 @@ def share(w, a: int) -> float:
     return float(_lib.load().sonde_combine_share(w.ctypes.data_as(C.c_void_p), int(a)))
 
 
-class SondeCombiner:
+class SondeCombiner(Handle):
     """The combiner of `antennas` (2..4) rows per sonde at `rate`.  process() takes a float32 device view [antennas * n_sondes, n, 2]
     (rows any stride apart, contiguous inside a row), n a positive multiple of `block` and <= max_samples, and returns [n_sondes, n, 2]
     or writes it into `out` (a float32 view [n_sondes, >= n, 2] that does not overlap the rows: a SondeBatch input buffer will do).
     readout() synchronises and returns the last submit's blocks (COMBINE_DTYPE: sonde, block, m, w, wf), sonde by sonde."""
+    DESTROY = "sonde_combine_destroy"
 
     def __init__(self, n_sondes: int, antennas: int, rate: int, max_samples: int, block: int = 0, device: int = 0, *, input_kind: int = INPUT_IQ):
-        self.L = _lib.load()
-        h = C.c_void_p()
-        _chk(self.L.sonde_combine_create(int(n_sondes), int(antennas), int(rate), int(max_samples), int(block), int(input_kind), int(device),
-                                         C.byref(h)))
-        self.h = h
+        self._create("sonde_combine_create", int(n_sondes), int(antennas), int(rate), int(max_samples), int(block), int(input_kind), int(device))
+        h = self.h
         self.n_sondes, self.antennas, self.rate, self.max_samples, self.device = int(n_sondes), int(antennas), int(rate), int(max_samples), int(device)
         self.block = int(self.L.sonde_combine_block(h))
         self._last = 0
 
-    @staticmethod
-    def _rows_ok(t, torch):
-        return (t.dtype == torch.float32 and t.is_cuda and t.dim() == 3 and t.shape[2] == 2 and t.stride(2) == 1 and t.stride(1) == 2
-                and not (t.shape[0] > 1 and t.stride(0) % 2))
-
     def process(self, rows, out=None, stream: int | None = None):
         import torch
-        if not self._rows_ok(rows, torch):
-            raise SondeError("the rows must be a float32 device view [antennas * n_sondes, n, 2], contiguous inside a row (complex64: REAL rows carry no phase)")
-        if rows.shape[0] != self.antennas * self.n_sondes:
-            raise SondeError(f"the combiner was created for {self.antennas} x {self.n_sondes} rows, got {rows.shape[0]}")
-        if rows.device.index is not None and rows.device.index != self.device:
-            raise SondeError(f"the rows live on device {rows.device.index}, the combiner on device {self.device}")
-        n = rows.shape[1]
+        n, stride = complex_rows(rows, self.antennas * self.n_sondes, self.device, "combiner", "antennas * n_sondes",
+                                 f"{self.antennas} x {self.n_sondes}", "phase")
         if out is None:
             out = torch.empty((self.n_sondes, n, 2), dtype=torch.float32, device=rows.device)
-        elif not self._rows_ok(out, torch) or out.shape[0] != self.n_sondes or out.shape[1] < n or out.device != rows.device:
+        ostride = complex_stride(out)
+        if ostride is None or out.shape[0] != self.n_sondes or out.shape[1] < n or out.device != rows.device:
             raise SondeError("out must be a float32 device view [n_sondes, >= n, 2], contiguous inside a row")
         if stream is None:
-            stream = torch.cuda.current_stream(rows.device).cuda_stream
+            stream = current_stream(rows.device)
         self._keep = (rows, out)
-        ostride = out.stride(0) // 2 if out.shape[0] > 1 else max(out.stride(0) // 2, out.shape[1])
-        _chk(self.L.sonde_combine_process(self.h, C.c_void_p(rows.data_ptr()), n, rows.stride(0) // 2, C.c_void_p(out.data_ptr()), ostride,
-                                          C.c_void_p(stream)))
+        chk(self.L.sonde_combine_process(self.h, C.c_void_p(rows.data_ptr()), n, stride, C.c_void_p(out.data_ptr()), ostride, C.c_void_p(stream)))
         self._last = n // self.block
         return out[:, :n]
 
     def restart(self, i: int):
         """sonde i's next block starts a stream of its own: block index 0, no previous weights (after a retune or a slot reuse)"""
-        _chk(self.L.sonde_combine_restart(self.h, int(i)))
+        chk(self.L.sonde_combine_restart(self.h, int(i)))
 
     def readout(self) -> np.ndarray:
         out = np.zeros(self.n_sondes * self._last, dtype=COMBINE_DTYPE)
-        n = _chk(self.L.sonde_combine_readout(self.h, out.ctypes.data_as(C.c_void_p), len(out)))
+        n = chk(self.L.sonde_combine_readout(self.h, out.ctypes.data_as(C.c_void_p), len(out)))
         return out[:n]
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.sonde_combine_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -15,41 +15,35 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DETECTION_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16
-from .batch import SondeError
+from ._handle import Handle, channel_rows, chk
+from ._lib import DETECTION_DTYPE, INPUT_IQ, SondeError
 
 NTYPES = 7
-
-
-def _chk(rc):
-    if rc < 0:
-        raise SondeError(_lib.last_error())
-    return rc
 
 
 def templates(sonde_type: int) -> np.ndarray:
     """the type's sync template as +-1 int8 at its stream rate (24 kS/s GFSK, 6 kS/s AFSK)"""
     L = _lib.load()
-    n = _chk(L.sonde_detect_templates(int(sonde_type), None, 0))
+    n = chk(L.sonde_detect_templates(int(sonde_type), None, 0))
     out = np.zeros(n, np.int8)
-    _chk(L.sonde_detect_templates(int(sonde_type), out.ctypes.data_as(C.c_void_p), n))
+    chk(L.sonde_detect_templates(int(sonde_type), out.ctypes.data_as(C.c_void_p), n))
     return out
 
 
 def thresholds() -> np.ndarray:
     """theta_k of the decision, float32 [7]"""
     out = np.zeros(NTYPES, np.float32)
-    _chk(_lib.load().sonde_detect_thresholds(out.ctypes.data_as(C.c_void_p)))
+    chk(_lib.load().sonde_detect_thresholds(out.ctypes.data_as(C.c_void_p)))
     return out
 
 
-class SondeDetector:
+class SondeDetector(Handle):
     """Sonde type of many 48 kS/s channels, one HIP workgroup per channel.  submit() takes the rows SondeBatch.submit takes:
     a device tensor [C, n, 2] (float32 IQ, int16 for INPUT_IQ16, int8 for INPUT_IQ8) or [C, n] float32 (INPUT_REAL), n % 2048 == 0,
     strided between channels only.  type_mask: None or C bitmasks (bit k: type k may be decided)."""
+    DESTROY = "sonde_detect_destroy"
 
     def __init__(self, n_channels: int, max_samples: int, *, input_kind: int = INPUT_IQ, type_mask=None, device: int = 0):
-        self.L = _lib.load()
         self.n_channels = int(n_channels)
         self.max_samples = int(max_samples)
         self.input_kind = input_kind
@@ -61,70 +55,41 @@ class SondeDetector:
             if self._mask.shape != (self.n_channels,):
                 raise SondeError("type_mask must hold one bitmask per channel")
             mp = self._mask.ctypes.data_as(C.c_void_p)
-        h = C.c_void_p()
-        _chk(self.L.sonde_detect_create(self.n_channels, self.max_samples, input_kind, mp, self.device, C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.sonde_detect_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        self._create("sonde_detect_create", self.n_channels, self.max_samples, input_kind, mp, self.device)
 
     def submit(self, samples, stream: int | None = None):
-        shape = tuple(samples.shape)
-        if shape[0] != self.n_channels:
-            raise SondeError("first dimension must be n_channels")
-        is_iq = self.input_kind in (INPUT_IQ, INPUT_IQ16, INPUT_IQ8)
-        if is_iq and (len(shape) != 3 or shape[2] != 2):
-            raise SondeError("IQ input must be [C, n, 2] (float32; int16 for INPUT_IQ16, int8 for INPUT_IQ8)")
-        if not is_iq and len(shape) != 2:
-            raise SondeError("real input must be [C, n] float32")
-        dt = str(getattr(samples, "dtype", ""))
-        want = {INPUT_IQ16: "int16", INPUT_IQ8: "int8"}.get(self.input_kind, "float32")
-        if not dt.endswith(want) or dt.endswith("u" + want):
-            raise SondeError(f"samples must be {want}, got {dt}")
-        dev = getattr(samples, "device", None)
-        if dev is None or getattr(dev, "type", "") != "cuda":
-            raise SondeError("samples must be a device (HIP) tensor")
-        if dev.index is not None and dev.index != self.device:
-            raise SondeError(f"samples live on device {dev.index}, the detector on device {self.device}")
-        st = tuple(samples.stride())
-        if (is_iq and st[1:] != (2, 1)) or (not is_iq and st[1] != 1):
-            raise SondeError("samples must be contiguous inside a channel (only the channel stride may be padded)")
-        stride = samples.stride(0) // (2 if is_iq else 1)
+        n, stride = channel_rows(samples, self.input_kind, self.n_channels, self.device, "detector")
         self._keep = samples
-        _chk(self.L.sonde_detect_submit(self.h, C.c_void_p(samples.data_ptr()), shape[1], stride, C.c_void_p(stream or 0)))
+        chk(self.L.sonde_detect_submit(self.h, C.c_void_p(samples.data_ptr()), n, stride, C.c_void_p(stream or 0)))
 
     def results(self) -> dict:
         """numpy arrays type [C] (int32, -1 = none), best [C, 7] (float64), pos [C, 7] (uint64, input samples), inverted [C, 7] (bool)"""
         out = np.zeros(self.n_channels, DETECTION_DTYPE)
-        _chk(self.L.sonde_detect_results(self.h, out.ctypes.data_as(C.c_void_p), self.n_channels))
+        chk(self.L.sonde_detect_results(self.h, out.ctypes.data_as(C.c_void_p), self.n_channels))
         inv = ((out["inverted"][:, None] >> np.arange(NTYPES, dtype=np.uint32)) & 1).astype(bool)
         return {"type": out["type"].copy(), "best": out["best"].copy(), "pos": out["pos"].copy(), "inverted": inv}
 
     def reset(self):
-        _chk(self.L.sonde_detect_reset(self.h))
+        chk(self.L.sonde_detect_reset(self.h))
 
     def restart_channels(self, channels):
         """the listed channels back to their state after create, ordered on the last submit's stream, no synchronisation
         (sonde_detect_restart_channels)"""
         ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
-        _chk(self.L.sonde_detect_restart_channels(self.h, ch.ctypes.data_as(C.c_void_p), len(ch)))
+        chk(self.L.sonde_detect_restart_channels(self.h, ch.ctypes.data_as(C.c_void_p), len(ch)))
 
     def test_shift_age(self, channels, samples):
         """Test introspection, not for hosts (sonde_detect_test_shift_age): the listed channels become the same streams, begun
         samples[i] input samples (a multiple of 30720) earlier; ordered like restart_channels."""
         ch = np.ascontiguousarray(channels, dtype=np.uint32).reshape(-1)
         sm = np.ascontiguousarray(np.broadcast_to(np.asarray(samples, dtype=np.uint64), ch.shape))
-        _chk(self.L.sonde_detect_test_shift_age(self.h, ch.ctypes.data_as(C.c_void_p), len(ch), sm.ctypes.data_as(C.c_void_p)))
+        chk(self.L.sonde_detect_test_shift_age(self.h, ch.ctypes.data_as(C.c_void_p), len(ch), sm.ctypes.data_as(C.c_void_p)))
 
     def read(self, channel: int):
         """the last submit's quantised streams of one channel: D [n/2], A_imet [n/8], A_c50 [n/8] (int32)"""
         D = np.zeros(self.max_samples // 2, np.int32)
         ai = np.zeros(self.max_samples // 8, np.int32)
         ac = np.zeros(self.max_samples // 8, np.int32)
-        n = _chk(self.L.sonde_detect_read(self.h, int(channel), D.ctypes.data_as(C.c_void_p), ai.ctypes.data_as(C.c_void_p),
-                                          ac.ctypes.data_as(C.c_void_p)))
+        n = chk(self.L.sonde_detect_read(self.h, int(channel), D.ctypes.data_as(C.c_void_p), ai.ctypes.data_as(C.c_void_p),
+                                         ac.ctypes.data_as(C.c_void_p)))
         return D[:n // 2], ai[:n // 8], ac[:n // 8]

@@ -8,18 +8,16 @@ libsonde_mi355.so.
     combine="coherent"  the same K tuners -> one SondeCombiner (combine.py, SPEC 3.14), which adds the K rows of each sonde before
                         detection -> one SondeBatch of one channel per sonde: any sonde type, the antennas on one sample clock
 
-The chain is WidebandReceiver's "iq48" (tuner.py): a tuner per antenna straight to 48 kHz IQ rows.  combine="frames" (the default):
-RS41 sondes only.  No tracking, no reference chain."""
+The chain is the "iq48" chain of _chain.py, which WidebandReceiver (tuner.py) and LiveReceiver share: a tuner per antenna straight to
+48 kHz IQ rows.  combine="frames" (the default): RS41 sondes only.  No tracking, no reference chain."""
 from __future__ import annotations
 
 import numpy as np
 
-from . import _lib
-from ._lib import FRAME_DUPLICATE, INPUT_IQ, TILE
-from .batch import VFO_RATE, SondeBatch, SondeError
-from .tuner import AFSK_TILE, C50, IMET4, IQ48_MAX_BW, SondeTuner, _lcm, _multiple_for, ratio
-
-RS41 = 0
+from . import _chain
+from ._handle import current_stream
+from ._lib import FRAME_DUPLICATE, INPUT_IQ, RS41, SondeError
+from .tuner import SondeTuner
 
 
 class DiversityReceiver:
@@ -45,7 +43,6 @@ class DiversityReceiver:
                  window_bits: int = 0, rescue: bool = False, chain: str = "iq48", track: bool = False, combine: str = "frames",
                  combine_block: int = 0, manchester_rescue: bool = False, dfm_rescue: bool = False, ims_rescue: bool = False,
                  afsk_rescue: bool = False):
-        import torch
         if chain != "iq48":
             raise SondeError('DiversityReceiver: only the "iq48" chain')
         if track:
@@ -56,81 +53,56 @@ class DiversityReceiver:
         self.sondes = [(int(f), int(t)) for f, t in sondes]
         if not self.sondes:
             raise SondeError("no sondes")
-        if combine == "coherent":
-            self._init_coherent(rate_in, antennas, input_kind, device, max_in, combine_block,
-                                _lib.rescue_flags(rescue, manchester_rescue, dfm_rescue, ims_rescue, afsk_rescue))
-            return
-        if manchester_rescue or dfm_rescue or ims_rescue or afsk_rescue:
-            raise SondeError('DiversityReceiver: combine="frames" is RS41 only and takes no rescue pass but rescue=')
-        if any(t != RS41 for _, t in self.sondes):
-            raise SondeError("DiversityReceiver: RS41 sondes only (the diversity pass is RS41's)")
-        self.antennas = int(antennas)
-        if not 2 <= self.antennas <= 4:
-            raise SondeError("DiversityReceiver: 2..4 antennas")
-        self.rate_in, self.device, self.input_kind = int(rate_in), int(device), int(input_kind)
-        fs, S, K = self.rate_in, len(self.sondes), self.antennas
-        self.granule = _lcm(ratio(fs, 48000)[1], _multiple_for(48000, fs, TILE))
-        self.max_in = int(max_in or self.granule)
-        if self.max_in % self.granule:
-            raise SondeError(f"max_in must be a multiple of the granule ({self.granule})")
-        n48 = self.max_in * 48000 // fs
-        vfos = [(f, min(VFO_RATE[RS41], IQ48_MAX_BW)) for f, _ in self.sondes]
-        self.tuners = [SondeTuner(fs, 48000, vfos, self.max_in, input_kind=input_kind, device=device) for _ in range(K)]
-        self.batch = SondeBatch(K * S, n48, types=np.zeros(K * S, dtype=np.uint8), input_kind=INPUT_IQ, device=device,
-                                flags=_lib.FLAG_RS41_RESCUE if rescue else 0)
-        self.batch.set_diversity([[a * S + i for a in range(K)] for i in range(S)], None, window_bits, learn=True, mark_duplicates=True)
-        stride = int(_lib.load().sonde_row_stride(n48, INPUT_IQ))
-        self._rows = torch.empty((K * S, stride, 2), dtype=torch.float32, device=f"cuda:{device}")
-        self._n48 = 0
-
-    def _init_coherent(self, rate_in, antennas, input_kind, device, max_in, combine_block, flags):
-        import torch
-        from .combine import SondeCombiner
-        self.antennas = int(antennas)
-        if not 2 <= self.antennas <= 4:
-            raise SondeError("DiversityReceiver: 2..4 antennas")
-        self.rate_in, self.device, self.input_kind = int(rate_in), int(device), int(input_kind)
-        fs, S, K = self.rate_in, len(self.sondes), self.antennas
+        coherent = combine == "coherent"
         types = [t for _, t in self.sondes]
-        tile = AFSK_TILE if any(t in (IMET4, C50) for t in types) else TILE
-        self.granule = _lcm(ratio(fs, 48000)[1], _multiple_for(48000, fs, tile))
-        self.max_in = int(max_in or self.granule)
-        if self.max_in % self.granule:
-            raise SondeError(f"max_in must be a multiple of the granule ({self.granule})")
-        n48 = self.max_in * 48000 // fs
-        vfos = [(f, min(VFO_RATE[t], IQ48_MAX_BW)) for f, t in self.sondes]
+        if not coherent:
+            if manchester_rescue or dfm_rescue or ims_rescue or afsk_rescue:
+                raise SondeError('DiversityReceiver: combine="frames" is RS41 only and takes no rescue pass but rescue=')
+            if any(t != RS41 for t in types):
+                raise SondeError("DiversityReceiver: RS41 sondes only (the diversity pass is RS41's)")
+        self.antennas = int(antennas)
+        if not 2 <= self.antennas <= 4:
+            raise SondeError("DiversityReceiver: 2..4 antennas")
+        self.rate_in, self.device, self.input_kind = int(rate_in), int(device), int(input_kind)
+        fs, S, K = self.rate_in, len(self.sondes), self.antennas
+        p = _chain.plan(fs, types, max_in)
+        self.granule, self.max_in = p.granule, p.max_in
+        vfos = [(f, _chain.iq48_bandwidth(t)) for f, t in self.sondes]
         self.tuners = [SondeTuner(fs, 48000, vfos, self.max_in, input_kind=input_kind, device=device) for _ in range(K)]
-        self.combiner = SondeCombiner(S, K, 48000, n48, combine_block, device)
-        g48 = self.granule * 48000 // fs
-        if g48 % self.combiner.block:
-            raise SondeError(f"combine_block must divide the granule's {g48} samples at 48 kHz")
-        self.batch = SondeBatch(S, n48, types=np.array(types, dtype=np.uint8), input_kind=INPUT_IQ, device=device, flags=flags)
-        stride = int(_lib.load().sonde_row_stride(n48, INPUT_IQ))
-        self._ant = torch.empty((K * S, n48, 2), dtype=torch.float32, device=f"cuda:{device}")      # the tuners' rows
-        self._rows = torch.empty((S, stride, 2), dtype=torch.float32, device=f"cuda:{device}")      # the combined rows: the batch's input
+        passes = (rescue, manchester_rescue, dfm_rescue, ims_rescue, afsk_rescue)
         self._n48 = 0
+        if coherent:          # the K rows of each sonde added before detection: one batch channel per sonde
+            import torch
+            from .combine import SondeCombiner
+            self.combiner = SondeCombiner(S, K, 48000, p.n48, combine_block, device)
+            g48 = _chain.out48(fs, self.granule)
+            if g48 % self.combiner.block:
+                raise SondeError(f"combine_block must divide the granule's {g48} samples at 48 kHz")
+            self.batch = _chain.batch(S, p.n48, types, device, passes)
+            self._ant = torch.empty((K * S, p.n48, 2), dtype=torch.float32, device=f"cuda:{device}")      # the tuners' rows
+            self._rows = _chain.rows(S, p.n48, device)                                                   # the combined rows
+        else:                 # one batch channel per antenna and sonde; the K channels of a sonde are a diversity group
+            self.batch = _chain.batch(K * S, p.n48, types * K, device, passes)
+            self.batch.set_diversity([[a * S + i for a in range(K)] for i in range(S)], None, window_bits, learn=True, mark_duplicates=True)
+            self._rows = _chain.rows(K * S, p.n48, device)
 
     def submit(self, blocks, stream: int | None = None):
-        import torch
         if len(blocks) != self.antennas:
             raise SondeError(f"submit takes {self.antennas} blocks, one per antenna")
         n = int(blocks[0].shape[0])
         if any(int(b.shape[0]) != n for b in blocks):
             raise SondeError("the antennas' blocks must be of equal length")
-        if n == 0 or n % self.granule or n > self.max_in:
-            raise SondeError(f"the blocks must hold a positive multiple of the granule ({self.granule}) samples, at most max_in ({self.max_in})")
+        _chain.check_block(n, self.granule, self.max_in, "blocks")
         if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = current_stream(self.device)
         S = len(self.sondes)
-        self._n48 = n * 48000 // self.rate_in
-        if self.combine == "coherent":
-            for a, (tu, block) in enumerate(zip(self.tuners, blocks)):
-                tu.process(block, out=self._ant[a * S:(a + 1) * S], stream=stream)
-            self.combiner.process(self._ant[:, :self._n48], out=self._rows, stream=stream)
-            self.batch.submit(self._rows[:, :self._n48], stream)
-            return
+        self._n48 = _chain.out48(self.rate_in, n)
+        coherent = self.combine == "coherent"
+        ant = self._ant if coherent else self._rows          # where the tuners write: antenna a's rows at a * S
         for a, (tu, block) in enumerate(zip(self.tuners, blocks)):
-            tu.process(block, out=self._rows[a * S:(a + 1) * S], stream=stream)
+            tu.process(block, out=ant[a * S:(a + 1) * S], stream=stream)
+        if coherent:
+            self.combiner.process(ant[:, :self._n48], out=self._rows, stream=stream)
         self.batch.submit(self._rows[:, :self._n48], stream)
 
     def frames(self):

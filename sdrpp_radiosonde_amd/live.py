@@ -4,6 +4,7 @@ appear and vanish.
     match           the matching rule: which scan candidate belongs to which live VFO (sonde_live_match: pure host)
     LivePolicy      the rule book, no GPU: scan candidates and probe detections in, actions and events out
     LiveReceiver    wideband stream -> slot tuner -> decoders / carrier meter / type detector, a scanner beside them; executes the policy
+                    (the "iq48" chain of _chain.py, which WidebandReceiver and DiversityReceiver share)
 
 Nothing here computes on the samples: the tuner, the batch, the meter, the detector and the scanner are the library's HIP objects."""
 from __future__ import annotations
@@ -12,12 +13,13 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from ._lib import INPUT_IQ, TILE
-from .batch import VFO_RATE, SondeBatch, SondeError
+from . import _chain, _lib
+from ._chain import IQ48_MAX_BW as PROBE_BW          # the bandwidth of every probe VFO
+from ._handle import chk, current_stream
+from ._lib import INPUT_IQ, SondeError
+from .batch import VFO_RATE
 
 MATCH_HZ = 10000           # the scanner's min_sep_hz default: a candidate this close to a VFO is that VFO's carrier
-PROBE_BW = 40000           # scan.DETECT_BW
 
 
 def match(vfo_offsets, cand_offsets, match_hz: int = 0):
@@ -25,9 +27,8 @@ def match(vfo_offsets, cand_offsets, match_hz: int = 0):
     v = np.ascontiguousarray(vfo_offsets, dtype=np.int32).reshape(-1)
     c = np.ascontiguousarray(cand_offsets, dtype=np.int32).reshape(-1)
     cv, vc = np.full(len(v), -1, np.int32), np.full(len(c), -1, np.int32)
-    if _lib.load().sonde_live_match(v.ctypes.data_as(C.c_void_p), len(v), c.ctypes.data_as(C.c_void_p), len(c), int(match_hz),
-                                    cv.ctypes.data_as(C.c_void_p), vc.ctypes.data_as(C.c_void_p)) < 0:
-        raise SondeError(_lib.last_error())
+    chk(_lib.load().sonde_live_match(v.ctypes.data_as(C.c_void_p), len(v), c.ctypes.data_as(C.c_void_p), len(c), int(match_hz),
+                                     cv.ctypes.data_as(C.c_void_p), vc.ctypes.data_as(C.c_void_p)))
     return cv, vc
 
 
@@ -221,28 +222,22 @@ class LiveReceiver:
                  scan_seconds: float = 1.0, probe_seconds: float = 2.0, lose_after: int = 3, max_probes: int = 3, track: bool = True,
                  track_params: dict | None = None, rescue: bool = False, manchester_rescue: bool = False,
                  dfm_rescue: bool = False, ims_rescue: bool = False, afsk_rescue: bool = False):
-        import torch
         from .detect import SondeDetector
         from .scan import SondeScanner
-        from .tuner import AFSK_TILE, IMET4, C50, IQ48_MAX_BW, SondeTuner, _lcm, _multiple_for, ratio
+        from .tuner import SondeTuner
         self.rate_in, self.device, self.input_kind = int(rate_in), int(device), int(input_kind)
         fs = self.rate_in
         self.scan_samples = max(1, int(round(float(scan_seconds) * fs)))
         self.policy = LivePolicy(fs, capacity, probes, probe_samples=max(1, int(round(float(probe_seconds) * fs))), lose_after=lose_after,
                                  max_probes=max_probes)
         pol = self.policy
-        tile = AFSK_TILE if any(t in (IMET4, C50) for t in pol.pools) else TILE
-        self.granule = _lcm(ratio(fs, 48000)[1], _multiple_for(48000, fs, tile))
-        self.max_in = int(max_in or self.granule)
-        if self.max_in % self.granule:
-            raise SondeError(f"max_in must be a multiple of the granule ({self.granule})")
-        n48 = self.max_in * 48000 // fs
+        p = _chain.plan(fs, pol.pools, max_in)
+        self.granule, self.max_in, n48 = p.granule, p.max_in, p.n48
         self.n_dec, self.n_probes = pol.n_slots, pol.n_probes
-        self._bw = {t: min(VFO_RATE[t], IQ48_MAX_BW) for t in pol.pools}
+        self._bw = {t: _chain.iq48_bandwidth(t) for t in pol.pools}
         self.tuner = SondeTuner.slots(fs, 48000, self.n_dec + self.n_probes, sorted(set(self._bw.values()) | {PROBE_BW}), self.max_in,
                                       input_kind=input_kind, device=device)
-        self.batch = SondeBatch(self.n_dec, n48, types=np.array(pol.slot_type, np.uint8), input_kind=INPUT_IQ, device=device,
-                                flags=_lib.rescue_flags(rescue, manchester_rescue, dfm_rescue, ims_rescue, afsk_rescue))
+        self.batch = _chain.batch(self.n_dec, n48, pol.slot_type, device, (rescue, manchester_rescue, dfm_rescue, ims_rescue, afsk_rescue))
         self.detector = SondeDetector(self.n_probes, n48, device=device)
         self.scanner = SondeScanner(fs, self.max_in, input_kind=input_kind, device=device)
         self.track = bool(track)
@@ -251,8 +246,7 @@ class LiveReceiver:
         if self.track:
             from .track import SondeTracker
             self.tracker = SondeTracker(self.n_dec, 48000, n48, device=device, look_samples=int(self.track_params.get("look_samples", 0)))
-        stride = int(_lib.load().sonde_row_stride(n48, INPUT_IQ))
-        self._rows = torch.empty((self.n_dec + self.n_probes, stride, 2), dtype=torch.float32, device=f"cuda:{device}")
+        self._rows = _chain.rows(self.n_dec + self.n_probes, n48, device)
         self._n48 = 0
         self._n_in = 0
         self._next_scan = self.scan_samples
@@ -301,22 +295,16 @@ class LiveReceiver:
 
     def _track_update(self):
         """the loop of SPEC 3.11 over the live slots whose carrier the last scan saw"""
-        from . import track as tk
         tr, tu, pol = self.tracker, self.tuner, self.policy
-        looks, _ = tr.results()
-        newest = {}
-        for lk in looks:
-            newest[int(lk["row"])] = lk
-        for slot, lk in newest.items():
-            if slot not in pol.vfos or pol.hold(slot) or pol.vfos[slot]["found_at"] >= self._n_in:
-                continue
-            new = tk.step(tu.offsets[slot], tu.bandwidths[slot], self.rate_in, tr.rate, tr.lag, lk["a_re"], lk["a_im"], self.track_params)
+
+        def skip(slot):          # unowned, held, or found in the submit the look was taken from
+            return slot not in pol.vfos or pol.hold(slot) or pol.vfos[slot]["found_at"] >= self._n_in
+        for slot, new, err, level in _chain.track_looks(tr, tu, self.rate_in, self.track_params, skip):
             if new != tu.offsets[slot]:
                 tu.retune(slot, new, continuous=True)
                 tr.restart(slot)
                 pol.moved(slot, new)
-            self.track_log[pol.vfos[slot]["id"]].append((self._n_in, new, tk.err_hz(tr.rate, tr.lag, lk["a_re"], lk["a_im"]),
-                                                        tk.level_db(lk["p"], tr.look_samples)))
+            self.track_log[pol.vfos[slot]["id"]].append((self._n_in, new, err, level))
 
     def _housekeeping(self):
         """between two submits: probes whose time is up, then the scan if one is due, then the tracking loop"""
@@ -342,15 +330,13 @@ class LiveReceiver:
         return self._rows[:, :self._n48]
 
     def submit(self, block, stream: int | None = None):
-        import torch
         n = int(block.shape[0])
-        if n == 0 or n % self.granule or n > self.max_in:
-            raise SondeError(f"the block must hold a positive multiple of the granule ({self.granule}) samples, at most max_in ({self.max_in})")
+        _chain.check_block(n, self.granule, self.max_in)
         if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = current_stream(self.device)
         if self._n_in:
             self._housekeeping()
-        n48 = n * 48000 // self.rate_in
+        n48 = _chain.out48(self.rate_in, n)
         self.scanner.submit(block, stream)
         self.tuner.process(block, out=self._rows, stream=stream)
         dec, prb = self._rows[:self.n_dec, :n48], self._rows[self.n_dec:, :n48]

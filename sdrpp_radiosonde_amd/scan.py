@@ -14,18 +14,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import CANDIDATE_DTYPE, INPUT_IQ, INPUT_IQ8, INPUT_IQ16, TILE, SondeScanParams
-from .batch import SondeError
+from ._chain import IQ48_MAX_BW as DETECT_BW          # survey(): the bandwidth of every detection VFO
+from ._handle import Handle, chk, current_stream, wideband_block
+from ._lib import CANDIDATE_DTYPE, INPUT_IQ, SondeError, SondeScanParams
 
 DETECT_RATE = 48000        # survey(): the rate of the detection rows
-DETECT_BW = 40000          # and the bandwidth of every detection VFO (tuner.IQ48_MAX_BW)
 MAX_CANDIDATES = 4096
-
-
-def _chk(rc):
-    if rc < 0:
-        raise SondeError(_lib.last_error())
-    return rc
 
 
 def _params(smooth_hz: int = 0, min_sep_hz: int = 0, centroid_hz: int = 0, threshold: float = 0.0) -> SondeScanParams:
@@ -35,13 +29,13 @@ def _params(smooth_hz: int = 0, min_sep_hz: int = 0, centroid_hz: int = 0, thres
 
 def auto_fft_size(rate_in: int) -> int:
     """the fft_size a scanner created with fft_size=0 takes (sonde_scan_auto_fft_size)"""
-    return _chk(_lib.load().sonde_scan_auto_fft_size(int(rate_in)))
+    return chk(_lib.load().sonde_scan_auto_fft_size(int(rate_in)))
 
 
 def window(n: int) -> np.ndarray:
     """the float32 periodic Hann window of n points (sonde_scan_window)"""
     w = np.zeros(int(n), np.float32)
-    _chk(_lib.load().sonde_scan_window(int(n), w.ctypes.data_as(C.c_void_p), w.size))
+    chk(_lib.load().sonde_scan_window(int(n), w.ctypes.data_as(C.c_void_p), w.size))
     return w
 
 
@@ -54,67 +48,47 @@ def search(P, rate_in: int, **params) -> np.ndarray:
     L = _lib.load()
     p = _params(**params)
     out = np.zeros(MAX_CANDIDATES, CANDIDATE_DTYPE)
-    n = _chk(L.sonde_scan_search(P.ctypes.data_as(C.c_void_p), P.size, int(rate_in), C.byref(p), out.ctypes.data_as(C.c_void_p), out.size))
+    n = chk(L.sonde_scan_search(P.ctypes.data_as(C.c_void_p), P.size, int(rate_in), C.byref(p), out.ctypes.data_as(C.c_void_p), out.size))
     return out[:min(n, out.size)].copy()
 
 
-class SondeScanner:
+class SondeScanner(Handle):
     """The averaged power spectrum of one wideband complex stream.  submit() takes a device block [n_in, 2] (float32; int16 for
     INPUT_IQ16, int8 for INPUT_IQ8) of any length 1 .. max_in: the unfinished segment is carried, and the spectrum does not depend
     on how the stream is cut into submits.  All submits of one scanner go on one stream."""
+    DESTROY = "sonde_scan_destroy"
 
     def __init__(self, rate_in: int, max_in: int, *, fft_size: int = 0, input_kind: int = INPUT_IQ, device: int = 0):
-        self.L = _lib.load()
-        h = C.c_void_p()
-        _chk(self.L.sonde_scan_create(int(rate_in), int(fft_size), int(max_in), int(input_kind), int(device), C.byref(h)))
-        self.h = h
+        self._create("sonde_scan_create", int(rate_in), int(fft_size), int(max_in), int(input_kind), int(device))
         self.rate_in, self.max_in, self.input_kind, self.device = int(rate_in), int(max_in), int(input_kind), int(device)
-        self.fft_size = _chk(self.L.sonde_scan_fft_size(self.h))
+        self.fft_size = chk(self.L.sonde_scan_fft_size(self.h))
 
     def submit(self, block, stream: int | None = None):
-        import torch
-        want = {INPUT_IQ16: torch.int16, INPUT_IQ8: torch.int8}.get(self.input_kind, torch.float32)
-        if block.dtype != want:
-            raise SondeError(f"the wideband block must be {want}, got {block.dtype}")
-        if not block.is_cuda or block.dim() != 2 or block.shape[1] != 2 or not block.is_contiguous():
-            raise SondeError("the wideband block must be a contiguous device tensor [n_in, 2]")
-        if block.device.index is not None and block.device.index != self.device:
-            raise SondeError(f"the block lives on device {block.device.index}, the scanner on device {self.device}")
+        n_in = wideband_block(block, self.input_kind, self.device, "scanner")
         if stream is None:
-            stream = torch.cuda.current_stream(block.device).cuda_stream
+            stream = current_stream(block.device)
         self._keep = block
-        _chk(self.L.sonde_scan_submit(self.h, C.c_void_p(block.data_ptr()), block.shape[0], C.c_void_p(stream)))
+        chk(self.L.sonde_scan_submit(self.h, C.c_void_p(block.data_ptr()), n_in, C.c_void_p(stream)))
 
     def reset(self):
-        _chk(self.L.sonde_scan_reset(self.h))
+        chk(self.L.sonde_scan_reset(self.h))
 
     @property
     def segments(self) -> int:
-        return _chk(self.L.sonde_scan_segments(self.h))
+        return chk(self.L.sonde_scan_segments(self.h))
 
     def spectrum(self):
         """(freqs_hz float64 [N], P float32 [N]) in ascending frequency; raises before the first whole segment"""
         n = self.fft_size
         P = np.zeros(n, np.float32)
-        _chk(self.L.sonde_scan_spectrum(self.h, P.ctypes.data_as(C.c_void_p), n))
+        chk(self.L.sonde_scan_spectrum(self.h, P.ctypes.data_as(C.c_void_p), n))
         return (np.arange(n, dtype=np.float64) - n // 2) * (self.rate_in / n), P
 
     def candidates(self, **params) -> np.ndarray:
         p = _params(**params)
         out = np.zeros(MAX_CANDIDATES, CANDIDATE_DTYPE)
-        n = _chk(self.L.sonde_scan_candidates(self.h, C.byref(p), out.ctypes.data_as(C.c_void_p), out.size))
+        n = chk(self.L.sonde_scan_candidates(self.h, C.byref(p), out.ctypes.data_as(C.c_void_p), out.size))
         return out[:min(n, out.size)].copy()
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.sonde_scan_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def survey(block, rate_in: int, *, input_kind: int = INPUT_IQ, device: int = 0, **params):
@@ -123,7 +97,8 @@ def survey(block, rate_in: int, *, input_kind: int = INPUT_IQ, device: int = 0, 
     decides the rows' types.  type -1: nothing decided (kept, so that the caller can look again later), or the VFO would not lie
     inside the band (not tuned).  Detection runs on the largest part of the block that leaves whole detector tiles at 48 kHz."""
     from .detect import SondeDetector
-    from .tuner import SondeTuner, _lcm, _multiple_for, ratio
+    from ._chain import plan
+    from .tuner import SondeTuner
     n = int(block.shape[0])
     sc = SondeScanner(rate_in, n, input_kind=input_kind, device=device)
     try:
@@ -134,7 +109,7 @@ def survey(block, rate_in: int, *, input_kind: int = INPUT_IQ, device: int = 0, 
     types = np.full(len(cand), -1, np.int64)
     fit = [i for i, c in enumerate(cand) if 2 * abs(int(c["offset_hz"])) + DETECT_BW <= int(rate_in)]
     if fit:
-        granule = _lcm(ratio(rate_in, DETECT_RATE)[1], _multiple_for(DETECT_RATE, int(rate_in), TILE))
+        granule = plan(rate_in, ()).granule          # of the iq48 chain with no AFSK sonde: whole detector tiles at DETECT_RATE
         n_use = n // granule * granule
         if not n_use:
             raise SondeError(f"survey() needs at least {granule} samples to detect the candidates' types")

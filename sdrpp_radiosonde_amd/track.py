@@ -14,19 +14,13 @@ import numpy as np
 
 from . import _lib
 from ._lib import INPUT_IQ, LOOK_DTYPE, TRACK_DEADBAND_HZ, TRACK_MAX_STEP_HZ
-from .batch import SondeError
-
-
-def _chk(rc):
-    if rc < 0:
-        raise SondeError(_lib.last_error())
-    return rc
+from ._handle import Handle, chk, complex_rows, current_stream
 
 
 def defaults(rate: int) -> tuple[int, int]:
     """(look_samples, lag) the meter picks for rows at `rate` (sonde_track_defaults)"""
     a, b = C.c_uint32(), C.c_uint32()
-    _chk(_lib.load().sonde_track_defaults(int(rate), C.byref(a), C.byref(b)))
+    chk(_lib.load().sonde_track_defaults(int(rate), C.byref(a), C.byref(b)))
     return a.value, b.value
 
 
@@ -57,51 +51,41 @@ def step(offset_hz: int, bandwidth_hz: int, rate_in: int, rate: int, lag: int, a
     look = _lib.SondeTrackLook()
     look.a_re, look.a_im = float(a_re), float(a_im)
     new = C.c_int32()
-    _chk(_lib.load().sonde_track_step(int(offset_hz), int(bandwidth_hz), int(rate_in), int(rate), int(lag), C.byref(look), _params(params),
-                                      C.byref(new)))
+    chk(_lib.load().sonde_track_step(int(offset_hz), int(bandwidth_hz), int(rate_in), int(rate), int(lag), C.byref(look), _params(params),
+                                     C.byref(new)))
     return new.value
 
 
-class SondeTracker:
+class SondeTracker(Handle):
     """The carrier meter over n_rows complex64 rows at `rate`.  submit() takes a float32 device view [n_rows, n, 2] (rows any stride
     apart, contiguous inside a row), n a positive multiple of 256 and <= max_samples; results() synchronises and returns the looks
     finished since the last call (LOOK_DTYPE: row, look, a_re, a_im, p) and how many older ones each row dropped."""
+    DESTROY = "sonde_track_destroy"
 
     def __init__(self, n_rows: int, rate: int, max_samples: int, *, look_samples: int = 0, lag: int = 0, input_kind: int = INPUT_IQ,
                  device: int = 0):
-        self.L = _lib.load()
-        h = C.c_void_p()
-        _chk(self.L.sonde_track_create(int(n_rows), int(rate), int(max_samples), int(look_samples), int(lag), int(input_kind), int(device),
-                                       C.byref(h)))
-        self.h = h
+        self._create("sonde_track_create", int(n_rows), int(rate), int(max_samples), int(look_samples), int(lag), int(input_kind), int(device))
+        h = self.h
         self.n_rows, self.rate, self.max_samples, self.device = int(n_rows), int(rate), int(max_samples), int(device)
         self.look_samples = int(self.L.sonde_track_look_samples(h))
         self.lag = int(self.L.sonde_track_lag(h))
         self.ring = int(self.L.sonde_track_ring(h))
 
     def submit(self, rows, stream: int | None = None):
-        import torch
-        if (rows.dtype != torch.float32 or not rows.is_cuda or rows.dim() != 3 or rows.shape[2] != 2 or rows.stride(2) != 1 or rows.stride(1) != 2
-                or (rows.shape[0] > 1 and rows.stride(0) % 2)):
-            raise SondeError("the rows must be a float32 device view [n_rows, n, 2], contiguous inside a row (complex64: REAL rows carry no carrier)")
-        if rows.shape[0] != self.n_rows:
-            raise SondeError(f"the meter was created for {self.n_rows} rows, got {rows.shape[0]}")
-        if rows.device.index is not None and rows.device.index != self.device:
-            raise SondeError(f"the rows live on device {rows.device.index}, the meter on device {self.device}")
+        n, stride = complex_rows(rows, self.n_rows, self.device, "meter", "n_rows", self.n_rows, "carrier")
         if stream is None:
-            stream = torch.cuda.current_stream(rows.device).cuda_stream
+            stream = current_stream(rows.device)
         self._keep = rows
-        stride = rows.stride(0) // 2 if rows.shape[0] > 1 else max(rows.stride(0) // 2, rows.shape[1])
-        _chk(self.L.sonde_track_submit(self.h, C.c_void_p(rows.data_ptr()), rows.shape[1], stride, C.c_void_p(stream)))
+        chk(self.L.sonde_track_submit(self.h, C.c_void_p(rows.data_ptr()), n, stride, C.c_void_p(stream)))
 
     def restart(self, row: int):
         """drop the row's unfinished look and lag history: its next look starts at the next submit's first sample"""
-        _chk(self.L.sonde_track_restart(self.h, int(row)))
+        chk(self.L.sonde_track_restart(self.h, int(row)))
 
     def results(self):
         out = np.zeros(self.n_rows * self.ring, dtype=LOOK_DTYPE)
         dropped = np.zeros(self.n_rows, dtype=np.uint64)
-        n = _chk(self.L.sonde_track_results(self.h, out.ctypes.data_as(C.c_void_p), len(out), dropped.ctypes.data_as(C.c_void_p)))
+        n = chk(self.L.sonde_track_results(self.h, out.ctypes.data_as(C.c_void_p), len(out), dropped.ctypes.data_as(C.c_void_p)))
         return out[:n], dropped
 
     def err_hz(self, looks) -> np.ndarray:
@@ -112,14 +96,3 @@ class SondeTracker:
 
     def quality(self, looks) -> np.ndarray:
         return np.array([quality(k["a_re"], k["a_im"], k["p"]) for k in looks])
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.sonde_track_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

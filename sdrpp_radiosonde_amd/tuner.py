@@ -3,50 +3,37 @@ libsonde_mi355.so.
 
     SondeTuner          a bank of VFOs at any integer-Hz offset over one wideband stream -> complex rows at rate_out
     WidebandReceiver    wideband stream -> tuner -> decoders, for a list of (offset, sonde type): the chain of the reference
-                        (VFO -> FM -> resampler -> decoder, /root/reference/src/main.cpp:55-68) or the tuner straight to 48 kHz IQ
+                        (VFO -> FM -> resampler -> decoder, /root/reference/src/main.cpp:55-68) or the tuner straight to 48 kHz IQ;
+                        the block arithmetic, the batch and its rows and the tracking loop are _chain's, shared with the
+                        diversity and the live receiver
 
 Use the tuner when the frequencies are known (any sonde type, M10 / M20 included; the cost grows with the number of VFOs), the
 channelizer (batch.SondeChannelizer) to decode every 19.53 kHz bin of the band at once (fixed cost, no M10 / M20)."""
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import numpy as np
 
-from . import _lib
-from ._lib import INPUT_IQ, INPUT_IQ8, INPUT_IQ16, INPUT_REAL, TILE
-from .batch import VFO_RATE, SondeBatch, SondeError, SondeVfo
-
-IMET4, C50 = _lib.IMET4, _lib.C50
-AFSK_TILE = 16384          # a batch with an AFSK sonde (iMet-4, SRS-C50) takes rows in multiples of this
-IQ48_MAX_BW = 40000        # the iq48 chain's VFO bandwidth cap (M10 / M20: 50 kHz does not fit a 48 kHz row)
-
-
-def _chk(rc):
-    if rc < 0:
-        raise SondeError(_lib.last_error())
-    return rc
-
-
-def ratio(rate_in: int, rate_out: int) -> tuple[int, int]:
-    """(up, down) = rate_out / rate_in in lowest terms (sonde_tuner_ratio; raises for rates the tuner refuses)"""
-    up, down = C.c_int(), C.c_int()
-    _chk(_lib.load().sonde_tuner_ratio(int(rate_in), int(rate_out), C.byref(up), C.byref(down)))
-    return up.value, down.value
+from . import _chain, _lib
+from ._chain import AFSK_TILE, IQ48_MAX_BW, ratio  # noqa: F401
+from ._chain import lcm as _lcm, multiple_for as _multiple_for  # noqa: F401  (the names they had here)
+from ._handle import Handle, chk, current_stream, wideband_block
+from ._lib import C50, IMET4, INPUT_IQ, INPUT_REAL, SondeError  # noqa: F401
+from .batch import SondeVfo
 
 
 def tuner_taps(rate_in: int, rate_out: int, bandwidth_hz: int = 0) -> np.ndarray:
     """the float32 taps g[p][t] of one bandwidth (SPEC 3.9): [up, T]"""
     L = _lib.load()
-    n = _chk(L.sonde_tuner_taps(int(rate_in), int(rate_out), int(bandwidth_hz), None, 0))
+    n = chk(L.sonde_tuner_taps(int(rate_in), int(rate_out), int(bandwidth_hz), None, 0))
     g = np.zeros(n, np.float32)
-    _chk(L.sonde_tuner_taps(int(rate_in), int(rate_out), int(bandwidth_hz), g.ctypes.data_as(C.c_void_p), n))
+    chk(L.sonde_tuner_taps(int(rate_in), int(rate_out), int(bandwidth_hz), g.ctypes.data_as(C.c_void_p), n))
     up, _ = ratio(rate_in, rate_out)
     return g.reshape(up, n // up)
 
 
-class SondeTuner:
+class SondeTuner(Handle):
     """A bank of VFOs over one wideband complex stream.  vfos: [(offset_hz, bandwidth_hz), ...] or [offset_hz, ...]
     (bandwidth 0 = rate_out).  process() takes a device block [n_in, 2] (float32; int16 for INPUT_IQ16, int8 for INPUT_IQ8),
     n_in a multiple of `down`, and returns [V, n_out, 2] float32 rows or writes them into `out` (a [V, >= n_out, 2] float32 view
@@ -54,17 +41,15 @@ class SondeTuner:
 
     SondeTuner.slots(...) makes a tuner of idle slots instead (SPEC 3.12): slot_set() / slot_clear() tune and idle them between
     two process() calls; an idle slot costs no mixing and its row is zeros.  `offsets[k]` / `bandwidths[k]` are None while idle."""
+    DESTROY = "sonde_tuner_destroy"
 
     def __init__(self, rate_in: int, rate_out: int, vfos, max_in: int, *, input_kind: int = INPUT_IQ, device: int = 0):
-        self.L = _lib.load()
         spec = [(v, 0) if np.isscalar(v) else (v[0], v[1]) for v in vfos]
         self.n_vfos = len(spec)
         arr = (_lib.SondeTunerVfo * max(1, self.n_vfos))()
         for i, (f, b) in enumerate(spec):
             arr[i].offset_hz, arr[i].bandwidth_hz = int(f), int(b)
-        h = C.c_void_p()
-        _chk(self.L.sonde_tuner_create(int(rate_in), int(rate_out), self.n_vfos, arr, int(max_in), int(input_kind), int(device), C.byref(h)))
-        self.h = h
+        self._create("sonde_tuner_create", int(rate_in), int(rate_out), self.n_vfos, arr, int(max_in), int(input_kind), int(device))
         self.rate_in, self.rate_out, self.max_in = int(rate_in), int(rate_out), int(max_in)
         self.input_kind, self.device = int(input_kind), int(device)
         self.offsets = [int(f) for f, _ in spec]
@@ -75,13 +60,10 @@ class SondeTuner:
     def slots(cls, rate_in: int, rate_out: int, n_slots: int, bandwidths, max_in: int, *, input_kind: int = INPUT_IQ, device: int = 0):
         """n_slots idle slots with one tap set per listed bandwidth (sonde_tuner_create_slots)"""
         self = cls.__new__(cls)
-        self.L = _lib.load()
         self.n_vfos = int(n_slots)
         bws = np.ascontiguousarray([int(b) for b in bandwidths], dtype=np.uint32)
-        h = C.c_void_p()
-        _chk(self.L.sonde_tuner_create_slots(int(rate_in), int(rate_out), self.n_vfos, bws.ctypes.data_as(C.c_void_p), len(bws), int(max_in),
-                                             int(input_kind), int(device), C.byref(h)))
-        self.h = h
+        self._create("sonde_tuner_create_slots", int(rate_in), int(rate_out), self.n_vfos, bws.ctypes.data_as(C.c_void_p), len(bws), int(max_in),
+                     int(input_kind), int(device))
         self.rate_in, self.rate_out, self.max_in = int(rate_in), int(rate_out), int(max_in)
         self.input_kind, self.device = int(input_kind), int(device)
         self.offsets = [None] * self.n_vfos
@@ -91,16 +73,16 @@ class SondeTuner:
 
     def slot_set(self, k: int, hz: int, bandwidth_hz: int = 0):
         """slot k to offset hz at a listed bandwidth from the next process() on, as if tuned there since create (theta = 0)"""
-        _chk(self.L.sonde_tuner_slot_set(self.h, int(k), int(hz), int(bandwidth_hz)))
+        chk(self.L.sonde_tuner_slot_set(self.h, int(k), int(hz), int(bandwidth_hz)))
         self.offsets[k], self.bandwidths[k] = int(hz), int(bandwidth_hz) or self.rate_out
 
     def slot_clear(self, k: int):
         """slot k idle from the next process() on: its row is zeros"""
-        _chk(self.L.sonde_tuner_slot_clear(self.h, int(k)))
+        chk(self.L.sonde_tuner_slot_clear(self.h, int(k)))
         self.offsets[k] = self.bandwidths[k] = None
 
     def slot_active(self, k: int) -> bool:
-        return bool(_chk(self.L.sonde_tuner_slot_active(self.h, int(k))))
+        return bool(chk(self.L.sonde_tuner_slot_active(self.h, int(k))))
 
     def out_samples(self, n_in: int) -> int:
         return int(self.L.sonde_tuner_out_samples(self.h, int(n_in)))
@@ -108,24 +90,17 @@ class SondeTuner:
     def retune(self, k: int, hz: int, continuous: bool = False):
         """VFO k to offset hz from the next process() on.  continuous=False restarts the mixer's phase "as if tuned there since
         create" (a phase jump in the row at the boundary); continuous=True keeps the mixer's phase at the boundary (SPEC 3.9)"""
-        _chk((self.L.sonde_tuner_retune_continuous if continuous else self.L.sonde_tuner_retune)(self.h, int(k), int(hz)))
+        chk((self.L.sonde_tuner_retune_continuous if continuous else self.L.sonde_tuner_retune)(self.h, int(k), int(hz)))
         self.offsets[k] = int(hz)
 
     def test_set_base(self, n_base: int):
         """Test introspection, not for hosts (sonde_tuner_test_set_base): the absolute input index of the first sample, for a tuner
         that has not processed or been retuned yet; a multiple of `down`, 0 .. 2^62."""
-        _chk(self.L.sonde_tuner_test_set_base(self.h, int(n_base)))
+        chk(self.L.sonde_tuner_test_set_base(self.h, int(n_base)))
 
     def process(self, block, out=None, stream: int | None = None):
         import torch
-        want = {INPUT_IQ16: torch.int16, INPUT_IQ8: torch.int8}.get(self.input_kind, torch.float32)
-        if block.dtype != want:
-            raise SondeError(f"the wideband block must be {want}, got {block.dtype}")
-        if not block.is_cuda or block.dim() != 2 or block.shape[1] != 2 or not block.is_contiguous():
-            raise SondeError("the wideband block must be a contiguous device tensor [n_in, 2]")
-        if block.device.index is not None and block.device.index != self.device:
-            raise SondeError(f"the block lives on device {block.device.index}, the tuner on device {self.device}")
-        n_in = block.shape[0]
+        n_in = wideband_block(block, self.input_kind, self.device, "tuner")
         n_out = self.out_samples(n_in)
         if out is None:
             out = torch.empty((self.n_vfos, n_out, 2), dtype=torch.float32, device=block.device)
@@ -133,36 +108,11 @@ class SondeTuner:
               or out.stride(1) != 2 or out.stride(2) != 1 or out.device != block.device):
             raise SondeError("out must be a float32 device view [n_vfos, >= n_out, 2], contiguous inside a row")
         if stream is None:
-            stream = torch.cuda.current_stream(block.device).cuda_stream
+            stream = current_stream(block.device)
         self._keep = block
-        _chk(self.L.sonde_tuner_process(self.h, C.c_void_p(block.data_ptr()), n_in, C.c_void_p(out.data_ptr()), out.stride(0) // 2,
-                                        C.c_void_p(stream)))
+        chk(self.L.sonde_tuner_process(self.h, C.c_void_p(block.data_ptr()), n_in, C.c_void_p(out.data_ptr()), out.stride(0) // 2,
+                                       C.c_void_p(stream)))
         return out[:, :n_out]
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.sonde_tuner_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _multiple_for(a: int, b: int, c: int) -> int:
-    """the smallest n > 0 with n * a / b a multiple of c (a / b in lowest terms or not)"""
-    g = math.gcd(a, b)
-    a, b = a // g, b // g
-    return c * b // math.gcd(a, c * b)
-
-
-def _lcm(*v: int) -> int:
-    out = 1
-    for x in v:
-        out = out * x // math.gcd(out, x)
-    return out
 
 
 class WidebandReceiver:
@@ -186,7 +136,6 @@ class WidebandReceiver:
                  track: bool = False, track_params: dict | None = None, rescue: bool = False,
                  manchester_rescue: bool = False, dfm_rescue: bool = False, ims_rescue: bool = False,
                  afsk_rescue: bool = False):
-        import torch
         if chain not in ("iq48", "reference"):
             raise SondeError('chain must be "iq48" or "reference"')
         self.rate_in, self.chain, self.device, self.input_kind = int(rate_in), chain, int(device), int(input_kind)
@@ -194,29 +143,11 @@ class WidebandReceiver:
         if not self.sondes:
             raise SondeError("no sondes")
         types = [t for _, t in self.sondes]
-        tile = AFSK_TILE if any(t in (IMET4, C50) for t in types) else TILE
         fs = self.rate_in
-        if chain == "iq48":
-            bws = [min(VFO_RATE[t], IQ48_MAX_BW) for t in types]
-            down = ratio(fs, 48000)[1]
-            self.granule = _lcm(down, _multiple_for(48000, fs, tile))
-            groups = {48000: list(range(len(types)))}
-        else:
-            groups = {}
-            for i, t in enumerate(types):
-                groups.setdefault(VFO_RATE[t], []).append(i)
-            parts = [_multiple_for(48000, fs, tile)]
-            for b in groups:
-                parts += [ratio(fs, b)[1], _multiple_for(b, fs, _vfo_down(b))]
-                if track:
-                    parts.append(_multiple_for(b, fs, 256))
-            self.granule = _lcm(*parts)
-        self.max_in = int(max_in or self.granule)
-        if self.max_in % self.granule:
-            raise SondeError(f"max_in must be a multiple of the granule ({self.granule})")
-        n48 = self.max_in * 48000 // fs
+        p = _chain.plan(fs, types, max_in, chain, track)
+        self.granule, self.max_in = p.granule, p.max_in
         # batch channel c = order[c]: the sondes grouped by tuner, so that every group's rows are evenly spaced
-        self.order = np.array([i for g in groups.values() for i in g], dtype=np.int64)
+        self.order = np.array([i for g in p.groups.values() for i in g], dtype=np.int64)
         self.stages = []          # (tuner, SondeVfo or None, first batch channel, sonde indices)
         self.track = bool(track)
         self.track_params = dict(track_params or {})
@@ -224,26 +155,20 @@ class WidebandReceiver:
         self.trackers = {}        # id(tuner) -> SondeTracker (track=True only)
         self._n_in = 0            # input samples submitted so far
         c0 = 0
-        for rate, idx in groups.items():
-            if chain == "iq48":
-                tu = SondeTuner(fs, 48000, [(self.sondes[i][0], bws[i]) for i in idx], self.max_in, input_kind=input_kind, device=device)
-                self.stages.append((tu, None, c0, idx))
-            else:
-                tu = SondeTuner(fs, rate, [(self.sondes[i][0], rate) for i in idx], self.max_in, input_kind=input_kind, device=device)
-                vo = SondeVfo(len(idx), rate, tu.out_samples(self.max_in), device=device)
-                self.stages.append((tu, vo, c0, idx))
+        for rate, idx in p.groups.items():
+            bws = [_chain.iq48_bandwidth(types[i]) if chain == "iq48" else rate for i in idx]
+            tu = SondeTuner(fs, rate, [(self.sondes[i][0], b) for i, b in zip(idx, bws)], self.max_in, input_kind=input_kind, device=device)
+            vo = SondeVfo(len(idx), rate, tu.out_samples(self.max_in), device=device) if chain == "reference" else None
+            self.stages.append((tu, vo, c0, idx))
             if self.track:
                 from .track import SondeTracker
                 self.trackers[id(tu)] = SondeTracker(len(idx), tu.rate_out, tu.out_samples(self.max_in), device=device,
                                                      look_samples=int(self.track_params.get("look_samples", 0)))
             c0 += len(idx)
-        bt = np.array([types[i] for i in self.order], dtype=np.uint8)
         kind = INPUT_IQ if chain == "iq48" else INPUT_REAL
-        flags = _lib.rescue_flags(rescue, manchester_rescue, dfm_rescue, ims_rescue, afsk_rescue)
-        self.batch = SondeBatch(len(types), n48, types=bt, input_kind=kind, device=device, flags=flags)
-        stride = int(_lib.load().sonde_row_stride(n48, kind))
-        shape = (len(types), stride, 2) if kind == INPUT_IQ else (len(types), stride)
-        self._rows = torch.empty(shape, dtype=torch.float32, device=f"cuda:{device}")
+        self.batch = _chain.batch(len(types), p.n48, [types[i] for i in self.order], device,
+                                  (rescue, manchester_rescue, dfm_rescue, ims_rescue, afsk_rescue), kind)
+        self._rows = _chain.rows(len(types), p.n48, device, kind)
         self._tmp = {}
         self._n48 = 0
         self._inv = np.empty(len(types), dtype=np.int64)
@@ -265,20 +190,11 @@ class WidebandReceiver:
 
     def _track_update(self):
         """the loop (SPEC 3.11): the newest look of every VFO -> step -> continuous retune + restart for those that moved"""
-        from . import track as tk
         for tu, _, _, idx in self.stages:
-            tr = self.trackers[id(tu)]
-            looks, _ = tr.results()
-            newest = {}
-            for lk in looks:
-                newest[int(lk["row"])] = lk           # rows come oldest look first
-            for k, lk in newest.items():
-                i = idx[k]
-                new = tk.step(tu.offsets[k], tu.bandwidths[k], self.rate_in, tr.rate, tr.lag, lk["a_re"], lk["a_im"], self.track_params)
+            for k, new, err, level in _chain.track_looks(self.trackers[id(tu)], tu, self.rate_in, self.track_params):
                 if new != tu.offsets[k]:
-                    self.retune(i, new, continuous=True)
-                self.track_log[i].append((self._n_in, new, tk.err_hz(tr.rate, tr.lag, lk["a_re"], lk["a_im"]),
-                                          tk.level_db(lk["p"], tr.look_samples)))
+                    self.retune(idx[k], new, continuous=True)
+                self.track_log[idx[k]].append((self._n_in, new, err, level))
 
     def rows(self):
         """the 48 kHz rows of the last submit, in batch-channel order (IQ [C, n, 2] for iq48, FM [C, n] for reference)"""
@@ -287,11 +203,10 @@ class WidebandReceiver:
     def submit(self, block, stream: int | None = None):
         import torch
         n = int(block.shape[0])
-        if n == 0 or n % self.granule or n > self.max_in:
-            raise SondeError(f"the block must hold a positive multiple of the granule ({self.granule}) samples, at most max_in ({self.max_in})")
+        _chain.check_block(n, self.granule, self.max_in)
         if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        n48 = n * 48000 // self.rate_in
+            stream = current_stream(self.device)
+        n48 = _chain.out48(self.rate_in, n)
         if self.track and self._n_in:
             self._track_update()
         for tu, vo, c0, idx in self.stages:
@@ -308,7 +223,7 @@ class WidebandReceiver:
                 tu.process(block, out=buf, stream=stream)
                 if self.track:
                     self.trackers[id(tu)].submit(buf[:, :m], stream)
-                _vfo_process(vo, buf[:, :m], self._rows[c0:c0 + nv], stream)
+                vo.process(buf[:, :m], out=self._rows[c0:c0 + nv], stream=stream)
         self._n48 = n48
         self._n_in += n
         self.batch.submit(self._rows[:, :n48], stream)
@@ -331,15 +246,3 @@ class WidebandReceiver:
                 vo.close()
         self.stages = []
         self.batch.close()
-
-
-def _vfo_down(rate: int) -> int:
-    down = C.c_int()
-    _chk(_lib.load().sonde_vfo_ratio(int(rate), None, C.byref(down)))
-    return down.value
-
-
-def _vfo_process(vo: SondeVfo, iq, out, stream):
-    """SondeVfo.process into a strided row view (its rows: the batch buffer's)"""
-    _chk(vo.L.sonde_vfo_process(vo.h, C.c_void_p(iq.data_ptr()), iq.shape[1], iq.stride(0) // 2, C.c_void_p(out.data_ptr()), out.stride(0),
-                                C.c_void_p(stream)))

@@ -2,7 +2,8 @@
 (a) a device that does not exist is refused with the entry point's name in the text and the handle left null;
 (b) an object created on memory that an object with dirty carried state has just given back starts from the same state as the
     first one: the same submits give the same outputs, bit for bit;
-(c) the channelizer's failures name their entry point in sonde_last_error()."""
+(c) the channelizer's failures name their entry point in sonde_last_error();
+(d) the eight Python wrappers close alike: twice is harmless, the handle is gone, a closed object refuses its calls."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,7 +13,8 @@ import pytest
 import torch
 
 from sdrpp_radiosonde_amd import _lib
-from sdrpp_radiosonde_amd.batch import SondeChannelizer, SondeVfo
+from sdrpp_radiosonde_amd.batch import SondeBatch, SondeChannelizer, SondeError, SondeVfo
+from sdrpp_radiosonde_amd.combine import SondeCombiner
 from sdrpp_radiosonde_amd.detect import SondeDetector
 from sdrpp_radiosonde_amd.scan import SondeScanner
 from sdrpp_radiosonde_amd.track import SondeTracker
@@ -135,4 +137,47 @@ def test_channelizer_failures_name_their_entry_point():
     assert L.sonde_vfo_ratio(1, None, None) != 0
     assert L.sonde_chan_submit(c.h, C.c_void_p(x.data_ptr()), c.samples_per_submit - 500, None) != 0
     assert "sonde_chan_submit" in _lib.last_error() and "n_samples" in _lib.last_error()
+    c.close()
+
+
+# ---------------------------------------------------------------- (d)
+# the smallest objects their create entries accept (CREATES above) and one call each that needs the handle; what a closed object
+# answers was read off the wrappers as they were before they shared a base: the library refuses a null handle, SondeError every time
+WRAPPERS = {
+    "batch": (lambda: SondeBatch(2, 2048), lambda o: o.sync()),
+    "channelizer": (lambda: SondeChannelizer(blocks_per_submit=1), lambda o: o.read()),
+    "vfo": (lambda: SondeVfo(2, 20_000, 1000), lambda o: o.process(torch.zeros((2, 1000, 2), device=DEV))),
+    "detector": (lambda: SondeDetector(2, 2048), lambda o: o.reset()),
+    "tuner": (lambda: SondeTuner(1_000_000, 48_000, [(0, 10_000)], 8000), lambda o: o.retune(0, 1000)),
+    "scanner": (lambda: SondeScanner(1_000_000, 1536, fft_size=1024), lambda o: o.reset()),
+    "tracker": (lambda: SondeTracker(2, 48_000, 2048), lambda o: o.restart(0)),
+    "combiner": (lambda: SondeCombiner(1, 2, 48_000, 256, 256), lambda o: o.restart(0)),
+}
+
+
+@pytest.mark.parametrize("name", list(WRAPPERS))
+def test_close_twice_then_drop(name):
+    make, call = WRAPPERS[name]
+    o = make()
+    assert o.h
+    call(o)                                     # the call works on a live object
+    o.close()
+    assert o.h is None
+    o.close()
+    assert o.h is None
+    with pytest.raises(SondeError, match="null argument"):
+        call(o)
+    o.__del__()                                 # what dropping it runs: nothing left to do, nothing raised
+    del o
+
+
+def test_the_channelizers_borrowed_batch_destroys_nothing():
+    c = SondeChannelizer(blocks_per_submit=1)
+    x = torch.zeros((c.samples_per_submit, 2), device=DEV)
+    c.batch.close()
+    assert c.batch.h and c.h
+    c.submit(x)
+    assert len(c.frames()) == 0
+    c.close()
+    assert c.h is None and c.batch.h is None
     c.close()
