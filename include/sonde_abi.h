@@ -111,11 +111,14 @@ enum { SONDE_INPUT_IQ = 0,      /* complex64 interleaved I,Q at 48 kS/s (vfo->ou
                                                     * iMet / C50 packet the bits SONDE_FLAG_AFSK_RESCUE flipped: 1, or 2 (an adjacent pair) */
 #define SONDE_FRAME_WORDS(f) (((f) >> 8) & 0xFu)   /* the same bits for DFM: codewords SONDE_FLAG_DFM_RESCUE decoded with erasures (1..8) */
 #define SONDE_FRAME_BLOCKS(f) (((f) >> 8) & 0xFu)  /* the same bits for iMS-100: BCH blocks SONDE_FLAG_IMS_RESCUE decoded (1..12) */
-#define SONDE_FRAME_COMBINED 4u  /* SondeFrame.flags: an RS41 frame sonde_batch_set_diversity put together from the copies of several receivers
-                                  * (always with SONDE_FRAME_RESCUED; then SONDE_FRAME_COPIES says from how many) */
-#define SONDE_FRAME_COPIES(f) (((f) >> 8) & 0xFu)  /* the same bits for a combined RS41 frame: the copies it was made from (2..4) */
-#define SONDE_FRAME_DUPLICATE 8u /* SondeFrame.flags: a good RS41 frame of which another receiver of its diversity group has delivered a copy
-                                  * (sonde_batch_set_diversity_auto with SONDE_DIVERSITY_MARK_DUPLICATES); sonde_batch_poll leaves its fragments out */
+#define SONDE_FRAME_COMBINED 4u  /* SondeFrame.flags: an RS41, M10 / M20 or MRZ-N1 frame sonde_batch_set_diversity put together from the copies of
+                                  * several receivers (always with SONDE_FRAME_RESCUED; then SONDE_FRAME_COPIES says from how many) */
+#define SONDE_FRAME_COPIES(f) (((f) >> 8) & 0xFu)  /* the same bits for a combined frame of any of these types: the copies it was made from (2..4) */
+#define SONDE_FRAME_UNKNOWNS(f) (((f) >> 12) & 0xFu) /* SondeFrame.flags bits 12..15 of a combined M10 / M20 / MRZ-N1 frame: the bits on which its copies
+                                  * differed, min(|V|, 15) (DESIGN SPEC 3.3l) -- the host's handle on wrong frames: a wrong subset fits with probability
+                                  * about 2^(|V| - 16).  Zero in every other record, combined RS41 frames included */
+#define SONDE_FRAME_DUPLICATE 8u /* SondeFrame.flags: a good RS41, M10 / M20 or MRZ-N1 frame of which another receiver of its diversity group has delivered
+                                  * a copy (sonde_batch_set_diversity_auto with SONDE_DIVERSITY_MARK_DUPLICATES); sonde_batch_poll leaves its fragments out */
 #define SONDE_TILE       2048   /* samples; submit lengths are multiples of this */
 #define SONDE_FRAME_MAX  528
 
@@ -124,7 +127,7 @@ typedef struct {
 	uint32_t type;
 	int32_t  len;            /* bytes valid in data[] */
 	int32_t  nerr[2];        /* RS41: bytes corrected per RS codeword, -1 = uncorrectable */
-	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED; SONDE_FRAME_COMBINED; SONDE_FRAME_DUPLICATE; SONDE_FRAME_FLIPS / _WORDS / _BLOCKS / _COPIES */
+	uint32_t flags;          /* bit0: signal polarity was inverted; SONDE_FRAME_RESCUED; SONDE_FRAME_COMBINED; SONDE_FRAME_DUPLICATE; SONDE_FRAME_FLIPS / _WORDS / _BLOCKS / _COPIES; SONDE_FRAME_UNKNOWNS */
 	uint64_t bitpos;         /* absolute index (since create) of the first sync bit */
 	uint8_t  data[SONDE_FRAME_MAX];   /* de-whitened, error-corrected frame */
 } SondeFrame;
@@ -283,14 +286,14 @@ int  sonde_batch_submit_host(SondeBatch *b, const void *samples, size_t n_sample
  * nothing (stream order already says so); it is what a SONDE_FLAG_LATE_JOIN / SONDE_FLAG_PIPELINE host calls before it refills a
  * single buffer, and what any host calls to release the buffer on ANOTHER stream (a copy engine's).  0 = ok. */
 int  sonde_batch_wait_input(SondeBatch *b, void *stream);
-/* SEVERAL RECEIVERS OF ONE SONDE (DESIGN SPEC 3.3j).  A host that hears a sonde more than once -- two antennas or polarisations at one
+/* SEVERAL RECEIVERS OF ONE SONDE (DESIGN SPEC 3.3j: RS41; 3.3l: M10 / M20 and MRZ-N1).  A host that hears a sonde more than once -- two antennas or polarisations at one
  * site, two sites of a network -- gives each receiver a channel and names the channels of one sonde a GROUP: group[ch] = -1 (none) or a
- * group id 0..G-1 (no gaps), 2..4 SONDE_RS41 channels per group.  offset_bits[ch] is where channel ch's bit count (SondeFrame.bitpos)
+ * group id 0..G-1 (no gaps), 2..4 channels of ONE type per group: SONDE_RS41, SONDE_M10 (M10 and M20) or SONDE_MRZN1.  offset_bits[ch] is where channel ch's bit count (SondeFrame.bitpos)
  * stands when the group's common clock reads 0 -- the host knows when it started each stream; NULL = zeros.  After every other pass
- * of a submit one more kernel visits the group's frame records in the order of the common clock.  A frame with a failed codeword
- * (nerr = -1) looks in every other member for the nearest record of the same length within window_bits (0 = 960, at most 1200) of
+ * of a submit one more kernel visits the group's frame records in the order of the common clock.  A failed frame (RS41: a codeword at
+ * nerr = -1; the others: nerr[0] = -1) looks in every other member for the nearest record of the same length within window_bits (0 = 960, at most 1200) of
  * its own time, among that member's records of this submit and the newest one it carried over from earlier submits.  If one of these
- * partners is good, the record stays (removing duplicates is the host's business).  Otherwise the copies are combined: a codeword a
+ * partners is good, the record stays (removing duplicates is the host's business).  Otherwise the copies are combined.  RS41: a codeword a
  * partner decoded is taken whole; a block whose CRC passes in any copy is trusted; elsewhere a byte more than half of the copies agree
  * on is taken; what is left is erased, and RS(255,231) fills up to 24 erasures per codeword.  The result is taken only if both
  * codewords and every block CRC of its own chain pass.  A combined record carries the result, nerr[c] = the bytes of codeword c that
@@ -300,11 +303,20 @@ int  sonde_batch_wait_input(SondeBatch *b, void *stream);
  * distinct good frames a group delivers does not.  Needs no learned layout (it works before a channel's first good frame) and reaches
  * the 93-byte GPS-raw block and the XDATA block.  Limits: a block damaged in BOTH copies is voted byte by byte and limited by 24
  * erasures per codeword; wrong bytes that are identical in all copies count as unknown errors; drift beyond window_bits (members
- * idling on noise, cycle slips) loses partners silently.  RS41 only.
+ * idling on noise, cycle slips) loses partners silently.
+ * M10 / M20 / MRZ-N1 (a 16-bit check, no FEC): the working frame is copy 0 (two copies) or the bitwise majority (three, four; a tie
+ * keeps copy 0's bit), the unknowns V are the bits on which the copies differ.  If the working frame's check passes it is the result;
+ * else, with 1..8 unknowns (and for M10 / M20 none of them in the length byte), the check is a linear system over GF(2) and the frame
+ * is taken iff exactly one subset of V explains the syndrome.  A combined record carries the result, nerr[0] = 0 (nerr[1] stays),
+ * SONDE_FRAME_RESCUED | SONDE_FRAME_COMBINED, SONDE_FRAME_COPIES and SONDE_FRAME_UNKNOWNS = min(|V|, 15).  Limits: a bit wrong in EVERY
+ * copy is no unknown, and then a wrong subset fits with probability about 2^(|V| - 16) -- a host that wants fewer wrong frames drops the
+ * combined ones above its own SONDE_FRAME_UNKNOWNS; more than 8 unknowns with two copies stay as recorded; frames SONDE_FLAG_MANCHESTER_RESCUE
+ * corrected count as good copies.  Not DFM, iMS-100, iMet or C50.
  * Called once, before the first submit; if it is never called nothing is allocated or launched.  Refused: a second call, a call after a
- * submit, a group of fewer than 2 or more than 4 members, a member that is not SONDE_RS41, group ids with gaps, window_bits > 1200, the
+ * submit, a group of fewer than 2 or more than 4 members, a member of any other type, members of different types in one group, group ids with gaps, window_bits > 1200, the
  * batch behind a channelizer, and a batch created with SONDE_FLAG_LATE_JOIN or SONDE_FLAG_PIPELINE (those never join their launch
- * units into one stream, and the pass needs all members' records).  One small launch more per submit; no host synchronisation.
+ * units into one stream, and the pass needs all members' records).  One small launch more per submit for the RS41 groups and one
+ * for the others, each only if the batch has such a group; no host synchronisation.
  * On a batch with groups sonde_batch_restart_channels takes all members of a group or none of them (their bit counts must stay
  * together); a restarted group loses its carried records and its counters. */
 int  sonde_batch_set_diversity(SondeBatch *b, const int32_t *group /* n_channels entries */, const int64_t *offset_bits /* n_channels entries or NULL */,
@@ -312,7 +324,9 @@ int  sonde_batch_set_diversity(SondeBatch *b, const int32_t *group /* n_channels
 /* THE SAME WITHOUT KNOWING THE OFFSETS (DESIGN SPEC 3.3k).  mode = 0 is sonde_batch_set_diversity itself; else an OR of
  *   SONDE_DIVERSITY_LEARN            the GPU finds offset_bits itself and keeps following it.  Two good records (len 320 or 518, both nerr
  *                                    >= 0, rescued ones included) of two members whose bytes 8 .. len are identical are the same
- *                                    transmitted frame -- an RS41 frame carries its number and the sonde's serial --, so the difference
+ *                                    transmitted frame -- an RS41 frame carries its number and the sonde's serial; for M10 / M20 /
+ *                                    MRZ-N1 groups: a length of the type, nerr[0] >= 0, bytes 0 .. len identical, on the standing
+ *                                    assumption that consecutive frames of one sonde differ (they carry time) --, so the difference
  *                                    of their bitpos is the difference of the members' offsets.  Before the combining pass of every
  *                                    submit an align step looks for such pairs among each member's records of the submit and its
  *                                    carried record, member pairs in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), per pair the
@@ -322,14 +336,14 @@ int  sonde_batch_set_diversity(SondeBatch *b, const int32_t *group /* n_channels
  *                                    are to the combining pass members without records.  offset_bits NULL: nothing is known, every
  *                                    member starts unlocked; else every member starts locked at what is given (good to within
  *                                    window_bits or not: the first common good frame corrects it).
- *   SONDE_DIVERSITY_MARK_DUPLICATES  a good record that is identical in bytes 8 .. len to the carried record of another member, or to a
+ *   SONDE_DIVERSITY_MARK_DUPLICATES  a good record that is identical in these bytes to the carried record of another member, or to a
  *                                    good record of this submit of a member with a lower index, gets SONDE_FRAME_DUPLICATE; nothing
  *                                    else of it changes.  One copy of a transmitted frame stays unmarked however the stream is cut,
  *                                    as long as no copy arrives later than one frame period after the first (a later one goes unmarked).
  * Limits: the two copies of a frame must be seen at once (records of one submit, or the other member's newest earlier record): the
  * streams may be fed up to one frame period out of step, while the bit counts themselves may stand anywhere;
  * a group locks at its first frame that is good in two members and not before; one that never has such a frame never locks,
- * and then nothing of it changes; two different sondes in one group never lock; failed copies teach nothing; RS41 only.  Refused: any
+ * and then nothing of it changes; two different sondes in one group never lock; failed copies teach nothing.  Refused: any
  * other mode bit, and everything sonde_batch_set_diversity refuses.  One more small launch per submit when mode != 0.
  * sonde_batch_restart_channels puts a restarted group back to what this call set: unlocked or locked at offset_bits, counters zero. */
 #define SONDE_DIVERSITY_LEARN           1u
@@ -434,12 +448,18 @@ int      sonde_batch_diversity_info(SondeBatch *b, uint32_t group, uint32_t *tri
  * out[i] = copy 0, rewritten or not; status[i] = the copies used, -1 (a codeword with more than 24 erasures), -2 (no decode) or -3
  * (rejected by the accept step). */
 int      sonde_batch_test_rs41_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status);
+/* The combining rule of M10 / M20 / MRZ-N1 groups alone (SPEC 3.3l steps 3 to 6), on any batch: the shape of
+ * sonde_batch_test_rs41_combine.  Copy 0: a SONDE_M10 record of 101 or 70 bytes or a SONDE_MRZN1 record of 45 with nerr[0] < 0; the
+ * other copies of the same type and length.  status[i] = the copies used, -1 (not attempted: no unknown, more than 8, or for M10 / M20
+ * a length-byte bit in doubt), -2 (no subset fits) or -3 (several fit).  Refused: n_copies outside 2..4, a good copy 0, copies of
+ * differing type or len. */
+int      sonde_batch_test_check_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status);
 /* sonde_batch_set_diversity_auto introspection: where each member of the group stands on the group's clock now (off[m], member m = the
  * group's m-th channel in ascending order; unused entries 0), which members are locked (bit m), how many offsets the align step has
  * set or changed and how many records it has marked SONDE_FRAME_DUPLICATE since the call / the group's restart.  Synchronises.  With
  * mode 0 the offsets are the host's, every member is locked and the counters are 0. */
 int      sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t off[4], uint32_t *locked_mask, uint32_t *learned, uint32_t *duplicates);
-/* The align step alone (SPEC 3.3k), on any batch: n cases of 4 members with max_rec record slots each.  Case k: n_members[k] = 2..4;
+/* The align step alone (SPEC 3.3k, with the predicates of RS41 groups), on any batch: n cases of 4 members with max_rec record slots each.  Case k: n_members[k] = 2..4;
  * member m's records of the submit are records[(4 k + m) * max_rec + i], i < counts[4 k + m] <= max_rec, its carried record is
  * carried[4 k + m] (len 0 = none); off[4 k + m] and locked[k] are the group's state, in and out; mode[k] as above (0 .. 3);
  * learned[k] and duplicates[k] = what the step counted.  The records come back with their flags as the step left them. */

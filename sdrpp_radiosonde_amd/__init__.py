@@ -7,7 +7,7 @@
     detect    SondeDetector: the sonde type of each channel (sync-template correlation on the GPU); detect, then build the batch
     tuner     SondeTuner (VFOs at any offset over one wideband stream), WidebandReceiver (wideband stream -> tuner -> decoders)
     scan      SondeScanner (where in a wideband stream the carriers are: averaged power spectrum on the GPU, candidate search), survey
-    diversity DiversityReceiver (K antennas' wideband streams -> one frame list per RS41 sonde: the diversity pass with learned offsets;
+    diversity DiversityReceiver (K antennas' wideband streams -> one frame list per RS41, M10 / M20 or MRZ-N1 sonde: the diversity pass with learned offsets;
               combine="coherent": the antennas' rows added before detection, any sonde type)
     combine   SondeCombiner (the K antennas' IQ rows of each sonde -> one row: weights per block from the block's own statistics)
     live      LiveReceiver (a wideband receiver left running: sondes that appear are probed, typed and decoded, those that vanish dropped), LivePolicy

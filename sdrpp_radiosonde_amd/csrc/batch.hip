@@ -177,11 +177,7 @@ static int build(SondeBatch *b, const SondeBatchConfig *cfg)
 		const SdRescuePass &p = k_rescue_passes[k];
 		if ((cfg->flags & p.flag) && (types_present & p.types)) HIPCHK(b->d_pass[k].zeros(C * p.words));
 	}
-	if (b->d_pass[SD_PASS_MANCHESTER]) {
-		uint16_t mrz[43 * 8];
-		fec_mrz_table(mrz);
-		HIPCHK(b->d_mrztab.upload(mrz, 43 * 8));
-	}
+	if (b->d_pass[SD_PASS_MANCHESTER] && sd_batch_need_mrztab(b)) return -1;
 	if (n_afsk) {
 		float wtab[2 * SD_AF_PER], wc[2 * SD_C50_PER];
 		make_mixer(wtab, 17, SD_AF_PER);         // iMet: 1700 Hz
@@ -565,14 +561,23 @@ static int record_completion(SondeBatch *b, SubmitCtx &cx)
 // late-joined modes): the pass over the groups of sonde_batch_set_diversity (SPEC 3.3j)
 static int launch_diversity(SondeBatch *b, SubmitCtx &cx)
 {
+	const uint32_t other_kinds = (b->div_kinds & ~(1u << SONDE_RS41)) != 0;       // with RS41 groups only the kernels run as they did
 	if (b->div_mode) {      // SPEC 3.3k: the align step first -- it sets the offsets and lock bits the pass reads, and marks duplicates
 		sd_launch_diversity_align(b->n_groups, cx.done, cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_groups, b->d_carried,
-			b->d_divstate, b->div_mode);
+			b->d_divstate, b->div_mode, other_kinds);
 		HIPCHK(hipGetLastError());
 	}
-	sd_launch_diversity(b->n_groups, cx.done, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, cx.slot->d_frames, cx.slot->d_counts, b->max_frames,
-		b->d_groups, b->d_divstate, b->div_window, b->d_carried, b->d_divcnt);
-	HIPCHK(hipGetLastError());
+	// each combining kernel takes the groups of its kinds out of the one table, and is launched only if there is one
+	if (b->div_kinds & (1u << SONDE_RS41)) {
+		sd_launch_diversity(b->n_groups, cx.done, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, cx.slot->d_frames, cx.slot->d_counts, b->max_frames,
+			b->d_groups, b->d_divstate, b->div_window, b->d_carried, b->d_divcnt, other_kinds);
+		HIPCHK(hipGetLastError());
+	}
+	if (b->div_kinds & ((1u << SONDE_M10) | (1u << SONDE_MRZN1))) {      // SPEC 3.3l
+		sd_launch_check_diversity(b->n_groups, cx.done, b->fec.m10tab, b->d_mrztab, cx.slot->d_frames, cx.slot->d_counts, b->max_frames,
+			b->d_groups, b->d_divstate, b->div_window, b->d_carried, b->d_divcnt);
+		HIPCHK(hipGetLastError());
+	}
 	cx.framer_launched = true;
 	return 0;
 }
@@ -788,7 +793,18 @@ extern "C" int sonde_batch_test_shift_age(SondeBatch *b, const uint32_t *channel
 	return 0;
 }
 
-// The receivers of one sonde (include/sonde_abi.h, SPEC 3.3j and 3.3k): the group table, the carried records, the counters and the
+// MRZ-N1's column table (SPEC 3.3f step 3), for SONDE_FLAG_MANCHESTER_RESCUE and for an MRZ-N1 diversity group (SPEC 3.3l): whoever
+// needs it first uploads it
+int sd_batch_need_mrztab(SondeBatch *b)
+{
+	if (b->d_mrztab) return 0;
+	uint16_t mrz[43 * 8];
+	fec_mrz_table(mrz);
+	HIPCHK(b->d_mrztab.upload(mrz, 43 * 8));
+	return 0;
+}
+
+// The receivers of one sonde (include/sonde_abi.h, SPEC 3.3j, 3.3k and 3.3l): the group table, the carried records, the counters and the
 // align step's state.  mode 0 is sonde_batch_set_diversity.
 extern "C" int sonde_batch_set_diversity(SondeBatch *b, const int32_t *group, const int64_t *offset_bits, uint32_t window_bits)
 {
@@ -814,11 +830,17 @@ extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *grou
 	if (top < 0) return sd_fail("sonde_batch_set_diversity: no group");
 	std::vector<SdDivGroup> gt((size_t)top + 1);
 	std::vector<int32_t> slot(b->n_channels, -1);
+	uint32_t kinds = 0;
 	for (SdDivGroup &g : gt) g = SdDivGroup{};
 	for (uint32_t c = 0; c < b->n_channels; c++) {
 		if (group[c] < 0) continue;
 		SdDivGroup &g = gt[(size_t)group[c]];
-		if (b->types[c] != SONDE_RS41) return sd_fail("sonde_batch_set_diversity: a member that is not SONDE_RS41");
+		const uint32_t t = b->types[c];
+		if (t != SONDE_RS41 && t != SONDE_M10 && t != SONDE_MRZN1)
+			return sd_fail("sonde_batch_set_diversity: a member that is not SONDE_RS41, SONDE_M10 or SONDE_MRZN1");
+		if (g.n && g.kind != t) return sd_fail("sonde_batch_set_diversity: members of different types in one group");
+		g.kind = t;
+		kinds |= 1u << t;
 		if (g.n == SD_DIV_MAX) return sd_fail("sonde_batch_set_diversity: a group with more than 4 members");
 		g.ch[g.n] = c;
 		g.off[g.n] = offset_bits ? offset_bits[c] : 0;
@@ -828,6 +850,7 @@ extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *grou
 	for (const SdDivGroup &g : gt)
 		if (g.n < 2) return sd_fail(g.n ? "sonde_batch_set_diversity: a group with fewer than 2 members" : "sonde_batch_set_diversity: group ids with gaps");
 	HIPCHK(hipSetDevice(b->device));
+	if ((kinds & (1u << SONDE_MRZN1)) && sd_batch_need_mrztab(b)) return -1;      // the pass of SPEC 3.3l reads MRZ-N1's columns from it
 	HIPCHK(b->d_groups.upload(gt.data(), gt.size()));
 	HIPCHK(b->d_carried.zeros(gt.size() * SD_DIV_MAX));
 	HIPCHK(b->d_divcnt.zeros(gt.size() * 2));
@@ -841,6 +864,7 @@ extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *grou
 		st[g].locked = unlocked ? 0u : (1u << gt[g].n) - 1u;
 	}
 	HIPCHK(b->d_divstate.upload(st.data(), st.size()));
+	b->div_kinds = kinds;
 	b->div_mode = mode;
 	b->div_unlocked = unlocked ? 1u : 0u;
 	b->div_slot = slot;

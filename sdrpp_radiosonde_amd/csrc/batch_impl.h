@@ -170,7 +170,8 @@ struct SondeBatch {
 	std::deque<std::pair<uint64_t, uint32_t>> parser_restarts;
 	bool behind_channelizer = false;
 	// the rescue passes (k_rescue_passes): per pass [n_channels][words] of state; null: its flag is off or the batch has no channel of its
-	// types, and nothing of it is allocated or launched.  d_mrztab: MRZ-N1's column table, with the Manchester pass
+	// types, and nothing of it is allocated or launched.  d_mrztab: MRZ-N1's column table, with the Manchester pass or with an MRZ-N1
+	// diversity group (sd_batch_need_mrztab)
 	DevBuf<uint32_t> d_pass[SD_N_PASSES];
 	DevBuf<uint16_t> d_mrztab;
 	// sonde_batch_set_diversity (SPEC 3.3j): the group table, per group SD_DIV_MAX carried records and two counters, the slot
@@ -178,7 +179,8 @@ struct SondeBatch {
 	// allocated or launched
 	// div_mode: sonde_batch_set_diversity_auto's mode (SPEC 3.3k; 0: no align step is launched), div_unlocked: its groups start unlocked;
 	// d_divstate: per group the offsets and lock bits the combining pass reads, and the align step's counters
-	uint32_t n_groups = 0, div_window = 0, div_mode = 0, div_unlocked = 0;
+	// div_kinds: a bit per sonde type that has a group (SPEC 3.3l): which of the two combining kernels are launched
+	uint32_t n_groups = 0, div_window = 0, div_mode = 0, div_unlocked = 0, div_kinds = 0;
 	DevBuf<SdDivGroup> d_groups;
 	DevBuf<SdDivState> d_divstate;
 	DevBuf<SondeFrame> d_carried;
@@ -186,6 +188,7 @@ struct SondeBatch {
 	DevBuf<int32_t> d_divslot;
 	std::vector<int32_t> div_slot;
 };
+int sd_batch_need_mrztab(SondeBatch *b);      // uploads d_mrztab if it is not there yet (batch.hip); the device is set
 static_assert(!std::is_copy_constructible<SondeBatch>::value && !std::is_copy_constructible<SondeBatch::Unit>::value, "owners of device resources");
 static_assert(!std::is_copy_constructible<DevBuf<uint8_t>>::value && !std::is_copy_constructible<PinnedBuf<uint32_t>>::value &&
 	!std::is_copy_constructible<DevEvent>::value && !std::is_copy_constructible<DevStream>::value, "owners of device resources");

@@ -174,6 +174,39 @@ extern "C" int sonde_batch_test_rs41_combine(SondeBatch *b, size_t n, const Sond
 	return 0;
 }
 
+// Steps 3 to 6 of SPEC 3.3l alone, through the kernel's own device function: the shape of sonde_batch_test_rs41_combine; status[i] =
+// copies used, -1 not attempted, -2 no subset fits, -3 several fit.
+extern "C" int sonde_batch_test_check_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status)
+{
+	if (!b || !copies || !n_copies || !out || !status || !n || n > (1u << 16)) return sd_fail("sonde_batch_test_check_combine: bad argument");
+	for (size_t i = 0; i < n; i++) {
+		const SondeFrame *c = copies + SD_DIV_MAX * i;
+		if (n_copies[i] < 2 || n_copies[i] > SD_DIV_MAX) return sd_fail("sonde_batch_test_check_combine: n_copies must be 2..4");
+		const bool known = (c[0].type == SONDE_M10 && (c[0].len == 101 || c[0].len == 70)) || (c[0].type == SONDE_MRZN1 && c[0].len == 45);
+		if (!known || c[0].nerr[0] >= 0)
+			return sd_fail("sonde_batch_test_check_combine: copy 0 must be a failed SONDE_M10 record of 101 or 70 bytes or a failed SONDE_MRZN1 record of 45");
+		for (uint32_t k = 1; k < n_copies[i]; k++)
+			if (c[k].len != c[0].len || c[k].type != c[0].type) return sd_fail("sonde_batch_test_check_combine: the copies of a case must have one type and one length");
+	}
+	HIPCHK(hipSetDevice(b->device));
+	DevBuf<SondeFrame> d_c, d_o;
+	DevBuf<uint32_t> d_n;
+	DevBuf<int32_t> d_st;
+	DevBuf<uint16_t> d_mrz;                 // a table of the call's own: the batch stays as it is
+	uint16_t mrz[43 * 8];
+	fec_mrz_table(mrz);
+	HIPCHK(d_mrz.upload(mrz, 43 * 8));
+	HIPCHK(d_c.upload(copies, SD_DIV_MAX * n));
+	HIPCHK(d_n.upload(n_copies, n));
+	HIPCHK(d_o.alloc(n));
+	HIPCHK(d_st.alloc(n));
+	sd_launch_check_diversity_unit(d_c, d_n, (uint32_t)n, d_o, d_st, b->fec.m10tab, d_mrz, nullptr);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpy(out, d_o, n * sizeof(SondeFrame), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
 extern "C" int sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t off[4], uint32_t *locked_mask, uint32_t *learned, uint32_t *duplicates)
 {
 	if (!b) return sd_fail("sonde_batch_diversity_offsets: bad argument");

@@ -1,0 +1,205 @@
+// check_diversity_kernel.hip -- sonde_batch_set_diversity for M10 / M20 and MRZ-N1 groups (DESIGN SPEC 3.3l): the pass over the frame
+// records of a submit that sees every receiver of one sonde.  These frames carry a 16-bit check and no FEC.  Two failed copies of one
+// frame are almost certainly right where they agree, and exactly one of them is wrong where they differ; both checks are linear over
+// GF(2) (SPEC 3.3f), so the differing bits are the unknowns of a 16-equation system: the working frame (copy 0, or the bitwise majority
+// of three or four copies) is taken if its check passes, else iff exactly one subset of the at most 8 differing bits explains its
+// syndrome.
+//   one 64-lane wave per group, four waves per workgroup.  The record search -- the next failed record and its partners, this submit's
+//   records plus the carried one -- is the RS41 pass's (sd_diversity_scan.h).  Lane i holds the 32-bit word i of every copy (a frame
+//   has at most 26), so majority and the differing bits are a handful of bitwise operations, V is gathered by ballot into lanes 0..7,
+//   and the <= 255 subsets are tried across the wave, four per lane (sd_check_cols.h, shared with check_rescue_kernel.hip).  No LDS.
+// Runs behind every other kernel of the submit and behind the align step, on the stream where the submit completes, and rewrites
+// records in place.  What one lane wrote to a record and another reads later (a rewritten record's nerr, the carried copy) is ordered
+// by a fence and read with agent-scope loads.  Vector stores only.  Bounds: min(counts, max_frames) records per member, 4 slots per
+// group, every byte index < len <= 101 (word index < 26 of the 132-word data).
+#include <hip/hip_runtime.h>
+#include "sonde_dev.h"
+#include "sd_check_cols.h"
+#include "sd_diversity_scan.h"
+#include "launch.h"
+
+#define CD_WAVES 4
+
+// word `lane` of a record's data, zero behind the frame's last word
+__device__ __forceinline__ uint32_t cd_word(const SondeFrame *f, int len, int lane)
+{
+	return 4 * lane < len ? reinterpret_cast<const uint32_t *>(f->data)[lane] : 0u;
+}
+// the bytes of word `lane` that belong to a frame of len bytes
+__device__ __forceinline__ uint32_t cd_mask(int len, int lane)
+{
+	const int rem = len - 4 * lane;
+	return rem >= 4 ? 0xFFFFFFFFu : rem > 0 ? (1u << (8 * rem)) - 1u : 0u;
+}
+
+// Steps 3 to 5 of SPEC 3.3l on K copies of a frame of len bytes; c[j]: this lane's word of copy j (copy 0 is the record to rewrite;
+// c[j] for j >= K is not looked at).  Wave-synchronous, every branch wave-uniform, all 64 lanes active.  Returns K (accepted: w = this
+// lane's word of the result, frame bytes only), -1 (not attempted), -2 (no subset fits) or -3 (several fit); nv = |V|.
+__device__ int cd_combine(const uint16_t *__restrict__ m10tab, const uint16_t *__restrict__ mrztab, bool mrz, int len, int K,
+	const uint32_t (&c)[SD_DIV_MAX], int lane, uint32_t &w, int &nv)
+{
+	// ---- 3. working frame and unknowns
+	const uint32_t bm = cd_mask(len, lane);
+	const uint32_t x0 = c[0] & bm, x1 = c[1] & bm, x2 = (K > 2 ? c[2] : c[0]) & bm, x3 = (K > 3 ? c[3] : c[0]) & bm;
+	const uint32_t diff = (x0 ^ x1) | (x0 ^ x2) | (x0 ^ x3);
+	if (K == 2) w = x0;
+	else if (K == 3) w = (x0 & x1) | (x0 & x2) | (x1 & x2);
+	else {      // four copies: three alike decide, two against two leave copy 0's bit
+		const uint32_t ones = (x0 & x1 & x2) | (x0 & x1 & x3) | (x0 & x2 & x3) | (x1 & x2 & x3);
+		const uint32_t zeros = (~x0 & ~x1 & ~x2) | (~x0 & ~x1 & ~x3) | (~x0 & ~x2 & ~x3) | (~x1 & ~x2 & ~x3);
+		w = ones | (x0 & ~zeros);
+	}
+	// frame bit k = 32 lane + q is bit 7 - q % 8 of byte q / 8 of the word: bit q of vm
+	const uint32_t vm = __brev(__builtin_bswap32(diff));
+	nv = __popc(vm);
+#pragma unroll
+	for (int off = 32; off > 0; off >>= 1) nv += __shfl_xor(nv, off, 64);
+
+	// ---- 4. majority alone: the syndrome of w (this lane's four bytes)
+	const uint16_t *tab = mrz ? mrztab : m10tab;
+	const int n_cov = len - 2;
+	const bool hi_first = !mrz;
+	uint32_t s = 0;
+#pragma unroll
+	for (int b = 0; b < 4; b++) {
+		const int i = 4 * lane + b;
+		if (i < len) s ^= mq_byte_syndrome(mq_row(tab, n_cov, hi_first, i), (w >> (8 * b)) & 0xFFu);
+	}
+#pragma unroll
+	for (int off = 32; off > 0; off >>= 1) s ^= (uint32_t)__shfl_xor((int)s, off, 64);
+	if (mrz) s ^= mq_mrz_crc_of_zeros();
+	if (s == 0u && nv >= 1) return K;
+
+	// ---- 5. solve
+	if (nv == 0 || nv > MQ_MAX_HINTS) return -1;
+	if (!mrz && (DV_U(vm) & 0xFF)) return -1;                  // M10 / M20: the length byte decides the layout
+	int myk = 0, n = 0;                                        // V, ascending, into lanes 0 .. nv - 1
+	for (unsigned long long lm = __ballot(vm != 0u); lm; lm &= lm - 1ull) {
+		const int l = __builtin_ctzll(lm);
+		for (uint32_t q = (uint32_t)__builtin_amdgcn_readlane((int)vm, l); q; q &= q - 1u) {
+			if (lane == n) myk = 32 * l + __builtin_ctz(q);
+			n++;
+		}
+	}
+	uint32_t col = 0;
+	if (lane < nv) col = mq_col(mq_row(tab, n_cov, hi_first, myk >> 3), 7 - (myk & 7));
+	uint32_t U = 0;
+	const int nhit = mq_solve(col, nv, s, lane, U);
+	if (nhit != 1) return nhit ? -3 : -2;
+#pragma unroll
+	for (int j = 0; j < MQ_MAX_HINTS; j++) {
+		const int kj = __builtin_amdgcn_readlane(myk, j);
+		if (((U >> j) & 1u) && (kj >> 5) == lane) w ^= 1u << (8 * ((kj >> 3) & 3) + 7 - (kj & 7));
+	}
+	return K;
+}
+
+// Step 6: the accepted result into the record; data behind len stays (c0: this lane's word of the record as it stands)
+__device__ __forceinline__ void cd_write_record(SondeFrame *fr, int len, int K, int nv, uint32_t w, uint32_t c0, int lane)
+{
+	const uint32_t bm = cd_mask(len, lane);
+	if (bm) reinterpret_cast<uint32_t *>(fr->data)[lane] = (w & bm) | (c0 & ~bm);
+	if (lane == 0) {
+		fr->nerr[0] = 0;
+		fr->flags = dv_load_fresh(&fr->flags) | SONDE_FRAME_RESCUED | SONDE_FRAME_COMBINED | ((uint32_t)K << 8) | ((uint32_t)min(nv, 15) << 12);
+	}
+}
+
+__global__ __launch_bounds__(64 * CD_WAVES) void sd_check_diversity_kernel(
+	const uint16_t *__restrict__ m10tab /* [99][8] */, const uint16_t *__restrict__ mrztab /* [43][8] */,
+	SondeFrame *frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
+	const SdDivGroup *__restrict__ groups, const SdDivState *states, uint32_t n_groups, uint32_t window, SondeFrame *carried,
+	uint32_t *counters /* [n_groups][2] */)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t g = CD_WAVES * blockIdx.x + (threadIdx.x >> 6);
+	if (g >= n_groups) return;
+	const SdDivGroup *G = groups + g;
+	const uint32_t kind = (uint32_t)DV_U(G->kind);
+	if (kind != SONDE_M10 && kind != SONDE_MRZN1) return;      // an RS41 group: diversity_kernel.hip's
+	const bool mrz = kind == SONDE_MRZN1;
+	DvMembers M;
+	dv_members(M, frames, counts, max_frames, G, states + g);
+
+	// ---- steps 1 and 2 (sd_diversity_scan.h): the failed records in ascending (t, member), each with its partners
+	uint32_t tried = 0, combined = 0;
+	int64_t last_t = INT64_MIN, t_r;
+	int last_m = -1;
+	uint32_t bk;
+	while (dv_next_failed(M, kind, lane, last_t, last_m, t_r, bk)) {
+		const int m_r = (int)(bk >> 16);
+		SondeFrame *fr = M.rec_of(m_r, bk & 0xFFFFu);
+		const int flen = DV_U(fr->len);
+		uint32_t c[SD_DIV_MAX] = { 0u, 0u, 0u, 0u };
+		int K = 1;
+		bool any_good = false;
+#pragma unroll
+		for (int b = 0; b < SD_DIV_MAX; b++) {
+			if (b >= M.nm || b == m_r || any_good || !((M.lockmask >> b) & 1u)) continue;
+			const SondeFrame *pf = dv_partner(M, b, flen, t_r, window, carried + (size_t)SD_DIV_MAX * g + b, lane);
+			if (!pf) continue;
+			if (DV_U(dv_load_fresh(reinterpret_cast<const uint32_t *>(&pf->nerr[0]))) >= 0) { any_good = true; continue; }
+			// a partner that is not good has not been rewritten: its data are as recorded
+			const uint32_t wd = cd_word(pf, flen, lane);
+			if (K == 1) c[1] = wd; else if (K == 2) c[2] = wd; else c[3] = wd;
+			K++;
+		}
+		if (K == 1 || any_good) continue;          // no partner, or the group has a good copy already: stays as recorded
+		tried++;
+		c[0] = cd_word(fr, flen, lane);
+		uint32_t w;
+		int nv;
+		if (cd_combine(m10tab, mrztab, mrz, flen, K, c, lane, w, nv) > 0) {
+			cd_write_record(fr, flen, K, nv, w, c[0], lane);
+			combined++;
+			__threadfence();
+		}
+	}
+
+	// ---- the carried records: each member's newest record of this submit with a frame length, as the pass left it
+	__threadfence();
+	dv_carry(M, kind, carried + (size_t)SD_DIV_MAX * g, lane);
+	if (lane == 0 && (tried | combined)) { counters[2 * g] += tried; counters[2 * g + 1] += combined; }
+}
+
+void sd_launch_check_diversity(uint32_t n_groups, hipStream_t stream, const uint16_t *m10tab, const uint16_t *mrztab, SondeFrame *frames,
+	const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, const SdDivState *states, uint32_t window, SondeFrame *carried,
+	uint32_t *counters)
+{
+	hipLaunchKernelGGL(sd_check_diversity_kernel, dim3((n_groups + CD_WAVES - 1) / CD_WAVES), dim3(64 * CD_WAVES), 0, stream,
+		m10tab, mrztab, frames, counts, max_frames, groups, states, n_groups, window, carried, counters);
+}
+
+// ---- test introspection: steps 3 to 6 alone on caller-made copies (sonde_batch_test_check_combine).  One wave per case; the host has
+// checked n_copies (2..4), the copies' type (SONDE_M10 or SONDE_MRZN1) and len (one of the type's, the same in all copies of a case)
+// and that copy 0 has failed.
+__global__ __launch_bounds__(64 * CD_WAVES) void sd_check_diversity_unit_kernel(
+	const uint16_t *__restrict__ m10tab, const uint16_t *__restrict__ mrztab,
+	const SondeFrame *__restrict__ copies /* [n][SD_DIV_MAX] */, const uint32_t *__restrict__ n_copies, uint32_t n, SondeFrame *out,
+	int32_t *__restrict__ status)
+{
+	const int lane = threadIdx.x & 63;
+	const uint32_t k = CD_WAVES * blockIdx.x + (threadIdx.x >> 6);
+	if (k >= n) return;
+	const SondeFrame *cps = copies + (size_t)SD_DIV_MAX * k;
+	const int K = DV_U(n_copies[k]), len = DV_U(cps[0].len);
+	const bool mrz = (uint32_t)DV_U(cps[0].type) == SONDE_MRZN1;
+	uint32_t c[SD_DIV_MAX];
+#pragma unroll
+	for (int j = 0; j < SD_DIV_MAX; j++) c[j] = j < K ? cd_word(cps + j, len, lane) : 0u;
+	// out = copy 0, in memory before the result is written over it (other lanes write the same words then)
+	for (int i = lane; i < DV_REC_WORDS; i += 64) reinterpret_cast<uint32_t *>(out + k)[i] = reinterpret_cast<const uint32_t *>(cps)[i];
+	__threadfence();
+	uint32_t w;
+	int nv;
+	const int st = cd_combine(m10tab, mrztab, mrz, len, K, c, lane, w, nv);
+	if (st > 0) cd_write_record(out + k, len, K, nv, w, c[0], lane);
+	if (lane == 0) status[k] = st;
+}
+
+void sd_launch_check_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
+	const uint16_t *m10tab, const uint16_t *mrztab, hipStream_t stream)
+{
+	hipLaunchKernelGGL(sd_check_diversity_unit_kernel, dim3((n + CD_WAVES - 1) / CD_WAVES), dim3(64 * CD_WAVES), 0, stream,
+		m10tab, mrztab, copies, n_copies, n, out, status);
+}

@@ -11,41 +11,10 @@
 // Vector stores only.
 #include <hip/hip_runtime.h>
 #include "sonde_dev.h"
+#include "sd_check_cols.h"
 #include "launch.h"
 
 #define MQ_WAVES 4
-#define MQ_MAX_HINTS 8         // SPEC 3.3f: at most this many marked bits (255 subsets)
-
-// CRC16 (reflected 0xA001) of the 43 zero bytes from 0xFFFF: the constant part of MRZ-N1's affine check
-static constexpr uint32_t mq_mrz_crc_of_zeros()
-{
-	uint32_t crc = 0xFFFFu;
-	for (int i = 0; i < 43 * 8; i++) crc = (crc & 1u) ? ((crc >> 1) ^ 0xA001u) : (crc >> 1);
-	return crc;
-}
-
-// the frame byte i of a record of n_cov covered bytes followed by the two stored check bytes: the eight columns of its bits (bit j
-// of the byte = LSB index j) as four dwords of two 16-bit columns each, like a row of m10tab.  hi_first: the stored check is big-endian.
-__device__ __forceinline__ uint4 mq_row(const uint16_t *__restrict__ tab, int n_cov, bool hi_first, int i)
-{
-	if (i < n_cov) return *reinterpret_cast<const uint4 *>(tab + 8 * (n_cov - 1 - i));
-	// a bit of the stored check flips that bit of the syndrome
-	const uint32_t sh = ((i == n_cov) == hi_first) ? 8u : 0u;
-	return make_uint4(0x00020001u << sh, 0x00080004u << sh, 0x00200010u << sh, 0x00800040u << sh);
-}
-__device__ __forceinline__ uint32_t mq_col(const uint4 row, int j)
-{
-	const uint32_t w = (j >> 1) == 0 ? row.x : ((j >> 1) == 1 ? row.y : ((j >> 1) == 2 ? row.z : row.w));
-	return (w >> (16 * (j & 1))) & 0xFFFFu;
-}
-// XOR of the columns of the bits set in byte b
-__device__ __forceinline__ uint32_t mq_byte_syndrome(const uint4 row, uint32_t b)
-{
-	uint32_t s = 0;
-#pragma unroll
-	for (int j = 0; j < 8; j++) if ((b >> j) & 1u) s ^= mq_col(row, j);
-	return s;
-}
 
 __global__ __launch_bounds__(64 * MQ_WAVES) void sd_manchester_rescue_kernel(
 	const uint16_t *__restrict__ m10tab /* [99][8] */, const uint16_t *__restrict__ mrztab /* [43][8] */,
@@ -138,22 +107,8 @@ __global__ __launch_bounds__(64 * MQ_WAVES) void sd_manchester_rescue_kernel(
 			tried++;
 
 			// 4. the subsets m = 1 .. 2^nv - 1 of the marked bits (bit j of m: lane j's), four per lane
-			uint32_t c[MQ_MAX_HINTS];
-#pragma unroll
-			for (int j = 0; j < MQ_MAX_HINTS; j++) c[j] = (uint32_t)__builtin_amdgcn_readlane((int)col, j);
-			int nhit = 0;
 			uint32_t U = 0;
-#pragma unroll
-			for (int it = 0; it < 4; it++) {
-				const uint32_t m = (uint32_t)(64 * it + lane);
-				uint32_t x = 0;
-#pragma unroll
-				for (int j = 0; j < MQ_MAX_HINTS; j++) if ((m >> j) & 1u) x ^= c[j];
-				const unsigned long long hm = __ballot(m != 0u && m < (1u << nv) && x == s);
-				nhit += __popcll(hm);
-				if (hm) U = (uint32_t)(64 * it + __builtin_ctzll(hm));
-			}
-			if (nhit != 1) continue;                                // none, or several: the frame stays
+			if (mq_solve(col, nv, s, lane, U) != 1) continue;       // none, or several: the frame stays
 
 			// 5. the record: every lane flips what falls into its two bytes
 #pragma unroll

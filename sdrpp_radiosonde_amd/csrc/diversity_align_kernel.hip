@@ -1,10 +1,11 @@
 // diversity_align_kernel.hip -- sonde_batch_set_diversity_auto (DESIGN SPEC 3.3k): the align step in front of the combining pass of
-// diversity_kernel.hip.  Two good RS41 records of different members whose bytes 8 .. len are identical are the same transmitted frame
-// (the frame carries its number and the sonde's serial); from such pairs the step learns where each member's bit count stands on the
+// diversity_kernel.hip and check_diversity_kernel.hip.  Two good RS41 records of different members whose bytes 8 .. len are identical
+// are the same transmitted frame (the frame carries its number and the sonde's serial), and so are two good M10 / M20 or MRZ-N1 records
+// whose bytes 0 .. len are (SPEC 3.3l: consecutive frames of one sonde differ); from such pairs the step learns where each member's bit count stands on the
 // group's clock (SONDE_DIVERSITY_LEARN), and it marks all but one copy of a frame (SONDE_DIVERSITY_MARK_DUPLICATES).
 //   one 64-lane wave per group, a launch of its own in front of sd_diversity_kernel on the stream where the submit completes.  The
 //   lanes take one member's records (any number: the loops stride by 64) and each walks the other member's; a record's key is two
-//   words of its RS parity bytes, which differ between any two frames, so the byte compare runs for true matches only.
+//   words that differ between any two frames (RS parity bytes; the check bytes), so the byte compare runs for true matches only.
 // Writes: the group's SdDivState (lane 0) and the duplicate bit of records (each record by the one lane that owns it).  Nothing the
 // step reads of a record (len, nerr, bitpos, data) is written here, and the carried records are only read.  Vector stores only.
 #include <hip/hip_runtime.h>
@@ -16,21 +17,35 @@
 // a member's candidates: recs[0 .. cnt) are its records of this submit, index cnt is its carried record
 struct AlMember { SondeFrame *recs; const SondeFrame *carried; uint32_t cnt; };
 
+// The two predicates of the step depend on the group's kind (SdDivGroup.kind; wave-uniform).  RS41 (SPEC 3.3k): good = len 320 or 518 and
+// both nerr >= 0, the same frame = data[8 .. len) identical.  M10 / M20 and MRZ-N1 (SPEC 3.3l): good = a length of the type and
+// nerr[0] >= 0 (nerr[1] counts Manchester violations there), the same frame = data[0 .. len) identical.
 __device__ __forceinline__ const SondeFrame *al_cand(const AlMember &M, uint32_t i) { return i < M.cnt ? M.recs + i : M.carried; }
-__device__ __forceinline__ bool al_good(const SondeFrame *f) { return (f->len == 320 || f->len == 518) && f->nerr[0] >= 0 && f->nerr[1] >= 0; }
-__device__ __forceinline__ uint32_t al_key(const SondeFrame *f)
+__device__ __forceinline__ bool al_good(uint32_t kind, const SondeFrame *f)
+{
+	if (kind == SONDE_M10) return (f->len == 101 || f->len == 70) && f->nerr[0] >= 0;
+	if (kind == SONDE_MRZN1) return f->len == 45 && f->nerr[0] >= 0;
+	return (f->len == 320 || f->len == 518) && f->nerr[0] >= 0 && f->nerr[1] >= 0;
+}
+// the quick reject: two words that differ between any two frames.  RS41: parity bytes of codeword 0 and of codeword 1; the others: the
+// frame's last two words, which hold the 16-bit check (the bytes of the last word behind len are not looked at)
+__device__ __forceinline__ uint32_t al_key(uint32_t kind, const SondeFrame *f)
 {
 	const uint32_t *w = reinterpret_cast<const uint32_t *>(f->data);
-	return w[2] ^ w[8];                                // parity bytes of codeword 0 and of codeword 1
+	if (kind == SONDE_RS41) return w[2] ^ w[8];
+	const int len = f->len, wl = (len - 1) >> 2;           // a good record: len is 45, 70 or 101, wl >= 11
+	const uint32_t last = (len & 3) ? w[wl] & ((1u << (8 * (len & 3))) - 1u) : w[wl];
+	return last ^ ((w[wl - 1] << 13) | (w[wl - 1] >> 19));
 }
-// two good records: the same length and data[8 .. len) identical (len is 320 or 518: whole words, and for 518 two bytes of word 129)
-__device__ __forceinline__ bool al_match(const SondeFrame *x, const SondeFrame *y)
+// two good records: the same length and data[8 .. len) (RS41), data[0 .. len) (the others) identical; whole words, and the bytes of a
+// last part-filled word
+__device__ __forceinline__ bool al_match(uint32_t kind, const SondeFrame *x, const SondeFrame *y)
 {
 	const int len = x->len;
-	if (y->len != len || al_key(x) != al_key(y)) return false;
+	if (y->len != len || al_key(kind, x) != al_key(kind, y)) return false;
 	const uint32_t *a = reinterpret_cast<const uint32_t *>(x->data), *b = reinterpret_cast<const uint32_t *>(y->data);
 	uint32_t diff = 0;
-	for (int i = 2; i < len / 4; i++) diff |= a[i] ^ b[i];
+	for (int i = kind == SONDE_RS41 ? 2 : 0; i < len / 4; i++) diff |= a[i] ^ b[i];
 	if (len & 3) diff |= (a[len / 4] ^ b[len / 4]) & ((1u << (8 * (len & 3))) - 1u);
 	return diff == 0;
 }
@@ -42,17 +57,17 @@ __device__ __forceinline__ int64_t al_u64(int64_t v)
 
 // the learn rule for the pair (A, B): the match with the greatest bitpos in B (of several, the one with the greatest bitpos in A).
 // Returns true if there is a match; then d = bitpos_B - bitpos_A.  Wave-uniform result.
-__device__ bool al_pair(const AlMember &A, const AlMember &B, int lane, int64_t &d)
+__device__ __forceinline__ bool al_pair(uint32_t kind, const AlMember &A, const AlMember &B, int lane, int64_t &d)
 {
 	int64_t bb = -1, ba = -1;                          // bitpos < 2^63
 	for (uint32_t j = (uint32_t)lane; j <= B.cnt; j += 64) {
 		const SondeFrame *fb = al_cand(B, j);
-		if (!al_good(fb)) continue;
+		if (!al_good(kind, fb)) continue;
 		const int64_t pb = (int64_t)fb->bitpos;
 		if (pb < bb) continue;
 		for (uint32_t i = 0; i <= A.cnt; i++) {
 			const SondeFrame *fa = al_cand(A, i);
-			if (!al_good(fa) || !al_match(fa, fb)) continue;
+			if (!al_good(kind, fa) || !al_match(kind, fa, fb)) continue;
 			const int64_t pa = (int64_t)fa->bitpos;
 			if (pb > bb || pa > ba) { bb = pb; ba = pa; }
 		}
@@ -67,8 +82,9 @@ __device__ bool al_pair(const AlMember &A, const AlMember &B, int lane, int64_t 
 	return bb >= 0;
 }
 
-// The align step of one group (SPEC 3.3k).  M[m], m < nm: the members; st: the group's state, read and written by this wave alone.
-__device__ void al_group(AlMember (&M)[SD_DIV_MAX], int nm, SdDivState *st, uint32_t mode, int lane)
+// The align step of one group (SPEC 3.3k) of the given kind.  M[m], m < nm: the members; st: the group's state, read and written by
+// this wave alone.  Inlined into each kernel: where the kernel knows the kind when it is compiled, the predicates fold to that kind's.
+__device__ __forceinline__ void al_group(uint32_t kind, AlMember (&M)[SD_DIV_MAX], int nm, SdDivState *st, uint32_t mode, int lane)
 {
 	int64_t off[SD_DIV_MAX];
 #pragma unroll
@@ -81,7 +97,7 @@ __device__ void al_group(AlMember (&M)[SD_DIV_MAX], int nm, SdDivState *st, uint
 			for (int b = a + 1; b < SD_DIV_MAX; b++) {
 				if (b >= nm) continue;
 				int64_t d;
-				if (!al_pair(M[a], M[b], lane, d)) continue;
+				if (!al_pair(kind, M[a], M[b], lane, d)) continue;
 				const bool la = (locked >> a) & 1u, lb = (locked >> b) & 1u;
 				if (lb && !la) { off[a] = off[b] - d; learned++; }
 				else if (!la || !lb || off[b] - off[a] != d) { off[b] = off[a] + d; learned++; }
@@ -96,14 +112,14 @@ __device__ void al_group(AlMember (&M)[SD_DIV_MAX], int nm, SdDivState *st, uint
 			for (uint32_t j0 = 0; j0 < M[b].cnt; j0 += 64) {
 				const uint32_t j = j0 + (uint32_t)lane;
 				bool dup = false;
-				if (j < M[b].cnt && al_good(M[b].recs + j)) {
+				if (j < M[b].cnt && al_good(kind, M[b].recs + j)) {
 					const SondeFrame *fb = M[b].recs + j;
 #pragma unroll
 					for (int a = 0; a < SD_DIV_MAX; a++) {
 						if (a >= nm || a == b || dup) continue;
-						if (al_good(M[a].carried) && al_match(M[a].carried, fb)) dup = true;
+						if (al_good(kind, M[a].carried) && al_match(kind, M[a].carried, fb)) dup = true;
 						for (uint32_t i = 0; a < b && !dup && i < M[a].cnt; i++)
-							dup = al_good(M[a].recs + i) && al_match(M[a].recs + i, fb);
+							dup = al_good(kind, M[a].recs + i) && al_match(kind, M[a].recs + i, fb);
 					}
 					if (dup) M[b].recs[j].flags |= SONDE_FRAME_DUPLICATE;
 				}
@@ -120,8 +136,10 @@ __device__ void al_group(AlMember (&M)[SD_DIV_MAX], int nm, SdDivState *st, uint
 	}
 }
 
-__global__ __launch_bounds__(64) void sd_diversity_align_kernel(SondeFrame *frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const SdDivGroup *__restrict__ groups, const SondeFrame *__restrict__ carried, SdDivState *states, uint32_t mode)
+// OTHER_KINDS = false: every group of the table is RS41 -- the kind word is not read and the code is the RS41 step alone; true: the
+// table has groups of SPEC 3.3l, and each group's kind is read from the table.  The host launches the one that fits the table.
+template <bool OTHER_KINDS> __global__ __launch_bounds__(64) void sd_diversity_align_kernel(SondeFrame *frames, const uint32_t *__restrict__ counts,
+	uint32_t max_frames, const SdDivGroup *__restrict__ groups, const SondeFrame *__restrict__ carried, SdDivState *states, uint32_t mode)
 {
 	const uint32_t g = blockIdx.x;
 	const int lane = (int)threadIdx.x;
@@ -135,16 +153,17 @@ __global__ __launch_bounds__(64) void sd_diversity_align_kernel(SondeFrame *fram
 		M[m].cnt = m < nm ? (uint32_t)AL_U(min(counts[ch], max_frames)) : 0u;
 		M[m].carried = carried + (size_t)SD_DIV_MAX * g + m;
 	}
-	al_group(M, nm, states + g, mode, lane);
+	al_group(OTHER_KINDS ? (uint32_t)AL_U(G->kind) : (uint32_t)SONDE_RS41, M, nm, states + g, mode, lane);
 }
 
 void sd_launch_diversity_align(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
-	const SdDivGroup *groups, const SondeFrame *carried, SdDivState *states, uint32_t mode)
+	const SdDivGroup *groups, const SondeFrame *carried, SdDivState *states, uint32_t mode, uint32_t other_kinds)
 {
-	hipLaunchKernelGGL(sd_diversity_align_kernel, dim3(n_groups), dim3(64), 0, stream, frames, counts, max_frames, groups, carried, states, mode);
+	if (other_kinds) hipLaunchKernelGGL(sd_diversity_align_kernel<true>, dim3(n_groups), dim3(64), 0, stream, frames, counts, max_frames, groups, carried, states, mode);
+	else hipLaunchKernelGGL(sd_diversity_align_kernel<false>, dim3(n_groups), dim3(64), 0, stream, frames, counts, max_frames, groups, carried, states, mode);
 }
 
-// ---- test introspection: the align step alone on caller-made records (sonde_batch_test_diversity_align).  One wave per case; case k
+// ---- test introspection: the align step alone on caller-made RS41 records (sonde_batch_test_diversity_align).  One wave per case; case k
 // has SD_DIV_MAX members of max_rec record slots each (counts[4 k + m] <= max_rec in use), SD_DIV_MAX carried records, its state and
 // its mode; the host has checked n_members (2..4), the counts and the modes.
 __global__ __launch_bounds__(64) void sd_diversity_align_unit_kernel(SondeFrame *records, const uint32_t *__restrict__ counts, uint32_t max_rec,
@@ -160,7 +179,7 @@ __global__ __launch_bounds__(64) void sd_diversity_align_unit_kernel(SondeFrame 
 		M[m].cnt = m < nm ? (uint32_t)AL_U(min(counts[SD_DIV_MAX * k + m], max_rec)) : 0u;
 		M[m].carried = carried + (size_t)SD_DIV_MAX * k + m;
 	}
-	al_group(M, nm, states + k, (uint32_t)AL_U(modes[k]), lane);
+	al_group(SONDE_RS41, M, nm, states + k, (uint32_t)AL_U(modes[k]), lane);
 }
 
 void sd_launch_diversity_align_unit(uint32_t n, hipStream_t stream, SondeFrame *records, const uint32_t *counts, uint32_t max_rec,

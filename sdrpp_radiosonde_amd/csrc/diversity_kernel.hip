@@ -13,12 +13,10 @@
 #include "sonde_dev.h"
 #include "sd_rsee.h"
 #include "sd_rs41_crc.h"
+#include "sd_diversity_scan.h"
 #include "launch.h"
 
 #define DV_WAVES 4
-#define DV_U(x) __builtin_amdgcn_readfirstlane((int)(x))
-constexpr int DV_REC_WORDS = (int)(sizeof(SondeFrame) / 4);
-constexpr int DV_DATA_WORD0 = (int)(offsetof(SondeFrame, data) / 4);
 constexpr int DV_DATA_WORDS = SONDE_FRAME_MAX / 4;
 
 struct DivLds {                    // one per wave: 5.7 KB
@@ -195,23 +193,9 @@ __device__ __forceinline__ void dv_stage_tabs(FramerTabs &tabs, GfSwar &swar, co
 	__syncthreads();
 }
 
-// a word of a record another lane of this wave may have written earlier in this kernel
-__device__ __forceinline__ uint32_t dv_load_fresh(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// a value all lanes hold alike -> scalar registers
-__device__ __forceinline__ int64_t dv_u64(int64_t v)
-{
-	return (int64_t)(((uint64_t)(uint32_t)DV_U((uint32_t)((uint64_t)v >> 32)) << 32) | (uint32_t)DV_U((uint32_t)(uint64_t)v));
-}
-
-__device__ __forceinline__ uint32_t dv_wave_min(uint32_t v)
-{
-#pragma unroll
-	for (int m = 32; m >= 1; m >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m, 64));
-	return v;
-}
-
-__global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(
+// OTHER_KINDS = false: every group of the table is RS41 and the kind word is not read; true: the table has groups of SPEC 3.3l, which
+// are check_diversity_kernel.hip's.  The host launches the one that fits the table.
+template <bool OTHER_KINDS> __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(
 	const uint8_t *__restrict__ gf_exp, const uint8_t *__restrict__ gf_log, const uint32_t *__restrict__ gf_swar,
 	SondeFrame *frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
 	const SdDivGroup *__restrict__ groups, const SdDivState *states, uint32_t n_groups, uint32_t window, SondeFrame *carried,
@@ -226,84 +210,28 @@ __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(
 	if (g >= n_groups) return;
 	DivLds &s = wl[w];
 	const SdDivGroup *G = groups + g;
-	const int nm = DV_U(G->n);
-	// the members: channel, offset, records of this submit (wave-uniform; the member loops below are unrolled over SD_DIV_MAX).  The
-	// offsets and the lock bits are the align step's (SPEC 3.3k; an earlier launch, or as set_diversity left them): to steps 1 to 8 an
-	// unlocked member has no records (cnt), all[] is what the carried records are kept up to date from
-	const SdDivState *S = states + g;
-	const uint32_t lockmask = (uint32_t)DV_U(dv_load_fresh(&S->locked));
-	uint32_t ch[SD_DIV_MAX], cnt[SD_DIV_MAX], all[SD_DIV_MAX], start[SD_DIV_MAX + 1];
-	int64_t ofs[SD_DIV_MAX];
-	start[0] = 0;
-#pragma unroll
-	for (int m = 0; m < SD_DIV_MAX; m++) {
-		ch[m] = m < nm ? (uint32_t)DV_U(G->ch[m]) : 0u;
-		all[m] = m < nm ? (uint32_t)DV_U(min(counts[ch[m]], max_frames)) : 0u;
-		cnt[m] = (lockmask >> m) & 1u ? all[m] : 0u;
-		ofs[m] = m < nm ? dv_u64((int64_t)__hip_atomic_load(reinterpret_cast<const uint64_t *>(&S->off[m]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0;
-		start[m + 1] = start[m] + cnt[m];
-	}
-	const uint32_t total = start[SD_DIV_MAX];
-	auto rec_of = [&](int m, uint32_t i) -> SondeFrame * {
-		const uint32_t c = m == 0 ? ch[0] : m == 1 ? ch[1] : m == 2 ? ch[2] : ch[3];
-		return frames + (size_t)c * max_frames + i;
-	};
-	auto ofs_of = [&](int m) -> int64_t { return m == 0 ? ofs[0] : m == 1 ? ofs[1] : m == 2 ? ofs[2] : ofs[3]; };
-	auto cnt_of = [&](int m) -> uint32_t { return m == 0 ? cnt[0] : m == 1 ? cnt[1] : m == 2 ? cnt[2] : cnt[3]; };
+	if (OTHER_KINDS && DV_U(G->kind) != SONDE_RS41) return;
+	DvMembers M;                                   // the members, steps 1 and 2 and the carried records: sd_diversity_scan.h
+	dv_members(M, frames, counts, max_frames, G, states + g);
+	const int nm = M.nm;
 
-	// ---- steps 1 and 2: the failed records in ascending (t, member); a record an earlier visit rewrote has been visited, so what
-	// the scan reads of the records still to visit is what the first pass recorded
+	// ---- steps 1 and 2: the failed records in ascending (t, member)
 	uint32_t tried = 0, combined = 0;
-	int64_t last_t = INT64_MIN;
+	int64_t last_t = INT64_MIN, t_r;
 	int last_m = -1;
-	for (;;) {
-		int64_t bt = INT64_MAX;
-		uint32_t bk = 0xFFFFFFFFu;                     // member << 16 | record
-		for (uint32_t p = (uint32_t)lane; p < total; p += 64) {
-			const int m = p >= start[3] ? 3 : p >= start[2] ? 2 : p >= start[1] ? 1 : 0;
-			const uint32_t i = p - (m == 3 ? start[3] : m == 2 ? start[2] : m == 1 ? start[1] : 0u);
-			const SondeFrame *f = rec_of(m, i);
-			const int len = f->len;
-			if ((len != 320 && len != 518) || (f->nerr[0] >= 0 && f->nerr[1] >= 0)) continue;
-			const int64_t t = (int64_t)f->bitpos - ofs_of(m);
-			if (t < last_t || (t == last_t && m <= last_m)) continue;
-			const uint32_t k = ((uint32_t)m << 16) | i;
-			if (t < bt || (t == bt && k < bk)) { bt = t; bk = k; }
-		}
-#pragma unroll
-		for (int sh = 32; sh >= 1; sh >>= 1) {
-			const int64_t ot = __shfl_xor((long long)bt, sh, 64);
-			const uint32_t ok = (uint32_t)__shfl_xor((int)bk, sh, 64);
-			if (ot < bt || (ot == bt && ok < bk)) { bt = ot; bk = ok; }
-		}
-		bk = (uint32_t)DV_U(bk);
-		if (bk == 0xFFFFFFFFu) break;
-		const int64_t t_r = dv_u64(bt);
+	uint32_t bk;
+	while (dv_next_failed(M, SONDE_RS41, lane, last_t, last_m, t_r, bk)) {
 		const int m_r = (int)(bk >> 16);
-		last_t = t_r; last_m = m_r;
-		SondeFrame *fr = rec_of(m_r, bk & 0xFFFFu);
+		SondeFrame *fr = M.rec_of(m_r, bk & 0xFFFFu);
 		const int flen = DV_U(fr->len);
 		// partners: in every other member the nearest record of the same length within the window, this submit's or the carried one
-		// (key: 2 |dt| + (dt > 0), so that of two equally near ones the earlier wins; low half: record + 1, 0 = the carried record)
 		int K = 1;
 		bool any_good = false;
 #pragma unroll
 		for (int b = 0; b < SD_DIV_MAX; b++) {
-			if (b >= nm || b == m_r || any_good || !((lockmask >> b) & 1u)) continue;
-			uint32_t best = 0xFFFFFFFFu;
-			const SondeFrame *cf = carried + (size_t)SD_DIV_MAX * g + b;
-			for (uint32_t j = (uint32_t)lane; j <= cnt_of(b); j += 64) {       // j = cnt: the carried record
-				const SondeFrame *f = j < cnt_of(b) ? rec_of(b, j) : cf;
-				if (f->len != flen) continue;
-				const int64_t dt = (int64_t)f->bitpos - ofs_of(b) - t_r;
-				const uint64_t ad = (uint64_t)(dt < 0 ? -dt : dt);
-				if (ad > (uint64_t)window) continue;
-				best = min(best, (((uint32_t)ad * 2u + (dt > 0 ? 1u : 0u)) << 16) | (j < cnt_of(b) ? j + 1u : 0u));
-			}
-			best = (uint32_t)DV_U(dv_wave_min(best));
-			if (best == 0xFFFFFFFFu) continue;
-			const uint32_t idx = best & 0xFFFFu;
-			const SondeFrame *pf = idx ? rec_of(b, idx - 1u) : cf;
+			if (b >= nm || b == m_r || any_good || !((M.lockmask >> b) & 1u)) continue;
+			const SondeFrame *pf = dv_partner(M, b, flen, t_r, window, carried + (size_t)SD_DIV_MAX * g + b, lane);
+			if (!pf) continue;
 			const int pn0 = DV_U(dv_load_fresh(reinterpret_cast<const uint32_t *>(&pf->nerr[0])));
 			const int pn1 = DV_U(dv_load_fresh(reinterpret_cast<const uint32_t *>(&pf->nerr[1])));
 			if (pn0 >= 0 && pn1 >= 0) { any_good = true; continue; }
@@ -330,29 +258,17 @@ __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(
 	// ---- the carried records: each member's newest record of this submit with a frame length, as the pass left it
 	__threadfence();
 	WAVE_SYNC();
-#pragma unroll
-	for (int m = 0; m < SD_DIV_MAX; m++) {
-		if (m >= nm) continue;
-		uint32_t newest = 0;                           // record + 1
-		for (uint32_t j = (uint32_t)lane; j < all[m]; j += 64) {
-			const int len = rec_of(m, j)->len;
-			if (len == 320 || len == 518) newest = j + 1u;
-		}
-		newest = ~(uint32_t)DV_U(dv_wave_min(~newest));
-		if (!newest) continue;
-		const uint32_t *from = reinterpret_cast<const uint32_t *>(rec_of(m, newest - 1u));
-		uint32_t *to = reinterpret_cast<uint32_t *>(carried + (size_t)SD_DIV_MAX * g + m);
-		for (int i = lane; i < DV_REC_WORDS; i += 64) to[i] = dv_load_fresh(from + i);
-	}
+	dv_carry(M, SONDE_RS41, carried + (size_t)SD_DIV_MAX * g, lane);
 	if (lane == 0 && (tried | combined)) { counters[2 * g] += tried; counters[2 * g + 1] += combined; }
 }
 
 void sd_launch_diversity(uint32_t n_groups, hipStream_t stream, const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar,
 	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, const SdDivState *states, uint32_t window,
-	SondeFrame *carried, uint32_t *counters)
+	SondeFrame *carried, uint32_t *counters, uint32_t other_kinds)
 {
-	hipLaunchKernelGGL(sd_diversity_kernel, dim3((n_groups + DV_WAVES - 1) / DV_WAVES), dim3(64 * DV_WAVES), 0, stream,
-		gf_exp, gf_log, gf_swar, frames, counts, max_frames, groups, states, n_groups, window, carried, counters);
+	const dim3 grid((n_groups + DV_WAVES - 1) / DV_WAVES), block(64 * DV_WAVES);
+	if (other_kinds) hipLaunchKernelGGL(sd_diversity_kernel<true>, grid, block, 0, stream, gf_exp, gf_log, gf_swar, frames, counts, max_frames, groups, states, n_groups, window, carried, counters);
+	else hipLaunchKernelGGL(sd_diversity_kernel<false>, grid, block, 0, stream, gf_exp, gf_log, gf_swar, frames, counts, max_frames, groups, states, n_groups, window, carried, counters);
 }
 
 // ---- a restarted group (sonde_batch_restart_channels lists all its members): no carried records, counters zero, the align step's

@@ -127,11 +127,14 @@ void sd_launch_ims_block_unit(const uint8_t *g64, uint64_t *blocks, const uint64
 // steps 1..5 of 3.3i: n records; status = 0 untouched, 1 rescued, 2 several patterns fit
 void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status, hipStream_t stream);
 
-// sonde_batch_set_diversity (diversity_kernel.hip, DESIGN SPEC 3.3j): a group = 2..4 RS41 channels that hear the same sonde; ch[m] and
-// off[m] (offset_bits) per member.  carried: [n_groups][SD_DIV_MAX] records (len = 0: none), counters: [n_groups][2] (tried, combined);
-// both carried from submit to submit.  One launch behind every other kernel of the submit.
+// sonde_batch_set_diversity (DESIGN SPEC 3.3j, 3.3l): a group = 2..4 channels of one type that hear the same sonde; ch[m] and off[m]
+// (offset_bits) per member, kind = the members' type: SONDE_RS41 (0: diversity_kernel.hip), SONDE_M10 or SONDE_MRZN1
+// (check_diversity_kernel.hip).  Each combining kernel is launched over the whole table and takes the groups of its kinds; the align
+// step, the carried records, the counters and the state are one space for all kinds.  carried: [n_groups][SD_DIV_MAX] records
+// (len = 0: none), counters: [n_groups][2] (tried, combined); both carried from submit to submit.  The launches stand behind every
+// other kernel of the submit.
 #define SD_DIV_MAX 4
-struct SdDivGroup { uint32_t n; uint32_t ch[SD_DIV_MAX]; uint32_t pad; int64_t off[SD_DIV_MAX]; };
+struct SdDivGroup { uint32_t n; uint32_t ch[SD_DIV_MAX]; uint32_t kind; int64_t off[SD_DIV_MAX]; };
 // What the align step (diversity_align_kernel.hip, DESIGN SPEC 3.3k) carries per group from submit to submit and the combining pass
 // reads: off[m] = where member m's bit count stands on the group's clock (SdDivGroup.off is its initial value), locked = a bit per
 // member (an unlocked member is to the combining pass a member without records), learned / duplicates = the step's counters.  Without
@@ -139,14 +142,14 @@ struct SdDivGroup { uint32_t n; uint32_t ch[SD_DIV_MAX]; uint32_t pad; int64_t o
 struct SdDivState { int64_t off[SD_DIV_MAX]; uint32_t locked, learned, duplicates, pad; };
 void sd_launch_diversity(uint32_t n_groups, hipStream_t stream, const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar,
 	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, const SdDivState *states, uint32_t window,
-	SondeFrame *carried, uint32_t *counters);
+	SondeFrame *carried, uint32_t *counters, uint32_t other_kinds /* the table has groups that are not RS41 */);
 // the groups of the listed channels back to "no carried record, counters zero, offsets and locks as set_diversity left them"
 // (unlocked_start: the members of a group start unlocked); slot_of[channel] = SD_DIV_MAX * group + member or -1
 void sd_launch_diversity_clear(uint32_t n, hipStream_t stream, const uint32_t *list, const int32_t *slot_of, SondeFrame *carried, uint32_t *counters,
 	const SdDivGroup *groups, SdDivState *states, uint32_t unlocked_start);
 // the align step, one launch in front of sd_launch_diversity when mode != 0 (SONDE_DIVERSITY_LEARN | SONDE_DIVERSITY_MARK_DUPLICATES)
 void sd_launch_diversity_align(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
-	const SdDivGroup *groups, const SondeFrame *carried, SdDivState *states, uint32_t mode);
+	const SdDivGroup *groups, const SondeFrame *carried, SdDivState *states, uint32_t mode, uint32_t other_kinds);
 // the align step alone: n cases of SD_DIV_MAX members with max_rec record slots each (records[(4 k + m) * max_rec + i], counts[4 k + m]
 // in use, n_members[k] = 2..4), carried[4 k + m] (len 0: none), states[k] in and out, modes[k]; all device memory
 void sd_launch_diversity_align_unit(uint32_t n, hipStream_t stream, SondeFrame *records, const uint32_t *counts, uint32_t max_rec,
@@ -155,6 +158,16 @@ void sd_launch_diversity_align_unit(uint32_t n, hipStream_t stream, SondeFrame *
 // rewrite); out[i] = copy 0, rewritten or not; status = copies used, -1 too many erasures, -2 no decode, -3 rejected
 void sd_launch_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
 	const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar, hipStream_t stream);
+
+// the combining pass of SPEC 3.3l over the M10 / M20 / MRZ-N1 groups of the table (check_diversity_kernel.hip); launched only when the
+// batch has such a group.  m10tab / mrztab: the column tables of SPEC 3.3f
+void sd_launch_check_diversity(uint32_t n_groups, hipStream_t stream, const uint16_t *m10tab, const uint16_t *mrztab, SondeFrame *frames,
+	const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, const SdDivState *states, uint32_t window, SondeFrame *carried,
+	uint32_t *counters);
+// steps 3 to 6 of SPEC 3.3l alone, the shape of sd_launch_diversity_unit: status = copies used, -1 not attempted, -2 none fits,
+// -3 several fit
+void sd_launch_check_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
+	const uint16_t *m10tab, const uint16_t *mrztab, hipStream_t stream);
 
 // sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);

@@ -1,0 +1,143 @@
+// sd_diversity_scan.h -- what the two combining passes of sonde_batch_set_diversity share (diversity_kernel.hip, DESIGN SPEC 3.3j: RS41;
+// check_diversity_kernel.hip, SPEC 3.3l: M10 / M20 / MRZ-N1): the members of a group, steps 1 and 2 of SPEC 3.3j -- the scan of the
+// members' record headers for the next failed record in (t, member) order and for its partner in another member -- and the carried
+// records.  The two passes differ in two predicates, both functions of the group's kind (SdDivGroup.kind = the members' sonde type):
+// which record lengths are frames, and when a record has failed.  One 64-lane wave per group; every result is wave-uniform.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "sonde_dev.h"
+#include "launch.h"
+
+#define DV_U(x) __builtin_amdgcn_readfirstlane((int)(x))
+constexpr int DV_REC_WORDS = (int)(sizeof(SondeFrame) / 4);
+constexpr int DV_DATA_WORD0 = (int)(offsetof(SondeFrame, data) / 4);
+
+// a frame length of the kind: RS41 {320, 518}, M10 / M20 {101, 70}, MRZ-N1 {45}
+__device__ __forceinline__ bool dv_len_ok(uint32_t kind, int len)
+{
+	return kind == SONDE_M10 ? (len == 101 || len == 70) : kind == SONDE_MRZN1 ? len == 45 : (len == 320 || len == 518);
+}
+// failed: RS41 a codeword at nerr < 0, the others the 16-bit check (nerr[0] < 0; nerr[1] counts Manchester violations there)
+__device__ __forceinline__ bool dv_failed(uint32_t kind, const SondeFrame *f) { return f->nerr[0] < 0 || (kind == SONDE_RS41 && f->nerr[1] < 0); }
+
+// a word of a record another lane of this wave may have written earlier in this kernel
+__device__ __forceinline__ uint32_t dv_load_fresh(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// a value all lanes hold alike -> scalar registers
+__device__ __forceinline__ int64_t dv_u64(int64_t v)
+{
+	return (int64_t)(((uint64_t)(uint32_t)DV_U((uint32_t)((uint64_t)v >> 32)) << 32) | (uint32_t)DV_U((uint32_t)(uint64_t)v));
+}
+
+__device__ __forceinline__ uint32_t dv_wave_min(uint32_t v)
+{
+#pragma unroll
+	for (int m = 32; m >= 1; m >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, m, 64));
+	return v;
+}
+
+// The members of a group: channel, offset, records of this submit (wave-uniform; the member loops are unrolled over SD_DIV_MAX and the
+// selectors below keep the arrays in registers).  The offsets and the lock bits are the align step's (SPEC 3.3k; an earlier launch, or
+// as set_diversity left them): to steps 1 to 8 an unlocked member has no records (cnt), all[] is what the carried records are kept up
+// to date from.
+struct DvMembers {
+	SondeFrame *frames;
+	uint32_t max_frames, lockmask, total;
+	int nm;
+	uint32_t ch[SD_DIV_MAX], cnt[SD_DIV_MAX], all[SD_DIV_MAX], start[SD_DIV_MAX + 1];
+	int64_t ofs[SD_DIV_MAX];
+	__device__ __forceinline__ SondeFrame *rec_of(int m, uint32_t i) const
+	{
+		const uint32_t c = m == 0 ? ch[0] : m == 1 ? ch[1] : m == 2 ? ch[2] : ch[3];
+		return frames + (size_t)c * max_frames + i;
+	}
+	__device__ __forceinline__ int64_t ofs_of(int m) const { return m == 0 ? ofs[0] : m == 1 ? ofs[1] : m == 2 ? ofs[2] : ofs[3]; }
+	__device__ __forceinline__ uint32_t cnt_of(int m) const { return m == 0 ? cnt[0] : m == 1 ? cnt[1] : m == 2 ? cnt[2] : cnt[3]; }
+};
+
+__device__ __forceinline__ void dv_members(DvMembers &M, SondeFrame *frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
+	const SdDivGroup *G, const SdDivState *S)
+{
+	M.frames = frames; M.max_frames = max_frames;
+	M.nm = DV_U(G->n);
+	M.lockmask = (uint32_t)DV_U(dv_load_fresh(&S->locked));
+	M.start[0] = 0;
+#pragma unroll
+	for (int m = 0; m < SD_DIV_MAX; m++) {
+		M.ch[m] = m < M.nm ? (uint32_t)DV_U(G->ch[m]) : 0u;
+		M.all[m] = m < M.nm ? (uint32_t)DV_U(min(counts[M.ch[m]], max_frames)) : 0u;
+		M.cnt[m] = (M.lockmask >> m) & 1u ? M.all[m] : 0u;
+		M.ofs[m] = m < M.nm ? dv_u64((int64_t)__hip_atomic_load(reinterpret_cast<const uint64_t *>(&S->off[m]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0;
+		M.start[m + 1] = M.start[m] + M.cnt[m];
+	}
+	M.total = M.start[SD_DIV_MAX];
+}
+
+// Step 1: the failed record with the smallest (t, member) above the last one visited (last_t, last_m; both are moved on).  A record an
+// earlier visit rewrote has been visited, so what the scan reads of the records still to visit is what the first pass recorded.
+// Returns false when there is none; else t_r, and bk = member << 16 | record.
+__device__ __forceinline__ bool dv_next_failed(const DvMembers &M, uint32_t kind, int lane, int64_t &last_t, int &last_m, int64_t &t_r, uint32_t &bk_out)
+{
+	int64_t bt = INT64_MAX;
+	uint32_t bk = 0xFFFFFFFFu;                     // member << 16 | record
+	for (uint32_t p = (uint32_t)lane; p < M.total; p += 64) {
+		const int m = p >= M.start[3] ? 3 : p >= M.start[2] ? 2 : p >= M.start[1] ? 1 : 0;
+		const uint32_t i = p - (m == 3 ? M.start[3] : m == 2 ? M.start[2] : m == 1 ? M.start[1] : 0u);
+		const SondeFrame *f = M.rec_of(m, i);
+		if (!dv_len_ok(kind, f->len) || !dv_failed(kind, f)) continue;
+		const int64_t t = (int64_t)f->bitpos - M.ofs_of(m);
+		if (t < last_t || (t == last_t && m <= last_m)) continue;
+		const uint32_t k = ((uint32_t)m << 16) | i;
+		if (t < bt || (t == bt && k < bk)) { bt = t; bk = k; }
+	}
+#pragma unroll
+	for (int sh = 32; sh >= 1; sh >>= 1) {
+		const int64_t ot = __shfl_xor((long long)bt, sh, 64);
+		const uint32_t ok = (uint32_t)__shfl_xor((int)bk, sh, 64);
+		if (ot < bt || (ot == bt && ok < bk)) { bt = ot; bk = ok; }
+	}
+	bk = (uint32_t)DV_U(bk);
+	if (bk == 0xFFFFFFFFu) return false;
+	t_r = dv_u64(bt);
+	last_t = t_r; last_m = (int)(bk >> 16);
+	bk_out = bk;
+	return true;
+}
+
+// Step 2: the partner in member b of a record of length flen at t_r -- the nearest record of the same length within the window, this
+// submit's or the carried one cf (key: 2 |dt| + (dt > 0), so that of two equally near ones the earlier wins; low half: record + 1,
+// 0 = the carried record).  Null: none.
+__device__ __forceinline__ const SondeFrame *dv_partner(const DvMembers &M, int b, int flen, int64_t t_r, uint32_t window, const SondeFrame *cf, int lane)
+{
+	uint32_t best = 0xFFFFFFFFu;
+	for (uint32_t j = (uint32_t)lane; j <= M.cnt_of(b); j += 64) {       // j = cnt: the carried record
+		const SondeFrame *f = j < M.cnt_of(b) ? M.rec_of(b, j) : cf;
+		if (f->len != flen) continue;
+		const int64_t dt = (int64_t)f->bitpos - M.ofs_of(b) - t_r;
+		const uint64_t ad = (uint64_t)(dt < 0 ? -dt : dt);
+		if (ad > (uint64_t)window) continue;
+		best = min(best, (((uint32_t)ad * 2u + (dt > 0 ? 1u : 0u)) << 16) | (j < M.cnt_of(b) ? j + 1u : 0u));
+	}
+	best = (uint32_t)DV_U(dv_wave_min(best));
+	if (best == 0xFFFFFFFFu) return nullptr;
+	const uint32_t idx = best & 0xFFFFu;
+	return idx ? M.rec_of(b, idx - 1u) : cf;
+}
+
+// The carried records: each member's newest record of this submit with a frame length, as the pass left it (carried_g: the group's
+// SD_DIV_MAX slots).  The caller has fenced its own record stores.
+__device__ __forceinline__ void dv_carry(const DvMembers &M, uint32_t kind, SondeFrame *carried_g, int lane)
+{
+#pragma unroll
+	for (int m = 0; m < SD_DIV_MAX; m++) {
+		if (m >= M.nm) continue;
+		uint32_t newest = 0;                           // record + 1
+		for (uint32_t j = (uint32_t)lane; j < M.all[m]; j += 64)
+			if (dv_len_ok(kind, M.rec_of(m, j)->len)) newest = j + 1u;
+		newest = ~(uint32_t)DV_U(dv_wave_min(~newest));
+		if (!newest) continue;
+		const uint32_t *from = reinterpret_cast<const uint32_t *>(M.rec_of(m, newest - 1u));
+		uint32_t *to = reinterpret_cast<uint32_t *>(carried_g + m);
+		for (int i = lane; i < DV_REC_WORDS; i += 64) to[i] = dv_load_fresh(from + i);
+	}
+}

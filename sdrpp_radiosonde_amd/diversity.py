@@ -1,4 +1,4 @@
-"""Python face of a receiver with several antennas (DESIGN SPEC 3.3k): thin, no compute -- every call goes through the C ABI of
+"""Python face of a receiver with several antennas (DESIGN SPEC 3.3k, 3.3l): thin, no compute -- every call goes through the C ABI of
 libsonde_mi355.so.
 
     DiversityReceiver   K wideband streams (one per antenna or polarisation, started whenever) -> K tuners with the same VFO list ->
@@ -9,22 +9,23 @@ libsonde_mi355.so.
                         detection -> one SondeBatch of one channel per sonde: any sonde type, the antennas on one sample clock
 
 The chain is the "iq48" chain of _chain.py, which WidebandReceiver (tuner.py) and LiveReceiver share: a tuner per antenna straight to
-48 kHz IQ rows.  combine="frames" (the default): RS41 sondes only.  No tracking, no reference chain."""
+48 kHz IQ rows.  combine="frames" (the default): RS41, M10 / M20 and MRZ-N1 sondes, in any mix.  No tracking, no reference chain."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import _chain
 from ._handle import current_stream
-from ._lib import FRAME_DUPLICATE, INPUT_IQ, RS41, SondeError
+from ._lib import FRAME_DUPLICATE, INPUT_IQ, M10, MRZN1, RS41, SondeError
 from .tuner import SondeTuner
 
 
 class DiversityReceiver:
-    """sondes: [(offset_hz, sonde type), ...], every type RS41; antennas = K = 2..4 wideband streams at rate_in that hear them.
+    """sondes: [(offset_hz, sonde type), ...], every type RS41, M10 (M10 and M20) or MRZN1; antennas = K = 2..4 wideband streams at rate_in that hear them.
     Batch channel a * len(sondes) + i is sonde i on antenna a; the K channels of sonde i are diversity group i, antenna a its member a,
     set with learn=True, mark_duplicates=True and no offsets: the streams need not start together, the group finds out where they
-    stand from the first frame that is good on two antennas (SondeBatch.set_diversity).
+    stand from the first frame that is good on two antennas (SondeBatch.set_diversity).  rescue= (RS41) and manchester_rescue= (M10 /
+    M20 / MRZ-N1) are the batch's second passes in front of the diversity pass; what they complete counts as a good copy.
 
     submit(blocks) takes K device blocks [n, 2] of equal length (float32 / int16 / int8 by input_kind), n a multiple of `granule`
     and <= max_in.  frames() returns (records, antenna): the last submit's records without the duplicates, `channel` = the sonde
@@ -56,10 +57,10 @@ class DiversityReceiver:
         coherent = combine == "coherent"
         types = [t for _, t in self.sondes]
         if not coherent:
-            if manchester_rescue or dfm_rescue or ims_rescue or afsk_rescue:
-                raise SondeError('DiversityReceiver: combine="frames" is RS41 only and takes no rescue pass but rescue=')
-            if any(t != RS41 for t in types):
-                raise SondeError("DiversityReceiver: RS41 sondes only (the diversity pass is RS41's)")
+            if dfm_rescue or ims_rescue or afsk_rescue:
+                raise SondeError('DiversityReceiver: combine="frames" takes no rescue pass but rescue= and manchester_rescue=')
+            if any(t not in (RS41, M10, MRZN1) for t in types):
+                raise SondeError('DiversityReceiver: the frame-level pass serves M10 / M20, MRZ-N1 and RS41 sondes only (combine="coherent" takes any type)')
         self.antennas = int(antennas)
         if not 2 <= self.antennas <= 4:
             raise SondeError("DiversityReceiver: 2..4 antennas")
