@@ -7,16 +7,14 @@
 //   covered bytes behind it, bit 8 + j / bit j of the syndrome itself for the two stored bytes.  Lane i owns byte i of the packet
 //   (at most 64), XORs the columns of its set bits into the wave's syndrome and compares its 15 patterns with it.
 //   C50: the two running byte sums are not linear over GF(2); lanes 2..8 recompute them over data XOR each of their 15 patterns.
-//   one 64-lane wave per channel, four waves per workgroup; lanes load the headers of 64 records at once and the wave works on
-//   the candidates among them one by one.  No LDS, no table in memory.
+//   The walk over the records is sd_rescue_walk.h's.  No LDS, no table in memory.
 // Runs behind sd_imet_kernel / sd_c50_kernel, on the same stream, and rewrites the records in place.  It reads the records only (not
 // the bit ring), and the records of a channel are independent of each other (only the two counters are shared), so the result
 // does not depend on the cut into submits.  Vector stores only.
 #include <hip/hip_runtime.h>
 #include "sonde_dev.h"
-#include "launch.h"
+#include "sd_rescue_walk.h"
 
-#define AQ_WAVES 4
 #define AQ_IMET_MAXLEN 64      // sd_imet_kernel records nothing longer: one lane per packet byte
 #define AQ_C50_LEN 9
 
@@ -50,13 +48,19 @@ __device__ __forceinline__ uint32_t aq_imet_cols(uint32_t c0, uint32_t m)
 // pattern q = 0 .. 14 of SPEC 3.3i step 3: the single-bit masks 1 << q, then the adjacent-pair masks 3 << (q - 8)
 __device__ __forceinline__ uint32_t aq_pattern(int q) { return q < 8 ? 1u << q : 3u << (q - 8); }
 
+// SPEC 3.3i step 1: the records the pass works on -- a packet of a known shape whose check failed
+__device__ __forceinline__ bool aq_imet(uint32_t type, int len) { return type == SONDE_IMET4 && len >= 5 && len <= AQ_IMET_MAXLEN; }
+__device__ __forceinline__ bool aq_eligible(uint32_t type, int len, int nerr0)
+{
+	return (aq_imet(type, len) || (type == SONDE_C50 && len == AQ_C50_LEN)) && nerr0 == -1;
+}
+
 // Steps 1..5 of SPEC 3.3i for ONE record, by a whole wave (type, len, nerr0: the record's header, wave-uniform).
 // Returns -1: not eligible; 0: no pattern fits; 1: rescued (the record is rewritten); 2: several patterns fit.
 __device__ __forceinline__ int aq_repair(SondeFrame *__restrict__ fr, uint32_t type, int len, int nerr0, int lane)
 {
-	const bool imet = type == SONDE_IMET4 && len >= 5 && len <= AQ_IMET_MAXLEN;
-	const bool c50 = type == SONDE_C50 && len == AQ_C50_LEN;
-	if (!(imet || c50) || nerr0 != -1) return -1;
+	if (!aq_eligible(type, len, nerr0)) return -1;
+	const bool imet = aq_imet(type, len);
 	const uint32_t d = lane < len ? fr->data[lane] : 0u;
 	int first = 2;
 	uint32_t fit = 0;                       // bit q: pattern q of this lane's byte fits
@@ -104,53 +108,30 @@ __device__ __forceinline__ int aq_repair(SondeFrame *__restrict__ fr, uint32_t t
 	return 1;
 }
 
-__global__ __launch_bounds__(64 * AQ_WAVES) void sd_afsk_rescue_kernel(SondeFrame *__restrict__ frames, const uint32_t *__restrict__ counts,
-	uint32_t max_frames, const uint32_t *__restrict__ chlist, uint32_t n_list, SdRescueCounters *__restrict__ states)
-{
-	const int lane = threadIdx.x & 63;
-	const uint32_t li_ch = AQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
-	if (li_ch >= n_list) return;
-	const uint32_t ch = chlist[li_ch];
-	const uint32_t nfr = min(counts[ch], max_frames);
-	if (nfr == 0) return;
-	SondeFrame *const chfr = frames + (size_t)ch * max_frames;
-	uint32_t tried = 0, rescued = 0;
+struct AqPass {
+	static constexpr uint32_t header = SD_H_TYPE | SD_H_LEN | SD_H_NERR0;          // no bitpos: the pass reads no ring
+	__device__ __forceinline__ bool candidate(const SdRecHeader &h) const { return aq_eligible(h.type, h.len, h.nerr0); }
+	__device__ __forceinline__ int repair(SondeFrame *fr, const SdRecHeader &h, const SdRescueCtx &ctx) const
+	{
+		const int r = aq_repair(fr, h.type, h.len, h.nerr0, ctx.lane);
+		return r < 0 ? SD_RESCUE_SKIPPED : r == 1 ? SD_RESCUE_DONE : SD_RESCUE_TRIED;
+	}
+};
 
-	for (uint32_t base = 0; base < nfr; base += 64) {
-		// the headers of records base .. base + 63, one per lane
-		int h_len = 0;
-		uint32_t h_type = 0;
-		bool cand = false;
-		if (base + (uint32_t)lane < nfr) {
-			const SondeFrame *f = chfr + base + lane;
-			h_type = f->type; h_len = f->len;
-			cand = f->nerr[0] == -1 && ((h_type == SONDE_IMET4 && h_len >= 5 && h_len <= AQ_IMET_MAXLEN) || (h_type == SONDE_C50 && h_len == AQ_C50_LEN));
-		}
-		for (unsigned long long cm = __ballot(cand); cm; cm &= cm - 1ull) {
-			const int q = __builtin_ctzll(cm);
-			const int r = aq_repair(chfr + base + q, (uint32_t)__builtin_amdgcn_readlane((int)h_type, q), __builtin_amdgcn_readlane(h_len, q), -1, lane);
-			tried += r >= 0;
-			rescued += r == 1;
-		}
-	}
-	if (tried && lane == 0) {
-		states[ch].tried += tried;
-		states[ch].rescued += rescued;
-	}
+__global__ __launch_bounds__(64 * SD_RESCUE_WAVES) void sd_afsk_rescue_kernel(SdRescueWalk a)
+{
+	AqPass pass;
+	sd_rescue_walk(a, pass);
 }
 
-void sd_launch_rescue_afsk(const SdRescueArgs &a)
-{
-	hipLaunchKernelGGL(sd_afsk_rescue_kernel, dim3((a.n_list + AQ_WAVES - 1) / AQ_WAVES), dim3(64 * AQ_WAVES), 0, a.stream,
-		a.frames, a.counts, a.max_frames, a.chlist, a.n_list, (SdRescueCounters *)a.states);
-}
+void sd_launch_rescue_afsk(const SdRescueArgs &a) { sd_rescue_launch(sd_afsk_rescue_kernel, a); }
 
 // ---- aq_repair alone over n caller-made records, one wave each (sonde_batch_test_afsk_repair): status 0 untouched, 1 rescued,
 // 2 several patterns fit
-__global__ __launch_bounds__(64 * AQ_WAVES) void sd_afsk_repair_unit_kernel(SondeFrame *__restrict__ records, uint32_t n, int32_t *__restrict__ status)
+__global__ __launch_bounds__(64 * SD_RESCUE_WAVES) void sd_afsk_repair_unit_kernel(SondeFrame *__restrict__ records, uint32_t n, int32_t *__restrict__ status)
 {
 	const int lane = threadIdx.x & 63;
-	const uint32_t i = AQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
+	const uint32_t i = SD_RESCUE_WAVES * blockIdx.x + (threadIdx.x >> 6);
 	if (i >= n) return;
 	SondeFrame *fr = records + i;
 	const uint32_t type = (uint32_t)__builtin_amdgcn_readfirstlane((int)fr->type);
@@ -160,5 +141,5 @@ __global__ __launch_bounds__(64 * AQ_WAVES) void sd_afsk_repair_unit_kernel(Sond
 }
 void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status, hipStream_t stream)
 {
-	hipLaunchKernelGGL(sd_afsk_repair_unit_kernel, dim3((n + AQ_WAVES - 1) / AQ_WAVES), dim3(64 * AQ_WAVES), 0, stream, records, n, status);
+	hipLaunchKernelGGL(sd_afsk_repair_unit_kernel, dim3((n + SD_RESCUE_WAVES - 1) / SD_RESCUE_WAVES), dim3(64 * SD_RESCUE_WAVES), 0, stream, records, n, status);
 }

@@ -5,27 +5,37 @@
 #include <vector>
 #include "batch_impl.h"
 
+// What every unit entry below does around its launch, on the device the caller has selected: the cases `in` (n_io elements; null: a
+// buffer for results only) and a status of n_st words in device memory, launch(cases, status), the launch's error, and cases and
+// status back into out and status.  A HIP call that fails here is reported under the entry's name.
+template <typename T, typename Launch>
+static int probe_unit(const char *who, const T *in, T *out, size_t n_io, int32_t *status, size_t n_st, Launch launch)
+{
+	DevBuf<T> d_io;
+	DevBuf<int32_t> d_st;
+	hipError_t e = in ? d_io.upload(in, n_io) : d_io.alloc(n_io);
+	if (e == hipSuccess) e = d_st.alloc(n_st);
+	if (e == hipSuccess) { launch((T *)d_io, (int32_t *)d_st); e = hipGetLastError(); }
+	if (e == hipSuccess) e = hipMemcpy(out, d_io, n_io * sizeof(T), hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(status, d_st, n_st * sizeof(int32_t), hipMemcpyDeviceToHost);
+	return e == hipSuccess ? 0 : sd_fail(who, e);
+}
+
 // The RS(255,231) corrector alone: n_pairs codeword pairs of [2][256] bytes (positions >= n zero), corrected in place;
 // status[2 * i + c]: 0 clean, > 0 corrected byte errors, -1 uncorrectable (word left as received).
 // erased = null: errors only (sd_rsdec.h); else the errors-and-erasures corrector of SONDE_FLAG_RS41_RESCUE (sd_rsee.h), with
 // erased[i][c][k] != 0 marking position k.
-#define RSCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return sd_fail(who, e_); } while (0)      // (the text is the entry's name, as it always was)
 static int test_rs255(const char *who, SondeBatch *b, uint8_t *cw_pairs, size_t n_pairs, int n, const uint8_t *erased, int32_t *status)
 {
 	HIPCHK(hipSetDevice(b->device));
-	DevBuf<uint8_t> d_cw, d_er;
-	DevBuf<int32_t> d_st;
-	RSCHK(d_cw.upload(cw_pairs, n_pairs * 512));
-	if (erased) RSCHK(d_er.upload(erased, n_pairs * 512));
-	RSCHK(d_st.alloc(n_pairs * 2));
-	if (erased) sd_launch_rsee_unit(d_cw, d_er, (uint32_t)n_pairs, n, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
-	else sd_launch_rs255_unit(d_cw, (uint32_t)n_pairs, n, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
-	RSCHK(hipGetLastError());
-	RSCHK(hipMemcpy(cw_pairs, d_cw, n_pairs * 512, hipMemcpyDeviceToHost));
-	RSCHK(hipMemcpy(status, d_st, n_pairs * 2 * sizeof(int32_t), hipMemcpyDeviceToHost));
-	return 0;
+	DevBuf<uint8_t> d_er;
+	const hipError_t e = erased ? d_er.upload(erased, n_pairs * 512) : hipSuccess;
+	if (e != hipSuccess) return sd_fail(who, e);
+	return probe_unit(who, cw_pairs, cw_pairs, n_pairs * 512, status, n_pairs * 2, [&](uint8_t *d_cw, int32_t *d_st) {
+		if (erased) sd_launch_rsee_unit(d_cw, d_er, (uint32_t)n_pairs, n, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
+		else sd_launch_rs255_unit(d_cw, (uint32_t)n_pairs, n, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
+	});
 }
-#undef RSCHK
 
 extern "C" int sonde_batch_test_rs255(SondeBatch *b, uint8_t *cw_pairs, size_t n_pairs, int n, int32_t *status)
 {
@@ -86,16 +96,10 @@ extern "C" int sonde_batch_test_hamming84_erasures(SondeBatch *b, uint8_t *words
 {
 	if (!b || !words || !erased || !status || !n || n > (1u << 24)) return sd_fail("sonde_batch_test_hamming84_erasures: bad argument");
 	HIPCHK(hipSetDevice(b->device));
-	DevBuf<uint8_t> d_w, d_e;
-	DevBuf<int32_t> d_st;
-	HIPCHK(d_w.upload(words, n));
+	DevBuf<uint8_t> d_e;
 	HIPCHK(d_e.upload(erased, n));
-	HIPCHK(d_st.alloc(n));
-	sd_launch_hamming84_unit(d_w, d_e, (uint32_t)n, d_st, nullptr);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(words, d_w, n, hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-	return 0;
+	return probe_unit("sonde_batch_test_hamming84_erasures", words, words, n, status, n,
+		[&](uint8_t *d_w, int32_t *d_st) { sd_launch_hamming84_unit(d_w, d_e, (uint32_t)n, d_st, nullptr); });
 }
 
 // Step 3 of SPEC 3.3h alone, through the kernel's own device function: n blocks (bit b of the block = bit 45 - b) and the masks of
@@ -104,16 +108,10 @@ extern "C" int sonde_batch_test_ims_block(SondeBatch *b, size_t n, uint64_t *blo
 {
 	if (!b || !blocks || !viol || !status || !n || n > (1u << 24)) return sd_fail("sonde_batch_test_ims_block: bad argument");
 	HIPCHK(hipSetDevice(b->device));
-	DevBuf<uint64_t> d_b, d_v;
-	DevBuf<int32_t> d_st;
-	HIPCHK(d_b.upload(blocks, n));
+	DevBuf<uint64_t> d_v;
 	HIPCHK(d_v.upload(viol, n));
-	HIPCHK(d_st.alloc(n));
-	sd_launch_ims_block_unit(b->fec.g64, d_b, d_v, (uint32_t)n, d_st, nullptr);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(blocks, d_b, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-	return 0;
+	return probe_unit("sonde_batch_test_ims_block", blocks, blocks, n, status, n,
+		[&](uint64_t *d_b, int32_t *d_st) { sd_launch_ims_block_unit(b->fec.g64, d_b, d_v, (uint32_t)n, d_st, nullptr); });
 }
 
 // Steps 1..5 of SPEC 3.3i alone, through the kernel's own device function: n caller-made records, rewritten in place where rescued;
@@ -122,15 +120,8 @@ extern "C" int sonde_batch_test_afsk_repair(SondeBatch *b, SondeFrame *records, 
 {
 	if (!b || !records || !status || !n || n > (1u << 20)) return sd_fail("sonde_batch_test_afsk_repair: bad argument");
 	HIPCHK(hipSetDevice(b->device));
-	DevBuf<SondeFrame> d_r;
-	DevBuf<int32_t> d_st;
-	HIPCHK(d_r.upload(records, n));
-	HIPCHK(d_st.alloc(n));
-	sd_launch_afsk_repair_unit(d_r, (uint32_t)n, d_st, nullptr);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(records, d_r, n * sizeof(SondeFrame), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-	return 0;
+	return probe_unit("sonde_batch_test_afsk_repair", records, records, n, status, n,
+		[&](SondeFrame *d_r, int32_t *d_st) { sd_launch_afsk_repair_unit(d_r, (uint32_t)n, d_st, nullptr); });
 }
 
 extern "C" int sonde_batch_diversity_info(SondeBatch *b, uint32_t group, uint32_t *tried, uint32_t *combined)
@@ -160,18 +151,13 @@ extern "C" int sonde_batch_test_rs41_combine(SondeBatch *b, size_t n, const Sond
 			if (c[k].len != c[0].len) return sd_fail("sonde_batch_test_rs41_combine: the copies of a case must have one length");
 	}
 	HIPCHK(hipSetDevice(b->device));
-	DevBuf<SondeFrame> d_c, d_o;
+	DevBuf<SondeFrame> d_c;
 	DevBuf<uint32_t> d_n;
-	DevBuf<int32_t> d_st;
 	HIPCHK(d_c.upload(copies, SD_DIV_MAX * n));
 	HIPCHK(d_n.upload(n_copies, n));
-	HIPCHK(d_o.alloc(n));
-	HIPCHK(d_st.alloc(n));
-	sd_launch_diversity_unit(d_c, d_n, (uint32_t)n, d_o, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(out, d_o, n * sizeof(SondeFrame), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-	return 0;
+	return probe_unit("sonde_batch_test_rs41_combine", (const SondeFrame *)nullptr, out, n, status, n, [&](SondeFrame *d_o, int32_t *d_st) {
+		sd_launch_diversity_unit(d_c, d_n, (uint32_t)n, d_o, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
+	});
 }
 
 // Steps 3 to 6 of SPEC 3.3l alone, through the kernel's own device function: the shape of sonde_batch_test_rs41_combine; status[i] =
@@ -189,22 +175,17 @@ extern "C" int sonde_batch_test_check_combine(SondeBatch *b, size_t n, const Son
 			if (c[k].len != c[0].len || c[k].type != c[0].type) return sd_fail("sonde_batch_test_check_combine: the copies of a case must have one type and one length");
 	}
 	HIPCHK(hipSetDevice(b->device));
-	DevBuf<SondeFrame> d_c, d_o;
+	DevBuf<SondeFrame> d_c;
 	DevBuf<uint32_t> d_n;
-	DevBuf<int32_t> d_st;
 	DevBuf<uint16_t> d_mrz;                 // a table of the call's own: the batch stays as it is
 	uint16_t mrz[43 * 8];
 	fec_mrz_table(mrz);
 	HIPCHK(d_mrz.upload(mrz, 43 * 8));
 	HIPCHK(d_c.upload(copies, SD_DIV_MAX * n));
 	HIPCHK(d_n.upload(n_copies, n));
-	HIPCHK(d_o.alloc(n));
-	HIPCHK(d_st.alloc(n));
-	sd_launch_check_diversity_unit(d_c, d_n, (uint32_t)n, d_o, d_st, b->fec.m10tab, d_mrz, nullptr);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpy(out, d_o, n * sizeof(SondeFrame), hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(status, d_st, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-	return 0;
+	return probe_unit("sonde_batch_test_check_combine", (const SondeFrame *)nullptr, out, n, status, n, [&](SondeFrame *d_o, int32_t *d_st) {
+		sd_launch_check_diversity_unit(d_c, d_n, (uint32_t)n, d_o, d_st, b->fec.m10tab, d_mrz, nullptr);
+	});
 }
 
 extern "C" int sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t off[4], uint32_t *locked_mask, uint32_t *learned, uint32_t *duplicates)

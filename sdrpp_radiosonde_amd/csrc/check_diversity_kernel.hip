@@ -73,24 +73,13 @@ __device__ int cd_combine(const uint16_t *__restrict__ m10tab, const uint16_t *_
 	// ---- 5. solve
 	if (nv == 0 || nv > MQ_MAX_HINTS) return -1;
 	if (!mrz && (DV_U(vm) & 0xFF)) return -1;                  // M10 / M20: the length byte decides the layout
-	int myk = 0, n = 0;                                        // V, ascending, into lanes 0 .. nv - 1
-	for (unsigned long long lm = __ballot(vm != 0u); lm; lm &= lm - 1ull) {
-		const int l = __builtin_ctzll(lm);
-		for (uint32_t q = (uint32_t)__builtin_amdgcn_readlane((int)vm, l); q; q &= q - 1u) {
-			if (lane == n) myk = 32 * l + __builtin_ctz(q);
-			n++;
-		}
-	}
+	const int myk = mq_gather<32>(vm, lane);                   // V, ascending, into lanes 0 .. nv - 1
 	uint32_t col = 0;
 	if (lane < nv) col = mq_col(mq_row(tab, n_cov, hi_first, myk >> 3), 7 - (myk & 7));
 	uint32_t U = 0;
 	const int nhit = mq_solve(col, nv, s, lane, U);
 	if (nhit != 1) return nhit ? -3 : -2;
-#pragma unroll
-	for (int j = 0; j < MQ_MAX_HINTS; j++) {
-		const int kj = __builtin_amdgcn_readlane(myk, j);
-		if (((U >> j) & 1u) && (kj >> 5) == lane) w ^= 1u << (8 * ((kj >> 3) & 3) + 7 - (kj & 7));
-	}
+	w ^= mq_flips<4>(U, myk, 4 * lane);
 	return K;
 }
 

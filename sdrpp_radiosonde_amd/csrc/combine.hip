@@ -5,8 +5,8 @@
 //
 // Three launches per submit on the caller's stream, and no workgroup ever waits for another:
 //   sd_combine_stats_kernel    one 256-lane workgroup per (sonde, block of L samples): M = sum x x^H, K powers and K (K - 1) / 2 complex
-//                              cross terms, in the carrier meter's arithmetic (track.hip: float32 products with one fmaf, each aligned
-//                              256-sample block in the meter's lane and butterfly order, block sums into doubles in ascending order)
+//                              cross terms, in the carrier meter's arithmetic (sd_blocksum.h: float32 products with one fmaf, each
+//                              aligned 256-sample block in the meter's lane and butterfly order, block sums into doubles in ascending order)
 //   sd_combine_weights_kernel  one lane per sonde walks its blocks in order: sd_combine_weights (sd_combine.h) from M and the previous
 //                              block's weights; the sonde's last weights are all that is carried to the next submit
 //   sd_combine_apply_kernel    one workgroup per (sonde, block): the float32 fmaf chain, 16-byte loads and nontemporal 16-byte stores
@@ -21,11 +21,10 @@
 #include "sd_host.h"
 #include "sd_devmem.h"
 #include "sd_combine.h"
+#include "sd_blocksum.h"
 #include "../../include/sonde_abi.h"
 
-#define CB_WG     256
-#define CB_BLK    256                   // samples per summation block (the meter's)
-#define CB_CHUNK  32                    // summation blocks per trip through LDS (8 per wave)
+#define CB_WG     SD_BS_WG              // the apply kernel's workgroup too
 #define CB_NQ     16                    // doubles of M
 #define CB_VMAX   512                   // sondes per weights launch: their restart bits travel with the launch, by value
 #define CB_MAXLB  16384                 // largest block, in summation blocks
@@ -39,12 +38,12 @@ template <int K> __global__ __launch_bounds__(CB_WG) void sd_combine_stats_kerne
 	uint32_t max_blocks, double *__restrict__ stat)
 {
 	constexpr int NP = K * (K - 1) / 2, NQ = K + 2 * NP;
-	__shared__ float s_bs[NQ][CB_CHUNK];
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	__shared__ float s_bs[NQ][SD_BS_CHUNK];
+	const uint32_t tid = threadIdx.x;
 	const uint32_t b = blockIdx.x, sonde = blockIdx.y;
 	const float2 *x[K];
 #pragma unroll
-	for (int a = 0; a < K; a++) x[a] = rows + ((size_t)a * S + sonde) * stride + (size_t)b * LB * CB_BLK;
+	for (int a = 0; a < K; a++) x[a] = rows + ((size_t)a * S + sonde) * stride + (size_t)b * LB * SD_BS_BLK;
 	// quantity tid < NQ -> its place among the 16 doubles: powers first, then the pairs (a, c), a < c, in the K = 4 numbering
 	int slot = 0;
 	if (tid < (uint32_t)K) slot = (int)tid;
@@ -54,48 +53,27 @@ template <int K> __global__ __launch_bounds__(CB_WG) void sd_combine_stats_kerne
 		const int p4 = a == 0 ? c - 1 : a == 1 ? c + 1 : 5;
 		slot = 4 + 2 * p4 + (((int)tid - K) & 1);
 	}
-	double acc = 0.0;
-	for (uint32_t c0 = 0; c0 < LB; c0 += CB_CHUNK) {
-		const uint32_t cn = min((uint32_t)CB_CHUNK, LB - c0);
-		for (uint32_t q = wave; q < cn; q += 4) {
-			const size_t m0 = (size_t)(c0 + q) * CB_BLK + lane;
-			float2 xv[K][4];
+	// the K powers, then re and im of x_a conj(x_c) for the pairs a < c, of sample m of the block
+	struct Across { float2 x[K]; };
+	const double acc = sd_blocksum<NQ>(0u, LB, 0.0, s_bs,
+		[&](int64_t m) {
+			Across v;
+#pragma unroll
+			for (int a = 0; a < K; a++) v.x[a] = x[a][m];
+			return v;
+		},
+		[](const Across &v, float (&p)[NQ]) {
+			int k = 0;
+#pragma unroll
+			for (int a = 0; a < K; a++, k++) p[k] = __builtin_fmaf(v.x[a].x, v.x[a].x, v.x[a].y * v.x[a].y);
 #pragma unroll
 			for (int a = 0; a < K; a++)
 #pragma unroll
-				for (int r = 0; r < 4; r++) xv[a][r] = x[a][m0 + 64 * r];
-			float s[NQ];
-#pragma unroll
-			for (int r = 0; r < 4; r++) {
-				int k = 0;
-#pragma unroll
-				for (int a = 0; a < K; a++, k++) {
-					const float pp = __builtin_fmaf(xv[a][r].x, xv[a][r].x, xv[a][r].y * xv[a][r].y);
-					s[k] = r ? s[k] + pp : pp;
+				for (int c = a + 1; c < K; c++, k += 2) {
+					p[k] = __builtin_fmaf(v.x[a].x, v.x[c].x, v.x[a].y * v.x[c].y);
+					p[k + 1] = __builtin_fmaf(v.x[a].y, v.x[c].x, -(v.x[a].x * v.x[c].y));
 				}
-#pragma unroll
-				for (int a = 0; a < K; a++)
-#pragma unroll
-					for (int c = a + 1; c < K; c++, k += 2) {
-						const float cr = __builtin_fmaf(xv[a][r].x, xv[c][r].x, xv[a][r].y * xv[c][r].y);
-						const float ci = __builtin_fmaf(xv[a][r].y, xv[c][r].x, -(xv[a][r].x * xv[c][r].y));
-						s[k] = r ? s[k] + cr : cr; s[k + 1] = r ? s[k + 1] + ci : ci;
-					}
-			}
-#pragma unroll
-			for (int o = 32; o >= 1; o >>= 1)
-#pragma unroll
-				for (int k = 0; k < NQ; k++) s[k] += __shfl_xor(s[k], o, 64);
-			if (lane == 0) {
-#pragma unroll
-				for (int k = 0; k < NQ; k++) s_bs[k][q] = s[k];
-			}
-		}
-		__syncthreads();
-		if (tid < (uint32_t)NQ)
-			for (uint32_t q = 0; q < cn; q++) acc += (double)s_bs[tid][q];
-		__syncthreads();
-	}
+		});
 	if (tid < (uint32_t)NQ) stat[((size_t)sonde * max_blocks + b) * CB_NQ + slot] = acc;
 }
 
@@ -232,7 +210,7 @@ extern "C" int sonde_combine_create(uint32_t n_sondes, uint32_t antennas, uint32
 	uint32_t L0;
 	if (sonde_combine_defaults(rate, &L0)) return sd_fail("sonde_combine_create: rate must be 5000 .. 100 000 Hz");
 	const uint32_t L = block ? block : L0;
-	if (L % CB_BLK || L / CB_BLK > CB_MAXLB) return sd_fail("sonde_combine_create: block must be a multiple of 256, at most 4 194 304 (0 = 1024)");
+	if (L % SD_BS_BLK || L / SD_BS_BLK > CB_MAXLB) return sd_fail("sonde_combine_create: block must be a multiple of 256, at most 4 194 304 (0 = 1024)");
 	if (!max_samples || max_samples % L || max_samples >= (1u << 30)) return sd_fail("sonde_combine_create: max_samples must be a positive multiple of the block length below 2^30");
 	if (sd_select_device(device, "sonde_combine_create")) return -1;
 	SondeCombiner *c = new SondeCombiner;
@@ -248,7 +226,7 @@ extern "C" int sonde_combine_block(const SondeCombiner *c) { return c ? (int)c->
 template <int K> static void cb_launch(SondeCombiner *c, const float2 *rows, size_t stride, uint32_t nblk, float2 *out, size_t out_stride, hipStream_t s)
 {
 	const dim3 grid(nblk, c->S);
-	hipLaunchKernelGGL(sd_combine_stats_kernel<K>, grid, dim3(CB_WG), 0, s, rows, stride, c->S, c->L / CB_BLK, c->max_blocks, (double *)c->d_stat);
+	hipLaunchKernelGGL(sd_combine_stats_kernel<K>, grid, dim3(CB_WG), 0, s, rows, stride, c->S, c->L / SD_BS_BLK, c->max_blocks, (double *)c->d_stat);
 	for (uint32_t vb = 0; vb < c->S; vb += CB_VMAX) {
 		const uint32_t nv = c->S - vb < CB_VMAX ? c->S - vb : CB_VMAX;
 		SdCombineFresh fr = {};

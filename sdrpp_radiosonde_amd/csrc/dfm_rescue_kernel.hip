@@ -3,17 +3,15 @@
 // with two wrong bits is given up (nerr[1]), and the host drops the frame.  The second chip of a pair says which bits are doubtful:
 // a pair with two equal chips is an ERASURE, and the extended Hamming code (distance 4) decodes any word with 2v + e <= 3, v unknown
 // errors and e erasures.  A frame is rescued iff every word the first pass gave up on decodes that way.
-//   one 64-lane wave per channel, four waves per workgroup; lanes load the headers of 64 records at once and the wave works on
-//   the candidates among them one by one: lane i < 33 owns codeword i, reads its byte of the record and the 16 chips of its eight
-//   pairs from the channel's bit ring, and decodes it on its own.  No LDS.
+//   the walk over the records is sd_rescue_walk.h's; for a candidate lane i < 33 owns codeword i, reads its byte of the record and
+//   the 16 chips of its eight pairs from the channel's bit ring, and decodes it on its own.  No LDS.
 // Runs behind whatever wrote the records, on the same stream, and rewrites them in place.  The records of a channel are
 // independent of each other (only the two counters are shared), so the result does not depend on the cut into submits.
 // Vector stores only.
 #include <hip/hip_runtime.h>
 #include "sonde_dev.h"
-#include "launch.h"
+#include "sd_rescue_walk.h"
 
-#define DQ_WAVES 4
 #define DQ_MAX_WORDS 8         // SPEC 3.3g step 3: at most this many failed words
 #define DQ_FRAME_CHIPS 560
 
@@ -48,95 +46,65 @@ __device__ __forceinline__ int sd_hamming84_erasures(uint32_t &w, uint32_t E)
 	}
 }
 
-__device__ __forceinline__ uint32_t dq_chip(const uint32_t *__restrict__ ring, uint32_t mask, uint64_t k)
-{
-	return (ring[(uint32_t)(k >> 5) & mask] >> ((uint32_t)k & 31u)) & 1u;
-}
+struct DqPass {
+	int il_off, il_n, il_i;        // where codeword `lane` lies in the frame (SPEC 3.3b's interleaving): its bit j is frame bit off + j N + i
+	static constexpr uint32_t header = SD_H_TYPE | SD_H_LEN | SD_H_NERR1 | SD_H_BITPOS;
 
-__global__ __launch_bounds__(64 * DQ_WAVES) void sd_dfm_rescue_kernel(
-	const SdChanState *__restrict__ chan_states, const uint32_t *__restrict__ bitring, uint32_t ring_words,
-	SondeFrame *__restrict__ frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const uint32_t *__restrict__ chlist, uint32_t n_list, SdRescueCounters *__restrict__ states)
-{
-	const int lane = threadIdx.x & 63;
-	const uint32_t li_ch = DQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
-	if (li_ch >= n_list) return;
-	const uint32_t ch = chlist[li_ch];
-	const uint32_t nfr = min(counts[ch], max_frames);
-	if (nfr == 0) return;
-	const uint64_t wpos = chan_states[ch].wpos;
-	const uint32_t *ring = bitring + (size_t)ch * ring_words;
-	const uint32_t mask = ring_words - 1;
-	SondeFrame *const chfr = frames + (size_t)ch * max_frames;
-	uint32_t tried = 0, rescued = 0;
+	__device__ __forceinline__ DqPass(int lane)
+	{
+		const int blk = lane < 7 ? 0 : (lane < 20 ? 1 : 2);
+		il_off = blk == 0 ? 0 : (blk == 1 ? 56 : 160); il_n = blk == 0 ? 7 : 13;
+		il_i = lane - (blk == 0 ? 0 : (blk == 1 ? 7 : 20));
+	}
 
-	// where codeword `lane` lies in the frame (SPEC 3.3b's interleaving): its bit j is frame bit off + j N + i
-	const int blk = lane < 7 ? 0 : (lane < 20 ? 1 : 2);
-	const int il_off = blk == 0 ? 0 : (blk == 1 ? 56 : 160), il_n = blk == 0 ? 7 : 13;
-	const int il_i = lane - (blk == 0 ? 0 : (blk == 1 ? 7 : 20));
+	__device__ __forceinline__ bool candidate(const SdRecHeader &h) const { return h.type == SONDE_DFM09 && h.len == 33 && h.nerr1 >= 1; }
 
-	for (uint32_t base = 0; base < nfr; base += 64) {
-		// the headers of records base .. base + 63, one per lane
-		uint32_t h_p_lo = 0, h_p_hi = 0;
-		bool cand = false;
-		if (base + (uint32_t)lane < nfr) {
-			const SondeFrame *f = chfr + base + lane;
-			h_p_lo = (uint32_t)f->bitpos; h_p_hi = (uint32_t)(f->bitpos >> 32);
-			cand = f->type == SONDE_DFM09 && f->len == 33 && f->nerr[1] >= 1;
+	__device__ __forceinline__ int repair(SondeFrame *fr, const SdRecHeader &h, const SdRescueCtx &ctx) const
+	{
+		const int lane = ctx.lane;
+		// 2. F: the words the first pass left as received
+		uint32_t w = 0;
+		bool failed = false;
+		if (lane < 33) {
+			w = fr->data[lane];
+			failed = dq_syndrome(w) != 0u;
 		}
-		for (unsigned long long cm = __ballot(cand); cm; cm &= cm - 1ull) {
-			const int q = __builtin_ctzll(cm);
-			SondeFrame *fr = chfr + base + q;
-			const uint64_t p = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)h_p_lo, q) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)h_p_hi, q) << 32);
+		const int nf = __popcll(__ballot(failed));
+		// 3. the cap, and the frame's chips must still be in the ring (always so for a record of this submit: DESIGN 3.3g)
+		if (nf == 0 || nf > DQ_MAX_WORDS) return SD_RESCUE_SKIPPED;
+		if (!sd_ring_holds(ctx.ring, h.bitpos, DQ_FRAME_CHIPS)) return SD_RESCUE_SKIPPED;
 
-			// 2. F: the words the first pass left as received
-			uint32_t w = 0;
-			bool failed = false;
-			if (lane < 33) {
-				w = fr->data[lane];
-				failed = dq_syndrome(w) != 0u;
-			}
-			const unsigned long long fm = __ballot(failed);
-			const int nf = __popcll(fm);
-			// 3. the cap, and the frame's chips must still be in the ring (always so for a record of this submit: DESIGN 3.3g)
-			if (nf == 0 || nf > DQ_MAX_WORDS) continue;
-			if (wpos < p + DQ_FRAME_CHIPS || wpos - p > 32ull * ring_words) continue;
-			tried++;
-
-			// 4. E of this lane's word from its eight pairs, and the decode
-			int st = 0;
-			if (failed) {
-				uint32_t E = 0;
+		// 4. E of this lane's word from its eight pairs, and the decode
+		int st = 0;
+		if (failed) {
+			uint32_t E = 0;
 #pragma unroll
-				for (int j = 0; j < 8; j++) {
-					const uint64_t k = p + 32u + 2u * (uint32_t)(il_off + j * il_n + il_i);
-					if (dq_chip(ring, mask, k) == dq_chip(ring, mask, k + 1)) E |= 0x80u >> j;
-				}
-				st = sd_hamming84_erasures(w, E);
+			for (int j = 0; j < 8; j++) {
+				const uint32_t x = sd_ring_chips32(ctx.ring, h.bitpos + 32u + 2u * (uint32_t)(il_off + j * il_n + il_i));
+				if (!((x ^ (x >> 1)) & 1u)) E |= 0x80u >> j;           // the pair's two chips are equal
 			}
-			if (__ballot(st < 0)) continue;                         // one word that does not decode: the whole frame stays
-
-			// 5. the record
-			if (failed) fr->data[lane] = (uint8_t)w;
-			if (lane == 0) {
-				fr->nerr[0] += nf;
-				fr->nerr[1] = 0;
-				fr->flags |= SONDE_FRAME_RESCUED | ((uint32_t)nf << 8);
-			}
-			rescued++;
+			st = sd_hamming84_erasures(w, E);
 		}
+		if (__ballot(st < 0)) return SD_RESCUE_TRIED;               // one word that does not decode: the whole frame stays
+
+		// 5. the record
+		if (failed) fr->data[lane] = (uint8_t)w;
+		if (lane == 0) {
+			fr->nerr[0] += nf;
+			fr->nerr[1] = 0;
+			fr->flags |= SONDE_FRAME_RESCUED | ((uint32_t)nf << 8);
+		}
+		return SD_RESCUE_DONE;
 	}
-	if (tried && lane == 0) {
-		states[ch].tried += tried;
-		states[ch].rescued += rescued;
-	}
+};
+
+__global__ __launch_bounds__(64 * SD_RESCUE_WAVES) void sd_dfm_rescue_kernel(SdRescueWalk a)
+{
+	DqPass pass(threadIdx.x & 63);
+	sd_rescue_walk(a, pass);
 }
 
-void sd_launch_rescue_dfm(const SdRescueArgs &a)
-{
-	hipLaunchKernelGGL(sd_dfm_rescue_kernel, dim3((a.n_list + DQ_WAVES - 1) / DQ_WAVES), dim3(64 * DQ_WAVES), 0, a.stream,
-		a.chan_states, a.bitring, a.ring_words, a.frames, a.counts, a.max_frames, a.chlist, a.n_list, (SdRescueCounters *)a.states);
-}
+void sd_launch_rescue_dfm(const SdRescueArgs &a) { sd_rescue_launch(sd_dfm_rescue_kernel, a); }
 
 // ---- test introspection: step 4 alone on caller-supplied (word, erasure mask) pairs (sonde_batch_test_hamming84_erasures)
 __global__ __launch_bounds__(256) void sd_hamming84_unit_kernel(uint8_t *__restrict__ words, const uint8_t *__restrict__ erased, uint32_t n,

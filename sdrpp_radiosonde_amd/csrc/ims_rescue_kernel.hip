@@ -4,44 +4,22 @@
 // to it is.  A block of BCH(46,34) the first pass rejected (three or more wrong bits) with 1..6 such boundaries is decoded by trying
 // the 2^m ways of blaming the left or the right cell of each; the block decodes iff exactly one distinct flip pattern is a codeword.
 // A frame is rescued iff every rejected block decodes.
-//   one 64-lane wave per channel, four waves per workgroup; lanes load the headers of 64 records at once and the wave works on the
-//   candidates among them one by one: lanes 0..11 rebuild their block, its boundaries and the first pass's verdict from the chips of
-//   the channel's bit ring; then, rejected block by rejected block, the 64 lanes are the up to 64 hypotheses.  LDS: each wave's own
-//   copy of the 192-byte GF(2^6) table (its look-ups are the kernel's critical path: read from global memory they added 25 us to the
-//   step of profiles/ims_rescue_notes.md).
+//   the walk over the records is sd_rescue_walk.h's; for a candidate lanes 0..11 rebuild their block, its boundaries and the first
+//   pass's verdict from the chips of the channel's bit ring; then, rejected block by rejected block, the 64 lanes are the up to 64
+//   hypotheses.  LDS: each wave's own copy of the 192-byte GF(2^6) table (its look-ups are the kernel's critical path: read from
+//   global memory they added 25 us to the step of profiles/ims_rescue_notes.md).
 // Runs behind whatever wrote the records, on the same stream, and rewrites them in place.  The records of a channel are
 // independent of each other (only the two counters are shared), so the result does not depend on the cut into submits.
 // Vector stores only.
 #include <hip/hip_runtime.h>
 #include "sonde_dev.h"
-#include "launch.h"
+#include "sd_rescue_walk.h"
 
-#define IQ_WAVES 4
 #define IQ_CAP 6               // SPEC 3.3h step 3: at most this many violated boundaries per block
 #define IQ_FRAME_CHIPS 1152
 #define IQ_BLOCKS 12
 #define IQ_BLK_BITS 46
 #define IQ_BLK_MASK ((1ull << IQ_BLK_BITS) - 1ull)
-
-// 64 chips of the ring from chip k on, the first in bit 0
-__device__ __forceinline__ uint64_t iq_chips64(const uint32_t *__restrict__ ring, uint32_t mask, uint64_t k)
-{
-	const uint32_t w = (uint32_t)(k >> 5), sft = (uint32_t)k & 31u;
-	const uint64_t lo = (uint64_t)ring[w & mask] | ((uint64_t)ring[(w + 1u) & mask] << 32);
-	const uint64_t hi = ring[(w + 2u) & mask];
-	return sft ? (lo >> sft) | (hi << (64u - sft)) : lo;
-}
-
-// bits 0, 2, 4 .. 62 of x, packed into bits 0 .. 31
-__device__ __forceinline__ uint64_t iq_even_bits(uint64_t x)
-{
-	x &= 0x5555555555555555ull;
-	x = (x | x >> 1) & 0x3333333333333333ull;
-	x = (x | x >> 2) & 0x0F0F0F0F0F0F0F0Full;
-	x = (x | x >> 4) & 0x00FF00FF00FF00FFull;
-	x = (x | x >> 8) & 0x0000FFFF0000FFFFull;
-	return (x | x >> 16) & 0xFFFFFFFFull;
-}
 
 // S1 and S3 of a block polynomial over GF(2^6) / x^6 + x + 1 (g64 = exp[128], log[64]), as in sd_ims_decode_frame
 __device__ __forceinline__ void iq_syndromes(uint64_t blk, const uint8_t *__restrict__ g_exp, uint32_t &s1, uint32_t &s3)
@@ -72,12 +50,6 @@ __device__ __forceinline__ bool iq_first_pass_rejects(uint32_t s1, uint32_t s3, 
 	return !(found == 2 && inside == 2);
 }
 
-__device__ __forceinline__ uint64_t iq_bcast64(uint64_t v, int src)
-{
-	return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src) |
-	       ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src) << 32);
-}
-
 // SPEC 3.3h step 3 for one block, by the whole wave: blk as received (bit b of the block = coefficient 45 - b), its syndromes, viol
 // = the mask of its violated boundaries (bit k: boundary k of the block, 0..46); all wave-uniform.  Lane h is hypothesis h: bit j of
 // h picks, for the j-th violated boundary v, the cell v (1) or v - 1 (0); a pick outside 0..45 flips nothing, a cell picked twice
@@ -101,138 +73,108 @@ __device__ __forceinline__ bool iq_decode_block(uint32_t s1, uint32_t s3, uint64
 	const bool fit = lane < (1 << m) && s1 == 0u && s3 == 0u;
 	const unsigned long long fm = __ballot(fit);
 	if (!fm) return false;
-	e = iq_bcast64(pat, __builtin_ctzll(fm));
+	e = sd_readlane64(pat, __builtin_ctzll(fm));
 	return __ballot(fit && pat != e) == 0ull;                    // several distinct patterns fit: no decode
 }
 
-__global__ __launch_bounds__(64 * IQ_WAVES) void sd_ims_rescue_kernel(
-	const uint8_t *__restrict__ g64, const SdChanState *__restrict__ chan_states, const uint32_t *__restrict__ bitring, uint32_t ring_words,
-	SondeFrame *__restrict__ frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const uint32_t *__restrict__ chlist, uint32_t n_list, SdRescueCounters *__restrict__ states)
+struct IqPass {
+	const uint8_t *g_exp, *g_log;          // the wave's own copy of the table in LDS
+	static constexpr uint32_t header = SD_H_TYPE | SD_H_LEN | SD_H_NERR1 | SD_H_BITPOS;
+
+	__device__ __forceinline__ bool candidate(const SdRecHeader &h) const { return h.type == SONDE_IMS100 && h.len == 51 && h.nerr1 >= 1; }
+
+	__device__ __forceinline__ int repair(SondeFrame *fr, const SdRecHeader &h, const SdRescueCtx &ctx) const
+	{
+		const int lane = ctx.lane;
+		// the frame's chips must still be in the ring (always so for a record of this submit: DESIGN 3.3h)
+		if (!sd_ring_holds(ctx.ring, h.bitpos, IQ_FRAME_CHIPS)) return SD_RESCUE_SKIPPED;
+
+		// 1. lane L < 12: block L and its boundaries 46 L .. 46 L + 46 from the 94 chips p + 47 + 92 L ..; chip j and chip j + 1 are
+		//    boundary j / 2 of the block for even j, cell (j - 1) / 2 for odd j.  Chip p + 1152 is not used: block 11 has no boundary 46.
+		uint64_t blk = 0, viol = 0;
+		uint32_t s1 = 0, s3 = 0;
+		bool failed = false;
+		if (lane < IQ_BLOCKS) {
+			const uint64_t c0 = h.bitpos + 47u + 92u * (uint32_t)lane;
+			const uint64_t x0 = sd_ring_chips64(ctx.ring, c0), x1 = sd_ring_chips64(ctx.ring, c0 + 64u);
+			const uint64_t eq0 = ~(x0 ^ (x0 >> 1 | x1 << 63)), eq1 = ~(x1 ^ (x1 >> 1));       // bit j: chip j == chip j + 1
+			viol = (sd_even_bits64(eq0) | sd_even_bits64(eq1) << 32) & ((2ull << IQ_BLK_BITS) - 1ull);  // bit n: boundary n, 0..46
+			const uint64_t cells = sd_even_bits64(eq0 >> 1) | sd_even_bits64(eq1 >> 1) << 32;         // bit b: cell b
+			blk = (__builtin_bitreverse64(cells) >> (64 - IQ_BLK_BITS)) & IQ_BLK_MASK;                  // bit b -> coefficient 45 - b
+			if (lane == IQ_BLOCKS - 1) viol &= IQ_BLK_MASK;
+			// 2. F: the blocks the first pass rejects
+			iq_syndromes(blk, g_exp, s1, s3);
+			failed = iq_first_pass_rejects(s1, s3, g_exp, g_log);
+		}
+		const unsigned long long fm = __ballot(failed);
+		const int nf = __popcll(fm);
+		if (nf != h.nerr1) return SD_RESCUE_SKIPPED;                // record and ring disagree
+
+		// 3. each failed block on its own, the lanes as its hypotheses; 4. one block that does not decode: the whole frame stays
+		uint64_t dec = blk;
+		int flips = 0;
+		for (unsigned long long m = fm; m; m &= m - 1ull) {
+			const int L = __builtin_ctzll(m);
+			uint64_t e = 0;
+			if (!iq_decode_block((uint32_t)__builtin_amdgcn_readlane((int)s1, L), (uint32_t)__builtin_amdgcn_readlane((int)s3, L),
+			                     sd_readlane64(viol, L), g_exp, lane, e)) return SD_RESCUE_TRIED;
+			if (lane == L) dec ^= e;
+			flips += __popcll(e);
+		}
+
+		// 5. the record: lane i < 51 owns byte i; data bit k is bit k % 34 of block k / 34, and a byte lies in at most two blocks
+		if (lane < 51) {
+			const int La = (8 * lane) / 34, Lb = (8 * lane + 7) / 34;
+			const uint64_t da = (uint64_t)(uint32_t)__shfl((int)(uint32_t)dec, La, 64) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(dec >> 32), La, 64) << 32);
+			const uint64_t db = (uint64_t)(uint32_t)__shfl((int)(uint32_t)dec, Lb, 64) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(dec >> 32), Lb, 64) << 32);
+			const uint32_t old = fr->data[lane];
+			uint32_t nb = old;
+#pragma unroll
+			for (int j = 0; j < 8; j++) {
+				const int k = 8 * lane + j, L = k / 34, b = k % 34;
+				if ((fm >> L) & 1ull) {
+					const uint32_t bit = (uint32_t)(((L == La ? da : db) >> (IQ_BLK_BITS - 1 - b)) & 1ull);
+					nb = (nb & ~(0x80u >> j)) | (bit << (7 - j));
+				}
+			}
+			if (nb != old) fr->data[lane] = (uint8_t)nb;
+		}
+		if (lane == 0) {
+			fr->nerr[0] += flips;
+			fr->nerr[1] = 0;
+			fr->flags |= SONDE_FRAME_RESCUED | ((uint32_t)nf << 8);
+		}
+		return SD_RESCUE_DONE;
+	}
+};
+
+__global__ __launch_bounds__(64 * SD_RESCUE_WAVES) void sd_ims_rescue_kernel(SdRescueWalk a, const uint8_t *__restrict__ g64)
 {
-	const int lane = threadIdx.x & 63;
-	const uint32_t li_ch = IQ_WAVES * blockIdx.x + (threadIdx.x >> 6);
-	if (li_ch >= n_list) return;
-	const uint32_t ch = chlist[li_ch];
-	const uint32_t nfr = min(counts[ch], max_frames);
-	if (nfr == 0) return;
-	const uint64_t wpos = chan_states[ch].wpos;
-	const uint32_t *ring = bitring + (size_t)ch * ring_words;
-	const uint32_t mask = ring_words - 1;
 	// the wave's own copy of the table (exp[128], log[64]); wave-private, so a fence and a wave barrier order it, as in sd_fixed.h
-	__shared__ uint32_t s_g64[IQ_WAVES][48];
+	__shared__ uint32_t s_g64[SD_RESCUE_WAVES][48];
+	const int lane = threadIdx.x & 63;
 	uint32_t *const tab = s_g64[threadIdx.x >> 6];
 	if (lane < 48) tab[lane] = reinterpret_cast<const uint32_t *>(g64)[lane];
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 	__builtin_amdgcn_wave_barrier();
-	const uint8_t *g_exp = reinterpret_cast<const uint8_t *>(tab), *g_log = g_exp + 128;
-	SondeFrame *const chfr = frames + (size_t)ch * max_frames;
-	uint32_t tried = 0, rescued = 0;
-
-	for (uint32_t base = 0; base < nfr; base += 64) {
-		// the headers of records base .. base + 63, one per lane
-		uint32_t h_p_lo = 0, h_p_hi = 0;
-		int h_bad = 0;
-		bool cand = false;
-		if (base + (uint32_t)lane < nfr) {
-			const SondeFrame *f = chfr + base + lane;
-			h_p_lo = (uint32_t)f->bitpos; h_p_hi = (uint32_t)(f->bitpos >> 32);
-			h_bad = f->nerr[1];
-			cand = f->type == SONDE_IMS100 && f->len == 51 && h_bad >= 1;
-		}
-		for (unsigned long long cm = __ballot(cand); cm; cm &= cm - 1ull) {
-			const int q = __builtin_ctzll(cm);
-			SondeFrame *fr = chfr + base + q;
-			const uint64_t p = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)h_p_lo, q) | ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)h_p_hi, q) << 32);
-			const int n_bad = __builtin_amdgcn_readlane(h_bad, q);
-			// the frame's chips must still be in the ring (always so for a record of this submit: DESIGN 3.3h)
-			if (wpos < p + IQ_FRAME_CHIPS || wpos - p > 32ull * ring_words) continue;
-
-			// 1. lane L < 12: block L and its boundaries 46 L .. 46 L + 46 from the 94 chips p + 47 + 92 L ..; chip j and chip j + 1 are
-			//    boundary j / 2 of the block for even j, cell (j - 1) / 2 for odd j.  Chip p + 1152 is not used: block 11 has no boundary 46.
-			uint64_t blk = 0, viol = 0;
-			uint32_t s1 = 0, s3 = 0;
-			bool failed = false;
-			if (lane < IQ_BLOCKS) {
-				const uint64_t c0 = p + 47u + 92u * (uint32_t)lane;
-				const uint64_t x0 = iq_chips64(ring, mask, c0), x1 = iq_chips64(ring, mask, c0 + 64u);
-				const uint64_t eq0 = ~(x0 ^ (x0 >> 1 | x1 << 63)), eq1 = ~(x1 ^ (x1 >> 1));       // bit j: chip j == chip j + 1
-				viol = (iq_even_bits(eq0) | iq_even_bits(eq1) << 32) & ((2ull << IQ_BLK_BITS) - 1ull);      // bit n: boundary n, 0..46
-				const uint64_t cells = iq_even_bits(eq0 >> 1) | iq_even_bits(eq1 >> 1) << 32;             // bit b: cell b
-				blk = (__builtin_bitreverse64(cells) >> (64 - IQ_BLK_BITS)) & IQ_BLK_MASK;                  // bit b -> coefficient 45 - b
-				if (lane == IQ_BLOCKS - 1) viol &= IQ_BLK_MASK;
-				// 2. F: the blocks the first pass rejects
-				iq_syndromes(blk, g_exp, s1, s3);
-				failed = iq_first_pass_rejects(s1, s3, g_exp, g_log);
-			}
-			const unsigned long long fm = __ballot(failed);
-			const int nf = __popcll(fm);
-			if (nf != n_bad) continue;                              // record and ring disagree
-			tried++;
-
-			// 3. each failed block on its own, the lanes as its hypotheses
-			uint64_t dec = blk;
-			int flips = 0;
-			bool all = true;
-			for (unsigned long long m = fm; m; m &= m - 1ull) {
-				const int L = __builtin_ctzll(m);
-				uint64_t e = 0;
-				if (!iq_decode_block((uint32_t)__builtin_amdgcn_readlane((int)s1, L), (uint32_t)__builtin_amdgcn_readlane((int)s3, L),
-				                     iq_bcast64(viol, L), g_exp, lane, e)) { all = false; break; }
-				if (lane == L) dec ^= e;
-				flips += __popcll(e);
-			}
-			if (!all) continue;                                     // 4. one block that does not decode: the whole frame stays
-
-			// 5. the record: lane i < 51 owns byte i; data bit k is bit k % 34 of block k / 34, and a byte lies in at most two blocks
-			if (lane < 51) {
-				const int La = (8 * lane) / 34, Lb = (8 * lane + 7) / 34;
-				const uint64_t da = (uint64_t)(uint32_t)__shfl((int)(uint32_t)dec, La, 64) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(dec >> 32), La, 64) << 32);
-				const uint64_t db = (uint64_t)(uint32_t)__shfl((int)(uint32_t)dec, Lb, 64) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(dec >> 32), Lb, 64) << 32);
-				const uint32_t old = fr->data[lane];
-				uint32_t nb = old;
-#pragma unroll
-				for (int j = 0; j < 8; j++) {
-					const int k = 8 * lane + j, L = k / 34, b = k % 34;
-					if ((fm >> L) & 1ull) {
-						const uint32_t bit = (uint32_t)(((L == La ? da : db) >> (IQ_BLK_BITS - 1 - b)) & 1ull);
-						nb = (nb & ~(0x80u >> j)) | (bit << (7 - j));
-					}
-				}
-				if (nb != old) fr->data[lane] = (uint8_t)nb;
-			}
-			if (lane == 0) {
-				fr->nerr[0] += flips;
-				fr->nerr[1] = 0;
-				fr->flags |= SONDE_FRAME_RESCUED | ((uint32_t)nf << 8);
-			}
-			rescued++;
-		}
-	}
-	if (tried && lane == 0) {
-		states[ch].tried += tried;
-		states[ch].rescued += rescued;
-	}
+	IqPass pass = { reinterpret_cast<const uint8_t *>(tab), reinterpret_cast<const uint8_t *>(tab) + 128 };
+	sd_rescue_walk(a, pass);
 }
 
-void sd_launch_rescue_ims(const SdRescueArgs &a)
-{
-	hipLaunchKernelGGL(sd_ims_rescue_kernel, dim3((a.n_list + IQ_WAVES - 1) / IQ_WAVES), dim3(64 * IQ_WAVES), 0, a.stream,
-		a.fec.g64, a.chan_states, a.bitring, a.ring_words, a.frames, a.counts, a.max_frames, a.chlist, a.n_list, (SdRescueCounters *)a.states);
-}
+void sd_launch_rescue_ims(const SdRescueArgs &a) { sd_rescue_launch(sd_ims_rescue_kernel, a, a.fec.g64); }
 
 // ---- test introspection: step 3 alone on caller-supplied (block, violation mask) pairs (sonde_batch_test_ims_block); one wave per
 // pair, IQ_UNIT_PAIRS pairs per wave
 #define IQ_UNIT_PAIRS 16
-__global__ __launch_bounds__(64 * IQ_WAVES) void sd_ims_block_unit_kernel(const uint8_t *__restrict__ g64, uint64_t *__restrict__ blocks,
+__global__ __launch_bounds__(64 * SD_RESCUE_WAVES) void sd_ims_block_unit_kernel(const uint8_t *__restrict__ g64, uint64_t *__restrict__ blocks,
 	const uint64_t *__restrict__ viols, uint32_t n, int32_t *__restrict__ status)
 {
 	const int lane = threadIdx.x & 63;
-	const uint32_t first = IQ_UNIT_PAIRS * (IQ_WAVES * blockIdx.x + (threadIdx.x >> 6));
+	const uint32_t first = IQ_UNIT_PAIRS * (SD_RESCUE_WAVES * blockIdx.x + (threadIdx.x >> 6));
 	for (uint32_t k = 0; k < IQ_UNIT_PAIRS; k++) {
 		const uint32_t i = first + k;
 		if (i >= n) return;
-		const uint64_t blk = iq_bcast64(blocks[i], 0) & IQ_BLK_MASK, viol = iq_bcast64(viols[i], 0) & ((1ull << (IQ_BLK_BITS + 1)) - 1ull);
+		const uint64_t blk = sd_readlane64(blocks[i], 0) & IQ_BLK_MASK, viol = sd_readlane64(viols[i], 0) & ((1ull << (IQ_BLK_BITS + 1)) - 1ull);
 		uint32_t s1, s3;
 		iq_syndromes(blk, g64, s1, s3);
 		uint64_t e = 0;
@@ -245,6 +187,6 @@ __global__ __launch_bounds__(64 * IQ_WAVES) void sd_ims_block_unit_kernel(const 
 }
 void sd_launch_ims_block_unit(const uint8_t *g64, uint64_t *blocks, const uint64_t *viols, uint32_t n, int32_t *status, hipStream_t stream)
 {
-	const uint32_t per_wg = IQ_WAVES * IQ_UNIT_PAIRS;
-	hipLaunchKernelGGL(sd_ims_block_unit_kernel, dim3((n + per_wg - 1) / per_wg), dim3(64 * IQ_WAVES), 0, stream, g64, blocks, viols, n, status);
+	const uint32_t per_wg = SD_RESCUE_WAVES * IQ_UNIT_PAIRS;
+	hipLaunchKernelGGL(sd_ims_block_unit_kernel, dim3((n + per_wg - 1) / per_wg), dim3(64 * SD_RESCUE_WAVES), 0, stream, g64, blocks, viols, n, status);
 }

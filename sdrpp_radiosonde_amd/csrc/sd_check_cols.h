@@ -39,6 +39,33 @@ __device__ __forceinline__ uint32_t mq_byte_syndrome(const uint4 row, uint32_t b
 	return s;
 }
 
+// The unknowns into lanes: vm = this lane's marked bits, bit q of it frame bit BPL * lane + q (frame bit k = bit 7 - k % 8 of byte
+// k / 8).  The marked bits of the wave, ascending, go to lanes 0 .. nv - 1: returns this lane's frame bit (0 for lane >= nv).
+template <int BPL> __device__ __forceinline__ int mq_gather(uint32_t vm, int lane)
+{
+	int myk = 0, n = 0;
+	for (unsigned long long lm = __ballot(vm != 0u); lm; lm &= lm - 1ull) {
+		const int l = __builtin_ctzll(lm);
+		for (uint32_t bm = (uint32_t)__builtin_amdgcn_readlane((int)vm, l); bm; bm &= bm - 1u) {
+			if (lane == n) myk = BPL * l + __builtin_ctz(bm);
+			n++;
+		}
+	}
+	return myk;
+}
+// The solution back into the frame: of the unknowns in U (bit j: lane j's, frame bit myk there) those that fall into the NB frame bytes
+// from byte `first` on, as an XOR mask over these bytes (byte first + b at bits 8 b .. 8 b + 7)
+template <int NB> __device__ __forceinline__ uint32_t mq_flips(uint32_t U, int myk, int first)
+{
+	uint32_t fm = 0;
+#pragma unroll
+	for (int j = 0; j < MQ_MAX_HINTS; j++) {
+		const int kj = __builtin_amdgcn_readlane(myk, j), b = (kj >> 3) - first;
+		if (((U >> j) & 1u) && b >= 0 && b < NB) fm ^= (0x80u >> (kj & 7)) << (8 * b);
+	}
+	return fm;
+}
+
 // SPEC 3.3f step 4: the subsets m = 1 .. 2^nv - 1 of nv <= MQ_MAX_HINTS unknowns (bit j of m: the unknown whose column lane j holds in
 // col) tried across the wave, four per lane.  Returns how many of them XOR to s; U = one that does (the one, if the count is 1).
 __device__ __forceinline__ int mq_solve(uint32_t col, int nv, uint32_t s, int lane, uint32_t &U)

@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "sonde_dev.h"
+#include "sd_ring.h"
 #include "launch.h"
 
 #define DV_U(x) __builtin_amdgcn_readfirstlane((int)(x))
@@ -22,12 +23,6 @@ __device__ __forceinline__ bool dv_failed(uint32_t kind, const SondeFrame *f) { 
 
 // a word of a record another lane of this wave may have written earlier in this kernel
 __device__ __forceinline__ uint32_t dv_load_fresh(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// a value all lanes hold alike -> scalar registers
-__device__ __forceinline__ int64_t dv_u64(int64_t v)
-{
-	return (int64_t)(((uint64_t)(uint32_t)DV_U((uint32_t)((uint64_t)v >> 32)) << 32) | (uint32_t)DV_U((uint32_t)(uint64_t)v));
-}
 
 __device__ __forceinline__ uint32_t dv_wave_min(uint32_t v)
 {
@@ -67,7 +62,7 @@ __device__ __forceinline__ void dv_members(DvMembers &M, SondeFrame *frames, con
 		M.ch[m] = m < M.nm ? (uint32_t)DV_U(G->ch[m]) : 0u;
 		M.all[m] = m < M.nm ? (uint32_t)DV_U(min(counts[M.ch[m]], max_frames)) : 0u;
 		M.cnt[m] = (M.lockmask >> m) & 1u ? M.all[m] : 0u;
-		M.ofs[m] = m < M.nm ? dv_u64((int64_t)__hip_atomic_load(reinterpret_cast<const uint64_t *>(&S->off[m]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0;
+		M.ofs[m] = m < M.nm ? (int64_t)sd_uniform64(__hip_atomic_load(reinterpret_cast<const uint64_t *>(&S->off[m]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : 0;
 		M.start[m + 1] = M.start[m] + M.cnt[m];
 	}
 	M.total = M.start[SD_DIV_MAX];
@@ -98,7 +93,7 @@ __device__ __forceinline__ bool dv_next_failed(const DvMembers &M, uint32_t kind
 	}
 	bk = (uint32_t)DV_U(bk);
 	if (bk == 0xFFFFFFFFu) return false;
-	t_r = dv_u64(bt);
+	t_r = (int64_t)sd_uniform64((uint64_t)bt);
 	last_t = t_r; last_m = (int)(bk >> 16);
 	bk_out = bk;
 	return true;

@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "sonde_dev.h"
+#include "sd_ring.h"              // sd_uniform64
 
 #define SD_K4_LIST 8
 #define RS41_SYNC_THR 6
@@ -31,12 +32,6 @@ struct SdSyncRun {                  // working copy of SdFramerState + the frame
 	uint64_t wp_seen;               // bits the lead wave has announced (and mirrored) so far
 	SdFrameDesc list[SD_K4_LIST];   // the first frames listed in this launch, for the FEC epilogue (the full list is in HBM)
 };
-
-__device__ __forceinline__ uint64_t sd_uniform64(unsigned long long v)    // a value all lanes hold alike -> scalar registers
-{
-	return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
-	       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
 
 // Advance the state machine over the bits [.., wp) of the channel.  `mirror` holds the ring words of the newest
 // SD_MIRROR_WORDS * 32 bits (word w of the stream at mirror[w % SD_MIRROR_WORDS]); the caller guarantees that the

@@ -4,13 +4,11 @@
 // pure-host step rule that turns one look into the VFO's next offset (sonde_track_step).  It stands where a person watches the
 // SDR++ waterfall and drags the VFO after a drifting sonde (/root/reference/src/main.cpp:55-68).
 //
-// One workgroup per (row, look-piece): the part of one look that lies in this submit.  Wave w takes the piece's 256-sample blocks
-// w, w + 4, ...; lane l the samples l, l + 64, l + 128, l + 192 of the block, products in float32 with explicit fmaf, the four added
-// in ascending order, then a fixed xor butterfly over the 64 lanes.  The block sums go through LDS, 32 blocks at a time; three lanes
-// (one per quantity) add them to a double each in ascending block order.  A look's sums therefore depend on the row's samples and
-// its restart points alone, never on how the stream was cut into submits.  A finished look goes to the row's ring, an unfinished
-// one to the carry; the carry and the lag history (the row's last d samples) are double-buffered, because the workgroup that
-// writes them is not the one that reads them.
+// One workgroup per (row, look-piece): the part of one look that lies in this submit, summed in sd_blocksum.h's order -- float32
+// products with one explicit fmaf, 256-sample blocks, block sums into three doubles in ascending order, the carry being what they
+// start from.  A look's sums therefore depend on the row's samples and its restart points alone, never on how the stream was cut
+// into submits.  A finished look goes to the row's ring, an unfinished one to the carry; the carry and the lag history (the row's
+// last d samples) are double-buffered, because the workgroup that writes them is not the one that reads them.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -21,11 +19,9 @@
 #include "sd_host.h"
 #include "sd_devmem.h"
 #include "sd_design.h"
+#include "sd_blocksum.h"
 #include "../../include/sonde_abi.h"
 
-#define TK_WG     256
-#define TK_BLK    256                   // samples per block
-#define TK_CHUNK  32                    // blocks per trip through LDS (8 per wave)
 #define TK_VMAX   512                   // rows per launch: their look phases and ring slots travel with the launch, by value (2 KB)
 #define TK_DMAX   64                    // largest lag
 #define TK_MAXLB  16384                 // largest look, in blocks (the phase travels in 15 bits)
@@ -33,12 +29,12 @@
 
 struct SdTrackRows { uint16_t ph[TK_VMAX]; uint16_t slot[TK_VMAX]; };     // blocks into the row's current look (| TK_FRESH); ring slot of its next look
 
-__global__ __launch_bounds__(TK_WG) void sd_track_kernel(const float2 *__restrict__ rows, size_t stride, uint32_t nb, uint32_t LB, uint32_t d,
+__global__ __launch_bounds__(SD_BS_WG) void sd_track_kernel(const float2 *__restrict__ rows, size_t stride, uint32_t nb, uint32_t LB, uint32_t d,
 	SdTrackRows rs, uint32_t vbase, const float2 *__restrict__ hist_in, float2 *__restrict__ hist_out,
 	const double *__restrict__ carry_in, double *__restrict__ carry_out, double *__restrict__ ring, uint32_t ring_len)
 {
-	__shared__ float s_bs[3][TK_CHUNK];
-	const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+	__shared__ float s_bs[3][SD_BS_CHUNK];
+	const uint32_t tid = threadIdx.x;
 	const uint32_t row = vbase + blockIdx.y;
 	const uint32_t ph = rs.ph[blockIdx.y] & (TK_FRESH - 1u);
 	const bool fresh = (rs.ph[blockIdx.y] & TK_FRESH) != 0;
@@ -52,40 +48,24 @@ __global__ __launch_bounds__(TK_WG) void sd_track_kernel(const float2 *__restric
 	const float2 *hi = hist_in + (size_t)row * TK_DMAX;
 	double acc = 0.0;
 	if (p == 0 && ph > 0 && tid < 3) acc = carry_in[(size_t)row * 3 + tid];
-	for (uint32_t c0 = b0; c0 < b1; c0 += TK_CHUNK) {
-		const uint32_t cn = min((uint32_t)TK_CHUNK, b1 - c0);
-		for (uint32_t q = wave; q < cn; q += 4) {
-			const int64_t m0 = (int64_t)(c0 + q) * TK_BLK + lane;
-			float2 xv[4], yv[4];
-#pragma unroll
-			for (int r = 0; r < 4; r++) {
-				const int64_t m = m0 + 64 * r, ml = m - (int64_t)d;
-				xv[r] = x[m];
-				yv[r] = ml >= 0 ? x[ml] : (fresh ? make_float2(0.0f, 0.0f) : hi[ml + (int64_t)d]);
-			}
-			float ar = 0.0f, ai = 0.0f, pw = 0.0f;
-#pragma unroll
-			for (int r = 0; r < 4; r++) {
-				const float cr = __builtin_fmaf(xv[r].x, yv[r].x, xv[r].y * yv[r].y);
-				const float ci = __builtin_fmaf(xv[r].y, yv[r].x, -(xv[r].x * yv[r].y));
-				const float pp = __builtin_fmaf(xv[r].x, xv[r].x, xv[r].y * xv[r].y);
-				ar = r ? ar + cr : cr; ai = r ? ai + ci : ci; pw = r ? pw + pp : pp;
-			}
-#pragma unroll
-			for (int o = 32; o >= 1; o >>= 1) { ar += __shfl_xor(ar, o, 64); ai += __shfl_xor(ai, o, 64); pw += __shfl_xor(pw, o, 64); }
-			if (lane == 0) { s_bs[0][q] = ar; s_bs[1][q] = ai; s_bs[2][q] = pw; }
-		}
-		__syncthreads();
-		if (tid < 3)
-			for (uint32_t q = 0; q < cn; q++) acc += (double)s_bs[tid][q];
-		__syncthreads();
-	}
+	// A (re, im) and P of sample m: x[m] against x[m - d], which in front of the submit is the row's history, or nothing
+	struct Pair { float2 x, y; };
+	acc = sd_blocksum<3>(b0, b1, acc, s_bs,
+		[&](int64_t m) {
+			const int64_t ml = m - (int64_t)d;
+			return Pair{ x[m], ml >= 0 ? x[ml] : (fresh ? make_float2(0.0f, 0.0f) : hi[ml + (int64_t)d]) };
+		},
+		[](const Pair &v, float (&q)[3]) {
+			q[0] = __builtin_fmaf(v.x.x, v.y.x, v.x.y * v.y.y);
+			q[1] = __builtin_fmaf(v.x.y, v.y.x, -(v.x.x * v.y.y));
+			q[2] = __builtin_fmaf(v.x.x, v.x.x, v.x.y * v.x.y);
+		});
 	const bool done = (p == 0 ? ph : 0u) + (b1 - b0) == LB;                // the look ends in this submit
 	if (tid < 3) {
 		if (done) ring[((size_t)row * ring_len + (rs.slot[blockIdx.y] + p) % ring_len) * 3 + tid] = acc;
 		else carry_out[(size_t)row * 3 + tid] = acc;
 	}
-	if (b1 == nb && tid < d) hist_out[(size_t)row * TK_DMAX + tid] = x[(size_t)nb * TK_BLK - d + tid];
+	if (b1 == nb && tid < d) hist_out[(size_t)row * TK_DMAX + tid] = x[(size_t)nb * SD_BS_BLK - d + tid];
 }
 
 // ---------------------------------------------------------------- host
@@ -123,7 +103,7 @@ static int tk_build(SondeTracker *t)
 extern "C" int sonde_track_defaults(uint32_t rate, uint32_t *look_samples, uint32_t *lag)
 {
 	if (rate < 5000u || rate > 100000u) return sd_fail("sonde_track_defaults: rate must be 5000 .. 100 000 Hz");
-	if (look_samples) *look_samples = TK_BLK * ((rate + 2559u) / 2560u);
+	if (look_samples) *look_samples = SD_BS_BLK * ((rate + 2559u) / 2560u);
 	if (lag) *lag = rate / 24000u > 1u ? rate / 24000u : 1u;
 	return 0;
 }
@@ -137,14 +117,14 @@ extern "C" int sonde_track_create(uint32_t n_rows, uint32_t rate, uint32_t max_s
 	uint32_t L0, d0;
 	if (sonde_track_defaults(rate, &L0, &d0)) return sd_fail("sonde_track_create: rate must be 5000 .. 100 000 Hz");
 	const uint32_t L = look_samples ? look_samples : L0, d = lag ? lag : d0;
-	if (L % TK_BLK || L / TK_BLK > TK_MAXLB) return sd_fail("sonde_track_create: look_samples must be a multiple of 256, at most 4 194 304 (0 = about 0.1 s)");
+	if (L % SD_BS_BLK || L / SD_BS_BLK > TK_MAXLB) return sd_fail("sonde_track_create: look_samples must be a multiple of 256, at most 4 194 304 (0 = about 0.1 s)");
 	if (d > TK_DMAX) return sd_fail("sonde_track_create: lag must be 1 .. 64 (0 = by rate)");
-	if (!max_samples || max_samples % TK_BLK || max_samples >= (1u << 30)) return sd_fail("sonde_track_create: max_samples must be a positive multiple of 256 below 2^30");
-	if ((max_samples / TK_BLK) / (L / TK_BLK) + 2 > 65535u) return sd_fail("sonde_track_create: max_samples holds more than 65 533 looks");
+	if (!max_samples || max_samples % SD_BS_BLK || max_samples >= (1u << 30)) return sd_fail("sonde_track_create: max_samples must be a positive multiple of 256 below 2^30");
+	if ((max_samples / SD_BS_BLK) / (L / SD_BS_BLK) + 2 > 65535u) return sd_fail("sonde_track_create: max_samples holds more than 65 533 looks");
 	if (sd_select_device(device, "sonde_track_create")) return -1;
 	SondeTracker *t = new SondeTracker;
-	t->device = device; t->n_rows = n_rows; t->rate = rate; t->max_samples = max_samples; t->L = L; t->LB = L / TK_BLK; t->d = d;
-	const uint32_t per_submit = (max_samples / TK_BLK) / t->LB + 2;       // looks one submit can finish, and one more
+	t->device = device; t->n_rows = n_rows; t->rate = rate; t->max_samples = max_samples; t->L = L; t->LB = L / SD_BS_BLK; t->d = d;
+	const uint32_t per_submit = (max_samples / SD_BS_BLK) / t->LB + 2;       // looks one submit can finish, and one more
 	t->ring_len = per_submit > 16u ? per_submit : 16u;
 	t->ph.assign(n_rows, 0); t->fresh.assign(n_rows, 1); t->look.assign(n_rows, 0); t->seq.assign(n_rows, 0);
 	t->pending.resize(n_rows); t->dropped.assign(n_rows, 0);
@@ -160,14 +140,14 @@ extern "C" int sonde_track_ring(const SondeTracker *t) { return t ? (int)t->ring
 extern "C" int sonde_track_submit(SondeTracker *t, const void *rows_dev, size_t n_samples, size_t row_stride, void *stream)
 {
 	if (!t || !rows_dev) return sd_fail("sonde_track_submit: null argument");
-	if (!n_samples || n_samples % TK_BLK || n_samples > t->max_samples)
+	if (!n_samples || n_samples % SD_BS_BLK || n_samples > t->max_samples)
 		return sd_fail("sonde_track_submit: n_samples must be a positive multiple of 256 and <= max_samples");
 	if (row_stride < n_samples) return sd_fail("sonde_track_submit: row_stride shorter than the row");
 	if ((uintptr_t)rows_dev & 7u) return sd_fail("sonde_track_submit: rows must be 8-byte aligned");
 	HIPCHK(hipSetDevice(t->device));
 	hipStream_t s = (hipStream_t)stream;
-	const uint32_t nb = (uint32_t)(n_samples / TK_BLK), LB = t->LB;
-	const dim3 wg(TK_WG);
+	const uint32_t nb = (uint32_t)(n_samples / SD_BS_BLK), LB = t->LB;
+	const dim3 wg(SD_BS_WG);
 	for (uint32_t vb = 0; vb < t->n_rows; vb += TK_VMAX) {
 		const uint32_t nv = t->n_rows - vb < TK_VMAX ? t->n_rows - vb : TK_VMAX;
 		SdTrackRows rs = {};
