@@ -111,13 +111,16 @@ enum { SONDE_INPUT_IQ = 0,      /* complex64 interleaved I,Q at 48 kS/s (vfo->ou
                                                     * iMet / C50 packet the bits SONDE_FLAG_AFSK_RESCUE flipped: 1, or 2 (an adjacent pair) */
 #define SONDE_FRAME_WORDS(f) (((f) >> 8) & 0xFu)   /* the same bits for DFM: codewords SONDE_FLAG_DFM_RESCUE decoded with erasures (1..8) */
 #define SONDE_FRAME_BLOCKS(f) (((f) >> 8) & 0xFu)  /* the same bits for iMS-100: BCH blocks SONDE_FLAG_IMS_RESCUE decoded (1..12) */
-#define SONDE_FRAME_COMBINED 4u  /* SondeFrame.flags: an RS41, M10 / M20 or MRZ-N1 frame sonde_batch_set_diversity put together from the copies of
+#define SONDE_FRAME_COMBINED 4u  /* SondeFrame.flags: an RS41, M10 / M20, MRZ-N1 or DFM frame sonde_batch_set_diversity put together from the copies of
                                   * several receivers (always with SONDE_FRAME_RESCUED; then SONDE_FRAME_COPIES says from how many) */
 #define SONDE_FRAME_COPIES(f) (((f) >> 8) & 0xFu)  /* the same bits for a combined frame of any of these types: the copies it was made from (2..4) */
 #define SONDE_FRAME_UNKNOWNS(f) (((f) >> 12) & 0xFu) /* SondeFrame.flags bits 12..15 of a combined M10 / M20 / MRZ-N1 frame: the bits on which its copies
                                   * differed, min(|V|, 15) (DESIGN SPEC 3.3l) -- the host's handle on wrong frames: a wrong subset fits with probability
                                   * about 2^(|V| - 16).  Zero in every other record, combined RS41 frames included */
-#define SONDE_FRAME_DUPLICATE 8u /* SondeFrame.flags: a good RS41, M10 / M20 or MRZ-N1 frame of which another receiver of its diversity group has delivered
+#define SONDE_FRAME_JOINT(f) (((f) >> 12) & 0xFu)  /* the same bits of a combined DFM frame: the Hamming words that had failed in EVERY copy and were decoded as
+                                  * the one codeword two bits from each (DESIGN SPEC 3.3m step 4b), capped at 15: a host that wants fewer wrong frames
+                                  * drops the combined DFM frames above its own limit */
+#define SONDE_FRAME_DUPLICATE 8u /* SondeFrame.flags: a good RS41, M10 / M20, MRZ-N1 or DFM frame of which another receiver of its diversity group has delivered
                                   * a copy (sonde_batch_set_diversity_auto with SONDE_DIVERSITY_MARK_DUPLICATES); sonde_batch_poll leaves its fragments out */
 #define SONDE_TILE       2048   /* samples; submit lengths are multiples of this */
 #define SONDE_FRAME_MAX  528
@@ -286,9 +289,9 @@ int  sonde_batch_submit_host(SondeBatch *b, const void *samples, size_t n_sample
  * nothing (stream order already says so); it is what a SONDE_FLAG_LATE_JOIN / SONDE_FLAG_PIPELINE host calls before it refills a
  * single buffer, and what any host calls to release the buffer on ANOTHER stream (a copy engine's).  0 = ok. */
 int  sonde_batch_wait_input(SondeBatch *b, void *stream);
-/* SEVERAL RECEIVERS OF ONE SONDE (DESIGN SPEC 3.3j: RS41; 3.3l: M10 / M20 and MRZ-N1).  A host that hears a sonde more than once -- two antennas or polarisations at one
+/* SEVERAL RECEIVERS OF ONE SONDE (DESIGN SPEC 3.3j: RS41; 3.3l: M10 / M20 and MRZ-N1; 3.3m: DFM).  A host that hears a sonde more than once -- two antennas or polarisations at one
  * site, two sites of a network -- gives each receiver a channel and names the channels of one sonde a GROUP: group[ch] = -1 (none) or a
- * group id 0..G-1 (no gaps), 2..4 channels of ONE type per group: SONDE_RS41, SONDE_M10 (M10 and M20) or SONDE_MRZN1.  offset_bits[ch] is where channel ch's bit count (SondeFrame.bitpos)
+ * group id 0..G-1 (no gaps), 2..4 channels of ONE type per group: SONDE_RS41, SONDE_M10 (M10 and M20), SONDE_MRZN1 or SONDE_DFM09.  offset_bits[ch] is where channel ch's bit count (SondeFrame.bitpos)
  * stands when the group's common clock reads 0 -- the host knows when it started each stream; NULL = zeros.  After every other pass
  * of a submit one more kernel visits the group's frame records in the order of the common clock.  A failed frame (RS41: a codeword at
  * nerr = -1; the others: nerr[0] = -1) looks in every other member for the nearest record of the same length within window_bits (0 = 960, at most 1200) of
@@ -311,12 +314,22 @@ int  sonde_batch_wait_input(SondeBatch *b, void *stream);
  * SONDE_FRAME_RESCUED | SONDE_FRAME_COMBINED, SONDE_FRAME_COPIES and SONDE_FRAME_UNKNOWNS = min(|V|, 15).  Limits: a bit wrong in EVERY
  * copy is no unknown, and then a wrong subset fits with probability about 2^(|V| - 16) -- a host that wants fewer wrong frames drops the
  * combined ones above its own SONDE_FRAME_UNKNOWNS; more than 8 unknowns with two copies stay as recorded; frames SONDE_FLAG_MANCHESTER_RESCUE
- * corrected count as good copies.  Not DFM, iMS-100, iMet or C50.
+ * corrected count as good copies.
+ * DFM (33 Hamming(8,4) words, no frame check; bitpos and offset_bits count CHIPS, frames lie 560 chips apart, so offset_bits must be good
+ * to within 279): failed = nerr[1] > 0, good = nerr[1] == 0 (frames SONDE_FLAG_DFM_RESCUE completed included).  A record keeps a word the
+ * first pass gave up on as received, so a byte's syndrome says whether the word failed in that copy.  Pairing guard: at least 17 words
+ * must be codewords in every copy and the copies may differ on at most 2 of those, else the record stays.  A word that failed in copy 0
+ * is the codeword most partners hold there (a tie: no result), taken only if every copy in which it failed lies exactly 2 bits from it;
+ * a word that failed in every copy decodes iff exactly one codeword lies 2 bits from each.  The frame is rewritten only if every such
+ * word decodes; words copy 0 holds as codewords are never touched.  A combined record carries the 33 codewords, nerr[0] raised by the
+ * words written, nerr[1] = 0, SONDE_FRAME_RESCUED | SONDE_FRAME_COMBINED, SONDE_FRAME_COPIES and SONDE_FRAME_JOINT.  Limits: a copy with
+ * four wrong bits in a word, or a partner's miscorrected word 2 bits from copy 0's, can give a wrong word, and nothing behind the code
+ * checks it -- SONDE_FRAME_JOINT is the host's handle.  Not iMS-100, iMet or C50.
  * Called once, before the first submit; if it is never called nothing is allocated or launched.  Refused: a second call, a call after a
  * submit, a group of fewer than 2 or more than 4 members, a member of any other type, members of different types in one group, group ids with gaps, window_bits > 1200, the
  * batch behind a channelizer, and a batch created with SONDE_FLAG_LATE_JOIN or SONDE_FLAG_PIPELINE (those never join their launch
- * units into one stream, and the pass needs all members' records).  One small launch more per submit for the RS41 groups and one
- * for the others, each only if the batch has such a group; no host synchronisation.
+ * units into one stream, and the pass needs all members' records).  One small launch more per submit for the RS41 groups, one for the
+ * M10 / M20 / MRZ-N1 groups and one for the DFM groups, each only if the batch has such a group; no host synchronisation.
  * On a batch with groups sonde_batch_restart_channels takes all members of a group or none of them (their bit counts must stay
  * together); a restarted group loses its carried records and its counters. */
 int  sonde_batch_set_diversity(SondeBatch *b, const int32_t *group /* n_channels entries */, const int64_t *offset_bits /* n_channels entries or NULL */,
@@ -327,7 +340,9 @@ int  sonde_batch_set_diversity(SondeBatch *b, const int32_t *group /* n_channels
  *                                    transmitted frame -- an RS41 frame carries its number and the sonde's serial; for M10 / M20 /
  *                                    MRZ-N1 groups: a length of the type, nerr[0] >= 0, bytes 0 .. len identical, on the standing
  *                                    assumption that consecutive frames of one sonde differ (they carry time) --, so the difference
- *                                    of their bitpos is the difference of the members' offsets.  Before the combining pass of every
+ *                                    of their bitpos is the difference of the members' offsets; for DFM groups: len 33, nerr[1] == 0,
+ *                                    bytes 0 .. 33 identical (a sonde at rest can repeat a subframe pair: of several identical
+ *                                    candidates the latest counts, DESIGN SPEC 3.3m).  Before the combining pass of every
  *                                    submit an align step looks for such pairs among each member's records of the submit and its
  *                                    carried record, member pairs in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), per pair the
  *                                    match that is latest in the higher member.  A member is LOCKED once it has an offset: two unlocked
@@ -454,6 +469,10 @@ int      sonde_batch_test_rs41_combine(SondeBatch *b, size_t n, const SondeFrame
  * a length-byte bit in doubt), -2 (no subset fits) or -3 (several fit).  Refused: n_copies outside 2..4, a good copy 0, copies of
  * differing type or len. */
 int      sonde_batch_test_check_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status);
+/* The combining rule of DFM groups alone (SPEC 3.3m steps 3 to 6), on any batch: the shape of sonde_batch_test_rs41_combine.  Every copy:
+ * a SONDE_DFM09 record of 33 bytes; copy 0 with nerr[1] > 0.  status[i] = the copies used, -1 (the pairing guard refuses), -2 (a word has
+ * no solution) or -3 (no word has none, one has several).  Refused: n_copies outside 2..4, a good copy 0, a copy of another type or len. */
+int      sonde_batch_test_dfm_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status);
 /* sonde_batch_set_diversity_auto introspection: where each member of the group stands on the group's clock now (off[m], member m = the
  * group's m-th channel in ascending order; unused entries 0), which members are locked (bit m), how many offsets the align step has
  * set or changed and how many records it has marked SONDE_FRAME_DUPLICATE since the call / the group's restart.  Synchronises.  With

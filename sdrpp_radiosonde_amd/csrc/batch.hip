@@ -578,6 +578,11 @@ static int launch_diversity(SondeBatch *b, SubmitCtx &cx)
 			b->d_groups, b->d_divstate, b->div_window, b->d_carried, b->d_divcnt);
 		HIPCHK(hipGetLastError());
 	}
+	if (b->div_kinds & (1u << SONDE_DFM09)) {      // SPEC 3.3m
+		sd_launch_dfm_diversity(b->n_groups, cx.done, cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_groups, b->d_divstate,
+			b->div_window, b->d_carried, b->d_divcnt);
+		HIPCHK(hipGetLastError());
+	}
 	cx.framer_launched = true;
 	return 0;
 }
@@ -804,7 +809,7 @@ int sd_batch_need_mrztab(SondeBatch *b)
 	return 0;
 }
 
-// The receivers of one sonde (include/sonde_abi.h, SPEC 3.3j, 3.3k and 3.3l): the group table, the carried records, the counters and the
+// The receivers of one sonde (include/sonde_abi.h, SPEC 3.3j, 3.3k, 3.3l and 3.3m): the group table, the carried records, the counters and the
 // align step's state.  mode 0 is sonde_batch_set_diversity.
 extern "C" int sonde_batch_set_diversity(SondeBatch *b, const int32_t *group, const int64_t *offset_bits, uint32_t window_bits)
 {
@@ -836,8 +841,8 @@ extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *grou
 		if (group[c] < 0) continue;
 		SdDivGroup &g = gt[(size_t)group[c]];
 		const uint32_t t = b->types[c];
-		if (t != SONDE_RS41 && t != SONDE_M10 && t != SONDE_MRZN1)
-			return sd_fail("sonde_batch_set_diversity: a member that is not SONDE_RS41, SONDE_M10 or SONDE_MRZN1");
+		if (t != SONDE_RS41 && t != SONDE_M10 && t != SONDE_MRZN1 && t != SONDE_DFM09)
+			return sd_fail("sonde_batch_set_diversity: a member that is not SONDE_RS41, SONDE_M10, SONDE_MRZN1 or SONDE_DFM09");
 		if (g.n && g.kind != t) return sd_fail("sonde_batch_set_diversity: members of different types in one group");
 		g.kind = t;
 		kinds |= 1u << t;

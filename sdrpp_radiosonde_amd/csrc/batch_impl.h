@@ -179,7 +179,7 @@ struct SondeBatch {
 	// allocated or launched
 	// div_mode: sonde_batch_set_diversity_auto's mode (SPEC 3.3k; 0: no align step is launched), div_unlocked: its groups start unlocked;
 	// d_divstate: per group the offsets and lock bits the combining pass reads, and the align step's counters
-	// div_kinds: a bit per sonde type that has a group (SPEC 3.3l): which of the two combining kernels are launched
+	// div_kinds: a bit per sonde type that has a group (SPEC 3.3l, 3.3m): which of the three combining kernels are launched
 	uint32_t n_groups = 0, div_window = 0, div_mode = 0, div_unlocked = 0, div_kinds = 0;
 	DevBuf<SdDivGroup> d_groups;
 	DevBuf<SdDivState> d_divstate;

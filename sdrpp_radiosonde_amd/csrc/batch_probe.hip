@@ -188,6 +188,28 @@ extern "C" int sonde_batch_test_check_combine(SondeBatch *b, size_t n, const Son
 	});
 }
 
+// Steps 3 to 6 of SPEC 3.3m alone, through the kernel's own device function: the shape of sonde_batch_test_rs41_combine; status[i] =
+// copies used, -1 the pairing guard refuses, -2 a word has no solution, -3 a word has several.
+extern "C" int sonde_batch_test_dfm_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status)
+{
+	if (!b || !copies || !n_copies || !out || !status || !n || n > (1u << 16)) return sd_fail("sonde_batch_test_dfm_combine: bad argument");
+	for (size_t i = 0; i < n; i++) {
+		const SondeFrame *c = copies + SD_DIV_MAX * i;
+		if (n_copies[i] < 2 || n_copies[i] > SD_DIV_MAX) return sd_fail("sonde_batch_test_dfm_combine: n_copies must be 2..4");
+		if (c[0].nerr[1] <= 0) return sd_fail("sonde_batch_test_dfm_combine: copy 0 must be a failed record (nerr[1] > 0)");
+		for (uint32_t k = 0; k < n_copies[i]; k++)
+			if (c[k].type != SONDE_DFM09 || c[k].len != 33) return sd_fail("sonde_batch_test_dfm_combine: every copy must be a SONDE_DFM09 record of 33 bytes");
+	}
+	HIPCHK(hipSetDevice(b->device));
+	DevBuf<SondeFrame> d_c;
+	DevBuf<uint32_t> d_n;
+	HIPCHK(d_c.upload(copies, SD_DIV_MAX * n));
+	HIPCHK(d_n.upload(n_copies, n));
+	return probe_unit("sonde_batch_test_dfm_combine", (const SondeFrame *)nullptr, out, n, status, n, [&](SondeFrame *d_o, int32_t *d_st) {
+		sd_launch_dfm_diversity_unit(d_c, d_n, (uint32_t)n, d_o, d_st, nullptr);
+	});
+}
+
 extern "C" int sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t off[4], uint32_t *locked_mask, uint32_t *learned, uint32_t *duplicates)
 {
 	if (!b) return sd_fail("sonde_batch_diversity_offsets: bad argument");

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(64 * CD_WAVES) void sd_check_diversity_kernel(
 	if (g >= n_groups) return;
 	const SdDivGroup *G = groups + g;
 	const uint32_t kind = (uint32_t)DV_U(G->kind);
-	if (kind != SONDE_M10 && kind != SONDE_MRZN1) return;      // an RS41 group: diversity_kernel.hip's
+	if (kind != SONDE_M10 && kind != SONDE_MRZN1) return;      // an RS41 or a DFM group: another kernel's
 	const bool mrz = kind == SONDE_MRZN1;
 	DvMembers M;
 	dv_members(M, frames, counts, max_frames, G, states + g);

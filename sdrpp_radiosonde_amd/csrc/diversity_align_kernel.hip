@@ -1,7 +1,7 @@
 // diversity_align_kernel.hip -- sonde_batch_set_diversity_auto (DESIGN SPEC 3.3k): the align step in front of the combining pass of
-// diversity_kernel.hip and check_diversity_kernel.hip.  Two good RS41 records of different members whose bytes 8 .. len are identical
+// diversity_kernel.hip, check_diversity_kernel.hip and dfm_diversity_kernel.hip.  Two good RS41 records of different members whose bytes 8 .. len are identical
 // are the same transmitted frame (the frame carries its number and the sonde's serial), and so are two good M10 / M20 or MRZ-N1 records
-// whose bytes 0 .. len are (SPEC 3.3l: consecutive frames of one sonde differ); from such pairs the step learns where each member's bit count stands on the
+// whose bytes 0 .. len are (SPEC 3.3l: consecutive frames of one sonde differ) and two good DFM records whose 33 bytes are (SPEC 3.3m); from such pairs the step learns where each member's bit count stands on the
 // group's clock (SONDE_DIVERSITY_LEARN), and it marks all but one copy of a frame (SONDE_DIVERSITY_MARK_DUPLICATES).
 //   one 64-lane wave per group, a launch of its own in front of sd_diversity_kernel on the stream where the submit completes.  The
 //   lanes take one member's records (any number: the loops stride by 64) and each walks the other member's; a record's key is two
@@ -19,21 +19,24 @@ struct AlMember { SondeFrame *recs; const SondeFrame *carried; uint32_t cnt; };
 
 // The two predicates of the step depend on the group's kind (SdDivGroup.kind; wave-uniform).  RS41 (SPEC 3.3k): good = len 320 or 518 and
 // both nerr >= 0, the same frame = data[8 .. len) identical.  M10 / M20 and MRZ-N1 (SPEC 3.3l): good = a length of the type and
-// nerr[0] >= 0 (nerr[1] counts Manchester violations there), the same frame = data[0 .. len) identical.
+// nerr[0] >= 0 (nerr[1] counts Manchester violations there), the same frame = data[0 .. len) identical.  DFM (SPEC 3.3m): good = len 33
+// and nerr[1] == 0 (no word the first pass gave up on; nerr[0] counts corrected words), the same frame = data[0 .. 33) identical.
 __device__ __forceinline__ const SondeFrame *al_cand(const AlMember &M, uint32_t i) { return i < M.cnt ? M.recs + i : M.carried; }
 __device__ __forceinline__ bool al_good(uint32_t kind, const SondeFrame *f)
 {
 	if (kind == SONDE_M10) return (f->len == 101 || f->len == 70) && f->nerr[0] >= 0;
 	if (kind == SONDE_MRZN1) return f->len == 45 && f->nerr[0] >= 0;
+	if (kind == SONDE_DFM09) return f->len == 33 && f->nerr[1] == 0;
 	return (f->len == 320 || f->len == 518) && f->nerr[0] >= 0 && f->nerr[1] >= 0;
 }
 // the quick reject: two words that differ between any two frames.  RS41: parity bytes of codeword 0 and of codeword 1; the others: the
-// frame's last two words, which hold the 16-bit check (the bytes of the last word behind len are not looked at)
+// frame's last two words, which hold the 16-bit check -- for DFM the end of the second data block -- (the bytes of the last word behind
+// len are not looked at)
 __device__ __forceinline__ uint32_t al_key(uint32_t kind, const SondeFrame *f)
 {
 	const uint32_t *w = reinterpret_cast<const uint32_t *>(f->data);
 	if (kind == SONDE_RS41) return w[2] ^ w[8];
-	const int len = f->len, wl = (len - 1) >> 2;           // a good record: len is 45, 70 or 101, wl >= 11
+	const int len = f->len, wl = (len - 1) >> 2;           // a good record: len is 33, 45, 70 or 101, wl >= 8
 	const uint32_t last = (len & 3) ? w[wl] & ((1u << (8 * (len & 3))) - 1u) : w[wl];
 	return last ^ ((w[wl - 1] << 13) | (w[wl - 1] >> 19));
 }

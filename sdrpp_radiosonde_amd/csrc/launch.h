@@ -127,9 +127,9 @@ void sd_launch_ims_block_unit(const uint8_t *g64, uint64_t *blocks, const uint64
 // steps 1..5 of 3.3i: n records; status = 0 untouched, 1 rescued, 2 several patterns fit
 void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status, hipStream_t stream);
 
-// sonde_batch_set_diversity (DESIGN SPEC 3.3j, 3.3l): a group = 2..4 channels of one type that hear the same sonde; ch[m] and off[m]
-// (offset_bits) per member, kind = the members' type: SONDE_RS41 (0: diversity_kernel.hip), SONDE_M10 or SONDE_MRZN1
-// (check_diversity_kernel.hip).  Each combining kernel is launched over the whole table and takes the groups of its kinds; the align
+// sonde_batch_set_diversity (DESIGN SPEC 3.3j, 3.3l, 3.3m): a group = 2..4 channels of one type that hear the same sonde; ch[m] and
+// off[m] (offset_bits) per member, kind = the members' type: SONDE_RS41 (0: diversity_kernel.hip), SONDE_M10 or SONDE_MRZN1
+// (check_diversity_kernel.hip), SONDE_DFM09 (dfm_diversity_kernel.hip).  Each combining kernel is launched over the whole table and takes the groups of its kinds; the align
 // step, the carried records, the counters and the state are one space for all kinds.  carried: [n_groups][SD_DIV_MAX] records
 // (len = 0: none), counters: [n_groups][2] (tried, combined); both carried from submit to submit.  The launches stand behind every
 // other kernel of the submit.
@@ -168,6 +168,14 @@ void sd_launch_check_diversity(uint32_t n_groups, hipStream_t stream, const uint
 // -3 several fit
 void sd_launch_check_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
 	const uint16_t *m10tab, const uint16_t *mrztab, hipStream_t stream);
+
+// the combining pass of SPEC 3.3m over the DFM groups of the table (dfm_diversity_kernel.hip); launched only when the batch has one
+void sd_launch_dfm_diversity(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
+	const SdDivGroup *groups, const SdDivState *states, uint32_t window, SondeFrame *carried, uint32_t *counters);
+// steps 3 to 6 of SPEC 3.3m alone, the shape of sd_launch_diversity_unit: status = copies used, -1 the pairing guard refuses, -2 a word
+// has no solution, -3 a word has several
+void sd_launch_dfm_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
+	hipStream_t stream);
 
 // sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);

@@ -1,7 +1,7 @@
-// sd_diversity_scan.h -- what the two combining passes of sonde_batch_set_diversity share (diversity_kernel.hip, DESIGN SPEC 3.3j: RS41;
-// check_diversity_kernel.hip, SPEC 3.3l: M10 / M20 / MRZ-N1): the members of a group, steps 1 and 2 of SPEC 3.3j -- the scan of the
-// members' record headers for the next failed record in (t, member) order and for its partner in another member -- and the carried
-// records.  The two passes differ in two predicates, both functions of the group's kind (SdDivGroup.kind = the members' sonde type):
+// sd_diversity_scan.h -- what the three combining passes of sonde_batch_set_diversity share (diversity_kernel.hip, DESIGN SPEC 3.3j: RS41;
+// check_diversity_kernel.hip, SPEC 3.3l: M10 / M20 / MRZ-N1; dfm_diversity_kernel.hip, SPEC 3.3m: DFM): the members of a group, steps 1
+// and 2 of SPEC 3.3j -- the scan of the members' record headers for the next failed record in (t, member) order and for its partner in
+// another member -- and the carried records.  The passes differ in two predicates, both functions of the group's kind (SdDivGroup.kind = the members' sonde type):
 // which record lengths are frames, and when a record has failed.  One 64-lane wave per group; every result is wave-uniform.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,13 +13,18 @@
 constexpr int DV_REC_WORDS = (int)(sizeof(SondeFrame) / 4);
 constexpr int DV_DATA_WORD0 = (int)(offsetof(SondeFrame, data) / 4);
 
-// a frame length of the kind: RS41 {320, 518}, M10 / M20 {101, 70}, MRZ-N1 {45}
+// a frame length of the kind: RS41 {320, 518}, M10 / M20 {101, 70}, MRZ-N1 {45}, DFM {33}
 __device__ __forceinline__ bool dv_len_ok(uint32_t kind, int len)
 {
-	return kind == SONDE_M10 ? (len == 101 || len == 70) : kind == SONDE_MRZN1 ? len == 45 : (len == 320 || len == 518);
+	return kind == SONDE_M10 ? (len == 101 || len == 70) : kind == SONDE_MRZN1 ? len == 45 : kind == SONDE_DFM09 ? len == 33 : (len == 320 || len == 518);
 }
-// failed: RS41 a codeword at nerr < 0, the others the 16-bit check (nerr[0] < 0; nerr[1] counts Manchester violations there)
-__device__ __forceinline__ bool dv_failed(uint32_t kind, const SondeFrame *f) { return f->nerr[0] < 0 || (kind == SONDE_RS41 && f->nerr[1] < 0); }
+// failed: RS41 a codeword at nerr < 0, M10 / M20 / MRZ-N1 the 16-bit check (nerr[0] < 0; nerr[1] counts Manchester violations there),
+// DFM a Hamming word the first pass gave up on (nerr[1] > 0; nerr[0] counts corrected words there)
+__device__ __forceinline__ bool dv_failed(uint32_t kind, const SondeFrame *f)
+{
+	if (kind == SONDE_DFM09) return f->nerr[1] > 0;
+	return f->nerr[0] < 0 || (kind == SONDE_RS41 && f->nerr[1] < 0);
+}
 
 // a word of a record another lane of this wave may have written earlier in this kernel
 __device__ __forceinline__ uint32_t dv_load_fresh(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }

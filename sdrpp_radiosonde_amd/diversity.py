@@ -1,4 +1,4 @@
-"""Python face of a receiver with several antennas (DESIGN SPEC 3.3k, 3.3l): thin, no compute -- every call goes through the C ABI of
+"""Python face of a receiver with several antennas (DESIGN SPEC 3.3k, 3.3l, 3.3m): thin, no compute -- every call goes through the C ABI of
 libsonde_mi355.so.
 
     DiversityReceiver   K wideband streams (one per antenna or polarisation, started whenever) -> K tuners with the same VFO list ->
@@ -9,23 +9,26 @@ libsonde_mi355.so.
                         detection -> one SondeBatch of one channel per sonde: any sonde type, the antennas on one sample clock
 
 The chain is the "iq48" chain of _chain.py, which WidebandReceiver (tuner.py) and LiveReceiver share: a tuner per antenna straight to
-48 kHz IQ rows.  combine="frames" (the default): RS41, M10 / M20 and MRZ-N1 sondes, in any mix.  No tracking, no reference chain."""
+48 kHz IQ rows.  combine="frames" (the default): RS41, M10 / M20 and MRZ-N1 sondes, in any mix, and with dfm_diversity=True DFM sondes too.  No tracking, no
+reference chain."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import _chain
 from ._handle import current_stream
-from ._lib import FRAME_DUPLICATE, INPUT_IQ, M10, MRZN1, RS41, SondeError
+from ._lib import DFM09, FRAME_DUPLICATE, INPUT_IQ, M10, MRZN1, RS41, SondeError
 from .tuner import SondeTuner
 
 
 class DiversityReceiver:
-    """sondes: [(offset_hz, sonde type), ...], every type RS41, M10 (M10 and M20) or MRZN1; antennas = K = 2..4 wideband streams at rate_in that hear them.
+    """sondes: [(offset_hz, sonde type), ...], every type RS41, M10 (M10 and M20) or MRZN1, with dfm_diversity=True DFM09 too; antennas = K = 2..4 wideband streams at rate_in that hear them.
     Batch channel a * len(sondes) + i is sonde i on antenna a; the K channels of sonde i are diversity group i, antenna a its member a,
     set with learn=True, mark_duplicates=True and no offsets: the streams need not start together, the group finds out where they
     stand from the first frame that is good on two antennas (SondeBatch.set_diversity).  rescue= (RS41) and manchester_rescue= (M10 /
     M20 / MRZ-N1) are the batch's second passes in front of the diversity pass; what they complete counts as a good copy.
+    dfm_diversity=True: DFM sondes are taken as well (SPEC 3.3m: failed copies are combined word by word), and dfm_rescue= is passed on
+    to the batch as the DFM second pass in front of it.
 
     submit(blocks) takes K device blocks [n, 2] of equal length (float32 / int16 / int8 by input_kind), n a multiple of `granule`
     and <= max_in.  frames() returns (records, antenna): the last submit's records without the duplicates, `channel` = the sonde
@@ -43,7 +46,7 @@ class DiversityReceiver:
     def __init__(self, rate_in: int, sondes, antennas: int = 2, *, input_kind: int = INPUT_IQ, device: int = 0, max_in: int | None = None,
                  window_bits: int = 0, rescue: bool = False, chain: str = "iq48", track: bool = False, combine: str = "frames",
                  combine_block: int = 0, manchester_rescue: bool = False, dfm_rescue: bool = False, ims_rescue: bool = False,
-                 afsk_rescue: bool = False):
+                 afsk_rescue: bool = False, dfm_diversity: bool = False):
         if chain != "iq48":
             raise SondeError('DiversityReceiver: only the "iq48" chain')
         if track:
@@ -57,9 +60,9 @@ class DiversityReceiver:
         coherent = combine == "coherent"
         types = [t for _, t in self.sondes]
         if not coherent:
-            if dfm_rescue or ims_rescue or afsk_rescue:
+            if (dfm_rescue and not dfm_diversity) or ims_rescue or afsk_rescue:
                 raise SondeError('DiversityReceiver: combine="frames" takes no rescue pass but rescue= and manchester_rescue=')
-            if any(t not in (RS41, M10, MRZN1) for t in types):
+            if any(t not in ((RS41, M10, MRZN1, DFM09) if dfm_diversity else (RS41, M10, MRZN1)) for t in types):
                 raise SondeError('DiversityReceiver: the frame-level pass serves M10 / M20, MRZ-N1 and RS41 sondes only (combine="coherent" takes any type)')
         self.antennas = int(antennas)
         if not 2 <= self.antennas <= 4:
