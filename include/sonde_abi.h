@@ -111,7 +111,7 @@ enum { SONDE_INPUT_IQ = 0,      /* complex64 interleaved I,Q at 48 kS/s (vfo->ou
                                                     * iMet / C50 packet the bits SONDE_FLAG_AFSK_RESCUE flipped: 1, or 2 (an adjacent pair) */
 #define SONDE_FRAME_WORDS(f) (((f) >> 8) & 0xFu)   /* the same bits for DFM: codewords SONDE_FLAG_DFM_RESCUE decoded with erasures (1..8) */
 #define SONDE_FRAME_BLOCKS(f) (((f) >> 8) & 0xFu)  /* the same bits for iMS-100: BCH blocks SONDE_FLAG_IMS_RESCUE decoded (1..12) */
-#define SONDE_FRAME_COMBINED 4u  /* SondeFrame.flags: an RS41, M10 / M20, MRZ-N1 or DFM frame sonde_batch_set_diversity put together from the copies of
+#define SONDE_FRAME_COMBINED 4u  /* SondeFrame.flags: an RS41, M10 / M20, MRZ-N1, DFM or iMS-100 frame sonde_batch_set_diversity put together from the copies of
                                   * several receivers (always with SONDE_FRAME_RESCUED; then SONDE_FRAME_COPIES says from how many) */
 #define SONDE_FRAME_COPIES(f) (((f) >> 8) & 0xFu)  /* the same bits for a combined frame of any of these types: the copies it was made from (2..4) */
 #define SONDE_FRAME_UNKNOWNS(f) (((f) >> 12) & 0xFu) /* SondeFrame.flags bits 12..15 of a combined M10 / M20 / MRZ-N1 frame: the bits on which its copies
@@ -119,8 +119,10 @@ enum { SONDE_INPUT_IQ = 0,      /* complex64 interleaved I,Q at 48 kS/s (vfo->ou
                                   * about 2^(|V| - 16).  Zero in every other record, combined RS41 frames included */
 #define SONDE_FRAME_JOINT(f) (((f) >> 12) & 0xFu)  /* the same bits of a combined DFM frame: the Hamming words that had failed in EVERY copy and were decoded as
                                   * the one codeword two bits from each (DESIGN SPEC 3.3m step 4b), capped at 15: a host that wants fewer wrong frames
-                                  * drops the combined DFM frames above its own limit */
-#define SONDE_FRAME_DUPLICATE 8u /* SondeFrame.flags: a good RS41, M10 / M20, MRZ-N1 or DFM frame of which another receiver of its diversity group has delivered
+                                  * drops the combined DFM frames above its own limit.  Of a combined iMS-100 frame: the BCH blocks that had been
+                                  * rejected in EVERY copy and were decoded from the bitwise majority of the copies (DESIGN SPEC 3.3n step 5b), capped
+                                  * at 15; SONDE_FRAME_COPIES = the copies it was made from (2..4) */
+#define SONDE_FRAME_DUPLICATE 8u /* SondeFrame.flags: a good RS41, M10 / M20, MRZ-N1, DFM or iMS-100 frame of which another receiver of its diversity group has delivered
                                   * a copy (sonde_batch_set_diversity_auto with SONDE_DIVERSITY_MARK_DUPLICATES); sonde_batch_poll leaves its fragments out */
 #define SONDE_TILE       2048   /* samples; submit lengths are multiples of this */
 #define SONDE_FRAME_MAX  528
@@ -261,6 +263,12 @@ typedef struct {
  * no host synchronisation.  Out of reach: candidates the framer dropped (a wrong start or stop bit, a damaged type, length or sync
  * byte), two separated wrong bits; no soft decisions, not the batch behind a channelizer. */
 #define SONDE_FLAG_AFSK_RESCUE 1024u
+/* iMS-100 / RS-11G channels may be members of sonde_batch_set_diversity groups (DESIGN SPEC 3.3n; see SEVERAL RECEIVERS OF ONE SONDE below).
+ * Opt-in at create because the pass differs from its siblings in what it costs: an iMS-100 record keeps data bits only, so the pass
+ * rebuilds every copy's twelve BCH(46,34) blocks from the chips of the members' bit rings.  Without the flag an iMS-100 member is
+ * refused as before; with the flag and no iMS-100 group in the table nothing is allocated or launched, and every record is byte for
+ * byte what it is without the flag. */
+#define SONDE_FLAG_IMS_DIVERSITY 2048u
 
 typedef struct SondeBatch SondeBatch;
 
@@ -289,9 +297,9 @@ int  sonde_batch_submit_host(SondeBatch *b, const void *samples, size_t n_sample
  * nothing (stream order already says so); it is what a SONDE_FLAG_LATE_JOIN / SONDE_FLAG_PIPELINE host calls before it refills a
  * single buffer, and what any host calls to release the buffer on ANOTHER stream (a copy engine's).  0 = ok. */
 int  sonde_batch_wait_input(SondeBatch *b, void *stream);
-/* SEVERAL RECEIVERS OF ONE SONDE (DESIGN SPEC 3.3j: RS41; 3.3l: M10 / M20 and MRZ-N1; 3.3m: DFM).  A host that hears a sonde more than once -- two antennas or polarisations at one
+/* SEVERAL RECEIVERS OF ONE SONDE (DESIGN SPEC 3.3j: RS41; 3.3l: M10 / M20 and MRZ-N1; 3.3m: DFM; 3.3n: iMS-100).  A host that hears a sonde more than once -- two antennas or polarisations at one
  * site, two sites of a network -- gives each receiver a channel and names the channels of one sonde a GROUP: group[ch] = -1 (none) or a
- * group id 0..G-1 (no gaps), 2..4 channels of ONE type per group: SONDE_RS41, SONDE_M10 (M10 and M20), SONDE_MRZN1 or SONDE_DFM09.  offset_bits[ch] is where channel ch's bit count (SondeFrame.bitpos)
+ * group id 0..G-1 (no gaps), 2..4 channels of ONE type per group: SONDE_RS41, SONDE_M10 (M10 and M20), SONDE_MRZN1, SONDE_DFM09 or (batches created with SONDE_FLAG_IMS_DIVERSITY) SONDE_IMS100.  offset_bits[ch] is where channel ch's bit count (SondeFrame.bitpos)
  * stands when the group's common clock reads 0 -- the host knows when it started each stream; NULL = zeros.  After every other pass
  * of a submit one more kernel visits the group's frame records in the order of the common clock.  A failed frame (RS41: a codeword at
  * nerr = -1; the others: nerr[0] = -1) looks in every other member for the nearest record of the same length within window_bits (0 = 960, at most 1200) of
@@ -324,12 +332,26 @@ int  sonde_batch_wait_input(SondeBatch *b, void *stream);
  * word decodes; words copy 0 holds as codewords are never touched.  A combined record carries the 33 codewords, nerr[0] raised by the
  * words written, nerr[1] = 0, SONDE_FRAME_RESCUED | SONDE_FRAME_COMBINED, SONDE_FRAME_COPIES and SONDE_FRAME_JOINT.  Limits: a copy with
  * four wrong bits in a word, or a partner's miscorrected word 2 bits from copy 0's, can give a wrong word, and nothing behind the code
- * checks it -- SONDE_FRAME_JOINT is the host's handle.  Not iMS-100, iMet or C50.
+ * checks it -- SONDE_FRAME_JOINT is the host's handle.
+ * iMS-100 / RS-11G (SONDE_FLAG_IMS_DIVERSITY; 12 blocks of BCH(46,34), t = 2, no frame check; bitpos and offset_bits count CHIPS, frames
+ * lie 1152 chips apart, window_bits 0 = 576, so offset_bits must be good to within 575): failed = nerr[1] > 0, good = nerr[1] == 0
+ * (frames SONDE_FLAG_IMS_RESCUE completed included).  A record keeps data bits only, so every copy's blocks are rebuilt from the chips
+ * of its channel's bit ring; a partner whose chips are no longer held, or whose chips do not say what its record says, is left out.
+ * Pairing guard: at least 6 blocks must be accepted in every copy and at most 1 of them may differ between the copies, else the record
+ * stays.  A block rejected in copy 0 is the codeword most partners hold there (a tie: no result), taken only if every copy that
+ * rejected it lies at most 5 bits from it; a block rejected in every copy is the bitwise majority of the received blocks, the
+ * positions without a majority (2 copies: where they differ; 4: two against two; at most 6) tried both ways, and decodes iff exactly
+ * one of those words is a codeword.  The frame is rewritten only if every rejected block decodes; blocks copy 0 holds as accepted are
+ * never touched.  A combined record carries the data bits of the decoded blocks, nerr[0] raised by the bits in which they differ from
+ * copy 0's received blocks, nerr[1] = 0, SONDE_FRAME_RESCUED | SONDE_FRAME_COMBINED, SONDE_FRAME_COPIES and SONDE_FRAME_JOINT.
+ * Nothing behind the code checks the result: a host that wants fewer wrong frames drops those with SONDE_FRAME_JOINT > 0.
+ * Not iMet or C50.
  * Called once, before the first submit; if it is never called nothing is allocated or launched.  Refused: a second call, a call after a
  * submit, a group of fewer than 2 or more than 4 members, a member of any other type, members of different types in one group, group ids with gaps, window_bits > 1200, the
  * batch behind a channelizer, and a batch created with SONDE_FLAG_LATE_JOIN or SONDE_FLAG_PIPELINE (those never join their launch
  * units into one stream, and the pass needs all members' records).  One small launch more per submit for the RS41 groups, one for the
- * M10 / M20 / MRZ-N1 groups and one for the DFM groups, each only if the batch has such a group; no host synchronisation.
+ * M10 / M20 / MRZ-N1 groups, one for the DFM groups and one for the iMS-100 groups, each only if the batch has such a group; no host
+ * synchronisation.
  * On a batch with groups sonde_batch_restart_channels takes all members of a group or none of them (their bit counts must stay
  * together); a restarted group loses its carried records and its counters. */
 int  sonde_batch_set_diversity(SondeBatch *b, const int32_t *group /* n_channels entries */, const int64_t *offset_bits /* n_channels entries or NULL */,
@@ -342,7 +364,8 @@ int  sonde_batch_set_diversity(SondeBatch *b, const int32_t *group /* n_channels
  *                                    assumption that consecutive frames of one sonde differ (they carry time) --, so the difference
  *                                    of their bitpos is the difference of the members' offsets; for DFM groups: len 33, nerr[1] == 0,
  *                                    bytes 0 .. 33 identical (a sonde at rest can repeat a subframe pair: of several identical
- *                                    candidates the latest counts, DESIGN SPEC 3.3m).  Before the combining pass of every
+ *                                    candidates the latest counts, DESIGN SPEC 3.3m); for iMS-100 groups: len 51, nerr[1] == 0,
+ *                                    bytes 0 .. 51 identical (SPEC 3.3n).  Before the combining pass of every
  *                                    submit an align step looks for such pairs among each member's records of the submit and its
  *                                    carried record, member pairs in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), per pair the
  *                                    match that is latest in the higher member.  A member is LOCKED once it has an offset: two unlocked
@@ -473,6 +496,14 @@ int      sonde_batch_test_check_combine(SondeBatch *b, size_t n, const SondeFram
  * a SONDE_DFM09 record of 33 bytes; copy 0 with nerr[1] > 0.  status[i] = the copies used, -1 (the pairing guard refuses), -2 (a word has
  * no solution) or -3 (no word has none, one has several).  Refused: n_copies outside 2..4, a good copy 0, a copy of another type or len. */
 int      sonde_batch_test_dfm_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status);
+/* The combining rule of iMS-100 groups alone (SPEC 3.3n steps 4 to 7), on any batch.  Case i: records[i] = copy 0's record (SONDE_IMS100,
+ * 51 bytes, nerr[1] > 0), n_copies[i] = 2..4, blocks[48 i + 12 j + L] = block L of copy j as received (bit b of the block = bit 45 - b
+ * of the word; copy 0's blocks are the record's own).  out[i] = the record after the rule; status[i] = the copies used, 0 (the
+ * record's nerr[1] is not the number of blocks the first pass rejects among copy 0's: the record stays, SPEC step 3), -1 (the pairing
+ * guard refuses), -2 (a block has no solution) or -3 (no block has none, one has several).  Refused: n_copies outside 2..4, a record
+ * of another type or len, a good copy 0. */
+int      sonde_batch_test_ims_combine(SondeBatch *b, size_t n, const SondeFrame *records, const uint32_t *n_copies, const uint64_t *blocks,
+                                      SondeFrame *out, int32_t *status);
 /* sonde_batch_set_diversity_auto introspection: where each member of the group stands on the group's clock now (off[m], member m = the
  * group's m-th channel in ascending order; unused entries 0), which members are locked (bit m), how many offsets the align step has
  * set or changed and how many records it has marked SONDE_FRAME_DUPLICATE since the call / the group's restart.  Synchronises.  With
@@ -485,6 +516,11 @@ int      sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t of
 int      sonde_batch_test_diversity_align(SondeBatch *b, size_t n, size_t max_rec, const uint32_t *n_members, SondeFrame *records, const uint32_t *counts,
                                           const SondeFrame *carried, int64_t *off, uint32_t *locked, const uint32_t *mode, uint32_t *learned,
                                           uint32_t *duplicates);
+/* The same with the predicates of another kind of group: kind = SONDE_RS41, SONDE_M10, SONDE_MRZN1, SONDE_DFM09 or SONDE_IMS100 (DESIGN SPEC
+ * 3.3k, 3.3l, 3.3m, 3.3n: which records are good, and when two are the same transmitted frame).  Refused: any other kind. */
+int      sonde_batch_test_diversity_align_kind(SondeBatch *b, uint32_t kind, size_t n, size_t max_rec, const uint32_t *n_members, SondeFrame *records,
+                                               const uint32_t *counts, const SondeFrame *carried, int64_t *off, uint32_t *locked, const uint32_t *mode,
+                                               uint32_t *learned, uint32_t *duplicates);
 /* STREAM AGE, test introspection only -- NOT FOR HOSTS (DESIGN "Stream age").  Each listed channel becomes "the same stream, begun
  * samples[i] input samples and bits_added[i] bits earlier": the call adds to every absolute position the batch carries for the channel
  * and leaves everything relative as it is, so that the tests can put a channel just below 2^31, 2^32, 2^37, 2^48 ... without feeding

@@ -94,10 +94,10 @@ def check_block(n: int, granule: int, max_in: int, noun: str = "block"):
         raise SondeError(f"the {noun} must hold a positive multiple of the granule ({granule}) samples, at most max_in ({max_in})")
 
 
-def batch(n_channels: int, n48: int, types, device: int, rescue, input_kind: int = INPUT_IQ) -> SondeBatch:
-    """the decoders of a chain; rescue: the receiver's five rescue keywords in _lib.rescue_flags' order"""
+def batch(n_channels: int, n48: int, types, device: int, rescue, input_kind: int = INPUT_IQ, flags: int = 0) -> SondeBatch:
+    """the decoders of a chain; rescue: the receiver's five rescue keywords in _lib.rescue_flags' order; flags: further create flags"""
     return SondeBatch(n_channels, n48, types=np.asarray(types, dtype=np.uint8), input_kind=input_kind, device=device,
-                      flags=_lib.rescue_flags(*rescue))
+                      flags=_lib.rescue_flags(*rescue) | int(flags))
 
 
 def rows(n_rows: int, n48: int, device: int, input_kind: int = INPUT_IQ):

@@ -115,8 +115,9 @@ FLAG_JOIN = 16           # accepted and ignored: joining at every submit is the 
 FLAG_LATE_JOIN = 32      # launch units joined into the caller's stream ONE SUBMIT LATE (SONDE_FLAG_LATE_JOIN; opt-in: round 5's default)
 FLAG_WIDE_AUTO = 8       # SONDE_FLAG_WIDE for the types whose reference channel is >= 20 kHz only (iMS-100, MRZ-N1, M10)
 FLAG_RS41_RESCUE = 64    # RS41: second pass over frames whose RS stage failed, block CRCs as erasure hints (SONDE_FLAG_RS41_RESCUE; opt-in)
+FLAG_IMS_DIVERSITY = 2048  # iMS-100 channels may be members of set_diversity groups (SONDE_FLAG_IMS_DIVERSITY, DESIGN SPEC 3.3n; opt-in)
 FRAME_RESCUED = 2        # SondeFrame.flags bit of a frame a second pass completed (SONDE_FRAME_RESCUED)
-FRAME_COMBINED = 4       # SondeFrame.flags bit of an RS41, M10 / M20, MRZ-N1 or DFM frame set_diversity put together from several receivers' copies (SONDE_FRAME_COMBINED)
+FRAME_COMBINED = 4       # SondeFrame.flags bit of an RS41, M10 / M20, MRZ-N1, DFM or iMS-100 frame set_diversity put together from several receivers' copies (SONDE_FRAME_COMBINED)
 FRAME_DUPLICATE = 8      # SondeFrame.flags bit of a good frame another receiver of its diversity group has delivered (SONDE_FRAME_DUPLICATE)
 DIVERSITY_LEARN = 1              # set_diversity modes (SONDE_DIVERSITY_LEARN, SONDE_DIVERSITY_MARK_DUPLICATES)
 DIVERSITY_MARK_DUPLICATES = 2
@@ -152,8 +153,9 @@ def frame_copies(flags):
 
 
 def frame_joint(flags):
-    """words of a combined DFM frame that failed in every copy and were decoded jointly, capped at 15 (SONDE_FRAME_JOINT); an int or a
-    numpy array of SondeFrame.flags"""
+    """words of a combined DFM frame that failed in every copy and were decoded jointly -- of a combined iMS-100 frame: the BCH blocks
+    rejected in every copy and decoded from the copies' majority --, capped at 15 (SONDE_FRAME_JOINT); an int or a numpy array of
+    SondeFrame.flags"""
     return (flags >> 12) & 0xF
 
 
@@ -198,8 +200,9 @@ ABI_SYMBOLS = [
     "sonde_batch_ims_rescue_info", "sonde_batch_test_ims_block",
     "sonde_batch_afsk_rescue_info", "sonde_batch_test_afsk_repair",
     "sonde_batch_set_diversity", "sonde_batch_diversity_info", "sonde_batch_test_rs41_combine", "sonde_batch_test_check_combine",
-    "sonde_batch_test_dfm_combine",
+    "sonde_batch_test_dfm_combine", "sonde_batch_test_ims_combine",
     "sonde_batch_set_diversity_auto", "sonde_batch_diversity_offsets", "sonde_batch_test_diversity_align",
+    "sonde_batch_test_diversity_align_kind",
     "sonde_batch_test_shift_age", "sonde_detect_test_shift_age", "sonde_tuner_test_set_base",
     "sonde_combine_defaults", "sonde_combine_create", "sonde_combine_destroy", "sonde_combine_block", "sonde_combine_process",
     "sonde_combine_restart", "sonde_combine_readout", "sonde_combine_weights", "sonde_combine_share",
@@ -275,10 +278,14 @@ def load() -> C.CDLL:
         L.sonde_batch_test_check_combine.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
     if hasattr(L, "sonde_batch_test_dfm_combine"):        # absent only in older A/B builds loaded through SONDE_MI355_LIB
         L.sonde_batch_test_dfm_combine.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
+    if hasattr(L, "sonde_batch_test_ims_combine"):        # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        L.sonde_batch_test_ims_combine.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
     if hasattr(L, "sonde_batch_set_diversity_auto"):      # absent only in older A/B builds loaded through SONDE_MI355_LIB
         L.sonde_batch_set_diversity_auto.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
         L.sonde_batch_diversity_offsets.argtypes = [vp, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.sonde_batch_test_diversity_align.argtypes = [vp, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "sonde_batch_test_diversity_align_kind"):   # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        L.sonde_batch_test_diversity_align_kind.argtypes = [vp, C.c_uint32, C.c_size_t, C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.sonde_get_taps.argtypes = [C.c_int, vp]
     L.sonde_parse_frame.argtypes = [vp, C.POINTER(SondeData), C.c_int]
     L.sonde_batch_poll.argtypes = [vp, C.POINTER(SondeData), C.POINTER(C.c_uint32), C.c_size_t]

@@ -213,7 +213,8 @@ class SondeBatch(Handle):
     def set_diversity(self, groups, offsets=None, window_bits: int = 0, *, learn: bool = False, mark_duplicates: bool = False):
         """The receivers of one sonde (sonde_batch_set_diversity): groups = [[channel, ...], ...], 2..4 channels of one type each -- RS41
         (DESIGN SPEC 3.3j), M10 / M20 or MRZ-N1 (SPEC 3.3l: failed copies are combined by their 16-bit check), DFM (SPEC 3.3m: word by
-        word, the better copy per Hamming codeword; bit counts are chips there) --; offsets[ch] =
+        word, the better copy per Hamming codeword; bit counts are chips there), iMS-100 on a batch created with FLAG_IMS_DIVERSITY (SPEC
+        3.3n: BCH block by block, from the chips of the members' bit rings; bit counts are chips, window_bits 0: 576) --; offsets[ch] =
         the channel's bit count when the group's common clock reads 0 (None: zeros); window_bits: how far apart two copies of a frame may
         lie on that clock (0: 960).  Once, before the first submit.
         learn=True (sonde_batch_set_diversity_auto, SONDE_DIVERSITY_LEARN): the GPU finds the offsets itself from frames that are good
@@ -249,9 +250,10 @@ class SondeBatch(Handle):
         return {"offsets": [int(v) for v in off], "locked": int(locked.value), "learned": int(learned.value), "duplicates": int(dups.value)}
 
     def test_diversity_align(self, records: np.ndarray, counts: np.ndarray, n_members: np.ndarray, carried: np.ndarray, off: np.ndarray,
-                             locked: np.ndarray, mode: np.ndarray):
+                             locked: np.ndarray, mode: np.ndarray, kind: int | None = None):
         """set_diversity's align step alone (sonde_batch_test_diversity_align): records [n, 4, R] FRAME_DTYPE, caller-made, counts [n, 4]
-        of them in use; n_members [n] = 2..4; carried [n, 4] (len 0: none); off [n, 4] int64, locked [n], mode [n].  Returns (records
+        of them in use; n_members [n] = 2..4; carried [n, 4] (len 0: none); off [n, 4] int64, locked [n], mode [n].  kind: the sonde
+        type whose predicates the step uses (sonde_batch_test_diversity_align_kind; None: RS41, the older entry).  Returns (records
         with their flags as the step left them, off, locked, learned [n], duplicates [n])."""
         rec = np.ascontiguousarray(records, dtype=FRAME_DTYPE).copy()
         assert rec.ndim == 3 and rec.shape[1] == 4
@@ -265,7 +267,11 @@ class SondeBatch(Handle):
         assert cnt.shape == (n, 4) and nm.shape == (n,) and car.shape == (n, 4) and o.shape == (n, 4) and lk.shape == (n,) and md.shape == (n,)
         learned, dups = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
         p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
-        self._chk(self.L.sonde_batch_test_diversity_align(self.h, n, R, p(nm), p(rec), p(cnt), p(car), p(o), p(lk), p(md), p(learned), p(dups)))
+        if kind is None:
+            self._chk(self.L.sonde_batch_test_diversity_align(self.h, n, R, p(nm), p(rec), p(cnt), p(car), p(o), p(lk), p(md), p(learned), p(dups)))
+        else:
+            self._chk(self.L.sonde_batch_test_diversity_align_kind(self.h, int(kind), n, R, p(nm), p(rec), p(cnt), p(car), p(o), p(lk), p(md),
+                                                                   p(learned), p(dups)))
         return rec, o, lk, learned, dups
 
     def diversity_info(self, g: int) -> dict:
@@ -312,6 +318,21 @@ class SondeBatch(Handle):
         status = np.zeros(len(cp), dtype=np.int32)
         self._chk(self.L.sonde_batch_test_dfm_combine(self.h, len(cp), cp.ctypes.data_as(C.c_void_p), nc.ctypes.data_as(C.c_void_p),
                                                       out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+        return out, status
+
+    def test_ims_combine(self, records: np.ndarray, n_copies: np.ndarray, blocks: np.ndarray):
+        """set_diversity's combining rule for iMS-100 alone (sonde_batch_test_ims_combine, SPEC 3.3n steps 4 to 7): records [n] FRAME_DTYPE,
+        copy 0's record of each case (iMS-100, 51 bytes, nerr[1] > 0); n_copies [n] = 2..4; blocks [n, 4, 12] uint64, block L of copy j as
+        received (bit b of the block is bit 45 - b).  Returns (the record after the rule [n], status [n]): status = the copies used, 0 the
+        record's nerr[1] is not what copy 0's blocks say, -1 the pairing guard refuses, -2 a block has no solution, -3 a block has several."""
+        rec = np.ascontiguousarray(records, dtype=FRAME_DTYPE)
+        nc = np.ascontiguousarray(n_copies, dtype=np.uint32)
+        bl = np.ascontiguousarray(blocks, dtype=np.uint64)
+        assert rec.ndim == 1 and nc.shape == (len(rec),) and bl.shape == (len(rec), 4, 12)
+        out = np.zeros(len(rec), dtype=FRAME_DTYPE)
+        status = np.zeros(len(rec), dtype=np.int32)
+        self._chk(self.L.sonde_batch_test_ims_combine(self.h, len(rec), rec.ctypes.data_as(C.c_void_p), nc.ctypes.data_as(C.c_void_p),
+                                                      bl.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
         return out, status
 
     def test_rs255_erasures(self, cw_pairs: np.ndarray, erased: np.ndarray, n: int):

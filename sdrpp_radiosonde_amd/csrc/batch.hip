@@ -91,6 +91,7 @@ static int build(SondeBatch *b, const SondeBatchConfig *cfg)
 	b->seg_force = (int)cfg->time_slices;
 	b->join_mode = (cfg->flags & SONDE_FLAG_PIPELINE) ? 2 : ((cfg->flags & SONDE_FLAG_LATE_JOIN) ? 1 : 0);
 	b->fuse_fec = (cfg->flags & SONDE_FLAG_SPLIT_FEC) ? 0u : 1u;
+	b->ims_diversity = (cfg->flags & SONDE_FLAG_IMS_DIVERSITY) != 0;
 	if (!b->fuse_fec) b->fixed_epi = 0;
 	modem_table(cfg->flags, cfg->input_kind, b->md);
 	const ModemDef *md = b->md;
@@ -583,6 +584,11 @@ static int launch_diversity(SondeBatch *b, SubmitCtx &cx)
 			b->div_window, b->d_carried, b->d_divcnt);
 		HIPCHK(hipGetLastError());
 	}
+	if (b->div_kinds & (1u << SONDE_IMS100)) {     // SPEC 3.3n: the one pass that reads chips
+		sd_launch_ims_diversity(b->n_groups, cx.done, cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_groups, b->d_divstate,
+			b->div_window_ims, b->d_carried, b->d_divcnt, b->d_states, b->d_bitring, b->ring_words, b->fec.g64);
+		HIPCHK(hipGetLastError());
+	}
 	cx.framer_launched = true;
 	return 0;
 }
@@ -809,7 +815,7 @@ int sd_batch_need_mrztab(SondeBatch *b)
 	return 0;
 }
 
-// The receivers of one sonde (include/sonde_abi.h, SPEC 3.3j, 3.3k, 3.3l and 3.3m): the group table, the carried records, the counters and the
+// The receivers of one sonde (include/sonde_abi.h, SPEC 3.3j, 3.3k, 3.3l, 3.3m and 3.3n): the group table, the carried records, the counters and the
 // align step's state.  mode 0 is sonde_batch_set_diversity.
 extern "C" int sonde_batch_set_diversity(SondeBatch *b, const int32_t *group, const int64_t *offset_bits, uint32_t window_bits)
 {
@@ -841,8 +847,9 @@ extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *grou
 		if (group[c] < 0) continue;
 		SdDivGroup &g = gt[(size_t)group[c]];
 		const uint32_t t = b->types[c];
-		if (t != SONDE_RS41 && t != SONDE_M10 && t != SONDE_MRZN1 && t != SONDE_DFM09)
-			return sd_fail("sonde_batch_set_diversity: a member that is not SONDE_RS41, SONDE_M10, SONDE_MRZN1 or SONDE_DFM09");
+		if (t != SONDE_RS41 && t != SONDE_M10 && t != SONDE_MRZN1 && t != SONDE_DFM09 && !(t == SONDE_IMS100 && b->ims_diversity))
+			return sd_fail(b->ims_diversity ? "sonde_batch_set_diversity: a member that is not SONDE_RS41, SONDE_M10, SONDE_MRZN1, SONDE_DFM09 or SONDE_IMS100"
+			                                : "sonde_batch_set_diversity: a member that is not SONDE_RS41, SONDE_M10, SONDE_MRZN1 or SONDE_DFM09");
 		if (g.n && g.kind != t) return sd_fail("sonde_batch_set_diversity: members of different types in one group");
 		g.kind = t;
 		kinds |= 1u << t;
@@ -874,6 +881,7 @@ extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *grou
 	b->div_unlocked = unlocked ? 1u : 0u;
 	b->div_slot = slot;
 	b->div_window = window_bits ? window_bits : 960u;
+	b->div_window_ims = window_bits ? window_bits : 576u;     // SPEC 3.3n: iMS-100 frames lie 1152 chips apart
 	b->n_groups = (uint32_t)gt.size();
 	return 0;
 }

@@ -179,8 +179,10 @@ struct SondeBatch {
 	// allocated or launched
 	// div_mode: sonde_batch_set_diversity_auto's mode (SPEC 3.3k; 0: no align step is launched), div_unlocked: its groups start unlocked;
 	// d_divstate: per group the offsets and lock bits the combining pass reads, and the align step's counters
-	// div_kinds: a bit per sonde type that has a group (SPEC 3.3l, 3.3m): which of the three combining kernels are launched
-	uint32_t n_groups = 0, div_window = 0, div_mode = 0, div_unlocked = 0, div_kinds = 0;
+	// div_kinds: a bit per sonde type that has a group (SPEC 3.3l, 3.3m, 3.3n): which of the four combining kernels are launched
+	// ims_diversity: SONDE_FLAG_IMS_DIVERSITY -- set_diversity takes iMS-100 groups; div_window_ims: their window (its default is 576 chips)
+	uint32_t n_groups = 0, div_window = 0, div_window_ims = 0, div_mode = 0, div_unlocked = 0, div_kinds = 0;
+	bool ims_diversity = false;
 	DevBuf<SdDivGroup> d_groups;
 	DevBuf<SdDivState> d_divstate;
 	DevBuf<SondeFrame> d_carried;

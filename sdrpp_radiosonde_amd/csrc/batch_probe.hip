@@ -210,6 +210,30 @@ extern "C" int sonde_batch_test_dfm_combine(SondeBatch *b, size_t n, const Sonde
 	});
 }
 
+// Steps 4 to 7 of SPEC 3.3n alone, through the kernel's own device function: per case copy 0's record and the received blocks of the
+// copies, [SD_DIV_MAX][12]; status[i] = copies used, 0 the record's nerr[1] is not what copy 0's blocks say, -1 the pairing guard
+// refuses, -2 a block has no solution, -3 a block has several.
+extern "C" int sonde_batch_test_ims_combine(SondeBatch *b, size_t n, const SondeFrame *records, const uint32_t *n_copies, const uint64_t *blocks,
+	SondeFrame *out, int32_t *status)
+{
+	if (!b || !records || !n_copies || !blocks || !out || !status || !n || n > (1u << 16)) return sd_fail("sonde_batch_test_ims_combine: bad argument");
+	for (size_t i = 0; i < n; i++) {
+		if (n_copies[i] < 2 || n_copies[i] > SD_DIV_MAX) return sd_fail("sonde_batch_test_ims_combine: n_copies must be 2..4");
+		if (records[i].type != SONDE_IMS100 || records[i].len != 51) return sd_fail("sonde_batch_test_ims_combine: copy 0 must be a SONDE_IMS100 record of 51 bytes");
+		if (records[i].nerr[1] <= 0) return sd_fail("sonde_batch_test_ims_combine: copy 0 must be a failed record (nerr[1] > 0)");
+	}
+	HIPCHK(hipSetDevice(b->device));
+	DevBuf<SondeFrame> d_r;
+	DevBuf<uint32_t> d_n;
+	DevBuf<uint64_t> d_b;
+	HIPCHK(d_r.upload(records, n));
+	HIPCHK(d_n.upload(n_copies, n));
+	HIPCHK(d_b.upload(blocks, SD_DIV_MAX * 12 * n));
+	return probe_unit("sonde_batch_test_ims_combine", (const SondeFrame *)nullptr, out, n, status, n, [&](SondeFrame *d_o, int32_t *d_st) {
+		sd_launch_ims_diversity_unit(d_r, d_n, d_b, (uint32_t)n, d_o, d_st, b->fec.g64, nullptr);
+	});
+}
+
 extern "C" int sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t off[4], uint32_t *locked_mask, uint32_t *learned, uint32_t *duplicates)
 {
 	if (!b) return sd_fail("sonde_batch_diversity_offsets: bad argument");
@@ -226,8 +250,8 @@ extern "C" int sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int6
 	return 0;
 }
 
-// The align step of SPEC 3.3k alone, through the kernel's own device function (include/sonde_abi.h)
-extern "C" int sonde_batch_test_diversity_align(SondeBatch *b, size_t n, size_t max_rec, const uint32_t *n_members, SondeFrame *records, const uint32_t *counts,
+// The align step of SPEC 3.3k alone, through the kernel's own device function (include/sonde_abi.h), with the predicates of `kind`
+static int test_diversity_align(uint32_t kind, SondeBatch *b, size_t n, size_t max_rec, const uint32_t *n_members, SondeFrame *records, const uint32_t *counts,
 	const SondeFrame *carried, int64_t *off, uint32_t *locked, const uint32_t *mode, uint32_t *learned, uint32_t *duplicates)
 {
 	if (!b || !n_members || !records || !counts || !carried || !off || !locked || !mode || !learned || !duplicates || !n || n > (1u << 12) || !max_rec ||
@@ -255,7 +279,7 @@ extern "C" int sonde_batch_test_diversity_align(SondeBatch *b, size_t n, size_t 
 	HIPCHK(d_nm.upload(n_members, n));
 	HIPCHK(d_mode.upload(mode, n));
 	HIPCHK(d_st.upload(st.data(), n));
-	sd_launch_diversity_align_unit((uint32_t)n, nullptr, d_r, d_cnt, (uint32_t)max_rec, d_nm, d_c, d_st, d_mode);
+	sd_launch_diversity_align_unit((uint32_t)n, nullptr, d_r, d_cnt, (uint32_t)max_rec, d_nm, d_c, d_st, d_mode, kind);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpy(records, d_r, SD_DIV_MAX * n * max_rec * sizeof(SondeFrame), hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(st.data(), d_st, n * sizeof(SdDivState), hipMemcpyDeviceToHost));
@@ -266,6 +290,20 @@ extern "C" int sonde_batch_test_diversity_align(SondeBatch *b, size_t n, size_t 
 		duplicates[k] = st[k].duplicates;
 	}
 	return 0;
+}
+
+extern "C" int sonde_batch_test_diversity_align(SondeBatch *b, size_t n, size_t max_rec, const uint32_t *n_members, SondeFrame *records, const uint32_t *counts,
+	const SondeFrame *carried, int64_t *off, uint32_t *locked, const uint32_t *mode, uint32_t *learned, uint32_t *duplicates)
+{
+	return test_diversity_align(SONDE_RS41, b, n, max_rec, n_members, records, counts, carried, off, locked, mode, learned, duplicates);
+}
+
+extern "C" int sonde_batch_test_diversity_align_kind(SondeBatch *b, uint32_t kind, size_t n, size_t max_rec, const uint32_t *n_members, SondeFrame *records,
+	const uint32_t *counts, const SondeFrame *carried, int64_t *off, uint32_t *locked, const uint32_t *mode, uint32_t *learned, uint32_t *duplicates)
+{
+	if (kind != SONDE_RS41 && kind != SONDE_M10 && kind != SONDE_MRZN1 && kind != SONDE_DFM09 && kind != SONDE_IMS100)
+		return sd_fail("sonde_batch_test_diversity_align_kind: a kind no diversity group can have");
+	return test_diversity_align(kind, b, n, max_rec, n_members, records, counts, carried, off, locked, mode, learned, duplicates);
 }
 
 // wait for the last submit and fetch the channel's demodulator state

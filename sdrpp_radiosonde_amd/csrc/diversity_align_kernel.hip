@@ -1,7 +1,7 @@
 // diversity_align_kernel.hip -- sonde_batch_set_diversity_auto (DESIGN SPEC 3.3k): the align step in front of the combining pass of
-// diversity_kernel.hip, check_diversity_kernel.hip and dfm_diversity_kernel.hip.  Two good RS41 records of different members whose bytes 8 .. len are identical
+// diversity_kernel.hip, check_diversity_kernel.hip, dfm_diversity_kernel.hip and ims_diversity_kernel.hip.  Two good RS41 records of different members whose bytes 8 .. len are identical
 // are the same transmitted frame (the frame carries its number and the sonde's serial), and so are two good M10 / M20 or MRZ-N1 records
-// whose bytes 0 .. len are (SPEC 3.3l: consecutive frames of one sonde differ) and two good DFM records whose 33 bytes are (SPEC 3.3m); from such pairs the step learns where each member's bit count stands on the
+// whose bytes 0 .. len are (SPEC 3.3l: consecutive frames of one sonde differ), two good DFM records whose 33 bytes are (SPEC 3.3m) and two good iMS-100 records whose 51 bytes are (SPEC 3.3n); from such pairs the step learns where each member's bit count stands on the
 // group's clock (SONDE_DIVERSITY_LEARN), and it marks all but one copy of a frame (SONDE_DIVERSITY_MARK_DUPLICATES).
 //   one 64-lane wave per group, a launch of its own in front of sd_diversity_kernel on the stream where the submit completes.  The
 //   lanes take one member's records (any number: the loops stride by 64) and each walks the other member's; a record's key is two
@@ -21,22 +21,25 @@ struct AlMember { SondeFrame *recs; const SondeFrame *carried; uint32_t cnt; };
 // both nerr >= 0, the same frame = data[8 .. len) identical.  M10 / M20 and MRZ-N1 (SPEC 3.3l): good = a length of the type and
 // nerr[0] >= 0 (nerr[1] counts Manchester violations there), the same frame = data[0 .. len) identical.  DFM (SPEC 3.3m): good = len 33
 // and nerr[1] == 0 (no word the first pass gave up on; nerr[0] counts corrected words), the same frame = data[0 .. 33) identical.
+// iMS-100 (SPEC 3.3n): good = len 51 and nerr[1] == 0 (no rejected block), the same frame = data[0 .. 51) identical.
 __device__ __forceinline__ const SondeFrame *al_cand(const AlMember &M, uint32_t i) { return i < M.cnt ? M.recs + i : M.carried; }
 __device__ __forceinline__ bool al_good(uint32_t kind, const SondeFrame *f)
 {
 	if (kind == SONDE_M10) return (f->len == 101 || f->len == 70) && f->nerr[0] >= 0;
 	if (kind == SONDE_MRZN1) return f->len == 45 && f->nerr[0] >= 0;
 	if (kind == SONDE_DFM09) return f->len == 33 && f->nerr[1] == 0;
+	if (kind == SONDE_IMS100) return f->len == 51 && f->nerr[1] == 0;
 	return (f->len == 320 || f->len == 518) && f->nerr[0] >= 0 && f->nerr[1] >= 0;
 }
 // the quick reject: two words that differ between any two frames.  RS41: parity bytes of codeword 0 and of codeword 1; the others: the
-// frame's last two words, which hold the 16-bit check -- for DFM the end of the second data block -- (the bytes of the last word behind
-// len are not looked at)
+// frame's last two words, which hold the 16-bit check -- for DFM the end of the second data block, for iMS-100 (len 51: words 11 and
+// 12, three bytes of the latter) the data bits of block 11 and the end of block 10 -- (the bytes of the last word behind len are not
+// looked at; the key only spares the byte compare, which decides)
 __device__ __forceinline__ uint32_t al_key(uint32_t kind, const SondeFrame *f)
 {
 	const uint32_t *w = reinterpret_cast<const uint32_t *>(f->data);
 	if (kind == SONDE_RS41) return w[2] ^ w[8];
-	const int len = f->len, wl = (len - 1) >> 2;           // a good record: len is 33, 45, 70 or 101, wl >= 8
+	const int len = f->len, wl = (len - 1) >> 2;           // a good record: len is 33, 45, 51, 70 or 101, wl >= 8
 	const uint32_t last = (len & 3) ? w[wl] & ((1u << (8 * (len & 3))) - 1u) : w[wl];
 	return last ^ ((w[wl - 1] << 13) | (w[wl - 1] >> 19));
 }
@@ -166,11 +169,12 @@ void sd_launch_diversity_align(uint32_t n_groups, hipStream_t stream, SondeFrame
 	else hipLaunchKernelGGL(sd_diversity_align_kernel<false>, dim3(n_groups), dim3(64), 0, stream, frames, counts, max_frames, groups, carried, states, mode);
 }
 
-// ---- test introspection: the align step alone on caller-made RS41 records (sonde_batch_test_diversity_align).  One wave per case; case k
-// has SD_DIV_MAX members of max_rec record slots each (counts[4 k + m] <= max_rec in use), SD_DIV_MAX carried records, its state and
+// ---- test introspection: the align step alone on caller-made records (sonde_batch_test_diversity_align: RS41;
+// sonde_batch_test_diversity_align_kind: any kind a group can have; OTHER_KINDS as above, so that the RS41 kernel stays what it was).
+// One wave per case; case k has SD_DIV_MAX members of max_rec record slots each (counts[4 k + m] <= max_rec in use), SD_DIV_MAX carried records, its state and
 // its mode; the host has checked n_members (2..4), the counts and the modes.
-__global__ __launch_bounds__(64) void sd_diversity_align_unit_kernel(SondeFrame *records, const uint32_t *__restrict__ counts, uint32_t max_rec,
-	const uint32_t *__restrict__ n_members, const SondeFrame *__restrict__ carried, SdDivState *states, const uint32_t *__restrict__ modes)
+template <bool OTHER_KINDS> __global__ __launch_bounds__(64) void sd_diversity_align_unit_kernel(SondeFrame *records, const uint32_t *__restrict__ counts, uint32_t max_rec,
+	const uint32_t *__restrict__ n_members, const SondeFrame *__restrict__ carried, SdDivState *states, const uint32_t *__restrict__ modes, uint32_t kind)
 {
 	const uint32_t k = blockIdx.x;
 	const int lane = (int)threadIdx.x;
@@ -182,11 +186,12 @@ __global__ __launch_bounds__(64) void sd_diversity_align_unit_kernel(SondeFrame 
 		M[m].cnt = m < nm ? (uint32_t)AL_U(min(counts[SD_DIV_MAX * k + m], max_rec)) : 0u;
 		M[m].carried = carried + (size_t)SD_DIV_MAX * k + m;
 	}
-	al_group(SONDE_RS41, M, nm, states + k, (uint32_t)AL_U(modes[k]), lane);
+	al_group(OTHER_KINDS ? (uint32_t)AL_U(kind) : (uint32_t)SONDE_RS41, M, nm, states + k, (uint32_t)AL_U(modes[k]), lane);
 }
 
 void sd_launch_diversity_align_unit(uint32_t n, hipStream_t stream, SondeFrame *records, const uint32_t *counts, uint32_t max_rec,
-	const uint32_t *n_members, const SondeFrame *carried, SdDivState *states, const uint32_t *modes)
+	const uint32_t *n_members, const SondeFrame *carried, SdDivState *states, const uint32_t *modes, uint32_t kind)
 {
-	hipLaunchKernelGGL(sd_diversity_align_unit_kernel, dim3(n), dim3(64), 0, stream, records, counts, max_rec, n_members, carried, states, modes);
+	if (kind != SONDE_RS41) hipLaunchKernelGGL(sd_diversity_align_unit_kernel<true>, dim3(n), dim3(64), 0, stream, records, counts, max_rec, n_members, carried, states, modes, kind);
+	else hipLaunchKernelGGL(sd_diversity_align_unit_kernel<false>, dim3(n), dim3(64), 0, stream, records, counts, max_rec, n_members, carried, states, modes, kind);
 }

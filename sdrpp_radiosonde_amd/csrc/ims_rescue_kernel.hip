@@ -5,7 +5,7 @@
 // the 2^m ways of blaming the left or the right cell of each; the block decodes iff exactly one distinct flip pattern is a codeword.
 // A frame is rescued iff every rejected block decodes.
 //   the walk over the records is sd_rescue_walk.h's; for a candidate lanes 0..11 rebuild their block, its boundaries and the first
-//   pass's verdict from the chips of the channel's bit ring; then, rejected block by rejected block, the 64 lanes are the up to 64
+//   pass's verdict from the chips of the channel's bit ring (sd_ims_block.h, shared with ims_diversity_kernel.hip); then, rejected block by rejected block, the 64 lanes are the up to 64
 //   hypotheses.  LDS: each wave's own copy of the 192-byte GF(2^6) table (its look-ups are the kernel's critical path: read from
 //   global memory they added 25 us to the step of profiles/ims_rescue_notes.md).
 // Runs behind whatever wrote the records, on the same stream, and rewrites them in place.  The records of a channel are
@@ -14,41 +14,9 @@
 #include <hip/hip_runtime.h>
 #include "sonde_dev.h"
 #include "sd_rescue_walk.h"
+#include "sd_ims_block.h"
 
 #define IQ_CAP 6               // SPEC 3.3h step 3: at most this many violated boundaries per block
-#define IQ_FRAME_CHIPS 1152
-#define IQ_BLOCKS 12
-#define IQ_BLK_BITS 46
-#define IQ_BLK_MASK ((1ull << IQ_BLK_BITS) - 1ull)
-
-// S1 and S3 of a block polynomial over GF(2^6) / x^6 + x + 1 (g64 = exp[128], log[64]), as in sd_ims_decode_frame
-__device__ __forceinline__ void iq_syndromes(uint64_t blk, const uint8_t *__restrict__ g_exp, uint32_t &s1, uint32_t &s3)
-{
-	s1 = 0; s3 = 0;
-#pragma unroll
-	for (int i = 0; i < IQ_BLK_BITS; i++) {                       // no branch: the look-ups do not wait for each other
-		const uint32_t on = 0u - (uint32_t)((blk >> i) & 1ull);
-		s1 ^= g_exp[i] & on; s3 ^= g_exp[(3 * i) % 63] & on;
-	}
-}
-
-// SPEC 3.3h step 2: does the first pass reject a block with these syndromes?  Its rule restated: nothing to do; a single error iff
-// S3 = S1^3, at a position < 46; otherwise the two roots of x^2 + S1 x + (S3 + S1^3) / S1, both < 46; otherwise rejected.
-__device__ __forceinline__ bool iq_first_pass_rejects(uint32_t s1, uint32_t s3, const uint8_t *__restrict__ g_exp, const uint8_t *__restrict__ g_log)
-{
-	if (!s1 && !s3) return false;
-	if (!s1) return true;
-	const uint32_t l1 = g_log[s1], s1c = g_exp[(3u * l1) % 63u];
-	if (s3 == s1c) return l1 >= IQ_BLK_BITS;
-	const uint32_t prod = g_exp[g_log[s3 ^ s1c] + 63u - l1];
-	int found = 0, inside = 0;
-#pragma unroll 9
-	for (uint32_t i = 0; i < 63u; i++) {
-		const bool root = (g_exp[(2u * i) % 63u] ^ g_exp[l1 + i] ^ prod) == 0u;
-		found += root; inside += root && i < IQ_BLK_BITS;
-	}
-	return !(found == 2 && inside == 2);
-}
 
 // SPEC 3.3h step 3 for one block, by the whole wave: blk as received (bit b of the block = coefficient 45 - b), its syndromes, viol
 // = the mask of its violated boundaries (bit k: boundary k of the block, 0..46); all wave-uniform.  Lane h is hypothesis h: bit j of
@@ -89,19 +57,12 @@ struct IqPass {
 		// the frame's chips must still be in the ring (always so for a record of this submit: DESIGN 3.3h)
 		if (!sd_ring_holds(ctx.ring, h.bitpos, IQ_FRAME_CHIPS)) return SD_RESCUE_SKIPPED;
 
-		// 1. lane L < 12: block L and its boundaries 46 L .. 46 L + 46 from the 94 chips p + 47 + 92 L ..; chip j and chip j + 1 are
-		//    boundary j / 2 of the block for even j, cell (j - 1) / 2 for odd j.  Chip p + 1152 is not used: block 11 has no boundary 46.
+		// 1. lane L < 12: block L and its boundaries 46 L .. 46 L + 46 (sd_ims_block.h)
 		uint64_t blk = 0, viol = 0;
 		uint32_t s1 = 0, s3 = 0;
 		bool failed = false;
 		if (lane < IQ_BLOCKS) {
-			const uint64_t c0 = h.bitpos + 47u + 92u * (uint32_t)lane;
-			const uint64_t x0 = sd_ring_chips64(ctx.ring, c0), x1 = sd_ring_chips64(ctx.ring, c0 + 64u);
-			const uint64_t eq0 = ~(x0 ^ (x0 >> 1 | x1 << 63)), eq1 = ~(x1 ^ (x1 >> 1));       // bit j: chip j == chip j + 1
-			viol = (sd_even_bits64(eq0) | sd_even_bits64(eq1) << 32) & ((2ull << IQ_BLK_BITS) - 1ull);  // bit n: boundary n, 0..46
-			const uint64_t cells = sd_even_bits64(eq0 >> 1) | sd_even_bits64(eq1 >> 1) << 32;         // bit b: cell b
-			blk = (__builtin_bitreverse64(cells) >> (64 - IQ_BLK_BITS)) & IQ_BLK_MASK;                  // bit b -> coefficient 45 - b
-			if (lane == IQ_BLOCKS - 1) viol &= IQ_BLK_MASK;
+			iq_rebuild_block(ctx.ring, h.bitpos, lane, blk, viol);
 			// 2. F: the blocks the first pass rejects
 			iq_syndromes(blk, g_exp, s1, s3);
 			failed = iq_first_pass_rejects(s1, s3, g_exp, g_log);
@@ -122,23 +83,8 @@ struct IqPass {
 			flips += __popcll(e);
 		}
 
-		// 5. the record: lane i < 51 owns byte i; data bit k is bit k % 34 of block k / 34, and a byte lies in at most two blocks
-		if (lane < 51) {
-			const int La = (8 * lane) / 34, Lb = (8 * lane + 7) / 34;
-			const uint64_t da = (uint64_t)(uint32_t)__shfl((int)(uint32_t)dec, La, 64) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(dec >> 32), La, 64) << 32);
-			const uint64_t db = (uint64_t)(uint32_t)__shfl((int)(uint32_t)dec, Lb, 64) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(dec >> 32), Lb, 64) << 32);
-			const uint32_t old = fr->data[lane];
-			uint32_t nb = old;
-#pragma unroll
-			for (int j = 0; j < 8; j++) {
-				const int k = 8 * lane + j, L = k / 34, b = k % 34;
-				if ((fm >> L) & 1ull) {
-					const uint32_t bit = (uint32_t)(((L == La ? da : db) >> (IQ_BLK_BITS - 1 - b)) & 1ull);
-					nb = (nb & ~(0x80u >> j)) | (bit << (7 - j));
-				}
-			}
-			if (nb != old) fr->data[lane] = (uint8_t)nb;
-		}
+		// 5. the record
+		iq_write_blocks(fr, fm, dec, lane);
 		if (lane == 0) {
 			fr->nerr[0] += flips;
 			fr->nerr[1] = 0;

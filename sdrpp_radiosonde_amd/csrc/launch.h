@@ -127,9 +127,9 @@ void sd_launch_ims_block_unit(const uint8_t *g64, uint64_t *blocks, const uint64
 // steps 1..5 of 3.3i: n records; status = 0 untouched, 1 rescued, 2 several patterns fit
 void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status, hipStream_t stream);
 
-// sonde_batch_set_diversity (DESIGN SPEC 3.3j, 3.3l, 3.3m): a group = 2..4 channels of one type that hear the same sonde; ch[m] and
+// sonde_batch_set_diversity (DESIGN SPEC 3.3j, 3.3l, 3.3m, 3.3n): a group = 2..4 channels of one type that hear the same sonde; ch[m] and
 // off[m] (offset_bits) per member, kind = the members' type: SONDE_RS41 (0: diversity_kernel.hip), SONDE_M10 or SONDE_MRZN1
-// (check_diversity_kernel.hip), SONDE_DFM09 (dfm_diversity_kernel.hip).  Each combining kernel is launched over the whole table and takes the groups of its kinds; the align
+// (check_diversity_kernel.hip), SONDE_DFM09 (dfm_diversity_kernel.hip), SONDE_IMS100 (ims_diversity_kernel.hip; SONDE_FLAG_IMS_DIVERSITY).  Each combining kernel is launched over the whole table and takes the groups of its kinds; the align
 // step, the carried records, the counters and the state are one space for all kinds.  carried: [n_groups][SD_DIV_MAX] records
 // (len = 0: none), counters: [n_groups][2] (tried, combined); both carried from submit to submit.  The launches stand behind every
 // other kernel of the submit.
@@ -151,9 +151,10 @@ void sd_launch_diversity_clear(uint32_t n, hipStream_t stream, const uint32_t *l
 void sd_launch_diversity_align(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
 	const SdDivGroup *groups, const SondeFrame *carried, SdDivState *states, uint32_t mode, uint32_t other_kinds);
 // the align step alone: n cases of SD_DIV_MAX members with max_rec record slots each (records[(4 k + m) * max_rec + i], counts[4 k + m]
-// in use, n_members[k] = 2..4), carried[4 k + m] (len 0: none), states[k] in and out, modes[k]; all device memory
+// in use, n_members[k] = 2..4), carried[4 k + m] (len 0: none), states[k] in and out, modes[k]; all device memory.  kind: the sonde type
+// whose predicates the step uses (SdDivGroup.kind)
 void sd_launch_diversity_align_unit(uint32_t n, hipStream_t stream, SondeFrame *records, const uint32_t *counts, uint32_t max_rec,
-	const uint32_t *n_members, const SondeFrame *carried, SdDivState *states, const uint32_t *modes);
+	const uint32_t *n_members, const SondeFrame *carried, SdDivState *states, const uint32_t *modes, uint32_t kind);
 // steps 3 to 7 of SPEC 3.3j alone: n cases of SD_DIV_MAX copies each (device memory; n_copies[i] of them in use, copy 0 the record to
 // rewrite); out[i] = copy 0, rewritten or not; status = copies used, -1 too many erasures, -2 no decode, -3 rejected
 void sd_launch_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
@@ -176,6 +177,17 @@ void sd_launch_dfm_diversity(uint32_t n_groups, hipStream_t stream, SondeFrame *
 // has no solution, -3 a word has several
 void sd_launch_dfm_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
 	hipStream_t stream);
+
+// the combining pass of SPEC 3.3n over the iMS-100 groups of the table (ims_diversity_kernel.hip); launched only when the batch has one.
+// It reads the copies' blocks from the chips: the channel states (wpos), the bit ring and its words per channel, and the GF(2^6) table
+void sd_launch_ims_diversity(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
+	const SdDivGroup *groups, const SdDivState *states, uint32_t window, SondeFrame *carried, uint32_t *counters,
+	const SdChanState *chan_states, const uint32_t *bitring, uint32_t ring_words, const uint8_t *g64);
+// steps 4 to 7 of SPEC 3.3n alone: n cases of copy 0's record, n_copies and the copies' received blocks [SD_DIV_MAX][12] (device memory);
+// out[i] = the record, rewritten or not; status = copies used, 0 the record's nerr[1] is not what copy 0's blocks say, -1 the pairing
+// guard refuses, -2 a block has no solution, -3 a block has several
+void sd_launch_ims_diversity_unit(const SondeFrame *records, const uint32_t *n_copies, const uint64_t *blocks, uint32_t n, SondeFrame *out,
+	int32_t *status, const uint8_t *g64, hipStream_t stream);
 
 // sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);

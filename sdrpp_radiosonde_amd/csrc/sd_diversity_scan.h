@@ -1,5 +1,6 @@
-// sd_diversity_scan.h -- what the three combining passes of sonde_batch_set_diversity share (diversity_kernel.hip, DESIGN SPEC 3.3j: RS41;
-// check_diversity_kernel.hip, SPEC 3.3l: M10 / M20 / MRZ-N1; dfm_diversity_kernel.hip, SPEC 3.3m: DFM): the members of a group, steps 1
+// sd_diversity_scan.h -- what the four combining passes of sonde_batch_set_diversity share (diversity_kernel.hip, DESIGN SPEC 3.3j: RS41;
+// check_diversity_kernel.hip, SPEC 3.3l: M10 / M20 / MRZ-N1; dfm_diversity_kernel.hip, SPEC 3.3m: DFM; ims_diversity_kernel.hip, SPEC
+// 3.3n: iMS-100): the members of a group, steps 1
 // and 2 of SPEC 3.3j -- the scan of the members' record headers for the next failed record in (t, member) order and for its partner in
 // another member -- and the carried records.  The passes differ in two predicates, both functions of the group's kind (SdDivGroup.kind = the members' sonde type):
 // which record lengths are frames, and when a record has failed.  One 64-lane wave per group; every result is wave-uniform.
@@ -13,16 +14,18 @@
 constexpr int DV_REC_WORDS = (int)(sizeof(SondeFrame) / 4);
 constexpr int DV_DATA_WORD0 = (int)(offsetof(SondeFrame, data) / 4);
 
-// a frame length of the kind: RS41 {320, 518}, M10 / M20 {101, 70}, MRZ-N1 {45}, DFM {33}
+// a frame length of the kind: RS41 {320, 518}, M10 / M20 {101, 70}, MRZ-N1 {45}, DFM {33}, iMS-100 {51}
 __device__ __forceinline__ bool dv_len_ok(uint32_t kind, int len)
 {
-	return kind == SONDE_M10 ? (len == 101 || len == 70) : kind == SONDE_MRZN1 ? len == 45 : kind == SONDE_DFM09 ? len == 33 : (len == 320 || len == 518);
+	return kind == SONDE_M10 ? (len == 101 || len == 70) : kind == SONDE_MRZN1 ? len == 45 : kind == SONDE_DFM09 ? len == 33 :
+	       kind == SONDE_IMS100 ? len == 51 : (len == 320 || len == 518);
 }
 // failed: RS41 a codeword at nerr < 0, M10 / M20 / MRZ-N1 the 16-bit check (nerr[0] < 0; nerr[1] counts Manchester violations there),
-// DFM a Hamming word the first pass gave up on (nerr[1] > 0; nerr[0] counts corrected words there)
+// DFM a Hamming word the first pass gave up on (nerr[1] > 0; nerr[0] counts corrected words there), iMS-100 a BCH block it rejected
+// (nerr[1] > 0; nerr[0] counts corrected bits there)
 __device__ __forceinline__ bool dv_failed(uint32_t kind, const SondeFrame *f)
 {
-	if (kind == SONDE_DFM09) return f->nerr[1] > 0;
+	if (kind == SONDE_DFM09 || kind == SONDE_IMS100) return f->nerr[1] > 0;
 	return f->nerr[0] < 0 || (kind == SONDE_RS41 && f->nerr[1] < 0);
 }
 
