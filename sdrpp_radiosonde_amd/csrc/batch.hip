@@ -91,7 +91,7 @@ static int build(SondeBatch *b, const SondeBatchConfig *cfg)
 	b->seg_force = (int)cfg->time_slices;
 	b->join_mode = (cfg->flags & SONDE_FLAG_PIPELINE) ? 2 : ((cfg->flags & SONDE_FLAG_LATE_JOIN) ? 1 : 0);
 	b->fuse_fec = (cfg->flags & SONDE_FLAG_SPLIT_FEC) ? 0u : 1u;
-	b->ims_diversity = (cfg->flags & SONDE_FLAG_IMS_DIVERSITY) != 0;
+	for (const SdDivPass &p : k_div_passes) b->div_flags |= cfg->flags & p.flag;
 	if (!b->fuse_fec) b->fixed_epi = 0;
 	modem_table(cfg->flags, cfg->input_kind, b->md);
 	const ModemDef *md = b->md;
@@ -559,34 +559,26 @@ static int record_completion(SondeBatch *b, SubmitCtx &cx)
 }
 
 // Behind every other kernel of the submit, where it completes (the launch units have joined there: set_diversity refuses the
-// late-joined modes): the pass over the groups of sonde_batch_set_diversity (SPEC 3.3j)
+// late-joined modes): the align step (SPEC 3.3k: it sets the offsets and lock bits the passes read, and marks duplicates), then the
+// passes of k_div_passes over the groups of sonde_batch_set_diversity: each kernel takes the groups of its kinds out of the one
+// table, and is launched only if there is one
 static int launch_diversity(SondeBatch *b, SubmitCtx &cx)
 {
-	const uint32_t other_kinds = (b->div_kinds & ~(1u << SONDE_RS41)) != 0;       // with RS41 groups only the kernels run as they did
-	if (b->div_mode) {      // SPEC 3.3k: the align step first -- it sets the offsets and lock bits the pass reads, and marks duplicates
-		sd_launch_diversity_align(b->n_groups, cx.done, cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_groups, b->d_carried,
-			b->d_divstate, b->div_mode, other_kinds);
+	SdDivArgs a = {};
+	a.n_groups = b->n_groups; a.stream = cx.done;
+	a.groups = b->d_groups; a.states = b->d_divstate; a.carried = b->d_carried; a.counters = b->d_divcnt;
+	a.other_kinds = (b->div_kinds & ~(1u << SONDE_RS41)) != 0;      // with RS41 groups only the kernels run as they did
+	a.frames = cx.slot->d_frames; a.counts = cx.slot->d_counts; a.max_frames = b->max_frames;
+	a.fec = b->fec; a.mrztab = b->d_mrztab;
+	a.chan_states = b->d_states; a.bitring = b->d_bitring; a.ring_words = b->ring_words;
+	if (b->div_mode) {
+		sd_launch_diversity_align(a, b->div_mode);
 		HIPCHK(hipGetLastError());
 	}
-	// each combining kernel takes the groups of its kinds out of the one table, and is launched only if there is one
-	if (b->div_kinds & (1u << SONDE_RS41)) {
-		sd_launch_diversity(b->n_groups, cx.done, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, cx.slot->d_frames, cx.slot->d_counts, b->max_frames,
-			b->d_groups, b->d_divstate, b->div_window, b->d_carried, b->d_divcnt, other_kinds);
-		HIPCHK(hipGetLastError());
-	}
-	if (b->div_kinds & ((1u << SONDE_M10) | (1u << SONDE_MRZN1))) {      // SPEC 3.3l
-		sd_launch_check_diversity(b->n_groups, cx.done, b->fec.m10tab, b->d_mrztab, cx.slot->d_frames, cx.slot->d_counts, b->max_frames,
-			b->d_groups, b->d_divstate, b->div_window, b->d_carried, b->d_divcnt);
-		HIPCHK(hipGetLastError());
-	}
-	if (b->div_kinds & (1u << SONDE_DFM09)) {      // SPEC 3.3m
-		sd_launch_dfm_diversity(b->n_groups, cx.done, cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_groups, b->d_divstate,
-			b->div_window, b->d_carried, b->d_divcnt);
-		HIPCHK(hipGetLastError());
-	}
-	if (b->div_kinds & (1u << SONDE_IMS100)) {     // SPEC 3.3n: the one pass that reads chips
-		sd_launch_ims_diversity(b->n_groups, cx.done, cx.slot->d_frames, cx.slot->d_counts, b->max_frames, b->d_groups, b->d_divstate,
-			b->div_window_ims, b->d_carried, b->d_divcnt, b->d_states, b->d_bitring, b->ring_words, b->fec.g64);
+	for (const SdDivPass &p : k_div_passes) {
+		if (!(b->div_kinds & p.kinds)) continue;
+		a.window = b->div_window ? b->div_window : p.window;
+		p.launch(a);
 		HIPCHK(hipGetLastError());
 	}
 	cx.framer_launched = true;
@@ -841,15 +833,22 @@ extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *grou
 	if (top < 0) return sd_fail("sonde_batch_set_diversity: no group");
 	std::vector<SdDivGroup> gt((size_t)top + 1);
 	std::vector<int32_t> slot(b->n_channels, -1);
-	uint32_t kinds = 0;
+	// the types a member can have: the kinds of the passes whose create flag is set; as the refusal lists them: "A, B or C"
+	uint32_t kinds = 0, takes = 0;
+	std::string not_one = "sonde_batch_set_diversity: a member that is not ";
+	for (const SdDivPass &p : k_div_passes) {
+		if ((b->div_flags & p.flag) != p.flag) continue;
+		if (takes) not_one += ", ";
+		not_one += p.names;
+		takes |= p.kinds;
+	}
+	not_one.replace(not_one.rfind(", "), 2, " or ");
 	for (SdDivGroup &g : gt) g = SdDivGroup{};
 	for (uint32_t c = 0; c < b->n_channels; c++) {
 		if (group[c] < 0) continue;
 		SdDivGroup &g = gt[(size_t)group[c]];
 		const uint32_t t = b->types[c];
-		if (t != SONDE_RS41 && t != SONDE_M10 && t != SONDE_MRZN1 && t != SONDE_DFM09 && !(t == SONDE_IMS100 && b->ims_diversity))
-			return sd_fail(b->ims_diversity ? "sonde_batch_set_diversity: a member that is not SONDE_RS41, SONDE_M10, SONDE_MRZN1, SONDE_DFM09 or SONDE_IMS100"
-			                                : "sonde_batch_set_diversity: a member that is not SONDE_RS41, SONDE_M10, SONDE_MRZN1 or SONDE_DFM09");
+		if (!(takes >> t & 1u)) return sd_fail(not_one.c_str());
 		if (g.n && g.kind != t) return sd_fail("sonde_batch_set_diversity: members of different types in one group");
 		g.kind = t;
 		kinds |= 1u << t;
@@ -862,7 +861,8 @@ extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *grou
 	for (const SdDivGroup &g : gt)
 		if (g.n < 2) return sd_fail(g.n ? "sonde_batch_set_diversity: a group with fewer than 2 members" : "sonde_batch_set_diversity: group ids with gaps");
 	HIPCHK(hipSetDevice(b->device));
-	if ((kinds & (1u << SONDE_MRZN1)) && sd_batch_need_mrztab(b)) return -1;      // the pass of SPEC 3.3l reads MRZ-N1's columns from it
+	for (const SdDivPass &p : k_div_passes)
+		if ((kinds & p.mrz_kinds) && sd_batch_need_mrztab(b)) return -1;      // the pass of SPEC 3.3l reads MRZ-N1's columns from it
 	HIPCHK(b->d_groups.upload(gt.data(), gt.size()));
 	HIPCHK(b->d_carried.zeros(gt.size() * SD_DIV_MAX));
 	HIPCHK(b->d_divcnt.zeros(gt.size() * 2));
@@ -880,8 +880,7 @@ extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *grou
 	b->div_mode = mode;
 	b->div_unlocked = unlocked ? 1u : 0u;
 	b->div_slot = slot;
-	b->div_window = window_bits ? window_bits : 960u;
-	b->div_window_ims = window_bits ? window_bits : 576u;     // SPEC 3.3n: iMS-100 frames lie 1152 chips apart
+	b->div_window = window_bits;
 	b->n_groups = (uint32_t)gt.size();
 	return 0;
 }

@@ -46,6 +46,34 @@ static const SdRescuePass k_rescue_passes[SD_N_PASSES] = {
 	  "sonde_batch_afsk_rescue_info", "an", "iMet or C50" },
 };
 
+// The combining passes of sonde_batch_set_diversity (launch.h, DESIGN "what a combining pass plugs into"), one row each: what
+// set_diversity, submit and the unit entries need to know about a pass.  The kernels are launched in this order, each over the whole
+// group table; the rows' kinds are disjoint
+struct SdDivPass {
+	uint32_t kinds;                        // bit t: the pass takes the groups of sonde type t
+	void (*launch)(const SdDivArgs &);
+	uint32_t window;                       // its window where the caller gives none: 960 bits; iMS-100 576 chips (frames lie 1152 apart)
+	uint32_t flag;                         // the create flag a member needs; 0: none
+	uint32_t mrz_kinds;                    // a group of one of these kinds: the pass reads d_mrztab
+	const char *names;                     // its kinds as the refusal of a member of no pass lists them
+	struct { uint32_t type, len; } frames[4];  // the frames of its kinds: (type, length) pairs, ended by a length of 0
+};
+enum { SD_DIV_RS41, SD_DIV_CHECK, SD_DIV_DFM, SD_DIV_IMS, SD_N_DIV_PASSES };
+static const SdDivPass k_div_passes[SD_N_DIV_PASSES] = {
+	{ 1u << SONDE_RS41, sd_launch_diversity, 960, 0, 0, "SONDE_RS41", { { SONDE_RS41, 320 }, { SONDE_RS41, 518 } } },
+	{ 1u << SONDE_M10 | 1u << SONDE_MRZN1, sd_launch_check_diversity, 960, 0, 1u << SONDE_MRZN1, "SONDE_M10, SONDE_MRZN1",
+	  { { SONDE_M10, 101 }, { SONDE_M10, 70 }, { SONDE_MRZN1, 45 } } },
+	{ 1u << SONDE_DFM09, sd_launch_dfm_diversity, 960, 0, 0, "SONDE_DFM09", { { SONDE_DFM09, 33 } } },
+	{ 1u << SONDE_IMS100, sd_launch_ims_diversity, 576, SONDE_FLAG_IMS_DIVERSITY, 0, "SONDE_IMS100", { { SONDE_IMS100, 51 } } },
+};
+// a frame of one of the pass's kinds
+static inline bool sd_div_is_frame(const SdDivPass &p, uint32_t type, uint32_t len)
+{
+	for (const auto &f : p.frames)
+		if (f.len && f.type == type && f.len == len) return true;
+	return false;
+}
+
 // Timing events.  An event record is a bubble of a few microseconds in the command stream (three of them cost a 0.29 ms step 3 %), so
 // only every `every`-th submit is timed (0: none), into the next of kSlots slots; all events are created with the batch.
 struct SdTiming {
@@ -179,10 +207,9 @@ struct SondeBatch {
 	// allocated or launched
 	// div_mode: sonde_batch_set_diversity_auto's mode (SPEC 3.3k; 0: no align step is launched), div_unlocked: its groups start unlocked;
 	// d_divstate: per group the offsets and lock bits the combining pass reads, and the align step's counters
-	// div_kinds: a bit per sonde type that has a group (SPEC 3.3l, 3.3m, 3.3n): which of the four combining kernels are launched
-	// ims_diversity: SONDE_FLAG_IMS_DIVERSITY -- set_diversity takes iMS-100 groups; div_window_ims: their window (its default is 576 chips)
-	uint32_t n_groups = 0, div_window = 0, div_window_ims = 0, div_mode = 0, div_unlocked = 0, div_kinds = 0;
-	bool ims_diversity = false;
+	// div_kinds: a bit per sonde type that has a group (SPEC 3.3l, 3.3m, 3.3n): which of the combining kernels (k_div_passes) are launched
+	// div_flags: the create flags a pass may ask for (SdDivPass.flag); div_window: the caller's window, 0: each pass's default
+	uint32_t n_groups = 0, div_window = 0, div_mode = 0, div_unlocked = 0, div_kinds = 0, div_flags = 0;
 	DevBuf<SdDivGroup> d_groups;
 	DevBuf<SdDivState> d_divstate;
 	DevBuf<SondeFrame> d_carried;

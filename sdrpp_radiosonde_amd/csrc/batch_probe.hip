@@ -1,5 +1,5 @@
 // batch_probe.hip -- introspection for the staged parity tests and the bench: the RS correctors alone, a channel's state and bits,
-// what the rescue pass has learned, and the HBM read probe.  Not on the product path.
+// what the rescue pass has learned, a combining pass's rule alone (test_combine), and the HBM read probe.  Not on the product path.
 #include <hip/hip_runtime.h>
 #include <string>
 #include <vector>
@@ -137,101 +137,88 @@ extern "C" int sonde_batch_diversity_info(SondeBatch *b, uint32_t group, uint32_
 	return 0;
 }
 
-// Steps 3 to 7 of SPEC 3.3j alone, through the kernel's own device function: n cases of 4 caller-made copies (n_copies[i] in use, copy 0
-// the record to rewrite); out[i] = copy 0, rewritten or not; status[i] = copies used, -1 too many erasures, -2 no decode, -3 rejected.
+// What the four combine entries below do around their pass's unit kernel (launch.h SdDivUnitArgs), each through the kernel's own device
+// function.  An entry: its name, its launcher, the records per case (SD_DIV_MAX copies, copy 0 the record to rewrite; iMS-100: copy
+// 0's record alone), the received blocks per case (iMS-100; else 0), and whether the kernel reads MRZ-N1's column table -- one of the
+// call's own: the batch stays as it is.  The cases, as the caller gave them: n of them, n_copies[i] = 2..4 copies in use; out[i] =
+// copy 0, rewritten or not, status[i] = what the rule answers.  why(c, k) = null, or why the case of the k copies c is refused
+struct CombineEntry { const char *who; void (*launch)(const SdDivUnitArgs &); size_t per, per_blocks; bool mrz; };
+struct CombineCases { size_t n; const SondeFrame *copies; const uint32_t *n_copies; const uint64_t *blocks; SondeFrame *out; int32_t *status; };
+template <typename Why> static int test_combine(const CombineEntry &e, SondeBatch *b, const CombineCases &c, Why why)
+{
+	const auto fail = [&e](const char *w) { std::string m(e.who); m += ": "; m += w; return sd_fail(m.c_str()); };
+	if (!b || !c.copies || !c.n_copies || (e.per_blocks && !c.blocks) || !c.out || !c.status || !c.n || c.n > (1u << 16)) return fail("bad argument");
+	for (size_t i = 0; i < c.n; i++) {
+		if (c.n_copies[i] < 2 || c.n_copies[i] > SD_DIV_MAX) return fail("n_copies must be 2..4");
+		if (const char *w = why(c.copies + e.per * i, c.n_copies[i])) return fail(w);
+	}
+	HIPCHK(hipSetDevice(b->device));
+	DevBuf<SondeFrame> d_c;
+	DevBuf<uint32_t> d_n;
+	DevBuf<uint64_t> d_b;
+	DevBuf<uint16_t> d_mrz;
+	if (e.mrz) {
+		uint16_t tab[43 * 8];
+		fec_mrz_table(tab);
+		HIPCHK(d_mrz.upload(tab, 43 * 8));
+	}
+	HIPCHK(d_c.upload(c.copies, e.per * c.n));
+	HIPCHK(d_n.upload(c.n_copies, c.n));
+	if (e.per_blocks) HIPCHK(d_b.upload(c.blocks, e.per_blocks * c.n));
+	return probe_unit(e.who, (const SondeFrame *)nullptr, c.out, c.n, c.status, c.n, [&](SondeFrame *d_o, int32_t *d_st) {
+		e.launch({ d_c, d_n, (uint32_t)c.n, d_o, d_st, b->fec, d_mrz, d_b, nullptr });
+	});
+}
+
+// Steps 3 to 7 of SPEC 3.3j alone: status[i] = copies used, -1 too many erasures, -2 no decode, -3 rejected.
 extern "C" int sonde_batch_test_rs41_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status)
 {
-	if (!b || !copies || !n_copies || !out || !status || !n || n > (1u << 16)) return sd_fail("sonde_batch_test_rs41_combine: bad argument");
-	for (size_t i = 0; i < n; i++) {
-		const SondeFrame *c = copies + SD_DIV_MAX * i;
-		if (n_copies[i] < 2 || n_copies[i] > SD_DIV_MAX) return sd_fail("sonde_batch_test_rs41_combine: n_copies must be 2..4");
-		if ((c[0].len != 320 && c[0].len != 518) || (c[0].nerr[0] >= 0 && c[0].nerr[1] >= 0))
-			return sd_fail("sonde_batch_test_rs41_combine: copy 0 must be a 320- or 518-byte record with a failed codeword");
-		for (uint32_t k = 1; k < n_copies[i]; k++)
-			if (c[k].len != c[0].len) return sd_fail("sonde_batch_test_rs41_combine: the copies of a case must have one length");
-	}
-	HIPCHK(hipSetDevice(b->device));
-	DevBuf<SondeFrame> d_c;
-	DevBuf<uint32_t> d_n;
-	HIPCHK(d_c.upload(copies, SD_DIV_MAX * n));
-	HIPCHK(d_n.upload(n_copies, n));
-	return probe_unit("sonde_batch_test_rs41_combine", (const SondeFrame *)nullptr, out, n, status, n, [&](SondeFrame *d_o, int32_t *d_st) {
-		sd_launch_diversity_unit(d_c, d_n, (uint32_t)n, d_o, d_st, b->fec.gfexp, b->fec.gflog, b->fec.gfswar, nullptr);
-	});
+	return test_combine({ "sonde_batch_test_rs41_combine", sd_launch_diversity_unit, SD_DIV_MAX, 0, false }, b, { n, copies, n_copies, nullptr, out, status },
+		[](const SondeFrame *c, uint32_t k) -> const char * {
+			if (!sd_div_is_frame(k_div_passes[SD_DIV_RS41], SONDE_RS41, c[0].len) || (c[0].nerr[0] >= 0 && c[0].nerr[1] >= 0))
+				return "copy 0 must be a 320- or 518-byte record with a failed codeword";
+			for (uint32_t j = 1; j < k; j++)
+				if (c[j].len != c[0].len) return "the copies of a case must have one length";
+			return nullptr;
+		});
 }
 
-// Steps 3 to 6 of SPEC 3.3l alone, through the kernel's own device function: the shape of sonde_batch_test_rs41_combine; status[i] =
-// copies used, -1 not attempted, -2 no subset fits, -3 several fit.
+// Steps 3 to 6 of SPEC 3.3l alone: status[i] = copies used, -1 not attempted, -2 no subset fits, -3 several fit.
 extern "C" int sonde_batch_test_check_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status)
 {
-	if (!b || !copies || !n_copies || !out || !status || !n || n > (1u << 16)) return sd_fail("sonde_batch_test_check_combine: bad argument");
-	for (size_t i = 0; i < n; i++) {
-		const SondeFrame *c = copies + SD_DIV_MAX * i;
-		if (n_copies[i] < 2 || n_copies[i] > SD_DIV_MAX) return sd_fail("sonde_batch_test_check_combine: n_copies must be 2..4");
-		const bool known = (c[0].type == SONDE_M10 && (c[0].len == 101 || c[0].len == 70)) || (c[0].type == SONDE_MRZN1 && c[0].len == 45);
-		if (!known || c[0].nerr[0] >= 0)
-			return sd_fail("sonde_batch_test_check_combine: copy 0 must be a failed SONDE_M10 record of 101 or 70 bytes or a failed SONDE_MRZN1 record of 45");
-		for (uint32_t k = 1; k < n_copies[i]; k++)
-			if (c[k].len != c[0].len || c[k].type != c[0].type) return sd_fail("sonde_batch_test_check_combine: the copies of a case must have one type and one length");
-	}
-	HIPCHK(hipSetDevice(b->device));
-	DevBuf<SondeFrame> d_c;
-	DevBuf<uint32_t> d_n;
-	DevBuf<uint16_t> d_mrz;                 // a table of the call's own: the batch stays as it is
-	uint16_t mrz[43 * 8];
-	fec_mrz_table(mrz);
-	HIPCHK(d_mrz.upload(mrz, 43 * 8));
-	HIPCHK(d_c.upload(copies, SD_DIV_MAX * n));
-	HIPCHK(d_n.upload(n_copies, n));
-	return probe_unit("sonde_batch_test_check_combine", (const SondeFrame *)nullptr, out, n, status, n, [&](SondeFrame *d_o, int32_t *d_st) {
-		sd_launch_check_diversity_unit(d_c, d_n, (uint32_t)n, d_o, d_st, b->fec.m10tab, d_mrz, nullptr);
-	});
+	return test_combine({ "sonde_batch_test_check_combine", sd_launch_check_diversity_unit, SD_DIV_MAX, 0, true }, b, { n, copies, n_copies, nullptr, out, status },
+		[](const SondeFrame *c, uint32_t k) -> const char * {
+			if (!sd_div_is_frame(k_div_passes[SD_DIV_CHECK], c[0].type, c[0].len) || c[0].nerr[0] >= 0)
+				return "copy 0 must be a failed SONDE_M10 record of 101 or 70 bytes or a failed SONDE_MRZN1 record of 45";
+			for (uint32_t j = 1; j < k; j++)
+				if (c[j].len != c[0].len || c[j].type != c[0].type) return "the copies of a case must have one type and one length";
+			return nullptr;
+		});
 }
 
-// Steps 3 to 6 of SPEC 3.3m alone, through the kernel's own device function: the shape of sonde_batch_test_rs41_combine; status[i] =
-// copies used, -1 the pairing guard refuses, -2 a word has no solution, -3 a word has several.
+// Steps 3 to 6 of SPEC 3.3m alone: status[i] = copies used, -1 the pairing guard refuses, -2 a word has no solution, -3 a word has several.
 extern "C" int sonde_batch_test_dfm_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status)
 {
-	if (!b || !copies || !n_copies || !out || !status || !n || n > (1u << 16)) return sd_fail("sonde_batch_test_dfm_combine: bad argument");
-	for (size_t i = 0; i < n; i++) {
-		const SondeFrame *c = copies + SD_DIV_MAX * i;
-		if (n_copies[i] < 2 || n_copies[i] > SD_DIV_MAX) return sd_fail("sonde_batch_test_dfm_combine: n_copies must be 2..4");
-		if (c[0].nerr[1] <= 0) return sd_fail("sonde_batch_test_dfm_combine: copy 0 must be a failed record (nerr[1] > 0)");
-		for (uint32_t k = 0; k < n_copies[i]; k++)
-			if (c[k].type != SONDE_DFM09 || c[k].len != 33) return sd_fail("sonde_batch_test_dfm_combine: every copy must be a SONDE_DFM09 record of 33 bytes");
-	}
-	HIPCHK(hipSetDevice(b->device));
-	DevBuf<SondeFrame> d_c;
-	DevBuf<uint32_t> d_n;
-	HIPCHK(d_c.upload(copies, SD_DIV_MAX * n));
-	HIPCHK(d_n.upload(n_copies, n));
-	return probe_unit("sonde_batch_test_dfm_combine", (const SondeFrame *)nullptr, out, n, status, n, [&](SondeFrame *d_o, int32_t *d_st) {
-		sd_launch_dfm_diversity_unit(d_c, d_n, (uint32_t)n, d_o, d_st, nullptr);
-	});
+	return test_combine({ "sonde_batch_test_dfm_combine", sd_launch_dfm_diversity_unit, SD_DIV_MAX, 0, false }, b, { n, copies, n_copies, nullptr, out, status },
+		[](const SondeFrame *c, uint32_t k) -> const char * {
+			if (c[0].nerr[1] <= 0) return "copy 0 must be a failed record (nerr[1] > 0)";
+			for (uint32_t j = 0; j < k; j++)
+				if (!sd_div_is_frame(k_div_passes[SD_DIV_DFM], c[j].type, c[j].len)) return "every copy must be a SONDE_DFM09 record of 33 bytes";
+			return nullptr;
+		});
 }
 
-// Steps 4 to 7 of SPEC 3.3n alone, through the kernel's own device function: per case copy 0's record and the received blocks of the
-// copies, [SD_DIV_MAX][12]; status[i] = copies used, 0 the record's nerr[1] is not what copy 0's blocks say, -1 the pairing guard
-// refuses, -2 a block has no solution, -3 a block has several.
+// Steps 4 to 7 of SPEC 3.3n alone: per case copy 0's record and the received blocks of the copies, [SD_DIV_MAX][12]; status[i] = copies
+// used, 0 the record's nerr[1] is not what copy 0's blocks say, -1 the pairing guard refuses, -2 a block has no solution, -3 a block
+// has several.
 extern "C" int sonde_batch_test_ims_combine(SondeBatch *b, size_t n, const SondeFrame *records, const uint32_t *n_copies, const uint64_t *blocks,
 	SondeFrame *out, int32_t *status)
 {
-	if (!b || !records || !n_copies || !blocks || !out || !status || !n || n > (1u << 16)) return sd_fail("sonde_batch_test_ims_combine: bad argument");
-	for (size_t i = 0; i < n; i++) {
-		if (n_copies[i] < 2 || n_copies[i] > SD_DIV_MAX) return sd_fail("sonde_batch_test_ims_combine: n_copies must be 2..4");
-		if (records[i].type != SONDE_IMS100 || records[i].len != 51) return sd_fail("sonde_batch_test_ims_combine: copy 0 must be a SONDE_IMS100 record of 51 bytes");
-		if (records[i].nerr[1] <= 0) return sd_fail("sonde_batch_test_ims_combine: copy 0 must be a failed record (nerr[1] > 0)");
-	}
-	HIPCHK(hipSetDevice(b->device));
-	DevBuf<SondeFrame> d_r;
-	DevBuf<uint32_t> d_n;
-	DevBuf<uint64_t> d_b;
-	HIPCHK(d_r.upload(records, n));
-	HIPCHK(d_n.upload(n_copies, n));
-	HIPCHK(d_b.upload(blocks, SD_DIV_MAX * 12 * n));
-	return probe_unit("sonde_batch_test_ims_combine", (const SondeFrame *)nullptr, out, n, status, n, [&](SondeFrame *d_o, int32_t *d_st) {
-		sd_launch_ims_diversity_unit(d_r, d_n, d_b, (uint32_t)n, d_o, d_st, b->fec.g64, nullptr);
-	});
+	return test_combine({ "sonde_batch_test_ims_combine", sd_launch_ims_diversity_unit, 1, SD_DIV_MAX * 12, false }, b, { n, records, n_copies, blocks, out, status },
+		[](const SondeFrame *r, uint32_t) -> const char * {
+			if (!sd_div_is_frame(k_div_passes[SD_DIV_IMS], r->type, r->len)) return "copy 0 must be a SONDE_IMS100 record of 51 bytes";
+			return r->nerr[1] <= 0 ? "copy 0 must be a failed record (nerr[1] > 0)" : nullptr;
+		});
 }
 
 extern "C" int sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t off[4], uint32_t *locked_mask, uint32_t *learned, uint32_t *duplicates)

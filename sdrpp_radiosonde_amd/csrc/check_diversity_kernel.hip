@@ -4,8 +4,9 @@
 // GF(2) (SPEC 3.3f), so the differing bits are the unknowns of a 16-equation system: the working frame (copy 0, or the bitwise majority
 // of three or four copies) is taken if its check passes, else iff exactly one subset of the at most 8 differing bits explains its
 // syndrome.
-//   one 64-lane wave per group, four waves per workgroup.  The record search -- the next failed record and its partners, this submit's
-//   records plus the carried one -- is the RS41 pass's (sd_diversity_scan.h).  Lane i holds the 32-bit word i of every copy (a frame
+//   one 64-lane wave per group, four waves per workgroup.  The loop over a group -- the next failed record and its partners, this
+//   submit's records plus the carried one, the counters, the carried records -- is dv_walk of sd_diversity_scan.h; this file is its
+//   pass CdPass.  Lane i holds the 32-bit word i of every copy (a frame
 //   has at most 26), so majority and the differing bits are a handful of bitwise operations, V is gathered by ballot into lanes 0..7,
 //   and the <= 255 subsets are tried across the wave, four per lane (sd_check_cols.h, shared with check_rescue_kernel.hip).  No LDS.
 // Runs behind every other kernel of the submit and behind the align step, on the stream where the submit completes, and rewrites
@@ -17,8 +18,6 @@
 #include "sd_check_cols.h"
 #include "sd_diversity_scan.h"
 #include "launch.h"
-
-#define CD_WAVES 4
 
 // word `lane` of a record's data, zero behind the frame's last word
 __device__ __forceinline__ uint32_t cd_word(const SondeFrame *f, int len, int lane)
@@ -94,91 +93,62 @@ __device__ __forceinline__ void cd_write_record(SondeFrame *fr, int len, int K, 
 	}
 }
 
-__global__ __launch_bounds__(64 * CD_WAVES) void sd_check_diversity_kernel(
-	const uint16_t *__restrict__ m10tab /* [99][8] */, const uint16_t *__restrict__ mrztab /* [43][8] */,
-	SondeFrame *frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const SdDivGroup *__restrict__ groups, const SdDivState *states, uint32_t n_groups, uint32_t window, SondeFrame *carried,
-	uint32_t *counters /* [n_groups][2] */)
-{
-	const int lane = threadIdx.x & 63;
-	const uint32_t g = CD_WAVES * blockIdx.x + (threadIdx.x >> 6);
-	if (g >= n_groups) return;
-	const SdDivGroup *G = groups + g;
-	const uint32_t kind = (uint32_t)DV_U(G->kind);
-	if (kind != SONDE_M10 && kind != SONDE_MRZN1) return;      // an RS41 or a DFM group: another kernel's
-	const bool mrz = kind == SONDE_MRZN1;
-	DvMembers M;
-	dv_members(M, frames, counts, max_frames, G, states + g);
-
-	// ---- steps 1 and 2 (sd_diversity_scan.h): the failed records in ascending (t, member), each with its partners
-	uint32_t tried = 0, combined = 0;
-	int64_t last_t = INT64_MIN, t_r;
-	int last_m = -1;
-	uint32_t bk;
-	while (dv_next_failed(M, kind, lane, last_t, last_m, t_r, bk)) {
-		const int m_r = (int)(bk >> 16);
-		SondeFrame *fr = M.rec_of(m_r, bk & 0xFFFFu);
-		const int flen = DV_U(fr->len);
-		uint32_t c[SD_DIV_MAX] = { 0u, 0u, 0u, 0u };
-		int K = 1;
-		bool any_good = false;
-#pragma unroll
-		for (int b = 0; b < SD_DIV_MAX; b++) {
-			if (b >= M.nm || b == m_r || any_good || !((M.lockmask >> b) & 1u)) continue;
-			const SondeFrame *pf = dv_partner(M, b, flen, t_r, window, carried + (size_t)SD_DIV_MAX * g + b, lane);
-			if (!pf) continue;
-			if (DV_U(dv_load_fresh(reinterpret_cast<const uint32_t *>(&pf->nerr[0]))) >= 0) { any_good = true; continue; }
-			// a partner that is not good has not been rewritten: its data are as recorded
-			const uint32_t wd = cd_word(pf, flen, lane);
-			if (K == 1) c[1] = wd; else if (K == 2) c[2] = wd; else c[3] = wd;
-			K++;
-		}
-		if (K == 1 || any_good) continue;          // no partner, or the group has a good copy already: stays as recorded
-		tried++;
+// The pass of the walk (sd_diversity_scan.h): lane i holds word i of every copy in registers
+struct CdPass {
+	const uint16_t *m10tab /* [99][8] */, *mrztab /* [43][8] */;
+	bool mrz;
+	uint32_t c[SD_DIV_MAX];
+	static constexpr uint32_t nerr = 1;
+	__device__ __forceinline__ bool takes(const SdDivGroup *G, uint32_t &kind)
+	{
+		const uint32_t k = (uint32_t)DV_U(G->kind);
+		mrz = k == SONDE_MRZN1;
+		kind = mrz ? SONDE_MRZN1 : SONDE_M10;      // one of two constants: the walk's predicates fold to these two kinds
+		return k == SONDE_M10 || mrz;
+	}
+	__device__ __forceinline__ int flen(const SondeFrame *fr) const { return DV_U(fr->len); }
+	__device__ __forceinline__ void partner(int K, const SondeFrame *pf, uint32_t, int, int, int flen, int lane)
+	{
+		dv_set_copy(c, K, cd_word(pf, flen, lane));
+	}
+	__device__ __forceinline__ int attempt(SondeFrame *fr, uint32_t, int K, int flen, int lane)
+	{
 		c[0] = cd_word(fr, flen, lane);
 		uint32_t w;
 		int nv;
-		if (cd_combine(m10tab, mrztab, mrz, flen, K, c, lane, w, nv) > 0) {
-			cd_write_record(fr, flen, K, nv, w, c[0], lane);
-			combined++;
-			__threadfence();
-		}
+		if (cd_combine(m10tab, mrztab, mrz, flen, K, c, lane, w, nv) <= 0) return DV_TRIED;
+		cd_write_record(fr, flen, K, nv, w, c[0], lane);
+		return DV_COMBINED;
 	}
+	__device__ __forceinline__ void sync() const {}
+};
 
-	// ---- the carried records: each member's newest record of this submit with a frame length, as the pass left it
-	__threadfence();
-	dv_carry(M, kind, carried + (size_t)SD_DIV_MAX * g, lane);
-	if (lane == 0 && (tried | combined)) { counters[2 * g] += tried; counters[2 * g + 1] += combined; }
-}
-
-void sd_launch_check_diversity(uint32_t n_groups, hipStream_t stream, const uint16_t *m10tab, const uint16_t *mrztab, SondeFrame *frames,
-	const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, const SdDivState *states, uint32_t window, SondeFrame *carried,
-	uint32_t *counters)
+__global__ __launch_bounds__(64 * DV_WAVES) void sd_check_diversity_kernel(SdDivWalk a, const uint16_t *__restrict__ m10tab,
+	const uint16_t *__restrict__ mrztab)
 {
-	hipLaunchKernelGGL(sd_check_diversity_kernel, dim3((n_groups + CD_WAVES - 1) / CD_WAVES), dim3(64 * CD_WAVES), 0, stream,
-		m10tab, mrztab, frames, counts, max_frames, groups, states, n_groups, window, carried, counters);
+	CdPass pass = { m10tab, mrztab, false, { 0u, 0u, 0u, 0u } };
+	dv_walk(a, pass);
 }
+
+void sd_launch_check_diversity(const SdDivArgs &a) { dv_launch(sd_check_diversity_kernel, a, a.fec.m10tab, a.mrztab); }
 
 // ---- test introspection: steps 3 to 6 alone on caller-made copies (sonde_batch_test_check_combine).  One wave per case; the host has
 // checked n_copies (2..4), the copies' type (SONDE_M10 or SONDE_MRZN1) and len (one of the type's, the same in all copies of a case)
 // and that copy 0 has failed.
-__global__ __launch_bounds__(64 * CD_WAVES) void sd_check_diversity_unit_kernel(
+__global__ __launch_bounds__(64 * DV_WAVES) void sd_check_diversity_unit_kernel(
 	const uint16_t *__restrict__ m10tab, const uint16_t *__restrict__ mrztab,
 	const SondeFrame *__restrict__ copies /* [n][SD_DIV_MAX] */, const uint32_t *__restrict__ n_copies, uint32_t n, SondeFrame *out,
 	int32_t *__restrict__ status)
 {
 	const int lane = threadIdx.x & 63;
-	const uint32_t k = CD_WAVES * blockIdx.x + (threadIdx.x >> 6);
-	if (k >= n) return;
+	uint32_t k;
+	if (!dv_unit_case(k, n, copies, SD_DIV_MAX, out, lane)) return;
 	const SondeFrame *cps = copies + (size_t)SD_DIV_MAX * k;
 	const int K = DV_U(n_copies[k]), len = DV_U(cps[0].len);
 	const bool mrz = (uint32_t)DV_U(cps[0].type) == SONDE_MRZN1;
 	uint32_t c[SD_DIV_MAX];
 #pragma unroll
 	for (int j = 0; j < SD_DIV_MAX; j++) c[j] = j < K ? cd_word(cps + j, len, lane) : 0u;
-	// out = copy 0, in memory before the result is written over it (other lanes write the same words then)
-	for (int i = lane; i < DV_REC_WORDS; i += 64) reinterpret_cast<uint32_t *>(out + k)[i] = reinterpret_cast<const uint32_t *>(cps)[i];
-	__threadfence();
 	uint32_t w;
 	int nv;
 	const int st = cd_combine(m10tab, mrztab, mrz, len, K, c, lane, w, nv);
@@ -186,9 +156,8 @@ __global__ __launch_bounds__(64 * CD_WAVES) void sd_check_diversity_unit_kernel(
 	if (lane == 0) status[k] = st;
 }
 
-void sd_launch_check_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
-	const uint16_t *m10tab, const uint16_t *mrztab, hipStream_t stream)
+void sd_launch_check_diversity_unit(const SdDivUnitArgs &a)
 {
-	hipLaunchKernelGGL(sd_check_diversity_unit_kernel, dim3((n + CD_WAVES - 1) / CD_WAVES), dim3(64 * CD_WAVES), 0, stream,
-		m10tab, mrztab, copies, n_copies, n, out, status);
+	hipLaunchKernelGGL(sd_check_diversity_unit_kernel, dim3((a.n + DV_WAVES - 1) / DV_WAVES), dim3(64 * DV_WAVES), 0, a.stream,
+		a.fec.m10tab, a.mrztab, a.copies, a.n_copies, a.n, a.out, a.status);
 }

@@ -5,8 +5,9 @@
 // that hold it as a codeword, or -- where it failed in every copy -- is the one codeword two bits away from every copy's word; a frame
 // is rewritten only if every failed word decodes, and only if the copies agree on their good words (the pairing guard: DFM has no
 // check behind the code that would catch copies of two different frames).
-//   one 64-lane wave per group, four waves per workgroup.  The record search -- the next failed record and its partners, this submit's
-//   records plus the carried one -- is the RS41 pass's (sd_diversity_scan.h).  Lane i < 33 holds byte i of every copy: the syndromes are
+//   one 64-lane wave per group, four waves per workgroup.  The loop over a group -- the next failed record and its partners, this
+//   submit's records plus the carried one, the counters, the carried records -- is dv_walk of sd_diversity_scan.h; this file is its
+//   pass DdPass.  Lane i < 33 holds byte i of every copy: the syndromes are
 //   parities of masked bytes, the 16 codewords are made from their nibbles in registers, and step 4 is lane-local; the word sets A, D, F,
 //   none and several are ballots.  No LDS, no tables in memory.
 // Runs behind every other kernel of the submit, behind the align step and the other two combining kernels (they take disjoint groups),
@@ -18,7 +19,6 @@
 #include "sd_diversity_scan.h"
 #include "launch.h"
 
-#define DD_WAVES 4
 constexpr int DD_WORDS = 33;          // Hamming(8,4) words of a DFM frame = bytes of its record
 constexpr int DD_MIN_AGREED = 17;     // SPEC 3.3m step 3: words that are codewords in every copy, at least
 constexpr int DD_MAX_DIFFER = 2;      // ... and of those, words on which the copies differ, at most
@@ -101,84 +101,55 @@ __device__ __forceinline__ void dd_write_record(SondeFrame *fr, int K, bool in_f
 	}
 }
 
-__global__ __launch_bounds__(64 * DD_WAVES) void sd_dfm_diversity_kernel(
-	SondeFrame *frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const SdDivGroup *__restrict__ groups, const SdDivState *states, uint32_t n_groups, uint32_t window, SondeFrame *carried,
-	uint32_t *counters /* [n_groups][2] */)
-{
-	const int lane = threadIdx.x & 63;
-	const uint32_t g = DD_WAVES * blockIdx.x + (threadIdx.x >> 6);
-	if (g >= n_groups) return;
-	const SdDivGroup *G = groups + g;
-	if ((uint32_t)DV_U(G->kind) != SONDE_DFM09) return;        // the other kinds: diversity_kernel.hip, check_diversity_kernel.hip
-	DvMembers M;
-	dv_members(M, frames, counts, max_frames, G, states + g);
-
-	// ---- steps 1 and 2 (sd_diversity_scan.h): the failed records in ascending (t, member), each with its partners
-	uint32_t tried = 0, combined = 0;
-	int64_t last_t = INT64_MIN, t_r;
-	int last_m = -1;
-	uint32_t bk;
-	while (dv_next_failed(M, SONDE_DFM09, lane, last_t, last_m, t_r, bk)) {
-		const int m_r = (int)(bk >> 16);
-		SondeFrame *fr = M.rec_of(m_r, bk & 0xFFFFu);
-		uint32_t x[SD_DIV_MAX] = { 0u, 0u, 0u, 0u };
-		int K = 1;
-		bool any_good = false;
-#pragma unroll
-		for (int b = 0; b < SD_DIV_MAX; b++) {
-			if (b >= M.nm || b == m_r || any_good || !((M.lockmask >> b) & 1u)) continue;
-			const SondeFrame *pf = dv_partner(M, b, DD_WORDS, t_r, window, carried + (size_t)SD_DIV_MAX * g + b, lane);
-			if (!pf) continue;
-			if (DV_U(dv_load_fresh(reinterpret_cast<const uint32_t *>(&pf->nerr[1]))) == 0) { any_good = true; continue; }
-			// a partner that is not good has not been rewritten: its data are as recorded
-			const uint32_t pb = dd_byte(pf, lane);
-			if (K == 1) x[1] = pb; else if (K == 2) x[2] = pb; else x[3] = pb;
-			K++;
-		}
-		if (K == 1 || any_good) continue;          // no partner, or the group has a good copy already: stays as recorded
-		tried++;
+// The pass of the walk (sd_diversity_scan.h): lane i < 33 holds byte i of every copy in registers
+struct DdPass {
+	uint32_t x[SD_DIV_MAX];
+	static constexpr uint32_t nerr = 2;
+	__device__ __forceinline__ bool takes(const SdDivGroup *G, uint32_t &kind) const
+	{
+		kind = SONDE_DFM09;
+		return (uint32_t)DV_U(G->kind) == SONDE_DFM09;
+	}
+	__device__ __forceinline__ int flen(const SondeFrame *) const { return DD_WORDS; }
+	__device__ __forceinline__ void partner(int K, const SondeFrame *pf, uint32_t, int, int, int, int lane)
+	{
+		dv_set_copy(x, K, dd_byte(pf, lane));
+	}
+	__device__ __forceinline__ int attempt(SondeFrame *fr, uint32_t, int K, int, int lane)
+	{
 		x[0] = dd_byte(fr, lane);
 		bool in_f;
 		uint32_t v;
 		int nf, nj;
-		if (dd_combine(K, x, lane, in_f, v, nf, nj) > 0) {
-			dd_write_record(fr, K, in_f, v, nf, nj, lane);
-			combined++;
-			__threadfence();
-		}
+		if (dd_combine(K, x, lane, in_f, v, nf, nj) <= 0) return DV_TRIED;
+		dd_write_record(fr, K, in_f, v, nf, nj, lane);
+		return DV_COMBINED;
 	}
+	__device__ __forceinline__ void sync() const {}
+};
 
-	// ---- the carried records: each member's newest record of this submit with the frame length, as the pass left it
-	__threadfence();
-	dv_carry(M, SONDE_DFM09, carried + (size_t)SD_DIV_MAX * g, lane);
-	if (lane == 0 && (tried | combined)) { counters[2 * g] += tried; counters[2 * g + 1] += combined; }
-}
-
-void sd_launch_dfm_diversity(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
-	const SdDivGroup *groups, const SdDivState *states, uint32_t window, SondeFrame *carried, uint32_t *counters)
+__global__ __launch_bounds__(64 * DV_WAVES) void sd_dfm_diversity_kernel(SdDivWalk a)
 {
-	hipLaunchKernelGGL(sd_dfm_diversity_kernel, dim3((n_groups + DD_WAVES - 1) / DD_WAVES), dim3(64 * DD_WAVES), 0, stream,
-		frames, counts, max_frames, groups, states, n_groups, window, carried, counters);
+	DdPass pass = { { 0u, 0u, 0u, 0u } };
+	dv_walk(a, pass);
 }
+
+void sd_launch_dfm_diversity(const SdDivArgs &a) { dv_launch(sd_dfm_diversity_kernel, a); }
 
 // ---- test introspection: steps 3 to 6 alone on caller-made copies (sonde_batch_test_dfm_combine).  One wave per case; the host has
 // checked n_copies (2..4), the copies' type (SONDE_DFM09) and len (33) and that copy 0 has failed.
-__global__ __launch_bounds__(64 * DD_WAVES) void sd_dfm_diversity_unit_kernel(
+__global__ __launch_bounds__(64 * DV_WAVES) void sd_dfm_diversity_unit_kernel(
 	const SondeFrame *__restrict__ copies /* [n][SD_DIV_MAX] */, const uint32_t *__restrict__ n_copies, uint32_t n, SondeFrame *out,
 	int32_t *__restrict__ status)
 {
 	const int lane = threadIdx.x & 63;
-	const uint32_t k = DD_WAVES * blockIdx.x + (threadIdx.x >> 6);
-	if (k >= n) return;
+	uint32_t k;
+	if (!dv_unit_case(k, n, copies, SD_DIV_MAX, out, lane)) return;
 	const SondeFrame *cps = copies + (size_t)SD_DIV_MAX * k;
 	const int K = DV_U(n_copies[k]);
 	uint32_t x[SD_DIV_MAX];
 #pragma unroll
 	for (int j = 0; j < SD_DIV_MAX; j++) x[j] = j < K ? dd_byte(cps + j, lane) : 0u;
-	// out = copy 0, in memory before the result is written over it
-	for (int i = lane; i < DV_REC_WORDS; i += 64) reinterpret_cast<uint32_t *>(out + k)[i] = reinterpret_cast<const uint32_t *>(cps)[i];
-	__threadfence();
 	bool in_f;
 	uint32_t v;
 	int nf, nj;
@@ -187,9 +158,8 @@ __global__ __launch_bounds__(64 * DD_WAVES) void sd_dfm_diversity_unit_kernel(
 	if (lane == 0) status[k] = st;
 }
 
-void sd_launch_dfm_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
-	hipStream_t stream)
+void sd_launch_dfm_diversity_unit(const SdDivUnitArgs &a)
 {
-	hipLaunchKernelGGL(sd_dfm_diversity_unit_kernel, dim3((n + DD_WAVES - 1) / DD_WAVES), dim3(64 * DD_WAVES), 0, stream,
-		copies, n_copies, n, out, status);
+	hipLaunchKernelGGL(sd_dfm_diversity_unit_kernel, dim3((a.n + DV_WAVES - 1) / DV_WAVES), dim3(64 * DV_WAVES), 0, a.stream,
+		a.copies, a.n_copies, a.n, a.out, a.status);
 }

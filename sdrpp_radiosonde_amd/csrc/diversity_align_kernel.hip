@@ -17,7 +17,9 @@
 // a member's candidates: recs[0 .. cnt) are its records of this submit, index cnt is its carried record
 struct AlMember { SondeFrame *recs; const SondeFrame *carried; uint32_t cnt; };
 
-// The two predicates of the step depend on the group's kind (SdDivGroup.kind; wave-uniform).  RS41 (SPEC 3.3k): good = len 320 or 518 and
+// The two predicates of the step depend on the group's kind (SdDivGroup.kind; wave-uniform).  al_good says per kind what
+// sd_diversity_scan.h says as dv_len_ok && !dv_failed: the step keeps its own statement, one branch on the kind, so that its code
+// object stays what it was (profiles/diversity_walk_notes.md).  RS41 (SPEC 3.3k): good = len 320 or 518 and
 // both nerr >= 0, the same frame = data[8 .. len) identical.  M10 / M20 and MRZ-N1 (SPEC 3.3l): good = a length of the type and
 // nerr[0] >= 0 (nerr[1] counts Manchester violations there), the same frame = data[0 .. len) identical.  DFM (SPEC 3.3m): good = len 33
 // and nerr[1] == 0 (no word the first pass gave up on; nerr[0] counts corrected words), the same frame = data[0 .. 33) identical.
@@ -162,11 +164,10 @@ template <bool OTHER_KINDS> __global__ __launch_bounds__(64) void sd_diversity_a
 	al_group(OTHER_KINDS ? (uint32_t)AL_U(G->kind) : (uint32_t)SONDE_RS41, M, nm, states + g, mode, lane);
 }
 
-void sd_launch_diversity_align(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
-	const SdDivGroup *groups, const SondeFrame *carried, SdDivState *states, uint32_t mode, uint32_t other_kinds)
+void sd_launch_diversity_align(const SdDivArgs &a, uint32_t mode)
 {
-	if (other_kinds) hipLaunchKernelGGL(sd_diversity_align_kernel<true>, dim3(n_groups), dim3(64), 0, stream, frames, counts, max_frames, groups, carried, states, mode);
-	else hipLaunchKernelGGL(sd_diversity_align_kernel<false>, dim3(n_groups), dim3(64), 0, stream, frames, counts, max_frames, groups, carried, states, mode);
+	const auto kernel = a.other_kinds ? sd_diversity_align_kernel<true> : sd_diversity_align_kernel<false>;
+	hipLaunchKernelGGL(kernel, dim3(a.n_groups), dim3(64), 0, a.stream, a.frames, a.counts, a.max_frames, a.groups, a.carried, a.states, mode);
 }
 
 // ---- test introspection: the align step alone on caller-made records (sonde_batch_test_diversity_align: RS41;

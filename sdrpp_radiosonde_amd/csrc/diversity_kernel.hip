@@ -3,9 +3,10 @@
 // codewords a partner decoded, blocks whose CRC passes in any copy, bytes the copies agree on; what is left is erased, and RS(255,231)
 // fills up to 24 erased bytes per codeword (sd_rsee.h).  The result is taken only if both codewords and every block CRC of its own
 // chain pass.
-//   one 64-lane wave per group, four waves per workgroup (the GF tables are staged once per workgroup, as in rescue_kernel.hip).  Lanes
-//   scan the members' record headers for the next record to visit and for its partners; one lane per candidate (length, copy) checks
-//   the block CRCs of the walk; the decoder is the wave-wide one of sd_rsee.h.
+//   one 64-lane wave per group, four waves per workgroup (the GF tables are staged once per workgroup, as in rescue_kernel.hip).  The
+//   loop over a group -- the next failed record, its partners, the counters, the carried records -- is dv_walk of sd_diversity_scan.h,
+//   shared with the other three combining kernels; this file is its pass DvPass: the copies in LDS, steps 3 to 8.  One lane per
+//   candidate (length, copy) checks the block CRCs of the chain walk; the decoder is the wave-wide one of sd_rsee.h.
 // Runs behind every other kernel of the submit, on the stream where the submit completes, and rewrites records in place.  What one
 // lane wrote to a record and another reads later (a rewritten record's nerr, the carried copy) is ordered by a fence and read with
 // agent-scope loads.  Vector stores only.
@@ -16,7 +17,6 @@
 #include "sd_diversity_scan.h"
 #include "launch.h"
 
-#define DV_WAVES 4
 constexpr int DV_DATA_WORDS = SONDE_FRAME_MAX / 4;
 
 struct DivLds {                    // one per wave: 5.7 KB
@@ -193,82 +193,51 @@ __device__ __forceinline__ void dv_stage_tabs(FramerTabs &tabs, GfSwar &swar, co
 	__syncthreads();
 }
 
-// OTHER_KINDS = false: every group of the table is RS41 and the kind word is not read; true: the table has groups of SPEC 3.3l, which
-// are check_diversity_kernel.hip's.  The host launches the one that fits the table.
-template <bool OTHER_KINDS> __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(
-	const uint8_t *__restrict__ gf_exp, const uint8_t *__restrict__ gf_log, const uint32_t *__restrict__ gf_swar,
-	SondeFrame *frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const SdDivGroup *__restrict__ groups, const SdDivState *states, uint32_t n_groups, uint32_t window, SondeFrame *carried,
-	uint32_t *counters /* [n_groups][2] */)
+// The RS41 pass of the walk (sd_diversity_scan.h): the copies and their nerr live in the wave's LDS slots, which every visit reuses.
+// OTHER_KINDS = false: every group of the table is RS41 and the kind word is not read; true: the table has groups of the other kinds,
+// which are the other combining kernels'.  The host launches the one that fits the table.
+template <bool OTHER_KINDS> struct DvPass {
+	const FramerTabs &tabs; DivLds &s;
+	static constexpr uint32_t nerr = 3;
+	GfSwar swar;                   // by value: a reference would hide from the inliner that the decoder's argument is this kernel's own
+	__device__ __forceinline__ bool takes(const SdDivGroup *G, uint32_t &kind) const
+	{
+		kind = SONDE_RS41;
+		return !OTHER_KINDS || DV_U(G->kind) == SONDE_RS41;
+	}
+	__device__ __forceinline__ int flen(const SondeFrame *fr) const { return DV_U(fr->len); }
+	__device__ __forceinline__ void copy(int K, const SondeFrame *f, int n0, int n1, int lane)
+	{
+		if (lane == 0) { s.nerr[K][0] = n0; s.nerr[K][1] = n1; }
+		dv_copy_frame(s.cp[K], f->data, lane);
+	}
+	__device__ __forceinline__ void partner(int K, const SondeFrame *pf, uint32_t, int n0, int n1, int, int lane) { copy(K, pf, n0, n1, lane); }
+	__device__ __forceinline__ int attempt(SondeFrame *fr, uint32_t, int K, int flen, int lane)
+	{
+		copy(0, fr, fr->nerr[0], fr->nerr[1], lane);
+		WAVE_SYNC();
+		int cnt0 = 0, cnt1 = 0;
+		if (dv_combine(tabs, s, K, flen, lane, swar, cnt0, cnt1) <= 0) return DV_TRIED;
+		dv_write_record(s, fr, K, flen, cnt0, cnt1, lane);
+		return DV_COMBINED;
+	}
+	__device__ __forceinline__ void sync() const { WAVE_SYNC(); }
+};
+
+template <bool OTHER_KINDS> __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_kernel(SdDivWalk a,
+	const uint8_t *__restrict__ gf_exp, const uint8_t *__restrict__ gf_log, const uint32_t *__restrict__ gf_swar)
 {
 	__shared__ __attribute__((aligned(16))) FramerTabs tabs;
 	__shared__ __attribute__((aligned(16))) DivLds wl[DV_WAVES];
-	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-	GfSwar swar;
-	dv_stage_tabs(tabs, swar, gf_exp, gf_log, gf_swar, tid);
-	const uint32_t g = DV_WAVES * blockIdx.x + (uint32_t)w;
-	if (g >= n_groups) return;
-	DivLds &s = wl[w];
-	const SdDivGroup *G = groups + g;
-	if (OTHER_KINDS && DV_U(G->kind) != SONDE_RS41) return;
-	DvMembers M;                                   // the members, steps 1 and 2 and the carried records: sd_diversity_scan.h
-	dv_members(M, frames, counts, max_frames, G, states + g);
-	const int nm = M.nm;
-
-	// ---- steps 1 and 2: the failed records in ascending (t, member)
-	uint32_t tried = 0, combined = 0;
-	int64_t last_t = INT64_MIN, t_r;
-	int last_m = -1;
-	uint32_t bk;
-	while (dv_next_failed(M, SONDE_RS41, lane, last_t, last_m, t_r, bk)) {
-		const int m_r = (int)(bk >> 16);
-		SondeFrame *fr = M.rec_of(m_r, bk & 0xFFFFu);
-		const int flen = DV_U(fr->len);
-		// partners: in every other member the nearest record of the same length within the window, this submit's or the carried one
-		int K = 1;
-		bool any_good = false;
-#pragma unroll
-		for (int b = 0; b < SD_DIV_MAX; b++) {
-			if (b >= nm || b == m_r || any_good || !((M.lockmask >> b) & 1u)) continue;
-			const SondeFrame *pf = dv_partner(M, b, flen, t_r, window, carried + (size_t)SD_DIV_MAX * g + b, lane);
-			if (!pf) continue;
-			const int pn0 = DV_U(dv_load_fresh(reinterpret_cast<const uint32_t *>(&pf->nerr[0])));
-			const int pn1 = DV_U(dv_load_fresh(reinterpret_cast<const uint32_t *>(&pf->nerr[1])));
-			if (pn0 >= 0 && pn1 >= 0) { any_good = true; continue; }
-			// a partner that is not good has not been rewritten: its data are as recorded
-			if (lane == 0) { s.nerr[K][0] = pn0; s.nerr[K][1] = pn1; }
-			dv_copy_frame(s.cp[K], pf->data, lane);
-			K++;
-		}
-		if (K == 1 || any_good) { WAVE_SYNC(); continue; }      // no partner, or the group has a good copy already: stays as recorded
-		tried++;
-		if (lane == 0) { s.nerr[0][0] = fr->nerr[0]; s.nerr[0][1] = fr->nerr[1]; }
-		dv_copy_frame(s.cp[0], fr->data, lane);
-		WAVE_SYNC();
-		int cnt0 = 0, cnt1 = 0;
-		const int st = dv_combine(tabs, s, K, flen, lane, swar, cnt0, cnt1);
-		if (st > 0) {
-			dv_write_record(s, fr, K, flen, cnt0, cnt1, lane);
-			combined++;
-			__threadfence();
-		}
-		WAVE_SYNC();
-	}
-
-	// ---- the carried records: each member's newest record of this submit with a frame length, as the pass left it
-	__threadfence();
-	WAVE_SYNC();
-	dv_carry(M, SONDE_RS41, carried + (size_t)SD_DIV_MAX * g, lane);
-	if (lane == 0 && (tried | combined)) { counters[2 * g] += tried; counters[2 * g + 1] += combined; }
+	DvPass<OTHER_KINDS> pass = { tabs, wl[threadIdx.x >> 6], {} };
+	dv_stage_tabs(tabs, pass.swar, gf_exp, gf_log, gf_swar, threadIdx.x);
+	dv_walk(a, pass);
 }
 
-void sd_launch_diversity(uint32_t n_groups, hipStream_t stream, const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar,
-	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, const SdDivState *states, uint32_t window,
-	SondeFrame *carried, uint32_t *counters, uint32_t other_kinds)
+void sd_launch_diversity(const SdDivArgs &a)
 {
-	const dim3 grid((n_groups + DV_WAVES - 1) / DV_WAVES), block(64 * DV_WAVES);
-	if (other_kinds) hipLaunchKernelGGL(sd_diversity_kernel<true>, grid, block, 0, stream, gf_exp, gf_log, gf_swar, frames, counts, max_frames, groups, states, n_groups, window, carried, counters);
-	else hipLaunchKernelGGL(sd_diversity_kernel<false>, grid, block, 0, stream, gf_exp, gf_log, gf_swar, frames, counts, max_frames, groups, states, n_groups, window, carried, counters);
+	if (a.other_kinds) dv_launch(sd_diversity_kernel<true>, a, a.fec.gfexp, a.fec.gflog, a.fec.gfswar);
+	else dv_launch(sd_diversity_kernel<false>, a, a.fec.gfexp, a.fec.gflog, a.fec.gfswar);
 }
 
 // ---- a restarted group (sonde_batch_restart_channels lists all its members): no carried records, counters zero, the align step's
@@ -307,30 +276,26 @@ __global__ __launch_bounds__(64 * DV_WAVES) void sd_diversity_unit_kernel(
 {
 	__shared__ __attribute__((aligned(16))) FramerTabs tabs;
 	__shared__ __attribute__((aligned(16))) DivLds wl[DV_WAVES];
-	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+	const int lane = threadIdx.x & 63;
 	GfSwar swar;
-	dv_stage_tabs(tabs, swar, gf_exp, gf_log, gf_swar, tid);
-	const uint32_t k = DV_WAVES * blockIdx.x + (uint32_t)w;
-	if (k >= n) return;
-	DivLds &s = wl[w];
+	dv_stage_tabs(tabs, swar, gf_exp, gf_log, gf_swar, threadIdx.x);
+	uint32_t k;
+	if (!dv_unit_case(k, n, copies, SD_DIV_MAX, out, lane)) return;
+	DivLds &s = wl[threadIdx.x >> 6];
 	const SondeFrame *cps = copies + (size_t)SD_DIV_MAX * k;
 	const int K = DV_U(n_copies[k]), flen = DV_U(cps[0].len);
 	for (int j = 0; j < K; j++) {
 		dv_copy_frame(s.cp[j], cps[j].data, lane);
 		if (lane < 2) s.nerr[j][lane] = cps[j].nerr[lane];
 	}
-	// out = copy 0, in memory before the result is written over it (other lanes write the same words then)
-	for (int i = lane; i < DV_REC_WORDS; i += 64) reinterpret_cast<uint32_t *>(out + k)[i] = reinterpret_cast<const uint32_t *>(cps)[i];
-	__threadfence();
 	WAVE_SYNC();
 	int cnt0 = 0, cnt1 = 0;
 	const int st = dv_combine(tabs, s, K, flen, lane, swar, cnt0, cnt1);
 	if (st > 0) dv_write_record(s, out + k, K, flen, cnt0, cnt1, lane);
 	if (lane == 0) status[k] = st;
 }
-void sd_launch_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
-	const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar, hipStream_t stream)
+void sd_launch_diversity_unit(const SdDivUnitArgs &a)
 {
-	hipLaunchKernelGGL(sd_diversity_unit_kernel, dim3((n + DV_WAVES - 1) / DV_WAVES), dim3(64 * DV_WAVES), 0, stream,
-		gf_exp, gf_log, gf_swar, copies, n_copies, n, out, status);
+	hipLaunchKernelGGL(sd_diversity_unit_kernel, dim3((a.n + DV_WAVES - 1) / DV_WAVES), dim3(64 * DV_WAVES), 0, a.stream,
+		a.fec.gfexp, a.fec.gflog, a.fec.gfswar, a.copies, a.n_copies, a.n, a.out, a.status);
 }

@@ -6,7 +6,8 @@
 // from the partners that accepted it, if every copy that rejected it lies within 5 bits of that codeword; a block rejected in every
 // copy is the bitwise majority of the received blocks, the positions without a majority (at most 6) tried both ways.  A frame is
 // rewritten only if every rejected block decodes, and only if the copies agree on their accepted blocks (the pairing guard).
-//   one 64-lane wave per group, four waves per workgroup.  The record search is the RS41 pass's (sd_diversity_scan.h).  Lane 12 j + L
+//   one 64-lane wave per group, four waves per workgroup.  The loop over a group is dv_walk of sd_diversity_scan.h; this file is its
+//   pass IdPass, whose attempt begins with step 3 and leaves a record uncounted where the chips do not serve.  Lane 12 j + L
 //   (48 lanes) rebuilds block L of copy j and holds its syndromes, verdict and codeword; the block sets A, D, F are ballots; for a block
 //   rejected everywhere the 64 lanes are the hypotheses, as in iq_decode_block.  LDS: each wave's own copy of the 192-byte GF(2^6) table.
 // Runs behind every other kernel of the submit (SONDE_FLAG_IMS_RESCUE's pass included), behind the align step and the other combining
@@ -20,7 +21,6 @@
 #include "sd_ims_block.h"
 #include "launch.h"
 
-#define ID_WAVES 4
 constexpr int ID_LEN = 51;            // bytes of an iMS-100 record: 12 x 34 data bits
 constexpr int ID_MIN_AGREED = 6;      // SPEC 3.3n step 4: blocks accepted in every copy, at least
 constexpr int ID_MAX_DIFFER = 1;      // ... and of those, blocks whose codewords are not all equal, at most
@@ -152,57 +152,35 @@ __device__ __forceinline__ void id_table(uint32_t *tab, const uint8_t *__restric
 	__builtin_amdgcn_wave_barrier();
 }
 
-__global__ __launch_bounds__(64 * ID_WAVES) void sd_ims_diversity_kernel(
-	SondeFrame *frames, const uint32_t *__restrict__ counts, uint32_t max_frames,
-	const SdDivGroup *__restrict__ groups, const SdDivState *states, uint32_t n_groups, uint32_t window, SondeFrame *carried,
-	uint32_t *counters /* [n_groups][2] */, const SdChanState *__restrict__ chan_states, const uint32_t *__restrict__ bitring,
-	uint32_t ring_words, const uint8_t *__restrict__ g64)
-{
-	__shared__ uint32_t s_g64[ID_WAVES][48];
-	const int lane = threadIdx.x & 63;
-	const uint32_t g = ID_WAVES * blockIdx.x + (threadIdx.x >> 6);
-	if (g >= n_groups) return;
-	const SdDivGroup *G = groups + g;
-	if ((uint32_t)DV_U(G->kind) != SONDE_IMS100) return;       // the other kinds: diversity_kernel.hip and its siblings
-	uint32_t *const tab = s_g64[threadIdx.x >> 6];
-	id_table(tab, g64, lane);
-	const uint8_t *g_exp = reinterpret_cast<const uint8_t *>(tab), *g_log = g_exp + 128;
-	DvMembers M;
-	dv_members(M, frames, counts, max_frames, G, states + g);
-	const int j_mine = lane / IQ_BLOCKS, L_mine = lane - IQ_BLOCKS * j_mine;
-
-	// ---- steps 1 and 2 (sd_diversity_scan.h): the failed records in ascending (t, member), each with its partners
-	uint32_t tried = 0, combined = 0;
-	int64_t last_t = INT64_MIN, t_r;
-	int last_m = -1;
-	uint32_t bk;
-	while (dv_next_failed(M, SONDE_IMS100, lane, last_t, last_m, t_r, bk)) {
-		const int m_r = (int)(bk >> 16);
-		SondeFrame *fr = M.rec_of(m_r, bk & 0xFFFFu);
-		// the copies: r first, then the failed partners in member order -- each its channel, where its frame begins, its nerr[1]
-		uint32_t c_ch[SD_DIV_MAX] = { m_r == 0 ? M.ch[0] : m_r == 1 ? M.ch[1] : m_r == 2 ? M.ch[2] : M.ch[3], 0u, 0u, 0u };
-		uint64_t c_pos[SD_DIV_MAX] = { sd_uniform64(fr->bitpos), 0ull, 0ull, 0ull };
-		int c_bad[SD_DIV_MAX] = { DV_U(dv_load_fresh(reinterpret_cast<const uint32_t *>(&fr->nerr[1]))), 0, 0, 0 };
-		int nc = 1;
-		bool any_good = false;
-#pragma unroll
-		for (int b = 0; b < SD_DIV_MAX; b++) {
-			if (b >= M.nm || b == m_r || any_good || !((M.lockmask >> b) & 1u)) continue;
-			const SondeFrame *pf = dv_partner(M, b, ID_LEN, t_r, window, carried + (size_t)SD_DIV_MAX * g + b, lane);
-			if (!pf) continue;
-			const int bad = DV_U(dv_load_fresh(reinterpret_cast<const uint32_t *>(&pf->nerr[1])));
-			if (bad == 0) { any_good = true; continue; }
-			const uint64_t pos = sd_uniform64(pf->bitpos);
-			if (nc == 1) { c_ch[1] = M.ch[b]; c_pos[1] = pos; c_bad[1] = bad; }
-			else if (nc == 2) { c_ch[2] = M.ch[b]; c_pos[2] = pos; c_bad[2] = bad; }
-			else { c_ch[3] = M.ch[b]; c_pos[3] = pos; c_bad[3] = bad; }
-			nc++;
-		}
-		if (nc == 1 || any_good) continue;         // no partner, or the group has a good copy already: stays as recorded
-
+// The pass of the walk (sd_diversity_scan.h).  A copy is where its chips are: channel, first chip, and the nerr[1] of its record
+struct IdPass {
+	const SdChanState *chan_states; const uint32_t *bitring; uint32_t ring_words;
+	const uint8_t *g_exp, *g_log;
+	uint32_t c_ch[SD_DIV_MAX];
+	uint64_t c_pos[SD_DIV_MAX];
+	int c_bad[SD_DIV_MAX];
+	static constexpr uint32_t nerr = 2;
+	__device__ __forceinline__ bool takes(const SdDivGroup *G, uint32_t &kind) const
+	{
+		kind = SONDE_IMS100;
+		return (uint32_t)DV_U(G->kind) == SONDE_IMS100;
+	}
+	__device__ __forceinline__ int flen(const SondeFrame *) const { return ID_LEN; }
+	__device__ __forceinline__ void partner(int K, const SondeFrame *pf, uint32_t ch, int, int bad, int, int)
+	{
+		dv_set_copy(c_ch, K, ch);
+		dv_set_copy(c_pos, K, (uint64_t)sd_uniform64(pf->bitpos));
+		dv_set_copy(c_bad, K, bad);
+	}
+	// the copies: r first, then the failed partners in member order
+	__device__ __forceinline__ int attempt(SondeFrame *fr, uint32_t ch, int nc, int, int lane)
+	{
+		c_ch[0] = ch; c_pos[0] = sd_uniform64(fr->bitpos);
+		c_bad[0] = DV_U(dv_load_fresh(reinterpret_cast<const uint32_t *>(&fr->nerr[1])));
 		// ---- 3. lane 12 j + L: block L of copy j from the chips of its channel's ring, and the first pass's verdict on it
-		const uint32_t my_ch = j_mine == 0 ? c_ch[0] : j_mine == 1 ? c_ch[1] : j_mine == 2 ? c_ch[2] : c_ch[3];
-		const uint64_t my_pos = j_mine == 0 ? c_pos[0] : j_mine == 1 ? c_pos[1] : j_mine == 2 ? c_pos[2] : c_pos[3];
+		const int j_mine = lane / IQ_BLOCKS, L_mine = lane - IQ_BLOCKS * j_mine;
+		const uint32_t my_ch = dv_copy_of(c_ch, j_mine);
+		const uint64_t my_pos = dv_copy_of(c_pos, j_mine);
 		uint64_t blk = 0, cw = 0;
 		bool rej = false, held = false;
 		if (j_mine < nc) {
@@ -221,46 +199,44 @@ __global__ __launch_bounds__(64 * ID_WAVES) void sd_ims_diversity_kernel(
 		uint32_t valid = 0;
 #pragma unroll
 		for (int j = 0; j < SD_DIV_MAX; j++)         // a copy takes part if its chips are held and they say what its record says
-			if (j < nc && ((heldm >> (IQ_BLOCKS * j)) & 1ull) && __popcll((rejm >> (IQ_BLOCKS * j)) & 0xFFFull) == c_bad[j]) valid |= 1u << j;
-		if (!(valid & 1u) || __popc(valid) < 2) continue;      // r itself, or fewer than two copies: stays as recorded, not counted
-		tried++;
+			if (j < nc && ((heldm >> (IQ_BLOCKS * j)) & 1ull) && __popcll((rejm >> (IQ_BLOCKS * j)) & 0xFFFull) == dv_copy_of(c_bad, j)) valid |= 1u << j;
+		if (!(valid & 1u) || __popc(valid) < 2) return DV_SKIPPED;      // r itself, or fewer than two copies: stays as recorded, not counted
 		unsigned long long fm;
 		uint64_t v;
 		int add, nj;
 		const int st = id_combine(valid, blk, rej, cw, lane, g_exp, g_log, fm, v, add, nj);
-		if (st > 0) {
-			id_write_record(fr, st, fm, v, add, nj, lane);
-			combined++;
-			__threadfence();
-		}
+		if (st <= 0) return DV_TRIED;
+		id_write_record(fr, st, fm, v, add, nj, lane);
+		return DV_COMBINED;
 	}
+	__device__ __forceinline__ void sync() const {}
+};
 
-	// ---- the carried records: each member's newest record of this submit with the frame length, as the pass left it
-	__threadfence();
-	dv_carry(M, SONDE_IMS100, carried + (size_t)SD_DIV_MAX * g, lane);
-	if (lane == 0 && (tried | combined)) { counters[2 * g] += tried; counters[2 * g + 1] += combined; }
-}
-
-void sd_launch_ims_diversity(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
-	const SdDivGroup *groups, const SdDivState *states, uint32_t window, SondeFrame *carried, uint32_t *counters,
-	const SdChanState *chan_states, const uint32_t *bitring, uint32_t ring_words, const uint8_t *g64)
+__global__ __launch_bounds__(64 * DV_WAVES) void sd_ims_diversity_kernel(SdDivWalk a, const SdChanState *__restrict__ chan_states,
+	const uint32_t *__restrict__ bitring, uint32_t ring_words, const uint8_t *__restrict__ g64)
 {
-	hipLaunchKernelGGL(sd_ims_diversity_kernel, dim3((n_groups + ID_WAVES - 1) / ID_WAVES), dim3(64 * ID_WAVES), 0, stream,
-		frames, counts, max_frames, groups, states, n_groups, window, carried, counters, chan_states, bitring, ring_words, g64);
+	__shared__ uint32_t s_g64[DV_WAVES][48];
+	uint32_t *const tab = s_g64[threadIdx.x >> 6];
+	id_table(tab, g64, threadIdx.x & 63);
+	const uint8_t *g_exp = reinterpret_cast<const uint8_t *>(tab);
+	IdPass pass = { chan_states, bitring, ring_words, g_exp, g_exp + 128, { 0u, 0u, 0u, 0u }, { 0ull, 0ull, 0ull, 0ull }, { 0, 0, 0, 0 } };
+	dv_walk(a, pass);
 }
+
+void sd_launch_ims_diversity(const SdDivArgs &a) { dv_launch(sd_ims_diversity_kernel, a, a.chan_states, a.bitring, a.ring_words, a.fec.g64); }
 
 // ---- test introspection: steps 4 to 7 alone on caller-made cases (sonde_batch_test_ims_combine).  One wave per case: copy 0's record,
 // n_copies and the copies' received blocks [SD_DIV_MAX][12] (bit b of a block = coefficient 45 - b).  The host has checked n_copies
 // (2..4), the record's type and len and that it has failed.  status 0: the record's nerr[1] is not the number of blocks the first pass
 // rejects among copy 0's (SPEC step 3: the record stays, nothing is tried).
-__global__ __launch_bounds__(64 * ID_WAVES) void sd_ims_diversity_unit_kernel(
+__global__ __launch_bounds__(64 * DV_WAVES) void sd_ims_diversity_unit_kernel(
 	const SondeFrame *__restrict__ records, const uint32_t *__restrict__ n_copies, const uint64_t *__restrict__ blocks, uint32_t n,
 	SondeFrame *out, int32_t *__restrict__ status, const uint8_t *__restrict__ g64)
 {
-	__shared__ uint32_t s_g64[ID_WAVES][48];
+	__shared__ uint32_t s_g64[DV_WAVES][48];
 	const int lane = threadIdx.x & 63;
-	const uint32_t k = ID_WAVES * blockIdx.x + (threadIdx.x >> 6);
-	if (k >= n) return;
+	uint32_t k;
+	if (!dv_unit_case(k, n, records, 1, out, lane)) return;
 	uint32_t *const tab = s_g64[threadIdx.x >> 6];
 	id_table(tab, g64, lane);
 	const uint8_t *g_exp = reinterpret_cast<const uint8_t *>(tab), *g_log = g_exp + 128;
@@ -275,9 +251,6 @@ __global__ __launch_bounds__(64 * ID_WAVES) void sd_ims_diversity_unit_kernel(
 		rej = iq_first_pass<true>(s1, s3, g_exp, g_log, e);
 		cw = rej ? blk : blk ^ e;
 	}
-	// out = copy 0's record, in memory before the result is written over it
-	for (int i = lane; i < DV_REC_WORDS; i += 64) reinterpret_cast<uint32_t *>(out + k)[i] = reinterpret_cast<const uint32_t *>(records + k)[i];
-	__threadfence();
 	int st = 0;
 	if (__popcll(__ballot(rej) & 0xFFFull) == DV_U(records[k].nerr[1])) {
 		unsigned long long fm;
@@ -289,9 +262,8 @@ __global__ __launch_bounds__(64 * ID_WAVES) void sd_ims_diversity_unit_kernel(
 	if (lane == 0) status[k] = st;
 }
 
-void sd_launch_ims_diversity_unit(const SondeFrame *records, const uint32_t *n_copies, const uint64_t *blocks, uint32_t n, SondeFrame *out,
-	int32_t *status, const uint8_t *g64, hipStream_t stream)
+void sd_launch_ims_diversity_unit(const SdDivUnitArgs &a)
 {
-	hipLaunchKernelGGL(sd_ims_diversity_unit_kernel, dim3((n + ID_WAVES - 1) / ID_WAVES), dim3(64 * ID_WAVES), 0, stream,
-		records, n_copies, blocks, n, out, status, g64);
+	hipLaunchKernelGGL(sd_ims_diversity_unit_kernel, dim3((a.n + DV_WAVES - 1) / DV_WAVES), dim3(64 * DV_WAVES), 0, a.stream,
+		a.copies, a.n_copies, a.blocks, a.n, a.out, a.status, a.fec.g64);
 }

@@ -129,7 +129,7 @@ void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status
 
 // sonde_batch_set_diversity (DESIGN SPEC 3.3j, 3.3l, 3.3m, 3.3n): a group = 2..4 channels of one type that hear the same sonde; ch[m] and
 // off[m] (offset_bits) per member, kind = the members' type: SONDE_RS41 (0: diversity_kernel.hip), SONDE_M10 or SONDE_MRZN1
-// (check_diversity_kernel.hip), SONDE_DFM09 (dfm_diversity_kernel.hip), SONDE_IMS100 (ims_diversity_kernel.hip; SONDE_FLAG_IMS_DIVERSITY).  Each combining kernel is launched over the whole table and takes the groups of its kinds; the align
+// (check_diversity_kernel.hip), SONDE_DFM09 (dfm_diversity_kernel.hip), SONDE_IMS100 (ims_diversity_kernel.hip; SONDE_FLAG_IMS_DIVERSITY).  Each combining kernel (one row of k_div_passes, batch_impl.h) is launched over the whole table and takes the groups of its kinds; the align
 // step, the carried records, the counters and the state are one space for all kinds.  carried: [n_groups][SD_DIV_MAX] records
 // (len = 0: none), counters: [n_groups][2] (tried, combined); both carried from submit to submit.  The launches stand behind every
 // other kernel of the submit.
@@ -140,54 +140,46 @@ struct SdDivGroup { uint32_t n; uint32_t ch[SD_DIV_MAX]; uint32_t kind; int64_t 
 // member (an unlocked member is to the combining pass a member without records), learned / duplicates = the step's counters.  Without
 // the step (mode 0) off is the host's and every member is locked, for good.
 struct SdDivState { int64_t off[SD_DIV_MAX]; uint32_t locked, learned, duplicates, pad; };
-void sd_launch_diversity(uint32_t n_groups, hipStream_t stream, const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar,
-	SondeFrame *frames, const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, const SdDivState *states, uint32_t window,
-	SondeFrame *carried, uint32_t *counters, uint32_t other_kinds /* the table has groups that are not RS41 */);
+// THE COMBINING PASSES (DESIGN "what a combining pass plugs into"; batch_impl.h k_div_passes): what a launcher may need; each picks
+// what its kernel takes
+struct SdDivArgs {
+	uint32_t n_groups; hipStream_t stream;
+	const SdDivGroup *groups; SdDivState *states; SondeFrame *carried; uint32_t *counters;
+	uint32_t window;                       // of the pass that is launched: the caller's, or the pass's default
+	uint32_t other_kinds;                  // the table has groups that are not RS41: the RS41 kernels read the kind word
+	SondeFrame *frames; const uint32_t *counts; uint32_t max_frames;
+	SdFecTables fec;
+	const uint16_t *mrztab;                // MRZ-N1's column table (null: the table has no MRZ-N1 group)
+	const SdChanState *chan_states; const uint32_t *bitring; uint32_t ring_words;      // iMS-100 reads the copies' blocks from the chips
+};
+void sd_launch_diversity(const SdDivArgs &a);                 // RS41 (diversity_kernel.hip, DESIGN SPEC 3.3j)
+void sd_launch_check_diversity(const SdDivArgs &a);           // M10 / M20 / MRZ-N1 (check_diversity_kernel.hip, 3.3l)
+void sd_launch_dfm_diversity(const SdDivArgs &a);             // DFM (dfm_diversity_kernel.hip, 3.3m)
+void sd_launch_ims_diversity(const SdDivArgs &a);             // iMS-100, SONDE_FLAG_IMS_DIVERSITY (ims_diversity_kernel.hip, 3.3n)
+// the align step, one launch in front of the passes when mode != 0 (SONDE_DIVERSITY_LEARN | SONDE_DIVERSITY_MARK_DUPLICATES)
+void sd_launch_diversity_align(const SdDivArgs &a, uint32_t mode);
 // the groups of the listed channels back to "no carried record, counters zero, offsets and locks as set_diversity left them"
 // (unlocked_start: the members of a group start unlocked); slot_of[channel] = SD_DIV_MAX * group + member or -1
 void sd_launch_diversity_clear(uint32_t n, hipStream_t stream, const uint32_t *list, const int32_t *slot_of, SondeFrame *carried, uint32_t *counters,
 	const SdDivGroup *groups, SdDivState *states, uint32_t unlocked_start);
-// the align step, one launch in front of sd_launch_diversity when mode != 0 (SONDE_DIVERSITY_LEARN | SONDE_DIVERSITY_MARK_DUPLICATES)
-void sd_launch_diversity_align(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
-	const SdDivGroup *groups, const SondeFrame *carried, SdDivState *states, uint32_t mode, uint32_t other_kinds);
 // the align step alone: n cases of SD_DIV_MAX members with max_rec record slots each (records[(4 k + m) * max_rec + i], counts[4 k + m]
 // in use, n_members[k] = 2..4), carried[4 k + m] (len 0: none), states[k] in and out, modes[k]; all device memory.  kind: the sonde type
 // whose predicates the step uses (SdDivGroup.kind)
 void sd_launch_diversity_align_unit(uint32_t n, hipStream_t stream, SondeFrame *records, const uint32_t *counts, uint32_t max_rec,
 	const uint32_t *n_members, const SondeFrame *carried, SdDivState *states, const uint32_t *modes, uint32_t kind);
-// steps 3 to 7 of SPEC 3.3j alone: n cases of SD_DIV_MAX copies each (device memory; n_copies[i] of them in use, copy 0 the record to
-// rewrite); out[i] = copy 0, rewritten or not; status = copies used, -1 too many erasures, -2 no decode, -3 rejected
-void sd_launch_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
-	const uint8_t *gf_exp, const uint8_t *gf_log, const uint32_t *gf_swar, hipStream_t stream);
-
-// the combining pass of SPEC 3.3l over the M10 / M20 / MRZ-N1 groups of the table (check_diversity_kernel.hip); launched only when the
-// batch has such a group.  m10tab / mrztab: the column tables of SPEC 3.3f
-void sd_launch_check_diversity(uint32_t n_groups, hipStream_t stream, const uint16_t *m10tab, const uint16_t *mrztab, SondeFrame *frames,
-	const uint32_t *counts, uint32_t max_frames, const SdDivGroup *groups, const SdDivState *states, uint32_t window, SondeFrame *carried,
-	uint32_t *counters);
-// steps 3 to 6 of SPEC 3.3l alone, the shape of sd_launch_diversity_unit: status = copies used, -1 not attempted, -2 none fits,
-// -3 several fit
-void sd_launch_check_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
-	const uint16_t *m10tab, const uint16_t *mrztab, hipStream_t stream);
-
-// the combining pass of SPEC 3.3m over the DFM groups of the table (dfm_diversity_kernel.hip); launched only when the batch has one
-void sd_launch_dfm_diversity(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
-	const SdDivGroup *groups, const SdDivState *states, uint32_t window, SondeFrame *carried, uint32_t *counters);
-// steps 3 to 6 of SPEC 3.3m alone, the shape of sd_launch_diversity_unit: status = copies used, -1 the pairing guard refuses, -2 a word
-// has no solution, -3 a word has several
-void sd_launch_dfm_diversity_unit(const SondeFrame *copies, const uint32_t *n_copies, uint32_t n, SondeFrame *out, int32_t *status,
-	hipStream_t stream);
-
-// the combining pass of SPEC 3.3n over the iMS-100 groups of the table (ims_diversity_kernel.hip); launched only when the batch has one.
-// It reads the copies' blocks from the chips: the channel states (wpos), the bit ring and its words per channel, and the GF(2^6) table
-void sd_launch_ims_diversity(uint32_t n_groups, hipStream_t stream, SondeFrame *frames, const uint32_t *counts, uint32_t max_frames,
-	const SdDivGroup *groups, const SdDivState *states, uint32_t window, SondeFrame *carried, uint32_t *counters,
-	const SdChanState *chan_states, const uint32_t *bitring, uint32_t ring_words, const uint8_t *g64);
-// steps 4 to 7 of SPEC 3.3n alone: n cases of copy 0's record, n_copies and the copies' received blocks [SD_DIV_MAX][12] (device memory);
-// out[i] = the record, rewritten or not; status = copies used, 0 the record's nerr[1] is not what copy 0's blocks say, -1 the pairing
-// guard refuses, -2 a block has no solution, -3 a block has several
-void sd_launch_ims_diversity_unit(const SondeFrame *records, const uint32_t *n_copies, const uint64_t *blocks, uint32_t n, SondeFrame *out,
-	int32_t *status, const uint8_t *g64, hipStream_t stream);
+// A pass's rule alone (the steps behind 1 and 2): n cases of SD_DIV_MAX copies each (device memory; n_copies[i] of them in use, copy 0
+// the record to rewrite); out[i] = copy 0, rewritten or not; status[i] = copies used, or what the rule answers: RS41 -1 too many
+// erasures, -2 no decode, -3 rejected; check -1 not attempted, -2 none fits, -3 several fit; DFM and iMS-100 -1 the pairing guard
+// refuses, -2 a word / block has no solution, -3 one has several.  iMS-100: copies = n records (copy 0's alone), blocks = the copies'
+// received blocks [n][SD_DIV_MAX][12]; status 0 = the record's nerr[1] is not what copy 0's blocks say
+struct SdDivUnitArgs {
+	const SondeFrame *copies; const uint32_t *n_copies; uint32_t n; SondeFrame *out; int32_t *status;
+	SdFecTables fec; const uint16_t *mrztab; const uint64_t *blocks; hipStream_t stream;
+};
+void sd_launch_diversity_unit(const SdDivUnitArgs &a);
+void sd_launch_check_diversity_unit(const SdDivUnitArgs &a);
+void sd_launch_dfm_diversity_unit(const SdDivUnitArgs &a);
+void sd_launch_ims_diversity_unit(const SdDivUnitArgs &a);
 
 // sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);

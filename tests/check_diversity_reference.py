@@ -93,49 +93,11 @@ new_div_state = dr.new_state
 
 
 def diversity(records, groups, offsets=None, window=960, state=None):
-    """One submit.  groups: [[channel, ...], ...]; offsets: {channel: offset_bits} or a sequence indexed by channel (None: zeros).
-    outcomes[i]: 'other' (not visited), 'good', 'no_partner', 'partner_good', 'combined', 'not_attempted', 'no_fit', 'several_fit'."""
-    state = dr.new_state(groups) if state is None else state
-    off_of = (lambda ch: 0) if offsets is None else (lambda ch: int(offsets[ch]))
-    out = records.copy()
-    outcomes = ["other"] * len(out)
-    for g, members in enumerate(groups):
-        idx = {ch: [i for i in range(len(out)) if int(out[i]["channel"]) == ch and is_frame(out[i])] for ch in members}
-        t_of = lambda i, ch: int(out[i]["bitpos"]) - off_of(ch)             # noqa: E731
-        # 1. visit in ascending t, ties in member order
-        for t_r, m_r, i in sorted((t_of(i, ch), m, i) for m, ch in enumerate(members) for i in idx[ch]):
-            r = out[i]
-            if not failed(r):
-                outcomes[i] = "good"
-                continue
-            # 2. partners: the nearest candidate of the same len within the window, this submit's or the carried one
-            partners = []
-            for m, ch in enumerate(members):
-                if m == m_r:
-                    continue
-                cands = [out[j] for j in idx[ch]]
-                if ch in state["carried"]:
-                    cands.append(state["carried"][ch])
-                cands = [c for c in cands if int(c["len"]) == int(r["len"]) and abs(int(c["bitpos"]) - off_of(ch) - t_r) <= window]
-                if cands:
-                    partners.append(min(cands, key=lambda c: (abs(int(c["bitpos"]) - off_of(ch) - t_r), int(c["bitpos"]))))
-            if not partners:
-                outcomes[i] = "no_partner"
-                continue
-            if any(not failed(p) for p in partners):
-                outcomes[i] = "partner_good"
-                continue
-            state["tried"][g] += 1
-            rec, st = combine([r] + partners)
-            outcomes[i] = STATUS.get(st, "combined")
-            if st > 0:
-                out[i] = rec
-                state["combined"][g] += 1
-        # the carried records: each member's newest record of this submit with a length of its type, as the pass left it
-        for ch in members:
-            if idx[ch]:
-                state["carried"][ch] = out[max(idx[ch], key=lambda i: int(out[i]["bitpos"]))].copy()
-    return out, outcomes, state
+    """One submit: diversity_reference.diversity on is_frame, failed, combine and STATUS above.  groups: [[channel, ...], ...]; offsets:
+    {channel: offset_bits} or a sequence indexed by channel (None: zeros).  outcomes[i]: 'other' (not visited), 'good', 'no_partner',
+    'partner_good', 'combined', 'not_attempted', 'no_fit', 'several_fit'."""
+    return dr.diversity(records, groups, offsets, window, state, is_frame=is_frame, failed=failed,
+                        attempt=lambda r, partners: combine([r] + partners), status=STATUS)
 
 
 restart_div_group = dr.restart_group
@@ -154,54 +116,11 @@ def match(x, y):
 
 
 def align(records, groups, state, mode):
-    """diversity_align_reference.align, rule for rule, on `good` and `match` above"""
-    out = records.copy()
-    carried = state["div"]["carried"]
-    for g, members in enumerate(groups):
-        now = {ch: [i for i in range(len(out)) if int(out[i]["channel"]) == ch and good(out[i])] for ch in members}
-        old = {ch: carried[ch] for ch in members if ch in carried and good(carried[ch])}
-        if mode & LEARN:
-            for a, b in da.PAIRS:
-                if b >= len(members):
-                    continue
-                ca, cb = members[a], members[b]
-                cand_a = [out[i] for i in now[ca]] + ([old[ca]] if ca in old else [])
-                cand_b = [out[i] for i in now[cb]] + ([old[cb]] if cb in old else [])
-                hits = [(int(y["bitpos"]), int(x["bitpos"])) for x in cand_a for y in cand_b if match(x, y)]
-                if not hits:
-                    continue
-                pb, pa = max(hits)                       # the latest in b; of several, the latest in a
-                d = pb - pa
-                off, lk = state["off"], state["locked"]
-                if lk[cb] and not lk[ca]:
-                    off[ca] = off[cb] - d
-                    state["learned"][g] += 1
-                elif not (lk[ca] and lk[cb]) or off[cb] - off[ca] != d:
-                    off[cb] = off[ca] + d
-                    state["learned"][g] += 1
-                lk[ca] = lk[cb] = True
-        if mode & MARK:
-            for b, cb in enumerate(members):
-                for i in now[cb]:
-                    dup = any(match(old[ca], out[i]) for ca in members if ca != cb and ca in old)
-                    dup = dup or any(match(out[k], out[i]) for ca in members[:b] for k in now[ca])
-                    if dup:
-                        out[i]["flags"] |= FRAME_DUPLICATE
-                        state["duplicates"][g] += 1
-    return out
+    """diversity_align_reference.align on `good` and `match` above"""
+    return da.align(records, groups, state, mode, good=good, match=match)
 
 
 def run(records, groups, state, mode=LEARN | MARK, window=960):
-    """One submit as the library runs it: align, the pass over the locked members at the learned offsets, the carried records of the
-    unlocked members.  Returns (records after both steps in the same order, outcomes, state)."""
-    out = align(records, groups, state, mode)
-    lk = state["locked"]
-    locked_groups = [[ch for ch in members if lk[ch]] for members in groups]
-    out, outcomes, state["div"] = diversity(out, locked_groups, state["off"], window, state["div"])
-    for members in groups:
-        for ch in members:
-            if not lk[ch]:
-                idx = [i for i in range(len(out)) if int(out[i]["channel"]) == ch and is_frame(out[i])]
-                if idx:
-                    state["div"]["carried"][ch] = out[max(idx, key=lambda i: int(out[i]["bitpos"]))].copy()
-    return out, outcomes, state
+    """One submit as the library runs it (diversity_align_reference.run): align, the pass over the locked members at the learned
+    offsets, the carried records of the unlocked members.  Returns (records after both steps in the same order, outcomes, state)."""
+    return da.run(records, groups, state, mode, window, good=good, match=match, diversity=diversity, is_frame=is_frame)

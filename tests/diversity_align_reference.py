@@ -8,6 +8,9 @@ twin of the combining pass (tests/diversity_reference.py, which it imports and d
                                           members at the learned offsets, then the carried records of the unlocked members.
     new_state(groups, offsets, mode)      what set_diversity leaves; restart_group(state, groups, g): what a restart leaves.
 
+The step is the same for every kind of group: the twins of the other kinds call align and run with their own good and match, and run
+with their own diversity and is_frame.
+
 state: {'off': {ch: int}, 'locked': {ch: bool}, 'learned': [per group], 'duplicates': [per group], 'div': the combining twin's state
 (carried records by channel, tried / combined per group), 'initial': (offsets or None, unlocked)}."""
 from __future__ import annotations
@@ -39,7 +42,7 @@ def restart_group(state, groups, g):
 
 
 def good(r):
-    return int(r["len"]) in LENGTHS and int(r["nerr"][0]) >= 0 and int(r["nerr"][1]) >= 0
+    return dr.is_frame(r) and not dr.failed(r)
 
 
 def match(x, y):
@@ -47,7 +50,7 @@ def match(x, y):
     return n == int(y["len"]) and bytes(x["data"][8:n]) == bytes(y["data"][8:n])
 
 
-def align(records, groups, state, mode):
+def align(records, groups, state, mode, *, good=good, match=match):
     out = records.copy()
     carried = state["div"]["carried"]
     for g, members in enumerate(groups):
@@ -84,17 +87,17 @@ def align(records, groups, state, mode):
     return out
 
 
-def run(records, groups, state, mode=LEARN | MARK, window=960):
+def run(records, groups, state, mode=LEARN | MARK, window=960, *, good=good, match=match, diversity=dr.diversity, is_frame=dr.is_frame):
     """One submit.  Returns (records after both steps in the same order, the combining twin's outcomes, state)."""
-    out = align(records, groups, state, mode)
+    out = align(records, groups, state, mode, good=good, match=match)
     lk = state["locked"]
     locked_groups = [[ch for ch in members if lk[ch]] for members in groups]
     # an unlocked member is to the combining pass a member without records: it is not in the group the twin sees
-    out, outcomes, state["div"] = dr.diversity(out, locked_groups, state["off"], window, state["div"])
+    out, outcomes, state["div"] = diversity(out, locked_groups, state["off"], window, state["div"])
     for members in groups:
         for ch in members:
             if not lk[ch]:                               # its carried record is kept up to date all the same
-                idx = [i for i in range(len(out)) if int(out[i]["channel"]) == ch and int(out[i]["len"]) in LENGTHS]
+                idx = [i for i in range(len(out)) if int(out[i]["channel"]) == ch and is_frame(out[i])]
                 if idx:
                     state["div"]["carried"][ch] = out[max(idx, key=lambda i: int(out[i]["bitpos"]))].copy()
     return out, outcomes, state

@@ -6,7 +6,9 @@
     diversity(records, groups, offsets, window, state)
                                one submit: `records` are its frame records (any order), `state` carries the members' carried
                                records and the groups' counters from call to call.  Returns (records after the pass in the same
-                               order, outcomes per record, state).
+                               order, outcomes per record, state).  Steps 1 and 2 are the same for every kind of group: the twins
+                               of the other kinds (check_, dfm_ and ims_diversity_reference.py) call it with their own is_frame,
+                               failed, attempt and status names.
 
 Nothing here is shared with the library: the tests compare whole records byte for byte."""
 from __future__ import annotations
@@ -115,24 +117,37 @@ def new_state(groups):
     return {"carried": {}, "tried": [0] * len(groups), "combined": [0] * len(groups)}
 
 
-def diversity(records, groups, offsets=None, window=960, state=None):
+def is_frame(r):
+    return int(r["len"]) in LENGTHS
+
+
+def failed(r):
+    return int(r["nerr"][0]) < 0 or int(r["nerr"][1]) < 0
+
+
+STATUS = {-1: "too_many", -2: "undecodable", -3: "rejected"}
+
+
+def diversity(records, groups, offsets=None, window=960, state=None, *, is_frame=is_frame, failed=failed,
+              attempt=lambda r, partners: combine([r] + partners), status=STATUS):
     """One submit.  groups: [[channel, ...], ...]; offsets: {channel: offset_bits} or a sequence indexed by channel (None: zeros).
-    outcomes[i]: 'other' (not visited), 'good', 'no_partner', 'partner_good', 'combined', 'too_many', 'undecodable', 'rejected'."""
+    outcomes[i]: 'other' (not visited), 'good', 'no_partner', 'partner_good', 'combined', or what `status` names: 'too_many',
+    'undecodable', 'rejected'.  The kind of the groups: is_frame(r) and failed(r) on a record, attempt(r, partners) -> (record, status)
+    as combine gives them, or None: nothing is tried and the record does not count ('left_out')."""
     state = new_state(groups) if state is None else state
     off_of = (lambda ch: 0) if offsets is None else (lambda ch: int(offsets[ch]))
     out = records.copy()
     outcomes = ["other"] * len(out)
     for g, members in enumerate(groups):
-        idx = {ch: [i for i in range(len(out)) if int(out[i]["channel"]) == ch and int(out[i]["len"]) in LENGTHS] for ch in members}
+        idx = {ch: [i for i in range(len(out)) if int(out[i]["channel"]) == ch and is_frame(out[i])] for ch in members}
         t_of = lambda i, ch: int(out[i]["bitpos"]) - off_of(ch)             # noqa: E731
         # 1. visit in ascending t, ties in member order
-        order = sorted(((t_of(i, ch), m, i) for m, ch in enumerate(members) for i in idx[ch]))
-        for t_r, m_r, i in order:
+        for t_r, m_r, i in sorted((t_of(i, ch), m, i) for m, ch in enumerate(members) for i in idx[ch]):
             r = out[i]
-            if int(r["nerr"][0]) >= 0 and int(r["nerr"][1]) >= 0:
+            if not failed(r):
                 outcomes[i] = "good"
                 continue
-            # 2. partners
+            # 2. partners: the nearest candidate of the same len within the window, this submit's or the carried one
             partners = []
             for m, ch in enumerate(members):
                 if m == m_r:
@@ -146,16 +161,20 @@ def diversity(records, groups, offsets=None, window=960, state=None):
             if not partners:
                 outcomes[i] = "no_partner"
                 continue
-            if any(int(p["nerr"][0]) >= 0 and int(p["nerr"][1]) >= 0 for p in partners):
+            if any(not failed(p) for p in partners):
                 outcomes[i] = "partner_good"
                 continue
+            got = attempt(r, partners)
+            if got is None:
+                outcomes[i] = "left_out"
+                continue
             state["tried"][g] += 1
-            rec, st = combine([r] + partners)
-            outcomes[i] = {-1: "too_many", -2: "undecodable", -3: "rejected"}.get(st, "combined")
+            rec, st = got
+            outcomes[i] = status.get(st, "combined")
             if st > 0:
                 out[i] = rec
                 state["combined"][g] += 1
-        # the carried records: each member's newest record of this submit, as the pass left it
+        # the carried records: each member's newest frame record of this submit, as the pass left it
         for ch in members:
             if idx[ch]:
                 state["carried"][ch] = out[max(idx[ch], key=lambda i: int(out[i]["bitpos"]))].copy()
