@@ -10,8 +10,8 @@
 // in one wave, in program order, with no hand-over: discriminator (16-bit wrapped phase difference) + composite 12/5 resampler -
 // 4:1 decimator (SPEC 3.5b) -> LDS tile -> low-pass at the timing loop's instants, Gardner detector, slicer (SPEC 3.2, four symbols
 // per lane) -> PI loop filter -> bit ring -> sync search (K4) -> RS41: de-whitening + RS(255,231) of the frames completed in
-// this submit (K5 / K6).  The arithmetic is SPEC 3.2 / 3.3 / 3.5b to the bit: same fmaf chains, same integer statistics; frames,
-// bits and loop state equal the oracle's (tests/test_channelizer.py).
+// this submit (K5 / K6).  The arithmetic is SPEC 3.2 / 3.3 / 3.5b to the bit: the timing loop is the very functions kernel A calls
+// (sd_timing.h), not a copy of them; frames, bits and loop state equal the oracle's (tests/test_channelizer.py).
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include "sonde_dev.h"
@@ -21,6 +21,7 @@
 #include "sd_rs41.h"
 #include "sd_rsdec.h"
 #include "sd_fixed.h"
+#include "sd_timing.h"
 #include "launch.h"
 
 #define BK_WAVES 8                         // bins per workgroup
@@ -192,8 +193,7 @@ __global__ __launch_bounds__(64 * BK_WAVES, 4) void sd_bins_kernel(
 	SdSyncRun k4;                              // K4's state: registers of this wave (the list of frames: LDS)
 	auto tile_rounds = [&]() {
 		n0 += BK_IT;
-		const int64_t limit = (((n0 - 1 - BK_NT / 2 - SD_MARGIN) << 16) | 0xFFFF);
-		int K = (st.t_next <= limit) ? (int)((uint32_t)(limit - st.t_next) / (uint32_t)st.period) + 1 : 0;
+		int K = sd_tile_symbols(n0, BK_NT, st.t_next, st.period);
 		if (K > SD_ROUND_MAX) K = SD_ROUND_MAX;
 		const int64_t base = (n0 - BK_IT - SD_LH) << 16;
 		const uint32_t rel0 = (uint32_t)(st.t_next - base);
@@ -214,12 +214,10 @@ __global__ __launch_bounds__(64 * BK_WAVES, 4) void sd_bins_kernel(
 			for (int h = 0; h < 2; h++) {
 				const bool act = sd_hw_symbol(lane) + 64 * (hh + h) < K;
 				const float yy = act ? y[h] : 0.0f;
-				const float yprev = sd_hw_prev(yy, lane);
-				float e = (yprev - yy) * (m[h] - bias);
-				e = sd_clamp(e * 1024.0f, -1.0e6f, 1.0e6f);
+				const float e = sd_gardner_term(yy, m[h], sd_hw_prev(yy, lane), bias);
 				Ei += (act && lane != 0) ? __float2int_rn(e) : 0;           // the first symbol of a 64-group carries no term
 				const bool bit = act && (yy > bias);
-				const int Y = __float2int_rn(sd_clamp(yy, -8.0f, 8.0f) * 4096.0f);
+				const int Y = sd_level_term(yy);
 				S1i += bit ? Y : 0;
 				S0i += (act && !bit) ? Y : 0;
 				const unsigned long long bal = __ballot(sd_hw_unpermute(bit ? 1 : 0, lane) != 0);      // bits in symbol order
@@ -232,46 +230,19 @@ __global__ __launch_bounds__(64 * BK_WAVES, 4) void sd_bins_kernel(
 		if (K <= 0) return;
 		// ---- the round's bits into the ring (HBM) and its mirror
 		if (lane < 9) {
-			const uint32_t sh = (uint32_t)wpos & 31u, w0 = (uint32_t)(wpos >> 5);
 			uint32_t vv = 0;
-			if ((uint32_t)(32 * lane) < sh + (uint32_t)K) {
-				const uint32_t lo = w.chunk[lane + 1], pvw = w.chunk[lane];
-				vv = sh ? ((lo << sh) | (pvw >> (32u - sh))) : lo;
-				if (lane == 0 && sh) vv |= partial & ((1u << sh) - 1u);
-				const uint32_t idx = (w0 + (uint32_t)lane) & ring_mask;
+			if (sd_ring_touched(lane, wpos, K)) {
+				vv = sd_ring_word(w.chunk, lane, wpos, &partial);
+				const uint32_t idx = sd_ring_index(lane, wpos, ring_mask);
 				ring_g[idx] = vv;
 				w.mirror[idx & (SD_MIRROR_WORDS - 1)] = vv;
 			}
 			partial = vv;
 		}
-		partial = (uint32_t)__builtin_amdgcn_readlane((int)partial, (int)((((uint32_t)wpos & 31u) + (uint32_t)K) >> 5));
+		partial = (uint32_t)__builtin_amdgcn_readlane((int)partial, (int)sd_ring_next_owner(wpos, K));
 		wpos += (uint64_t)K;
-		// ---- slicer levels and the PI loop filter (the lead wave's round_back of kernel A, here in line)
-		const int C0 = K - C1;
-		if (C1 > 0 && C0 > 0) {
-			const f32x2 cnt = {(float)C1, (float)C0};
-			const f32x2 rc = sd_recip2(cnt);
-			const float hi = ((float)S1 * rc.x) * (1.0f / 4096.0f);
-			const float lo = ((float)S0 * rc.y) * (1.0f / 4096.0f);
-			const float c = 0.5f * (hi + lo), a = 0.5f * (hi - lo);
-			if (st.nstat == 0) { st.bias = c; st.amp = a; }
-			else { st.bias = st.bias + 0.5f * (c - st.bias); st.amp = st.amp + 0.5f * (a - st.amp); }
-			if (!(st.amp >= 1.0e-3f)) st.amp = 1.0e-3f;
-			st.nstat = 1;
-		} else {
-			st.bias = ((float)(S1 + S0) * sd_recip((float)K)) * (1.0f / 4096.0f);
-		}
-		if (n0 <= 3 * (int64_t)BK_IT) st.bias = ((float)(S1 + S0) * sd_recip((float)K)) * (1.0f / 4096.0f);      // SPEC 3.2b: acquisition, the mean of the round
-		const f32x2 den = {(float)K, st.amp * st.amp};
-		const f32x2 rd = sd_recip2(den);
-		float err = ((float)E * rd.x) * (1.0f / 1024.0f);
-		err = err * rd.y;
-		err = sd_clamp(err, -1.0f, 1.0f);
-		const int dphase = __float2int_rn(err * md.kp), dper = __float2int_rn(err * md.ki);
-		st.t_next += (int64_t)K * st.period + dphase;
-		st.period += dper;
-		if (st.period < md.pmin) st.period = md.pmin;
-		if (st.period > md.pmax) st.period = md.pmax;
+		// ---- slicer levels and the PI loop filter (K is capped: every symbol fed the detector; acquisition: the first three tiles)
+		sd_loop_update(st, md, K, K, E, S1, S0, C1, n0 <= 3 * (int64_t)BK_IT, false);
 	};
 	// ---- K4: the sync search over the bits that are now in the mirror.  ONCE PER BLOCK (round 6; per tile before): a block adds at most
 	// 3 x 256 bits, the mirror holds the newest 2048, and what the search finds does not depend on how its calls are cut -- three calls
@@ -281,11 +252,7 @@ __global__ __launch_bounds__(64 * BK_WAVES, 4) void sd_bins_kernel(
 		if (!framing) return;
 		WAVE_SYNC();
 		SdFrameDesc *dch = (SdFrameDesc *)P.fo.descs + (size_t)ch * P.fo.max_frames;
-		const uint32_t mf = P.fo.max_frames;
-		if (is_rs41) sd_rs41_sync_step<true>(k4, wpos, w.mirror, lane, dch, mf, w.k4list);
-		else if (is_dfm) sd_fixed_sync_step<SONDE_DFM09, true>(k4, wpos, w.mirror, lane, dch, mf, w.k4list);
-		else if (is_ims) sd_fixed_sync_step<SONDE_IMS100, true>(k4, wpos, w.mirror, lane, dch, mf, w.k4list);
-		else sd_fixed_sync_step<SONDE_MRZN1, true>(k4, wpos, w.mirror, lane, dch, mf, w.k4list);
+		sd_sync_step_of<true>(is_rs41, is_dfm, false, is_ims, true, k4, wpos, w.mirror, lane, dch, P.fo.max_frames, w.k4list);      // (framing: what is left is MRZ-N1)
 	};
 	// the tile is consumed: its last 64 samples become the history, what the last pass produced beyond it the head of the next tile
 	auto roll = [&]() {
@@ -351,25 +318,13 @@ __global__ __launch_bounds__(64 * BK_WAVES, 4) void sd_bins_kernel(
 			}
 			WAVE_SYNC();
 			FramerLds &wl = *reinterpret_cast<FramerLds *>(&w.A[0]);
-			GfSwar swar;
-			const uint32_t *sw = s.et.swar + 8 * (lane % RS_R);
-			swar.a_lo = sw[0]; swar.a_hi = sw[1]; swar.b_lo = sw[2]; swar.b_hi = sw[3]; swar.c = sw[4];
-			const unsigned long long *dg = reinterpret_cast<const unsigned long long *>((const SdFrameDesc *)P.fo.descs + (size_t)ch * max_frames);
+			const GfSwar swar = gf_swar_row(s.et.swar + 8 * (lane % RS_R));
+			const SdFrameDesc *dch = (const SdFrameDesc *)P.fo.descs + (size_t)ch * max_frames;
 			SondeFrame *fout = P.fo.frames + (size_t)ch * max_frames;
 			for (uint32_t k = 0; k < nfr; k++) {
 				unsigned long long d0, d1;
-				if (k < SD_K4_LIST) {
-					const unsigned long long *dl = reinterpret_cast<const unsigned long long *>(&w.k4list[k]);
-					d0 = dl[0]; d1 = dl[1];
-				} else {
-					d0 = __hip_atomic_load(dg + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					d1 = __hip_atomic_load(dg + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				}
-				SdFrameDesc d;
-				d.fstart = sd_uniform64(d0);
-				d.flen = __builtin_amdgcn_readfirstlane((int)(uint32_t)d1);
-				d.inv = __builtin_amdgcn_readfirstlane((int)(d1 >> 32));
-				sd_rs41_decode_frame<true>(s.et.tabs, wl, swar, ring_g, ring_mask, d, fout + k, ch, lane);
+				sd_k4_desc_words(w.k4list, dch, k, d0, d1);
+				sd_rs41_decode_frame<true>(s.et.tabs, wl, swar, ring_g, ring_mask, sd_frame_desc(d0, d1), fout + k, ch, lane);
 			}
 		}
 	}

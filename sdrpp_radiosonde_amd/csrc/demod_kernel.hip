@@ -5,7 +5,7 @@
 //   K1  FM quadrature discriminator      (SDR++ dsp::demod::FM<float>, /root/reference/src/main.cpp:57)
 //   K2  polyphase low-pass FIR, evaluated only at the timing loop's sampling instants
 //   K3  Gardner timing-error detector + PI loop filter, updated once per round (<= 256 symbols)
-//       and hard slicer -> bit ring in HBM
+//       and hard slicer -> bit ring in HBM (the loop's arithmetic: sd_timing.h, the functions bins_kernel.hip calls too)
 //   K4  RS41 channels: frame-sync correlator over the newest bits (sd_rs41.h), on a round wave that would
 //       otherwise spin while the lead wave runs the loop filter -> frame descriptors
 //   K5/K6  RS41 channels, epilogue: the frames completed in this submit are de-whitened and RS(255,231)-decoded
@@ -25,6 +25,7 @@
 #include "sd_rs41.h"
 #include "sd_rsdec.h"
 #include "sd_fixed.h"
+#include "sd_timing.h"
 #include "launch.h"
 
 typedef float sd_f32x4 __attribute__((ext_vector_type(4)));
@@ -131,13 +132,7 @@ static_assert(8 * sizeof(FixedLds) <= (2 * SD_BUF + SD_BUF) * sizeof(float), "pe
 static __device__ __attribute__((noinline)) void sd_rs41_decode_frame_call(const FramerTabs &tabs, FramerLds &s, const uint32_t *__restrict__ swar_row,
 	const uint32_t *__restrict__ ring, uint32_t mask, unsigned long long d0, unsigned long long d1, SondeFrame *__restrict__ fr, uint32_t ch, int lane)
 {
-	GfSwar swar;
-	swar.a_lo = swar_row[0]; swar.a_hi = swar_row[1]; swar.b_lo = swar_row[2]; swar.b_hi = swar_row[3]; swar.c = swar_row[4];
-	SdFrameDesc d;
-	d.fstart = sd_uniform64(d0);
-	d.flen = __builtin_amdgcn_readfirstlane((int)(uint32_t)d1);
-	d.inv = __builtin_amdgcn_readfirstlane((int)(d1 >> 32));
-	sd_rs41_decode_frame<true>(tabs, s, swar, ring, mask, d, fr, ch, lane);
+	sd_rs41_decode_frame<true>(tabs, s, gf_swar_row(swar_row), ring, mask, sd_frame_desc(d0, d1), fr, ch, lane);
 }
 
 // ---------------------------------------------------------------- the kernel
@@ -519,8 +514,7 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 			}
 			if (h == 0) {
 				const float yprev = HW ? sd_hw_prev(y, lane) : sd_wave_shr1(y, 0.0f);            // (the 64-group's first symbol's term is not used)
-				float e = (yprev - y) * (m - bias);
-				e = sd_clamp(e * 1024.0f, -1.0e6f, 1.0e6f);
+				const float e = sd_gardner_term(y, m, yprev, bias);
 				Ei += (act && lane != 0) ? __float2int_rn(e) : 0;    // first symbol of a 64-group (lane 0 in either mapping): no term (SPEC 3.2)
 				if (AF) {                                            // SPEC 3.6b: same symbols as the detector's
 					SYi += (act && lane != 0) ? __float2int_rn(sd_clamp(fabsf(y - bias), 0.0f, 8.0f) * 4096.0f) : 0;
@@ -528,7 +522,7 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 				}
 			}
 			const bool bit = act && (y > bias);
-			const int Y = __float2int_rn(sd_clamp(y, -8.0f, 8.0f) * 4096.0f);
+			const int Y = sd_level_term(y);
 			S1i += bit ? Y : 0;
 			S0i += (act && !bit) ? Y : 0;
 			const unsigned long long bal = HW ? __ballot(sd_hw_unpermute(bit ? 1 : 0, lane) != 0) : __ballot(bit);      // bits in symbol order
@@ -557,21 +551,15 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 			return;
 		}
 		if (lane < 8 * SPL + 1) {
-			const uint32_t sh = (uint32_t)wpos_w & 31u;
-			const uint32_t w0 = (uint32_t)(wpos_w >> 5);
 			uint32_t vv = 0;
-			const bool touched = (uint32_t)(32 * lane) < sh + (uint32_t)K;
-			if (touched) {
-				const uint32_t lo = s.chunk[par][lane + 1];
-				const uint32_t pvw = s.chunk[par][lane];
-				vv = sh ? ((lo << sh) | (pvw >> (32u - sh))) : lo;
-				const uint32_t idx = (w0 + lane) & ring_mask;
-				if (lane == 0 && sh) vv |= s.partial[par] & ((1u << sh) - 1u);
+			if (sd_ring_touched(lane, wpos_w, K)) {
+				vv = sd_ring_word(s.chunk[par], lane, wpos_w, &s.partial[par]);
+				const uint32_t idx = sd_ring_index(lane, wpos_w, ring_mask);
 				sd_st_coh(ring_g + idx, vv, sliced);
 				s.mirror[idx & (SD_MIRROR_WORDS - 1)] = vv;
 			}
 			// whoever owns the word the next round starts in publishes it (read after a barrier)
-			if ((uint32_t)lane == ((sh + (uint32_t)K) >> 5)) s.partial[par ^ 1] = vv;
+			if ((uint32_t)lane == sd_ring_next_owner(wpos_w, K)) s.partial[par ^ 1] = vv;
 		}
 		wpos_w += (uint64_t)K;
 		// every bit below it is in the ring and in the mirror (this wave's LDS stores execute in order; K4 reads it whenever it looks:
@@ -586,49 +574,15 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 		const int S1 = r0.y + r1.y + r2.y + r3.y;
 		const int S0 = r0.z + r1.z + r2.z + r3.z;
 		const int C1 = r0.w + r1.w + r2.w + r3.w;
-		const int C0 = K - C1;
-		if (C1 > 0 && C0 > 0) {
-			const f32x2 cnt = {(float)C1, (float)C0};
-			const f32x2 rc = sd_recip2(cnt);
-			const float hi = ((float)S1 * rc.x) * (1.0f / 4096.0f);
-			const float lo = ((float)S0 * rc.y) * (1.0f / 4096.0f);
-			const float c = 0.5f * (hi + lo);
-			const float a = 0.5f * (hi - lo);
-			if (st.nstat == 0) {
-				st.bias = c;
-				st.amp = a;
-			} else {
-				st.bias = st.bias + 0.5f * (c - st.bias);
-				st.amp = st.amp + 0.5f * (a - st.amp);
-			}
-			if (!(st.amp >= 1.0e-3f)) st.amp = 1.0e-3f;
-			st.nstat = 1;
-		} else {
-			// one-sided round (carrier offset larger than the deviation): no level estimate; move the threshold to the
-			// mean of the round so that the next one sees both levels (SPEC 3.2)
-			st.bias = ((float)(S1 + S0) * sd_recip((float)K)) * (1.0f / 4096.0f);
-		}
-		// SPEC 3.2b (round 5), acquisition: during a stream's first three tiles the threshold is the mean of the round (the level estimate
-		// above is built from the slicer's own decisions: with the carrier 2 kHz off it needs several tiles to find the offset)
-		if (!afsk && n_done <= 3 * (int64_t)IT) st.bias = ((float)(S1 + S0) * sd_recip((float)K)) * (1.0f / 4096.0f);
-		const f32x2 den = {(float)(K > SD_ROUND_MAX ? SD_ROUND_MAX : K), st.amp * st.amp};      // the symbols that fed the detector
-		const f32x2 rd = sd_recip2(den);
-		float err = ((float)E * rd.x) * (1.0f / 1024.0f);
-		err = err * rd.y;
-		err = sd_clamp(err, -1.0f, 1.0f);
-		const int dphase = __float2int_rn(err * md.kp);
-		const int dper = __float2int_rn(err * md.ki);
-		st.t_next += (int64_t)K * st.period + dphase;
-		if (AF && afsk && st.nstat) {
-			// SPEC 3.6b, acquisition aid of the AFSK streams: half a symbol off, the Gardner detector sits on its unstable zero and a loop
-			// closed 3-6 times a second takes seconds to leave it; there the mid-symbol samples show the open eye.  Jump half a symbol.
+		bool half_jump = false;
+		if (AF && afsk) {
+			// SPEC 3.6b: the eye at the mid-symbol instants wider than at the on-time ones (sd_loop_update says what follows).  Below: only a
+			// round's first SD_ROUND_MAX symbols feed the detector (round_front), and the AFSK streams have no acquisition rule
 			const int2 q0 = s.red2[par][0], q1 = s.red2[par][1], q2 = s.red2[par][2], q3 = s.red2[par][3];
 			const int64_t SY = (int64_t)q0.x + q1.x + q2.x + q3.x, SM = (int64_t)q0.y + q1.y + q2.y + q3.y;
-			if (16 * SM > 17 * SY) st.t_next += st.period >> 1;
+			half_jump = 16 * SM > 17 * SY;
 		}
-		st.period += dper;
-		if (st.period < md.pmin) st.period = md.pmin;
-		if (st.period > md.pmax) st.period = md.pmax;
+		sd_loop_update(st, md, K, K > SD_ROUND_MAX ? SD_ROUND_MAX : K, E, S1, S0, C1, !afsk && n_done <= 3 * (int64_t)IT, half_jump);
 		st.wpos += (uint64_t)K;
 	};
 
@@ -662,12 +616,7 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 	};
 	auto k4_run = [&](uint64_t wp) {   // one step of the channel's sync-search state machine (wave-uniform type dispatch)
 		SdFrameDesc *dch = (SdFrameDesc *)fo->descs + (size_t)ch * fo->max_frames;
-		const uint32_t mf = fo->max_frames;
-		if (is_rs41) sd_rs41_sync_step(s.k4, wp, s.mirror, lane, dch, mf);
-		else if (is_dfm) sd_fixed_sync_step<SONDE_DFM09>(s.k4, wp, s.mirror, lane, dch, mf);
-		else if (is_m10) sd_fixed_sync_step<SONDE_M10>(s.k4, wp, s.mirror, lane, dch, mf);
-		else if (is_ims) sd_fixed_sync_step<SONDE_IMS100>(s.k4, wp, s.mirror, lane, dch, mf);
-		else if (is_mrz) sd_fixed_sync_step<SONDE_MRZN1>(s.k4, wp, s.mirror, lane, dch, mf);
+		sd_sync_step_of<false>(is_rs41, is_dfm, is_m10, is_ims, is_mrz, s.k4, wp, s.mirror, lane, dch, fo->max_frames);
 	};
 	auto k4_finish = [&]() {       // K4's wave, after barrier E: catch up with the last rounds' bits, state and frame count back to HBM
 		k4_run(sd_uniform64(s.pub.wpos));
@@ -752,10 +701,7 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 						round_back(pendK, par ^ 1, r == 0 ? n0 - IT : n0);      // the previous round's update (n0 already counts this round's tile)
 						if (IS_IQ) afc_step(tile - 1);                // (IQ classes run one round per tile)
 					}
-					if (r == 0) {
-						const int64_t limit = (((n0 - 1 - NT / 2 - SD_MARGIN) << 16) | 0xFFFF);
-						K_total = (st.t_next <= limit) ? (int)((uint32_t)(limit - st.t_next) / (uint32_t)st.period) + 1 : 0;
-					}
+					if (r == 0) K_total = sd_tile_symbols(n0, NT, st.t_next, st.period);
 					K = K_total > SPL * SD_ROUND_MAX ? SPL * SD_ROUND_MAX : K_total;
 					K_total -= K;
 					t_next = st.t_next; period = st.period; bias = st.bias;
@@ -811,24 +757,14 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 		const uint32_t nf0 = sliced ? (uint32_t)__builtin_amdgcn_readfirstlane((int)s.nout0) : 0u;      // (the earlier segments decoded theirs)
 		if (nf0 + (uint32_t)wave < nfr) {
 			FramerLds &wl = reinterpret_cast<FramerLds *>(&s.A[0][0])[wave];
-			GfSwar swar;
 			const uint32_t *sw = et.swar + 8 * (lane % RS_R);
-			swar.a_lo = sw[0]; swar.a_hi = sw[1]; swar.b_lo = sw[2]; swar.b_hi = sw[3]; swar.c = sw[4];
-			const unsigned long long *dg = reinterpret_cast<const unsigned long long *>((const SdFrameDesc *)fo->descs + (size_t)ch * max_frames);
+			const SdFrameDesc *dch = (const SdFrameDesc *)fo->descs + (size_t)ch * max_frames;
 			SondeFrame *fout = fo->frames + (size_t)ch * max_frames;
 			const uint32_t done_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.fec.done_mask);      // records the loop has written
 			for (uint32_t k = nf0 + (uint32_t)wave; k < nfr; k += SD_WGT / 64) {
 				if (k < 32u && ((done_mask >> k) & 1u)) continue;
-				// the descriptor: from K4's list in LDS, or (beyond its first entries) from HBM, where wave 3 of this workgroup
-				// stored it a moment ago: agent-scope loads (L2), like the ring words
 				unsigned long long d0, d1;
-				if (k < SD_K4_LIST) {
-					const unsigned long long *dl = reinterpret_cast<const unsigned long long *>(&s.k4.list[k]);
-					d0 = dl[0]; d1 = dl[1];
-				} else {
-					d0 = __hip_atomic_load(dg + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					d1 = __hip_atomic_load(dg + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				}
+				sd_k4_desc_words(s.k4.list, dch, k, d0, d1);
 				sd_rs41_decode_frame_call(et.tabs, wl, sw, ring_g, ring_mask, d0, d1, fout + k, ch, lane);
 			}
 		}
@@ -846,21 +782,12 @@ __device__ __forceinline__ void sd_demod_body(DemodLds &s, const uint32_t bidx, 
 		const uint32_t nf0 = sliced ? (uint32_t)__builtin_amdgcn_readfirstlane((int)s.nout0) : 0u;
 		if (nf0 + (uint32_t)wave < nfr) {
 			FixedLds &wl = reinterpret_cast<FixedLds *>(&s.A[0][0])[wave];
-			const unsigned long long *dg = reinterpret_cast<const unsigned long long *>((const SdFrameDesc *)fo->descs + (size_t)ch * max_frames);
+			const SdFrameDesc *dch = (const SdFrameDesc *)fo->descs + (size_t)ch * max_frames;
 			SondeFrame *fout = fo->frames + (size_t)ch * max_frames;
 			for (uint32_t k = nf0 + (uint32_t)wave; k < nfr; k += SD_WGT / 64) {
 				unsigned long long d0, d1;
-				if (k < SD_K4_LIST) {
-					const unsigned long long *dl = reinterpret_cast<const unsigned long long *>(&s.k4.list[k]);
-					d0 = dl[0]; d1 = dl[1];
-				} else {
-					d0 = __hip_atomic_load(dg + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					d1 = __hip_atomic_load(dg + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-				}
-				SdFrameDesc d;
-				d.fstart = sd_uniform64(d0);
-				d.flen = __builtin_amdgcn_readfirstlane((int)(uint32_t)d1);
-				d.inv = __builtin_amdgcn_readfirstlane((int)(d1 >> 32));
+				sd_k4_desc_words(s.k4.list, dch, k, d0, d1);
+				const SdFrameDesc d = sd_frame_desc(d0, d1);
 				// (inlined: as a real call like RS41's these short decoders keep their small arrays on the stack and cost 7 %: DFM 4096 x 24
 				// 0.2886 -> 0.3122 ms, mixed 0.298 -> 0.319)
 				if (is_dfm) sd_dfm_decode_frame<true>(wl, ring_g, ring_mask, d, fout + k, ch, lane);

@@ -33,6 +33,25 @@ struct SdSyncRun {                  // working copy of SdFramerState + the frame
 	SdFrameDesc list[SD_K4_LIST];   // the first frames listed in this launch, for the FEC epilogue (the full list is in HBM)
 };
 
+// Descriptor k of a channel for the FEC epilogue, as its two qwords: from K4's list in LDS or (beyond its first entries) from HBM,
+// where the wave that ran K4 stored it a moment ago: agent-scope loads (L2), like the ring words
+__device__ __forceinline__ void sd_k4_desc_words(const SdFrameDesc *list, const SdFrameDesc *descs_ch, uint32_t k,
+	unsigned long long &d0, unsigned long long &d1)
+{
+	if (k < SD_K4_LIST) {
+		const unsigned long long *dl = reinterpret_cast<const unsigned long long *>(&list[k]);
+		d0 = dl[0]; d1 = dl[1];
+		return;
+	}
+	const unsigned long long *dg = reinterpret_cast<const unsigned long long *>(descs_ch);
+	d0 = __hip_atomic_load(dg + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	d1 = __hip_atomic_load(dg + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ SdFrameDesc sd_frame_desc(unsigned long long d0, unsigned long long d1)      // ... and unpacked, wave-uniform
+{
+	return SdFrameDesc{sd_uniform64(d0), __builtin_amdgcn_readfirstlane((int)(uint32_t)d1), __builtin_amdgcn_readfirstlane((int)(d1 >> 32))};
+}
+
 // Advance the state machine over the bits [.., wp) of the channel.  `mirror` holds the ring words of the newest
 // SD_MIRROR_WORDS * 32 bits (word w of the stream at mirror[w % SD_MIRROR_WORDS]); the caller guarantees that the
 // search never trails wp by more than that (it is called at least once per tile).  Wave-synchronous, 64 lanes,

@@ -71,6 +71,8 @@ __device__ __forceinline__ uint8_t byte_at(const uint32_t *ring, uint32_t mask, 
 // (the LDS byte-table form cost one conflicting LDS read per multiplication: 65 % of the kernel's LDS cycles
 // were bank conflicts, profiles/r1_v16_counters.csv).
 struct GfSwar { uint32_t a_lo, a_hi, b_lo, b_hi, c; };       // the 20 table bytes of one multiplier
+// one multiplier from its row (8 words, 5 in use) of the table the host built
+__device__ __forceinline__ GfSwar gf_swar_row(const uint32_t *sw) { return GfSwar{sw[0], sw[1], sw[2], sw[3], sw[4]}; }
 
 __device__ __forceinline__ uint32_t gf_swar_mul(uint32_t s, const GfSwar &t)
 {
@@ -470,16 +472,14 @@ __device__ __attribute__((noinline)) void sd_rs41_loop_step(SdFecJob &job, const
 		(void)sd_rs41_deinterleave(wl, d.flen, lane);
 		WAVE_SYNC();
 		if (lane < 2 * RS_R) {
-			const uint32_t *sw = swar_tab + 8 * j;
-			t.a_lo = sw[0]; t.a_hi = sw[1]; t.b_lo = sw[2]; t.b_hi = sw[3]; t.c = sw[4];
+			t = gf_swar_row(swar_tab + 8 * j);
 			job.usave[lane] = syndrome_swar_part(wl.cw[c], W, Wh, 0u, t);
 		}
 		next_phase = 2;
 	} else if (phase == 2) {
 		uint32_t syn = 0;
 		if (lane < 2 * RS_R) {
-			const uint32_t *sw = swar_tab + 8 * j;
-			t.a_lo = sw[0]; t.a_hi = sw[1]; t.b_lo = sw[2]; t.b_hi = sw[3]; t.c = sw[4];
+			t = gf_swar_row(swar_tab + 8 * j);
 			syn = syndrome_swar_finish(tb, syndrome_swar_part(wl.cw[c], Wh, 0, job.usave[lane], t), j);
 		}
 		if (__ballot(syn != 0) == 0ull) next_phase = 3;          // clean: the record is the de-whitened frame as it stands

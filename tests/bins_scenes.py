@@ -6,7 +6,8 @@ Transmitters (synth.make_wideband_scene, one white noise floor, exact carrier of
   all four bin types (RS41, DFM, iMS-100, MRZ-N1), each at Eb/N0 10 and 20 dB;
   carriers at 0, +2 kHz and -4.5 kHz from the bin centre (the last makes the 16-bit phase difference wrap under noise);
   bins 0 and 511; four types in the eight bins 64 .. 71 of one workgroup of the bins kernel, two of them silent (65, 67);
-  two transmitters half a bin off (odd bins 100 and 333, for the dual bank)."""
+  two transmitters half a bin off (odd bins 100 and 333, for the dual bank).
+A second, small scene (late_scene: two blocks, one carrier that comes on the air late) holds the one-sided round of SPEC 3.2."""
 from __future__ import annotations
 
 import numpy as np
@@ -61,7 +62,29 @@ def scene() -> np.ndarray:
     return _cache["iq"]
 
 
-INT16_SCALE = 200000.0       # the noise floor (sigma 0.02) at 4000 counts: the sum of the carriers stays inside 16 bits, clipped beyond
+# The late carrier: one stream of two blocks, one RS41 transmitter 4.5 kHz below its bin centre (beyond its deviation: both levels lie
+# on one side of 0) that comes on the air 4.8 ms (23 symbols) before the second block, so that the bank's and the filters' memory of the
+# noise is gone by then.  Block 1 is the acquisition (SPEC 3.2b: its three tiles set the threshold to the mean of a round, here of
+# noise and at the end a few symbols: about 0); the first tile of block 2 is then a ONE-SIDED round (every symbol below the threshold:
+# no level estimate, the threshold moves to the round's mean), behind the acquisition boundary and on a state carried over a submit.
+# No round of scene() takes that branch of the loop update: a carrier that is there from the start is found by the acquisition rule.
+LATE_TX = (130, -4500.0, RS41, 20.0)     # (an RS41 bin of bin_types())
+LATE_NBLK = 2
+LATE_LEAD = 48_000          # wideband samples
+
+
+def late_scene() -> np.ndarray:
+    """the float32 stream [LATE_NBLK * BLOCK, 2]"""
+    if "late" not in _cache:
+        from sdrpp_radiosonde_amd import synth
+        k, df, ty, e = LATE_TX
+        iq, _, _ = synth.make_wideband_scene([(k * F.BIN_HZ + df, ty)], LATE_NBLK * BLOCK, ebn0_db=[e], seed=SEED + 1, cfo_max_hz=0.0,
+                                             active=[(BLOCK - LATE_LEAD, LATE_NBLK * BLOCK)])
+        _cache["late"] = iq.numpy()
+    return _cache["late"]
+
+
+INT16_SCALE = 200000.0      # the noise floor (sigma 0.02) at 4000 counts: the sum of the carriers stays inside 16 bits, clipped beyond
 
 
 def scene_int16() -> np.ndarray:

@@ -21,14 +21,14 @@ ODD_WATCH = [(k, ty, e) for k, _, ty, e in B.ODD_TX]
 _cache: dict = {}
 
 
-def oracle_bank(oracle, odd: bool, watch, all_rs41: bool = False):
-    """the scene through or_chan_block2 (one bank) and one oracle channel per watched bin, one block per feed:
-    {bin: (q [NBLK * 2560] int64, rows [NBLK * 1536] float32, states per block, bits per block)}"""
-    key = (odd, all_rs41)
+def oracle_bank(oracle, odd: bool, watch, all_rs41: bool = False, late: bool = False):
+    """the scene (late: bins_scenes.late_scene) through or_chan_block2 (one bank) and one oracle channel per watched bin, one block
+    per feed: {bin: (q [NBLK * 2560] int64, rows [NBLK * 1536] float32, states per block, bits per block)}"""
+    key = (odd, all_rs41, late)
     if key in _cache:
         return _cache[key]
     L = oracle.lib()
-    x = B.scene()
+    x = B.late_scene() if late else B.scene()
     ch = L.or_chan_new_odd() if odd else L.or_chan_new()
     n_out = B.STEPS * 12 // 5
     decs = np.zeros(512, np.uint8)
@@ -41,7 +41,7 @@ def oracle_bank(oracle, odd: bool, watch, all_rs41: bool = False):
     outdec = np.zeros((512, n_out // 2), np.float32)
     res = {k: ([], [], [], []) for k in dec}
     nb = {k: 0 for k in dec}
-    for b in range(B.NBLK):
+    for b in range(x.shape[0] // B.BLOCK):
         blk = np.ascontiguousarray(x[b * B.BLOCK:(b + 1) * B.BLOCK]).reshape(-1)
         L.or_chan_block2(ch, oracle.fptr(blk), B.STEPS, oracle.fptr(bins.reshape(-1)), oracle.fptr(out48.reshape(-1)), decs.ctypes.data,
                          oracle.fptr(outdec.reshape(-1)))
@@ -189,3 +189,17 @@ def test_oracle_wideband_block_replay(oracle, case):
         watch, res = B.watched_even(), oracle_bank(oracle, False, B.watched_even())
     chks = wideband_checks(res, watch, int(every) // 3, all_rs41=bank == "rs41")
     print(B.summarise(f"oracle {case}", chks, [e for _, _, e in watch], AMB_LIMIT))
+
+
+def test_late_carrier_takes_the_one_sided_round(oracle):
+    """bins_scenes.late_scene through the oracle, one block per feed: the replay accepts both spans, and the scene holds what it was made
+    for: block 2's first tile (about 205 symbols, behind the three tiles of the acquisition) is sliced to one value throughout -- a
+    one-sided round of SPEC 3.2 -- and the tiles after it, with the threshold at that round's mean, see both levels again."""
+    k, _, ty, e = B.LATE_TX
+    res = oracle_bank(oracle, False, [(k, ty, e)], late=True)
+    print(B.summarise("oracle late-3", wideband_checks(res, [(k, ty, e)], 1), [e], AMB_LIMIT))
+    _, _, states, bits = res[k]
+    print("late carrier: bits per block", [len(b) for b in bits], "ones among block 2's first 190 bits:", int(bits[1][:190].sum()),
+          "share of ones behind them: %.3f" % bits[1][230:].mean())
+    assert len(bits) == B.LATE_NBLK
+    assert len(set(bits[1][:190].tolist())) == 1 and 0.25 < bits[1][230:].mean() < 0.75

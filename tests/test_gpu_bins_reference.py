@@ -22,18 +22,18 @@ _dev: dict = {}
 _runs: dict = {}
 
 
-def device_scene(int16: bool = False) -> torch.Tensor:
-    key = "i16" if int16 else "f32"
+def device_scene(int16: bool = False, late: bool = False) -> torch.Tensor:
+    key = "late" if late else "i16" if int16 else "f32"
     if key not in _dev:
-        _dev[key] = torch.from_numpy(B.scene_int16() if int16 else B.scene()).cuda()
+        _dev[key] = torch.from_numpy(B.late_scene() if late else B.scene_int16() if int16 else B.scene()).cuda()
     return _dev[key]
 
 
 def run_chz(channels, *, types=None, bps: int = 1, dual: bool = False, int16: bool = False, streams: int = 1, nblk: int = B.NBLK,
-            phases: bool = True):
-    """the scene through a fused SondeChannelizer, bps blocks per submit (the same content in every stream):
-    {channel: (q over the whole run or None, states per submit, new bits per submit)}"""
-    x = device_scene(int16)
+            phases: bool = True, late: bool = False):
+    """the scene (late: bins_scenes.late_scene) through a fused SondeChannelizer, bps blocks per submit (the same content in every
+    stream): {channel: (q over the whole run or None, states per submit, new bits per submit)}"""
+    x = device_scene(int16, late)
     chz = SondeChannelizer(types=types, blocks_per_submit=bps, n_streams=streams, dual=dual, input_kind=INPUT_IQ16 if int16 else INPUT_IQ)
     assert chz.fused and chz.samples_per_submit == bps * B.BLOCK
     res = {c: ([], [], []) for c in channels}
@@ -93,6 +93,17 @@ def test_bins_kernel_block_replay(case):
     Observed on the MI355X: see profiles/bins_reference_notes.md (no span unresolved in any case; the oracle, on the same samples: none)."""
     _, line = replayed(case)
     print(line)
+
+
+def test_bins_kernel_late_carrier_replay():
+    """bins_scenes.late_scene, one stream, one block per submit, two submits: the branch of the loop update that no round of the scene
+    above takes, the ONE-SIDED round (SPEC 3.2: block 2's first tile, every symbol below the threshold), behind the acquisition boundary
+    (SPEC 3.2b: block 1) and on a state carried from one submit to the next.  The block replay of the cases above, the same conditions;
+    that the round is one-sided is asserted of the bits (test_bins_reference.py asserts it of the oracle's)."""
+    k, _, ty, e = B.LATE_TX
+    q, states, bits = run_chz([k], types=B.bin_types(), bps=1, nblk=B.LATE_NBLK, late=True)[k]
+    print(B.summarise("late-1", [(f"ch{k}", B.replay_bin(q, ty, states, bits, B.TILES_PER_BLOCK))], [e], AMB_LIMIT))
+    assert len(set(bits[1][:190].tolist())) == 1 and 0.25 < bits[1][230:].mean() < 0.75
 
 
 @pytest.mark.parametrize("shape", ["5-blocks", "8-streams-x-4-blocks"])
