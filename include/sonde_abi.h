@@ -269,6 +269,11 @@ typedef struct {
  * refused as before; with the flag and no iMS-100 group in the table nothing is allocated or launched, and every record is byte for
  * byte what it is without the flag. */
 #define SONDE_FLAG_IMS_DIVERSITY 2048u
+/* iMet-1/4 and SRS-C50 channels may be members of sonde_batch_set_diversity groups (DESIGN SPEC 3.3o; see SEVERAL RECEIVERS OF ONE SONDE
+ * below).  Opt-in at create as SONDE_FLAG_IMS_DIVERSITY is: these packets carry a 16-bit check and nothing else, C50's check is weak,
+ * and C50 groups run with given offsets only.  Without the flag such a member is refused as before; with the flag and no iMet or C50
+ * group in the table nothing is allocated or launched, and every record is byte for byte what it is without the flag. */
+#define SONDE_FLAG_AFSK_DIVERSITY 4096u
 
 typedef struct SondeBatch SondeBatch;
 
@@ -297,9 +302,9 @@ int  sonde_batch_submit_host(SondeBatch *b, const void *samples, size_t n_sample
  * nothing (stream order already says so); it is what a SONDE_FLAG_LATE_JOIN / SONDE_FLAG_PIPELINE host calls before it refills a
  * single buffer, and what any host calls to release the buffer on ANOTHER stream (a copy engine's).  0 = ok. */
 int  sonde_batch_wait_input(SondeBatch *b, void *stream);
-/* SEVERAL RECEIVERS OF ONE SONDE (DESIGN SPEC 3.3j: RS41; 3.3l: M10 / M20 and MRZ-N1; 3.3m: DFM; 3.3n: iMS-100).  A host that hears a sonde more than once -- two antennas or polarisations at one
+/* SEVERAL RECEIVERS OF ONE SONDE (DESIGN SPEC 3.3j: RS41; 3.3l: M10 / M20 and MRZ-N1; 3.3m: DFM; 3.3n: iMS-100; 3.3o: iMet and C50).  A host that hears a sonde more than once -- two antennas or polarisations at one
  * site, two sites of a network -- gives each receiver a channel and names the channels of one sonde a GROUP: group[ch] = -1 (none) or a
- * group id 0..G-1 (no gaps), 2..4 channels of ONE type per group: SONDE_RS41, SONDE_M10 (M10 and M20), SONDE_MRZN1, SONDE_DFM09 or (batches created with SONDE_FLAG_IMS_DIVERSITY) SONDE_IMS100.  offset_bits[ch] is where channel ch's bit count (SondeFrame.bitpos)
+ * group id 0..G-1 (no gaps), 2..4 channels of ONE type per group: SONDE_RS41, SONDE_M10 (M10 and M20), SONDE_MRZN1, SONDE_DFM09 or (batches created with SONDE_FLAG_IMS_DIVERSITY) SONDE_IMS100, or (batches created with SONDE_FLAG_AFSK_DIVERSITY) SONDE_IMET4 or SONDE_C50.  offset_bits[ch] is where channel ch's bit count (SondeFrame.bitpos)
  * stands when the group's common clock reads 0 -- the host knows when it started each stream; NULL = zeros.  After every other pass
  * of a submit one more kernel visits the group's frame records in the order of the common clock.  A failed frame (RS41: a codeword at
  * nerr = -1; the others: nerr[0] = -1) looks in every other member for the nearest record of the same length within window_bits (0 = 960, at most 1200) of
@@ -345,12 +350,22 @@ int  sonde_batch_wait_input(SondeBatch *b, void *stream);
  * never touched.  A combined record carries the data bits of the decoded blocks, nerr[0] raised by the bits in which they differ from
  * copy 0's received blocks, nerr[1] = 0, SONDE_FRAME_RESCUED | SONDE_FRAME_COMBINED, SONDE_FRAME_COPIES and SONDE_FRAME_JOINT.
  * Nothing behind the code checks the result: a host that wants fewer wrong frames drops those with SONDE_FRAME_JOINT > 0.
- * Not iMet or C50.
+ * iMet and SRS-C50 (SONDE_FLAG_AFSK_DIVERSITY; a 16-bit check, no FEC; bitpos and offset_bits count on-air SYMBOLS, a character is 10 of
+ * them; iMet packets of 5..64 bytes, window_bits 0 = 160; C50 packets of 9 bytes lie 90 symbols apart, window_bits 0 = 40 and at most
+ * 44 for a table with a C50 group): failed = nerr[0] < 0, good = nerr[0] >= 0 (packets SONDE_FLAG_AFSK_RESCUE repaired included: that
+ * pass runs in front).  Working frame and unknowns as for M10.  If the working frame's check passes it is the result; else, with 1..8
+ * unknowns (for iMet none of them in bytes 0 and 1, nor in byte 2 of an XDATA packet: they decide the layout), the packet is taken iff
+ * exactly one non-empty subset of V makes the check pass -- iMet's CRC16-CCITT as a linear system, C50's two byte sums recomputed per
+ * subset.  The record is M10's: nerr[0] = 0, SONDE_FRAME_RESCUED | SONDE_FRAME_COMBINED, SONDE_FRAME_COPIES, SONDE_FRAME_UNKNOWNS.
+ * Limits: as for M10; C50's sums are weak (two wrong bits 6 or 7 in different bytes can look like others), so a host that wants few
+ * wrong C50 packets drops the combined ones above a small SONDE_FRAME_UNKNOWNS (profiles/afsk_diversity_notes.md).  C50 packets carry
+ * no identity (serial, date and time repeat several times a second): sonde_batch_set_diversity_auto refuses any mode bit for a table
+ * with a C50 group -- C50 groups run with given offsets only.  Packets the framer dropped (a wrong start or stop bit) are not found.
  * Called once, before the first submit; if it is never called nothing is allocated or launched.  Refused: a second call, a call after a
- * submit, a group of fewer than 2 or more than 4 members, a member of any other type, members of different types in one group, group ids with gaps, window_bits > 1200, the
+ * submit, a group of fewer than 2 or more than 4 members, a member of any other type, members of different types in one group, group ids with gaps, window_bits > 1200 (> 44 with a C50 group), the
  * batch behind a channelizer, and a batch created with SONDE_FLAG_LATE_JOIN or SONDE_FLAG_PIPELINE (those never join their launch
  * units into one stream, and the pass needs all members' records).  One small launch more per submit for the RS41 groups, one for the
- * M10 / M20 / MRZ-N1 groups, one for the DFM groups and one for the iMS-100 groups, each only if the batch has such a group; no host
+ * M10 / M20 / MRZ-N1 groups, one for the DFM groups, one for the iMS-100 groups, one for the iMet and one for the C50 groups, each only if the batch has such a group; no host
  * synchronisation.
  * On a batch with groups sonde_batch_restart_channels takes all members of a group or none of them (their bit counts must stay
  * together); a restarted group loses its carried records and its counters. */
@@ -365,7 +380,11 @@ int  sonde_batch_set_diversity(SondeBatch *b, const int32_t *group /* n_channels
  *                                    of their bitpos is the difference of the members' offsets; for DFM groups: len 33, nerr[1] == 0,
  *                                    bytes 0 .. 33 identical (a sonde at rest can repeat a subframe pair: of several identical
  *                                    candidates the latest counts, DESIGN SPEC 3.3m); for iMS-100 groups: len 51, nerr[1] == 0,
- *                                    bytes 0 .. 51 identical (SPEC 3.3n).  Before the combining pass of every
+ *                                    bytes 0 .. 51 identical (SPEC 3.3n); for iMet groups: len 14, 18 or 20 (PTU, GPS and PTUX
+ *                                    packets: they carry a counter or the time), nerr[0] >= 0, bytes 0 .. len identical -- XDATA
+ *                                    packets may repeat byte for byte, so they teach no offset and are never marked: their
+ *                                    duplicates stay the host's business (SPEC 3.3o); a table with a C50 group: refused (its
+ *                                    packets carry no identity).  Before the combining pass of every
  *                                    submit an align step looks for such pairs among each member's records of the submit and its
  *                                    carried record, member pairs in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), per pair the
  *                                    match that is latest in the higher member.  A member is LOCKED once it has an offset: two unlocked
@@ -504,6 +523,12 @@ int      sonde_batch_test_dfm_combine(SondeBatch *b, size_t n, const SondeFrame 
  * of another type or len, a good copy 0. */
 int      sonde_batch_test_ims_combine(SondeBatch *b, size_t n, const SondeFrame *records, const uint32_t *n_copies, const uint64_t *blocks,
                                       SondeFrame *out, int32_t *status);
+/* The combining rule of iMet and C50 groups alone (SPEC 3.3o steps 3 to 6), on any batch: the shape of sonde_batch_test_check_combine.
+ * Copy 0: a SONDE_IMET4 record of 5..64 bytes or a SONDE_C50 record of 9 with nerr[0] < 0; the other copies of the same type and
+ * length.  status[i] = the copies used, -1 (not attempted: no unknown, more than 8, or for iMet a bit of the type byte or of XDATA's
+ * length byte in doubt), -2 (no subset fits) or -3 (several fit).  Refused: n_copies outside 2..4, a good copy 0, copies of differing
+ * type or len. */
+int      sonde_batch_test_afsk_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status);
 /* sonde_batch_set_diversity_auto introspection: where each member of the group stands on the group's clock now (off[m], member m = the
  * group's m-th channel in ascending order; unused entries 0), which members are locked (bit m), how many offsets the align step has
  * set or changed and how many records it has marked SONDE_FRAME_DUPLICATE since the call / the group's restart.  Synchronises.  With

@@ -116,6 +116,7 @@ FLAG_LATE_JOIN = 32      # launch units joined into the caller's stream ONE SUBM
 FLAG_WIDE_AUTO = 8       # SONDE_FLAG_WIDE for the types whose reference channel is >= 20 kHz only (iMS-100, MRZ-N1, M10)
 FLAG_RS41_RESCUE = 64    # RS41: second pass over frames whose RS stage failed, block CRCs as erasure hints (SONDE_FLAG_RS41_RESCUE; opt-in)
 FLAG_IMS_DIVERSITY = 2048  # iMS-100 channels may be members of set_diversity groups (SONDE_FLAG_IMS_DIVERSITY, DESIGN SPEC 3.3n; opt-in)
+FLAG_AFSK_DIVERSITY = 4096  # iMet and C50 channels may be members of set_diversity groups (SONDE_FLAG_AFSK_DIVERSITY, DESIGN SPEC 3.3o; opt-in)
 FRAME_RESCUED = 2        # SondeFrame.flags bit of a frame a second pass completed (SONDE_FRAME_RESCUED)
 FRAME_COMBINED = 4       # SondeFrame.flags bit of an RS41, M10 / M20, MRZ-N1, DFM or iMS-100 frame set_diversity put together from several receivers' copies (SONDE_FRAME_COMBINED)
 FRAME_DUPLICATE = 8      # SondeFrame.flags bit of a good frame another receiver of its diversity group has delivered (SONDE_FRAME_DUPLICATE)
@@ -200,7 +201,7 @@ ABI_SYMBOLS = [
     "sonde_batch_ims_rescue_info", "sonde_batch_test_ims_block",
     "sonde_batch_afsk_rescue_info", "sonde_batch_test_afsk_repair",
     "sonde_batch_set_diversity", "sonde_batch_diversity_info", "sonde_batch_test_rs41_combine", "sonde_batch_test_check_combine",
-    "sonde_batch_test_dfm_combine", "sonde_batch_test_ims_combine",
+    "sonde_batch_test_dfm_combine", "sonde_batch_test_ims_combine", "sonde_batch_test_afsk_combine",
     "sonde_batch_set_diversity_auto", "sonde_batch_diversity_offsets", "sonde_batch_test_diversity_align",
     "sonde_batch_test_diversity_align_kind",
     "sonde_batch_test_shift_age", "sonde_detect_test_shift_age", "sonde_tuner_test_set_base",
@@ -280,6 +281,8 @@ def load() -> C.CDLL:
         L.sonde_batch_test_dfm_combine.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
     if hasattr(L, "sonde_batch_test_ims_combine"):        # absent only in older A/B builds loaded through SONDE_MI355_LIB
         L.sonde_batch_test_ims_combine.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
+    if hasattr(L, "sonde_batch_test_afsk_combine"):       # absent only in older A/B builds loaded through SONDE_MI355_LIB
+        L.sonde_batch_test_afsk_combine.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
     if hasattr(L, "sonde_batch_set_diversity_auto"):      # absent only in older A/B builds loaded through SONDE_MI355_LIB
         L.sonde_batch_set_diversity_auto.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32]
         L.sonde_batch_diversity_offsets.argtypes = [vp, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]

@@ -214,7 +214,9 @@ class SondeBatch(Handle):
         """The receivers of one sonde (sonde_batch_set_diversity): groups = [[channel, ...], ...], 2..4 channels of one type each -- RS41
         (DESIGN SPEC 3.3j), M10 / M20 or MRZ-N1 (SPEC 3.3l: failed copies are combined by their 16-bit check), DFM (SPEC 3.3m: word by
         word, the better copy per Hamming codeword; bit counts are chips there), iMS-100 on a batch created with FLAG_IMS_DIVERSITY (SPEC
-        3.3n: BCH block by block, from the chips of the members' bit rings; bit counts are chips, window_bits 0: 576) --; offsets[ch] =
+        3.3n: BCH block by block, from the chips of the members' bit rings; bit counts are chips, window_bits 0: 576), iMet or C50 on a
+        batch created with FLAG_AFSK_DIVERSITY (SPEC 3.3o: by their 16-bit check; bit counts are on-air symbols, window_bits 0: 160 for
+        iMet, 40 for C50 and at most 44 with a C50 group; C50 groups take given offsets only: no learn, no mark_duplicates) --; offsets[ch] =
         the channel's bit count when the group's common clock reads 0 (None: zeros); window_bits: how far apart two copies of a frame may
         lie on that clock (0: 960).  Once, before the first submit.
         learn=True (sonde_batch_set_diversity_auto, SONDE_DIVERSITY_LEARN): the GPU finds the offsets itself from frames that are good
@@ -333,6 +335,19 @@ class SondeBatch(Handle):
         status = np.zeros(len(rec), dtype=np.int32)
         self._chk(self.L.sonde_batch_test_ims_combine(self.h, len(rec), rec.ctypes.data_as(C.c_void_p), nc.ctypes.data_as(C.c_void_p),
                                                       bl.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
+        return out, status
+
+    def test_afsk_combine(self, copies: np.ndarray, n_copies: np.ndarray):
+        """set_diversity's combining rule for iMet and C50 alone (sonde_batch_test_afsk_combine, SPEC 3.3o steps 3 to 6): copies [n, 4]
+        FRAME_DTYPE, caller-made, copy 0 the failed record to rewrite; n_copies [n] = 2..4.  Returns (copy 0 after the rule [n], status
+        [n]): status = the copies used, -1 not attempted, -2 no subset fits, -3 several fit."""
+        cp = np.ascontiguousarray(copies, dtype=FRAME_DTYPE)
+        nc = np.ascontiguousarray(n_copies, dtype=np.uint32)
+        assert cp.ndim == 2 and cp.shape[1] == 4 and nc.shape == (len(cp),)
+        out = np.zeros(len(cp), dtype=FRAME_DTYPE)
+        status = np.zeros(len(cp), dtype=np.int32)
+        self._chk(self.L.sonde_batch_test_afsk_combine(self.h, len(cp), cp.ctypes.data_as(C.c_void_p), nc.ctypes.data_as(C.c_void_p),
+                                                       out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p)))
         return out, status
 
     def test_rs255_erasures(self, cw_pairs: np.ndarray, erased: np.ndarray, n: int):

@@ -14,36 +14,9 @@
 #include <hip/hip_runtime.h>
 #include "sonde_dev.h"
 #include "sd_rescue_walk.h"
+#include "sd_ccitt_cols.h"      // AQ_IMET_MAXLEN, aq_pow, aq_imet_cols: the CRC-CCITT columns, shared with afsk_diversity_kernel.hip
 
-#define AQ_IMET_MAXLEN 64      // sd_imet_kernel records nothing longer: one lane per packet byte
 #define AQ_C50_LEN 9
-
-// x^(16 + 8 k) mod (x^16 + x^12 + x^5 + 1), k = 0 .. 61: the column of bit 0 of the byte with k covered bytes behind it
-struct AqPow { uint16_t v[AQ_IMET_MAXLEN - 2]; };
-static constexpr uint32_t aq_mulx(uint32_t c) { return (c & 0x8000u) ? ((c << 1) ^ 0x1021u) & 0xFFFFu : (c << 1) & 0xFFFFu; }
-static constexpr AqPow aq_make_pow()
-{
-	AqPow t{};
-	uint32_t c = 0x1021u;                  // x^16
-	for (int k = 0; k < AQ_IMET_MAXLEN - 2; k++) {
-		t.v[k] = (uint16_t)c;
-		for (int s = 0; s < 8; s++) c = aq_mulx(c);
-	}
-	return t;
-}
-__device__ const AqPow aq_pow = aq_make_pow();
-
-// the change of the iMet syndrome when the bits `m` of this lane's byte flip; c0 = the column of its bit 0
-__device__ __forceinline__ uint32_t aq_imet_cols(uint32_t c0, uint32_t m)
-{
-	uint32_t s = 0, c = c0;
-#pragma unroll
-	for (int j = 0; j < 8; j++) {
-		if ((m >> j) & 1u) s ^= c;
-		c = aq_mulx(c);
-	}
-	return s;
-}
 
 // pattern q = 0 .. 14 of SPEC 3.3i step 3: the single-bit masks 1 << q, then the adjacent-pair masks 3 << (q - 8)
 __device__ __forceinline__ uint32_t aq_pattern(int q) { return q < 8 ? 1u << q : 3u << (q - 8); }

@@ -578,6 +578,7 @@ static int launch_diversity(SondeBatch *b, SubmitCtx &cx)
 	for (const SdDivPass &p : k_div_passes) {
 		if (!(b->div_kinds & p.kinds)) continue;
 		a.window = b->div_window ? b->div_window : p.window;
+		a.kinds = p.kinds;
 		p.launch(a);
 		HIPCHK(hipGetLastError());
 	}
@@ -860,6 +861,13 @@ extern "C" int sonde_batch_set_diversity_auto(SondeBatch *b, const int32_t *grou
 	}
 	for (const SdDivGroup &g : gt)
 		if (g.n < 2) return sd_fail(g.n ? "sonde_batch_set_diversity: a group with fewer than 2 members" : "sonde_batch_set_diversity: group ids with gaps");
+	for (const SdDivPass &p : k_div_passes) {      // SPEC 3.3o: what a C50 group asks of the whole call
+		if (!(kinds & p.kinds)) continue;
+		if (p.max_window && window_bits > p.max_window)
+			return sd_fail("sonde_batch_set_diversity: window_bits > 44 with a SONDE_C50 group (its packets lie 90 symbols apart)");
+		if (p.given_offsets_only && mode)
+			return sd_fail("sonde_batch_set_diversity_auto: a SONDE_C50 group takes given offsets only (its packets carry no identity: mode must be 0)");
+	}
 	HIPCHK(hipSetDevice(b->device));
 	for (const SdDivPass &p : k_div_passes)
 		if ((kinds & p.mrz_kinds) && sd_batch_need_mrztab(b)) return -1;      // the pass of SPEC 3.3l reads MRZ-N1's columns from it

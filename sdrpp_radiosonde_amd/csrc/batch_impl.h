@@ -56,21 +56,27 @@ struct SdDivPass {
 	uint32_t flag;                         // the create flag a member needs; 0: none
 	uint32_t mrz_kinds;                    // a group of one of these kinds: the pass reads d_mrztab
 	const char *names;                     // its kinds as the refusal of a member of no pass lists them
-	struct { uint32_t type, len; } frames[4];  // the frames of its kinds: (type, length) pairs, ended by a length of 0
+	struct { uint32_t type, len, to; } frames[4];  // the frames of its kinds: (type, length) pairs, or (type, len .. to) with to != 0; ended by a length of 0
+	uint32_t max_window;                   // the largest window a caller may give a table with one of its groups; 0: the call's own limit
+	bool given_offsets_only;               // its frames carry no identity: no align step (sonde_batch_set_diversity_auto's mode bits are refused)
 };
-enum { SD_DIV_RS41, SD_DIV_CHECK, SD_DIV_DFM, SD_DIV_IMS, SD_N_DIV_PASSES };
+enum { SD_DIV_RS41, SD_DIV_CHECK, SD_DIV_DFM, SD_DIV_IMS, SD_DIV_IMET, SD_DIV_C50, SD_N_DIV_PASSES };
 static const SdDivPass k_div_passes[SD_N_DIV_PASSES] = {
 	{ 1u << SONDE_RS41, sd_launch_diversity, 960, 0, 0, "SONDE_RS41", { { SONDE_RS41, 320 }, { SONDE_RS41, 518 } } },
 	{ 1u << SONDE_M10 | 1u << SONDE_MRZN1, sd_launch_check_diversity, 960, 0, 1u << SONDE_MRZN1, "SONDE_M10, SONDE_MRZN1",
 	  { { SONDE_M10, 101 }, { SONDE_M10, 70 }, { SONDE_MRZN1, 45 } } },
 	{ 1u << SONDE_DFM09, sd_launch_dfm_diversity, 960, 0, 0, "SONDE_DFM09", { { SONDE_DFM09, 33 } } },
 	{ 1u << SONDE_IMS100, sd_launch_ims_diversity, 576, SONDE_FLAG_IMS_DIVERSITY, 0, "SONDE_IMS100", { { SONDE_IMS100, 51 } } },
+	// SPEC 3.3o: one launcher, one row per kind -- bitpos counts on-air symbols, an iMet packet of one length comes once a second, C50
+	// packets lie 90 symbols apart: 160 and 40, and no caller's window above 44 for a table with a C50 group
+	{ 1u << SONDE_IMET4, sd_launch_afsk_diversity, 160, SONDE_FLAG_AFSK_DIVERSITY, 0, "SONDE_IMET4", { { SONDE_IMET4, 5, 64 } } },
+	{ 1u << SONDE_C50, sd_launch_afsk_diversity, 40, SONDE_FLAG_AFSK_DIVERSITY, 0, "SONDE_C50", { { SONDE_C50, 9 } }, 44, true },
 };
 // a frame of one of the pass's kinds
 static inline bool sd_div_is_frame(const SdDivPass &p, uint32_t type, uint32_t len)
 {
 	for (const auto &f : p.frames)
-		if (f.len && f.type == type && f.len == len) return true;
+		if (f.len && f.type == type && len >= f.len && len <= (f.to ? f.to : f.len)) return true;
 	return false;
 }
 

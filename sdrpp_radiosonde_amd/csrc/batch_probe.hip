@@ -221,6 +221,20 @@ extern "C" int sonde_batch_test_ims_combine(SondeBatch *b, size_t n, const Sonde
 		});
 }
 
+// Steps 3 to 6 of SPEC 3.3o alone: status[i] = copies used, -1 not attempted, -2 no subset fits, -3 several fit.
+extern "C" int sonde_batch_test_afsk_combine(SondeBatch *b, size_t n, const SondeFrame *copies, const uint32_t *n_copies, SondeFrame *out, int32_t *status)
+{
+	return test_combine({ "sonde_batch_test_afsk_combine", sd_launch_afsk_diversity_unit, SD_DIV_MAX, 0, false }, b, { n, copies, n_copies, nullptr, out, status },
+		[](const SondeFrame *c, uint32_t k) -> const char * {
+			if ((!sd_div_is_frame(k_div_passes[SD_DIV_IMET], c[0].type, c[0].len) && !sd_div_is_frame(k_div_passes[SD_DIV_C50], c[0].type, c[0].len)) ||
+				c[0].nerr[0] >= 0)
+				return "copy 0 must be a failed SONDE_IMET4 record of 5 to 64 bytes or a failed SONDE_C50 record of 9";
+			for (uint32_t j = 1; j < k; j++)
+				if (c[j].len != c[0].len || c[j].type != c[0].type) return "the copies of a case must have one type and one length";
+			return nullptr;
+		});
+}
+
 extern "C" int sonde_batch_diversity_offsets(SondeBatch *b, uint32_t group, int64_t off[4], uint32_t *locked_mask, uint32_t *learned, uint32_t *duplicates)
 {
 	if (!b) return sd_fail("sonde_batch_diversity_offsets: bad argument");
@@ -289,7 +303,7 @@ extern "C" int sonde_batch_test_diversity_align_kind(SondeBatch *b, uint32_t kin
 	const uint32_t *counts, const SondeFrame *carried, int64_t *off, uint32_t *locked, const uint32_t *mode, uint32_t *learned, uint32_t *duplicates)
 {
 	if (kind != SONDE_RS41 && kind != SONDE_M10 && kind != SONDE_MRZN1 && kind != SONDE_DFM09 && kind != SONDE_IMS100)
-		return sd_fail("sonde_batch_test_diversity_align_kind: a kind no diversity group can have");
+		return sd_fail("sonde_batch_test_diversity_align_kind: a kind this entry does not take (iMet groups are tested on scenes, C50 has no align step)");
 	return test_diversity_align(kind, b, n, max_rec, n_members, records, counts, carried, off, locked, mode, learned, duplicates);
 }
 

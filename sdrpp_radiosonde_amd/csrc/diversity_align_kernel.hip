@@ -24,6 +24,9 @@ struct AlMember { SondeFrame *recs; const SondeFrame *carried; uint32_t cnt; };
 // nerr[0] >= 0 (nerr[1] counts Manchester violations there), the same frame = data[0 .. len) identical.  DFM (SPEC 3.3m): good = len 33
 // and nerr[1] == 0 (no word the first pass gave up on; nerr[0] counts corrected words), the same frame = data[0 .. 33) identical.
 // iMS-100 (SPEC 3.3n): good = len 51 and nerr[1] == 0 (no rejected block), the same frame = data[0 .. 51) identical.
+// iMet (SPEC 3.3o): good = len 14, 18 or 20 (PTU, GPS, PTUX: they carry a packet counter or the time) and nerr[0] >= 0, the same
+// frame = data[0 .. len) identical.  XDATA packets may repeat byte for byte: they are never good here, so they teach no offset and
+// are not marked.  C50 packets carry no identity: set_diversity refuses the step for a table with a C50 group.
 __device__ __forceinline__ const SondeFrame *al_cand(const AlMember &M, uint32_t i) { return i < M.cnt ? M.recs + i : M.carried; }
 __device__ __forceinline__ bool al_good(uint32_t kind, const SondeFrame *f)
 {
@@ -31,6 +34,7 @@ __device__ __forceinline__ bool al_good(uint32_t kind, const SondeFrame *f)
 	if (kind == SONDE_MRZN1) return f->len == 45 && f->nerr[0] >= 0;
 	if (kind == SONDE_DFM09) return f->len == 33 && f->nerr[1] == 0;
 	if (kind == SONDE_IMS100) return f->len == 51 && f->nerr[1] == 0;
+	if (kind == SONDE_IMET4) return (f->len == 14 || f->len == 18 || f->len == 20) && f->nerr[0] >= 0;
 	return (f->len == 320 || f->len == 518) && f->nerr[0] >= 0 && f->nerr[1] >= 0;
 }
 // the quick reject: two words that differ between any two frames.  RS41: parity bytes of codeword 0 and of codeword 1; the others: the
@@ -41,7 +45,7 @@ __device__ __forceinline__ uint32_t al_key(uint32_t kind, const SondeFrame *f)
 {
 	const uint32_t *w = reinterpret_cast<const uint32_t *>(f->data);
 	if (kind == SONDE_RS41) return w[2] ^ w[8];
-	const int len = f->len, wl = (len - 1) >> 2;           // a good record: len is 33, 45, 51, 70 or 101, wl >= 8
+	const int len = f->len, wl = (len - 1) >> 2;           // a good record: len is 33, 45, 51, 70 or 101, wl >= 8; iMet 14, 18 or 20, wl >= 3
 	const uint32_t last = (len & 3) ? w[wl] & ((1u << (8 * (len & 3))) - 1u) : w[wl];
 	return last ^ ((w[wl - 1] << 13) | (w[wl - 1] >> 19));
 }

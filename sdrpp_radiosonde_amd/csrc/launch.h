@@ -127,9 +127,9 @@ void sd_launch_ims_block_unit(const uint8_t *g64, uint64_t *blocks, const uint64
 // steps 1..5 of 3.3i: n records; status = 0 untouched, 1 rescued, 2 several patterns fit
 void sd_launch_afsk_repair_unit(SondeFrame *records, uint32_t n, int32_t *status, hipStream_t stream);
 
-// sonde_batch_set_diversity (DESIGN SPEC 3.3j, 3.3l, 3.3m, 3.3n): a group = 2..4 channels of one type that hear the same sonde; ch[m] and
+// sonde_batch_set_diversity (DESIGN SPEC 3.3j, 3.3l, 3.3m, 3.3n, 3.3o): a group = 2..4 channels of one type that hear the same sonde; ch[m] and
 // off[m] (offset_bits) per member, kind = the members' type: SONDE_RS41 (0: diversity_kernel.hip), SONDE_M10 or SONDE_MRZN1
-// (check_diversity_kernel.hip), SONDE_DFM09 (dfm_diversity_kernel.hip), SONDE_IMS100 (ims_diversity_kernel.hip; SONDE_FLAG_IMS_DIVERSITY).  Each combining kernel (one row of k_div_passes, batch_impl.h) is launched over the whole table and takes the groups of its kinds; the align
+// (check_diversity_kernel.hip), SONDE_DFM09 (dfm_diversity_kernel.hip), SONDE_IMS100 (ims_diversity_kernel.hip; SONDE_FLAG_IMS_DIVERSITY), SONDE_IMET4 or SONDE_C50 (afsk_diversity_kernel.hip; SONDE_FLAG_AFSK_DIVERSITY).  Each combining kernel (one row of k_div_passes, batch_impl.h) is launched over the whole table and takes the groups of its kinds; the align
 // step, the carried records, the counters and the state are one space for all kinds.  carried: [n_groups][SD_DIV_MAX] records
 // (len = 0: none), counters: [n_groups][2] (tried, combined); both carried from submit to submit.  The launches stand behind every
 // other kernel of the submit.
@@ -146,6 +146,7 @@ struct SdDivArgs {
 	uint32_t n_groups; hipStream_t stream;
 	const SdDivGroup *groups; SdDivState *states; SondeFrame *carried; uint32_t *counters;
 	uint32_t window;                       // of the pass that is launched: the caller's, or the pass's default
+	uint32_t kinds;                        // of the pass that is launched (SdDivPass.kinds): a launcher of several rows tells them apart by it
 	uint32_t other_kinds;                  // the table has groups that are not RS41: the RS41 kernels read the kind word
 	SondeFrame *frames; const uint32_t *counts; uint32_t max_frames;
 	SdFecTables fec;
@@ -156,6 +157,7 @@ void sd_launch_diversity(const SdDivArgs &a);                 // RS41 (diversity
 void sd_launch_check_diversity(const SdDivArgs &a);           // M10 / M20 / MRZ-N1 (check_diversity_kernel.hip, 3.3l)
 void sd_launch_dfm_diversity(const SdDivArgs &a);             // DFM (dfm_diversity_kernel.hip, 3.3m)
 void sd_launch_ims_diversity(const SdDivArgs &a);             // iMS-100, SONDE_FLAG_IMS_DIVERSITY (ims_diversity_kernel.hip, 3.3n)
+void sd_launch_afsk_diversity(const SdDivArgs &a);            // iMet or C50 (a.kinds), SONDE_FLAG_AFSK_DIVERSITY (afsk_diversity_kernel.hip, 3.3o)
 // the align step, one launch in front of the passes when mode != 0 (SONDE_DIVERSITY_LEARN | SONDE_DIVERSITY_MARK_DUPLICATES)
 void sd_launch_diversity_align(const SdDivArgs &a, uint32_t mode);
 // the groups of the listed channels back to "no carried record, counters zero, offsets and locks as set_diversity left them"
@@ -169,7 +171,7 @@ void sd_launch_diversity_align_unit(uint32_t n, hipStream_t stream, SondeFrame *
 	const uint32_t *n_members, const SondeFrame *carried, SdDivState *states, const uint32_t *modes, uint32_t kind);
 // A pass's rule alone (the steps behind 1 and 2): n cases of SD_DIV_MAX copies each (device memory; n_copies[i] of them in use, copy 0
 // the record to rewrite); out[i] = copy 0, rewritten or not; status[i] = copies used, or what the rule answers: RS41 -1 too many
-// erasures, -2 no decode, -3 rejected; check -1 not attempted, -2 none fits, -3 several fit; DFM and iMS-100 -1 the pairing guard
+// erasures, -2 no decode, -3 rejected; check and AFSK -1 not attempted, -2 none fits, -3 several fit; DFM and iMS-100 -1 the pairing guard
 // refuses, -2 a word / block has no solution, -3 one has several.  iMS-100: copies = n records (copy 0's alone), blocks = the copies'
 // received blocks [n][SD_DIV_MAX][12]; status 0 = the record's nerr[1] is not what copy 0's blocks say
 struct SdDivUnitArgs {
@@ -180,6 +182,7 @@ void sd_launch_diversity_unit(const SdDivUnitArgs &a);
 void sd_launch_check_diversity_unit(const SdDivUnitArgs &a);
 void sd_launch_dfm_diversity_unit(const SdDivUnitArgs &a);
 void sd_launch_ims_diversity_unit(const SdDivUnitArgs &a);
+void sd_launch_afsk_diversity_unit(const SdDivUnitArgs &a);
 
 // sets the text sonde_last_error() returns; returns -1 (sd_host.cpp)
 int sd_fail(const char *what, hipError_t e = hipSuccess);

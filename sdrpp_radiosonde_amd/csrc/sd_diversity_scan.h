@@ -1,6 +1,6 @@
-// sd_diversity_scan.h -- what the four combining passes of sonde_batch_set_diversity share (DESIGN "what a combining pass plugs into";
+// sd_diversity_scan.h -- what the five combining passes of sonde_batch_set_diversity share (DESIGN "what a combining pass plugs into";
 // diversity_kernel.hip, SPEC 3.3j: RS41; check_diversity_kernel.hip, SPEC 3.3l: M10 / M20 / MRZ-N1; dfm_diversity_kernel.hip, SPEC 3.3m:
-// DFM; ims_diversity_kernel.hip, SPEC 3.3n: iMS-100): the two predicates of a group's kind (SdDivGroup.kind = the members' sonde type)
+// DFM; ims_diversity_kernel.hip, SPEC 3.3n: iMS-100; afsk_diversity_kernel.hip, SPEC 3.3o: iMet and C50): the two predicates of a group's kind (SdDivGroup.kind = the members' sonde type)
 // -- which record lengths are frames, and when a record has failed --, the members of a group, steps 1 and 2 of SPEC 3.3j -- the scan
 // of the members' record headers for the next failed record in (t, member) order and for its partner in another member --, the
 // carried records, and dv_walk, the loop that strings them together: one 64-lane wave per group, DV_WAVES waves per workgroup, every
@@ -29,13 +29,14 @@
 constexpr int DV_REC_WORDS = (int)(sizeof(SondeFrame) / 4);
 constexpr int DV_DATA_WORD0 = (int)(offsetof(SondeFrame, data) / 4);
 
-// a frame length of the kind: RS41 {320, 518}, M10 / M20 {101, 70}, MRZ-N1 {45}, DFM {33}, iMS-100 {51}
+// a frame length of the kind: RS41 {320, 518}, M10 / M20 {101, 70}, MRZ-N1 {45}, DFM {33}, iMS-100 {51}, iMet 5 .. 64, C50 {9}
 __device__ __forceinline__ bool dv_len_ok(uint32_t kind, int len)
 {
 	return kind == SONDE_M10 ? (len == 101 || len == 70) : kind == SONDE_MRZN1 ? len == 45 : kind == SONDE_DFM09 ? len == 33 :
-	       kind == SONDE_IMS100 ? len == 51 : (len == 320 || len == 518);
+	       kind == SONDE_IMS100 ? len == 51 : kind == SONDE_IMET4 ? (len >= 5 && len <= 64) : kind == SONDE_C50 ? len == 9 :
+	       (len == 320 || len == 518);
 }
-// failed: RS41 a codeword at nerr < 0, M10 / M20 / MRZ-N1 the 16-bit check (nerr[0] < 0; nerr[1] counts Manchester violations there),
+// failed: RS41 a codeword at nerr < 0, M10 / M20 / MRZ-N1 and iMet / C50 the 16-bit check (nerr[0] < 0; nerr[1] counts Manchester violations there),
 // DFM a Hamming word the first pass gave up on (nerr[1] > 0; nerr[0] counts corrected words there), iMS-100 a BCH block it rejected
 // (nerr[1] > 0; nerr[0] counts corrected bits there).  A record with a frame length that has not failed is good: to the scan and as a
 // partner (the align step, diversity_align_kernel.hip, states the same per kind as al_good)
@@ -242,7 +243,7 @@ template <class... P, class... A> static inline void dv_launch(void (*kernel)(Sd
 	hipLaunchKernelGGL(kernel, dim3((a.n_groups + DV_WAVES - 1) / DV_WAVES), dim3(64 * DV_WAVES), 0, a.stream, w, extra...);
 }
 
-// ---- what the four unit kernels (test introspection: a pass's rule alone on caller-made cases, one wave per case) begin with: the
+// ---- what the five unit kernels (test introspection: a pass's rule alone on caller-made cases, one wave per case) begin with: the
 // case k of this wave (false: there is none), and out[k] = copy 0 of the case (copy0[stride * k]) in memory before the result is
 // written over it (other lanes write the same words then)
 __device__ __forceinline__ bool dv_unit_case(uint32_t &k, uint32_t n, const SondeFrame *copy0, uint32_t stride, SondeFrame *out, int lane)

@@ -1,4 +1,4 @@
-"""Python face of a receiver with several antennas (DESIGN SPEC 3.3k, 3.3l, 3.3m, 3.3n): thin, no compute -- every call goes through the C ABI of
+"""Python face of a receiver with several antennas (DESIGN SPEC 3.3k, 3.3l, 3.3m, 3.3n, 3.3o): thin, no compute -- every call goes through the C ABI of
 libsonde_mi355.so.
 
     DiversityReceiver   K wideband streams (one per antenna or polarisation, started whenever) -> K tuners with the same VFO list ->
@@ -10,19 +10,19 @@ libsonde_mi355.so.
 
 The chain is the "iq48" chain of _chain.py, which WidebandReceiver (tuner.py) and LiveReceiver share: a tuner per antenna straight to
 48 kHz IQ rows.  combine="frames" (the default): RS41, M10 / M20 and MRZ-N1 sondes, in any mix, and with dfm_diversity=True DFM sondes, with
-ims_diversity=True iMS-100 sondes too.  No tracking, no reference chain."""
+ims_diversity=True iMS-100 sondes, with afsk_diversity=True iMet sondes too.  No tracking, no reference chain."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import _chain
 from ._handle import current_stream
-from ._lib import DFM09, FLAG_IMS_DIVERSITY, FRAME_DUPLICATE, IMS100, INPUT_IQ, M10, MRZN1, RS41, SondeError
+from ._lib import DFM09, FLAG_AFSK_DIVERSITY, FLAG_IMS_DIVERSITY, FRAME_DUPLICATE, IMET4, IMS100, INPUT_IQ, M10, MRZN1, RS41, SondeError
 from .tuner import SondeTuner
 
 
 class DiversityReceiver:
-    """sondes: [(offset_hz, sonde type), ...], every type RS41, M10 (M10 and M20) or MRZN1, with dfm_diversity=True DFM09, with ims_diversity=True IMS100 too; antennas = K = 2..4 wideband streams at rate_in that hear them.
+    """sondes: [(offset_hz, sonde type), ...], every type RS41, M10 (M10 and M20) or MRZN1, with dfm_diversity=True DFM09, with ims_diversity=True IMS100, with afsk_diversity=True IMET4 too; antennas = K = 2..4 wideband streams at rate_in that hear them.
     Batch channel a * len(sondes) + i is sonde i on antenna a; the K channels of sonde i are diversity group i, antenna a its member a,
     set with learn=True, mark_duplicates=True and no offsets: the streams need not start together, the group finds out where they
     stand from the first frame that is good on two antennas (SondeBatch.set_diversity).  rescue= (RS41) and manchester_rescue= (M10 /
@@ -31,6 +31,10 @@ class DiversityReceiver:
     to the batch as the DFM second pass in front of it.
     ims_diversity=True: iMS-100 / RS-11G sondes are taken as well (SPEC 3.3n: failed copies are combined BCH block by block, from the
     chips; the batch is created with FLAG_IMS_DIVERSITY), and ims_rescue= is passed on to the batch as the iMS-100 second pass in front.
+    afsk_diversity=True: iMet sondes are taken as well (SPEC 3.3o: failed copies are combined by their CRC; the batch is created with
+    FLAG_AFSK_DIVERSITY), and afsk_rescue= is passed on to the batch as the iMet second pass in front.  XDATA packets are never marked
+    as duplicates (they may repeat byte for byte): frames() returns every good copy of them.  C50 sondes are not taken: their packets
+    carry no identity, so a C50 group has no learned offsets (SondeBatch.set_diversity with given offsets serves them).
 
     submit(blocks) takes K device blocks [n, 2] of equal length (float32 / int16 / int8 by input_kind), n a multiple of `granule`
     and <= max_in.  frames() returns (records, antenna): the last submit's records without the duplicates, `channel` = the sonde
@@ -48,7 +52,7 @@ class DiversityReceiver:
     def __init__(self, rate_in: int, sondes, antennas: int = 2, *, input_kind: int = INPUT_IQ, device: int = 0, max_in: int | None = None,
                  window_bits: int = 0, rescue: bool = False, chain: str = "iq48", track: bool = False, combine: str = "frames",
                  combine_block: int = 0, manchester_rescue: bool = False, dfm_rescue: bool = False, ims_rescue: bool = False,
-                 afsk_rescue: bool = False, dfm_diversity: bool = False, ims_diversity: bool = False):
+                 afsk_rescue: bool = False, dfm_diversity: bool = False, ims_diversity: bool = False, afsk_diversity: bool = False):
         if chain != "iq48":
             raise SondeError('DiversityReceiver: only the "iq48" chain')
         if track:
@@ -62,9 +66,9 @@ class DiversityReceiver:
         coherent = combine == "coherent"
         types = [t for _, t in self.sondes]
         if not coherent:
-            if (dfm_rescue and not dfm_diversity) or (ims_rescue and not ims_diversity) or afsk_rescue:
+            if (dfm_rescue and not dfm_diversity) or (ims_rescue and not ims_diversity) or (afsk_rescue and not afsk_diversity):
                 raise SondeError('DiversityReceiver: combine="frames" takes no rescue pass but rescue= and manchester_rescue=')
-            served = (RS41, M10, MRZN1) + ((DFM09,) if dfm_diversity else ()) + ((IMS100,) if ims_diversity else ())
+            served = (RS41, M10, MRZN1) + ((DFM09,) if dfm_diversity else ()) + ((IMS100,) if ims_diversity else ()) + ((IMET4,) if afsk_diversity else ())
             if any(t not in served for t in types):
                 raise SondeError('DiversityReceiver: the frame-level pass serves M10 / M20, MRZ-N1 and RS41 sondes only (combine="coherent" takes any type)')
         self.antennas = int(antennas)
@@ -89,7 +93,7 @@ class DiversityReceiver:
             self._ant = torch.empty((K * S, p.n48, 2), dtype=torch.float32, device=f"cuda:{device}")      # the tuners' rows
             self._rows = _chain.rows(S, p.n48, device)                                                   # the combined rows
         else:                 # one batch channel per antenna and sonde; the K channels of a sonde are a diversity group
-            self.batch = _chain.batch(K * S, p.n48, types * K, device, passes, flags=FLAG_IMS_DIVERSITY if ims_diversity else 0)
+            self.batch = _chain.batch(K * S, p.n48, types * K, device, passes, flags=(FLAG_IMS_DIVERSITY if ims_diversity else 0) | (FLAG_AFSK_DIVERSITY if afsk_diversity else 0))
             self.batch.set_diversity([[a * S + i for a in range(K)] for i in range(S)], None, window_bits, learn=True, mark_duplicates=True)
             self._rows = _chain.rows(K * S, p.n48, device)
 
